@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the wakeword training inner loop on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N>1 without a launcher: this process starts the N ranks itself (``python -m torch.distributed.run``) BEFORE anything
 touches the GPU and relays rank 0's JSON line; under ``torch.distributed.run`` (the driver's command) it is a rank.
@@ -9,9 +9,11 @@ touches the GPU and relays rank 0's JSON line; under ``torch.distributed.run`` (
 One "step" = the whole hot path on one batch of synthetic 16 kHz x 1.5 s clips already resident in HBM:
 fused log-mel(40)+SpecAugment -> cnn_small forward -> 2-class loss -> backward -> [RCCL all-reduce of the flat
 gradient bucket] -> grad-norm clip -> AdamW step, i.e. wakeword_trainer_home_amd.training.Trainer._step_native
-(BASELINE.json config 2: cnn_small + log-mel 40, batch 512 per GPU).  Rank 0 prints ONE JSON line with the
-metric, the roofline of the dominant kernel (HIP-event timed inside the timed region) and the CPU baseline
-(the oracle's PyTorch CPU step on the host cores, bounded sample).
+(BASELINE.json config 2: cnn_small + log-mel 40, batch 512 per GPU).  A plain run sets up, warms up, times exactly
+K steps, writes the last step's outputs if asked, and rank 0 prints ONE JSON line with the metric.  --full adds what
+takes runs of its own: the roofline of the dominant kernel (HIP events in one more pass of the region), the input-stage
+kernel alone, the CPU baseline (the oracle's PyTorch CPU step on the host cores, bounded sample), and three timed
+passes instead of one.
 """
 import argparse
 import json
@@ -132,6 +134,66 @@ def cpu_baseline(batch, seconds_budget=20.0):
                       f"{dt:.1f} s wall"}
 
 
+def full_report(args, world, value, esz, dominant, warm, prof, alone, ev_dt, input_stage_workgroups):
+    """--full: the roofline of the dominant kernel class and of the input stage, from the HIP events of the warm-up, of the
+    input-stage kernel alone and of the extra event pass."""
+    ms, launches = prof.get(dominant, (0.0, 0))
+    per_launch_s = (ms / launches) * 1e-3 if launches else float("nan")
+    algo = algo_bytes(dominant, esz) * args.batch
+    achieved = algo / per_launch_s / 1e9 if launches else float("nan")
+    traffic, traffic_src = measured_traffic(dominant, args.batch, args.dtype)
+
+    def logmel_leg(ms_n, where):
+        if not ms_n[1]:
+            return None
+        sec = ms_n[0] / ms_n[1] * 1e-3
+        gbs = ALGO_BYTES["logmel_specaug"] * args.batch / sec / 1e9
+        tf = LOGMEL_FLOPS * args.batch / sec / 1e12
+        return {"where": where, "launch_us": round(sec * 1e6, 2), "launches_timed": ms_n[1],
+                "achieved_GBps": round(gbs, 1), "frac_hbm": round(gbs / HBM_PEAK_GBS, 4),
+                "achieved_TFLOPs": round(tf, 2), "frac_valu_f32": round(tf / VALU_PEAK_TFLOPS, 4)}
+    return {
+        "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                     "traffic": traffic, "traffic_source": traffic_src,
+                     "launch_us": round(per_launch_s * 1e6, 2), "launches_timed": launches,
+                     "timed_in": "eager warm-up steps (nodes of the replayed graph cannot carry HIP events)" if args.graph
+                     else f"one more pass of the same {args.steps}-step region right after the timed passes, events on "
+                          f"this class + the input stage only ({ev_dt / args.steps * 1e3:.4f} ms/step with them)",
+                     "algorithmic_bytes_per_launch": algo,
+                     "step_frac_of_hbm_roofline": round(value / world * step_algo_bytes(esz) / (HBM_PEAK_GBS * 1e9), 4),
+                     # the input stage: NOT on the critical path (side stream, one batch ahead), far from both of its
+                     # rooflines -- latency/LDS-bound FFT; algorithmic 120 160 B and 4.41 MFLOP per clip
+                     "side_stream": {"kernel": "logmel_specaug",
+                                     "algorithmic_bytes_per_launch": ALGO_BYTES["logmel_specaug"] * args.batch,
+                                     "alone": logmel_leg(alone, "idle GPU, before the timed region, full-device grid"),
+                                     "in_step": logmel_leg(prof.get("logmel_specaug", (0.0, 0)),
+                                                           "timed region, sharing the CUs with the conv kernels, "
+                                                           f"{input_stage_workgroups} persistent workgroups "
+                                                           "(Trainer.input_stage_workgroups: one per CU)")}},
+        # HIP-event SPANS around each class's launches during the warm-up steps (all classes on): they include queue
+        # gaps and the stretch of running beside the other stream, so they do not add up to ms_per_step
+        "event_span_ms_per_step_warmup": {k: round(v[0] / max(args.warmup, 1), 4) for k, v in sorted(warm.items())},
+    }
+
+
+def dump_outputs(out_dir, model, done):
+    """--dump-outputs: what the timed path handed its caller in its last step, for comparing two builds output for output.
+    The step's loss and accuracy (float64), and after its optimizer update the model state -- every floating tensor of
+    state_dict(), parameters and BatchNorm statistics -- and the gradient left in the parameters' .grad, each flattened in
+    state_dict() / parameters() order and concatenated (float32; cnn_small: 22 k values, far below 64 MB)."""
+    import numpy as np
+    import torch
+    out_dir.mkdir(parents=True, exist_ok=True)
+    loss, acc = (float("nan"), float("nan")) if done is None else (done[1], done[2])      # None: the step was skipped
+    state = [v.detach().flatten() for v in model.state_dict().values() if v.is_floating_point()]
+    grad = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().flatten() for p in model.parameters()]
+    arrays = {"loss": np.array([loss], np.float64), "accuracy": np.array([acc], np.float64),
+              "model_state": torch.cat(state).float().cpu().numpy(), "param_grad": torch.cat(grad).float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
 class _fd1_to_stderr:
     """RCCL prints its version banner on fd 1 when the communicator is created; stdout must carry ONE JSON line."""
 
@@ -155,7 +217,7 @@ def main():
     ap.add_argument("--dtype", choices=("bf16", "f32", "f16"), default="bf16",
                     help="storage of the conv-stack activations/gradients (arithmetic is fp32 either way); "
                          "BASELINE config 2 names bf16, f32 is the 1e-3 parity mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=128)
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the RCCL process group even for one rank (plumbing test on a 1-GPU box)")
@@ -166,13 +228,22 @@ def main():
     ap.add_argument("--dp-overlap", action="store_true", help="two gradient buckets (Trainer.dp_overlap)")
     ap.add_argument("--graph", action="store_true",
                     help="replay the step as a captured HIP graph (Trainer.enable_hip_graph; not the headline line)")
-    ap.add_argument("--passes", type=int, default=3,
-                    help="the timed region (--steps steps) is run this many times; the MEDIAN is reported (SURVEY §8d)")
+    ap.add_argument("--passes", type=int, default=None,
+                    help="the timed region (--steps steps) is run this many times; the MEDIAN is reported (SURVEY §8d). "
+                         "Default 1, so that --steps is the number of timed steps; 3 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline of the dominant kernel (HIP "
+                         "events in the warm-up and in one more pass of the region), the input-stage kernel alone, and the "
+                         "CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="process-group backend; gloo exists for tests/ only (the spawner path on a one-GPU box)")
     ap.add_argument("--share-device0", action="store_true",
                     help="tests/ only: every rank uses cuda:0 (a one-GPU box rehearsing the N-rank command path)")
     args = ap.parse_args()
+    if args.passes is None:
+        args.passes = 3 if args.full else 1
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the N ranks from here.  Nothing in this process has touched HIP (torch is not even imported),
@@ -298,25 +369,27 @@ def main():
     import gc
     gc.collect()
     gc.disable()
-    # warm-up with HIP events on every kernel class; the first steps also tell which class dominates
-    nat.prof_enable(dev, None)
+    # --full: the warm-up runs with HIP events on every kernel class; the first steps also tell which class dominates
+    if args.full:
+        nat.prof_enable(dev, None)
     run_steps(0, args.warmup)
     fence()
-    warm = nat.prof_collect(dev)
-    # the roofline kernel is the largest class on the step's critical path (the main stream).  The input stage (log-mel,
-    # waveform augmentation) runs a batch ahead on the side stream and is reported separately as roofline.side_stream:
-    # its event spans include the time it shares CUs with the conv kernels, and it is timed alone below as well.
-    side = ("logmel_specaug", "audio_augment")
-    main_classes = {k: v for k, v in warm.items() if k not in side}
-    dominant = max(main_classes, key=lambda k: main_classes[k][0]) if main_classes else "dwconv3x3_bwd"
+    if args.full:
+        warm = nat.prof_collect(dev)
+        # the roofline kernel is the largest class on the step's critical path (the main stream).  The input stage (log-mel,
+        # waveform augmentation) runs a batch ahead on the side stream and is reported separately as roofline.side_stream:
+        # its event spans include the time it shares CUs with the conv kernels, and it is timed alone below as well.
+        side = ("logmel_specaug", "audio_augment")
+        main_classes = {k: v for k, v in warm.items() if k not in side}
+        dominant = max(main_classes, key=lambda k: main_classes[k][0]) if main_classes else "dwconv3x3_bwd"
 
-    # the input-stage kernel alone on an idle GPU (north_star: "achieved HBM GB/s for STFT/mel")
-    nat.prof_enable(dev, ["logmel_specaug"])
-    for i in range(5):
-        trainer._features(pool[i % len(pool)][0], training=True, step=i)
-    fence()
-    alone = nat.prof_collect(dev).get("logmel_specaug", (0.0, 0))
-    nat.prof_enable(dev, [])
+        # the input-stage kernel alone on an idle GPU (north_star: "achieved HBM GB/s for STFT/mel")
+        nat.prof_enable(dev, ["logmel_specaug"])
+        for i in range(5):
+            trainer._features(pool[i % len(pool)][0], training=True, step=i)
+        fence()
+        alone = nat.prof_collect(dev).get("logmel_specaug", (0.0, 0))
+        nat.prof_enable(dev, [])
     nxt = args.warmup
     if args.graph:
         # the step as ONE replayed HIP graph (Trainer._graph_capture): captured after the next eager step, then two replays
@@ -336,10 +409,12 @@ def main():
         fence()
         pass_dt.append(time.perf_counter() - t0)
         nxt += args.steps
-    # per-kernel HIP events: one more pass of the same region with events around the dominant class and the input stage
-    # (on the streams they are launched on), so the event records cost the timed passes nothing
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), trainer.model, last_done[0])
+    # --full, per-kernel HIP events: one more pass of the same region with events around the dominant class and the input
+    # stage (on the streams they are launched on), so the event records cost the timed passes nothing
     ev_dt = None
-    if not args.graph:
+    if args.full and not args.graph:
         nat.prof_enable(dev, [dominant, "logmel_specaug"])
         fence()
         t0 = time.perf_counter()
@@ -349,8 +424,9 @@ def main():
         nxt += args.steps
     last = None if last_done[0] is None else (last_done[0][1], last_done[0][2])
     gc.enable()
-    prof = nat.prof_collect(dev) if not args.graph else {k: v for k, v in warm.items()}
-    nat.prof_enable(dev, [])
+    if args.full:
+        prof = nat.prof_collect(dev) if not args.graph else {k: v for k, v in warm.items()}
+        nat.prof_enable(dev, [])
     devices = [torch.cuda.get_device_name(local_rank) + f" (cuda:{local_rank})"]
     if use_dist:
         t = torch.tensor(pass_dt, dtype=torch.float64, device=dev)
@@ -364,21 +440,6 @@ def main():
         dt = sorted(pass_dt)[len(pass_dt) // 2]               # median pass
         total = args.batch * world * args.steps
         value = total / dt
-        ms, launches = prof.get(dominant, (0.0, 0))
-        per_launch_s = (ms / launches) * 1e-3 if launches else float("nan")
-        algo = algo_bytes(dominant, esz) * args.batch
-        achieved = algo / per_launch_s / 1e9 if launches else float("nan")
-        traffic, traffic_src = measured_traffic(dominant, args.batch, args.dtype)
-
-        def logmel_leg(ms_n, where):
-            if not ms_n[1]:
-                return None
-            sec = ms_n[0] / ms_n[1] * 1e-3
-            gbs = ALGO_BYTES["logmel_specaug"] * args.batch / sec / 1e9
-            tf = LOGMEL_FLOPS * args.batch / sec / 1e12
-            return {"where": where, "launch_us": round(sec * 1e6, 2), "launches_timed": ms_n[1],
-                    "achieved_GBps": round(gbs, 1), "frac_hbm": round(gbs / HBM_PEAK_GBS, 4),
-                    "achieved_TFLOPs": round(tf, 2), "frac_valu_f32": round(tf / VALU_PEAK_TFLOPS, 4)}
         out = {
             "metric": "training samples/sec (16kHz x 1.5s clips)", "value": round(value, 1), "unit": "samples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
@@ -397,30 +458,12 @@ def main():
                                          else "in-stream after the backward")) if use_dist else None,
                        "hip_graph": bool(args.graph),
                        "last_loss": None if last is None else round(last[0], 6)},
-            "roofline": {"bound": "hbm", "kernel": dominant, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "launch_us": round(per_launch_s * 1e6, 2), "launches_timed": launches,
-                         "timed_in": "eager warm-up steps (nodes of the replayed graph cannot carry HIP events)" if args.graph
-                         else f"one more pass of the same {args.steps}-step region right after the timed passes, events on "
-                              f"this class + the input stage only ({ev_dt / args.steps * 1e3:.4f} ms/step with them)",
-                         "algorithmic_bytes_per_launch": algo,
-                         "step_frac_of_hbm_roofline": round(value / world * step_algo_bytes(esz) / (HBM_PEAK_GBS * 1e9), 4),
-                         # the input stage: NOT on the critical path (side stream, one batch ahead), far from both of its
-                         # rooflines -- latency/LDS-bound FFT; algorithmic 120 160 B and 4.41 MFLOP per clip
-                         "side_stream": {"kernel": "logmel_specaug",
-                                         "algorithmic_bytes_per_launch": ALGO_BYTES["logmel_specaug"] * args.batch,
-                                         "alone": logmel_leg(alone, "idle GPU, before the timed region, full-device grid"),
-                                         "in_step": logmel_leg(prof.get("logmel_specaug", (0.0, 0)),
-                                                               "timed region, sharing the CUs with the conv kernels, "
-                                                               f"{trainer.input_stage_workgroups} persistent workgroups "
-                                                               "(Trainer.input_stage_workgroups: one per CU)")}},
-            # HIP-event SPANS around each class's launches during the warm-up steps (all classes on): they include queue
-            # gaps and the stretch of running beside the other stream, so they do not add up to ms_per_step
-            "event_span_ms_per_step_warmup": {k: round(v[0] / max(args.warmup, 1), 4) for k, v in sorted(warm.items())},
         }
-        if not args.no_cpu_baseline and world == 1:       # reported at N=1 only (bounded sample, rank 0)
-            out["cpu_baseline"] = cpu_baseline(args.cpu_batch)
+        if args.full:
+            out.update(full_report(args, world, value, esz, dominant, warm, prof, alone, ev_dt,
+                                   trainer.input_stage_workgroups))
+            if not args.no_cpu_baseline and world == 1:   # reported at N=1 only (bounded sample, rank 0)
+                out["cpu_baseline"] = cpu_baseline(args.cpu_batch)
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

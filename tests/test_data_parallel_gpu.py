@@ -293,6 +293,39 @@ def test_bench_one_rank_rccl_plumbing():
     assert out["value"] > 0 and np.isfinite(out["config"]["last_loss"])
 
 
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_its_steps_dumps_outputs_and_full_adds_the_rest(tmp_path):
+    """A plain bench.py run times exactly --steps steps in one pass and reports the headline only; --dump-outputs writes the
+    last timed step's loss / accuracy / model state / gradient as float arrays; --full adds the roofline and the median of
+    three passes."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+
+    def bench(*extra):
+        r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--steps", "3", "--warmup", "2", "--batch", "64", *extra],
+                           capture_output=True, text=True, env=env, timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout                               # stdout carries exactly ONE JSON line
+        return json.loads(lines[0])
+
+    out = bench("--dump-outputs", str(tmp_path / "plain"))
+    assert out["steps"] == 3 and out["passes_ms_per_step"] == [out["ms_per_step"]] and out["value"] > 0
+    assert "roofline" not in out and "cpu_baseline" not in out
+    arrays = {f.stem: np.load(f) for f in (tmp_path / "plain").glob("*.npy")}
+    assert set(arrays) == {"loss", "accuracy", "model_state", "param_grad"}
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64) and a.size and np.isfinite(a).all(), name
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert abs(arrays["loss"][0] - out["config"]["last_loss"]) < 1e-6
+    full = bench("--full", "--no-cpu-baseline")
+    assert len(full["passes_ms_per_step"]) == 3 and full["roofline"]["launches_timed"] > 0
+    assert full["event_span_ms_per_step_warmup"] and "cpu_baseline" not in full
+
+
 @pytest.mark.timeout(900)
 def test_bench_two_ranks_through_its_own_spawner():
     """``python bench.py --gpus 2`` with no launcher around it: bench.py starts its own ranks (torch.distributed.run, before

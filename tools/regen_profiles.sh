@@ -24,6 +24,6 @@ rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $O/pmc_write --
 python tools/pmc_traffic.py $O/pmc_fetch $O/pmc_write $L
 cp profiles/pmc_traffic.json $O/pmc_traffic.json
 rm -rf $O/kt $O/pmc_fetch $O/pmc_write
-# last, so that roofline.traffic comes from the PMC file written above (same kernel-source digest); the driver's command line
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+# last, so that roofline.traffic comes from the PMC file written above (same kernel-source digest); the driver's command line + --full
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
 python -c "import json;d=json.load(open('$O/bench.json'));print('bench',d['value'],d['ms_per_step'],d['roofline']['frac'],d['roofline']['launch_us'])"

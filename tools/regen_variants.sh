@@ -5,7 +5,7 @@ set -e
 L=${1:-variants}
 O=gpurun_out/$L
 mkdir -p $O
-run() { python bench.py --no-cpu-baseline "${@:2}" > $O/bench_$1.json 2>/dev/null; python -c "import json;d=json.load(open('$O/bench_$1.json'));print('$1',d['value'],d['ms_per_step'])"; }
+run() { python bench.py --full --no-cpu-baseline "${@:2}" > $O/bench_$1.json 2>/dev/null; python -c "import json;d=json.load(open('$O/bench_$1.json'));print('$1',d['value'],d['ms_per_step'])"; }
 run bf16
 run f16 --dtype f16
 run f32 --dtype f32
