@@ -138,3 +138,149 @@ def test_fp16_graph_replay_is_bit_exact(tmp_path):
         out.append((losses, model.flat_param.clone(), t.scaler.state_dict(), t._graph is not None))
     assert out[1][3] and not out[0][3]
     assert out[0][0] == out[1][0] and torch.equal(out[0][1], out[1][1]) and out[0][2] == out[1][2]
+
+
+# ------------------------------------------------------------------------------------------ single conv layers in fp16 storage
+EPS_F16 = 2.0 ** -10          # one RNE rounding is <= 2^-11 relative; 2^-10 leaves room for fp32 order effects (cf. EPS_BF16)
+
+
+def _rh(t):
+    """round a float64/32 tensor to fp16 and back (what the device stores)."""
+    return t.float().half().double()
+
+
+@pytest.mark.parametrize("kind", ["dw", "pw"])
+@pytest.mark.parametrize("B,H,W", [(3, 20, 76), (2, 7, 25), (5, 17, 10)])
+def test_conv_fwd_layers_fp16(kind, B, H, W):
+    """tests/test_bf16_mode.py:test_conv_fwd_layers_bf16 in fp16 storage: one rounding (depthwise) or three (pointwise: the
+    stored output and both MFMA operands) of 2^-11, and statistics of exactly the stored tensor.  Measured (of the output's
+    scale): depthwise 4.3e-4 against 2^-10 = 9.8e-4, pointwise 5.8e-4 against 2.9e-3."""
+    from wakeword_trainer_home_amd import _native as nat
+    from tests.test_hip_kernels import cu, nhwc, rel_err, _bn_tensors
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(31)
+    y_in = _rh(torch.randn(B, 64, H, W, generator=g, dtype=torch.float64))
+    s_in = torch.rand(64, generator=g, dtype=torch.float64) + 0.5
+    t_in = torch.randn(64, generator=g, dtype=torch.float64) * 0.5
+    a = torch.relu(y_in * s_in[None, :, None, None] + t_in[None, :, None, None])
+    if kind == "dw":
+        w = torch.randn(64, 1, 3, 3, generator=g, dtype=torch.float64) * 0.3
+        ref = F.conv2d(a, w, padding=1, groups=64)
+    else:
+        w = torch.randn(64, 64, 1, 1, generator=g, dtype=torch.float64) * 0.2
+        ref = F.conv2d(a, w)
+    gamma, beta, rm, rv = _bn_tensors(2)
+    ga, be, rm_g, rv_g = cu(gamma), cu(beta), cu(rm), cu(rv)          # (the BN struct holds raw pointers: keep them alive)
+    bn = nat.make_bn(ga, be, rm_g, rv_g)
+    fn = nat.dwconv3x3_fwd if kind == "dw" else nat.pwconv1x1_fwd
+    y, ss, mr = fn(cu(nhwc(y_in), torch.float16), cu(torch.cat([s_in, t_in])), cu(w), bn, nat.layer_scratch(DEV))
+    assert y.dtype == torch.float16
+    yd = y.float().cpu().double()
+    tol = EPS_F16 * (3 if kind == "pw" else 1)
+    print(f"fp16 conv fwd {kind} {B}x{H}x{W}: y={((yd - nhwc(ref)).abs().max() / nhwc(ref).abs().max()).item():.2e}")
+    assert (yd - nhwc(ref)).abs().max() <= tol * nhwc(ref).abs().max()
+    mean = yd.mean(dim=(0, 1, 2))
+    var = yd.var(dim=(0, 1, 2), unbiased=False)
+    assert np.abs(mr[:64].cpu().numpy() - mean.numpy()).max() < 1e-5 * (mean.abs().max().item() + 1)
+    assert rel_err(mr[64:].cpu(), 1.0 / torch.sqrt(var + 1e-5)) < 2e-5
+
+
+@pytest.mark.parametrize("scale", [1024.0, 65536.0])
+@pytest.mark.parametrize("kind", ["dw", "pw"])
+@pytest.mark.parametrize("B,H,W", [(3, 20, 76), (2, 7, 25)])
+def test_conv_bwd_layers_fp16(kind, B, H, W, scale):
+    """tests/test_bf16_mode.py:test_conv_bwd_layers_bf16 in fp16 storage.  The incoming gradient has a real gradient's size
+    (~1/pixels) and is multiplied by the loss scale on the way in, as the device scaler does -- 1024 or GradScaler's 65536 --
+    and the results are divided by it: bounds of 2^-11 per rounding as the bf16 file's 2^-8, and the stored gradients finite.
+    Measured (both scales alike): g_in depthwise 3.0e-4 against 9.8e-4, pointwise 5.0e-4 against 2.9e-3; dW pointwise 5.6e-4
+    against 2 x 2^-10, depthwise (fp32 operands) 2.0e-7 against 2e-6."""
+    from wakeword_trainer_home_amd import _native as nat
+    from tests.test_hip_kernels import cu, nhwc, rel_err, _coef_from
+    import torch.nn.functional as F
+    gen = torch.Generator().manual_seed(41)
+    y_in = _rh(torch.randn(B, 64, H, W, generator=gen, dtype=torch.float64))
+    bn_in, bn_out = torch.nn.BatchNorm2d(64).double(), torch.nn.BatchNorm2d(64).double()
+    with torch.no_grad():
+        for bn in (bn_in, bn_out):
+            bn.weight.copy_(torch.rand(64, generator=gen, dtype=torch.float64) + 0.5)
+            bn.bias.copy_(torch.randn(64, generator=gen, dtype=torch.float64) * 0.3)
+    shape = (64, 1, 3, 3) if kind == "dw" else (64, 64, 1, 1)
+    w = (torch.randn(*shape, generator=gen, dtype=torch.float64) * 0.25).requires_grad_(True)
+    z_in = bn_in(y_in)
+    z_in.retain_grad()
+    a = torch.relu(z_in)
+    y_raw = F.conv2d(a, w, padding=1, groups=64) if kind == "dw" else F.conv2d(a, w)
+    y = y_raw + (_rh(y_raw.detach()) - y_raw.detach())
+    z = bn_out(y)
+    g0 = torch.randn(B, 64, H, W, generator=gen, dtype=torch.float64) * (torch.rand(B, 64, H, W, generator=gen) > 0.4) / (B * H * W)
+    g = _rh(g0 * scale)                                   # the scaled gradient as the device stores it
+    (z * g).sum().backward()
+    coef, _, _ = _coef_from(g, y.detach(), bn_out.weight.detach())
+    mean_in = y_in.mean(dim=(0, 2, 3))
+    rstd_in = 1.0 / torch.sqrt(y_in.var(dim=(0, 2, 3), unbiased=False) + 1e-5)
+    scale_in = bn_in.weight.detach() * rstd_in
+    ss_in = torch.cat([scale_in, bn_in.bias.detach() - mean_in * scale_in])
+    F16 = torch.float16
+    args = dict(y_out=cu(nhwc(y.detach()), F16), coef=cu(coef), y_in=cu(nhwc(y_in), F16), ss_in=cu(ss_in),
+                mr_in=cu(torch.cat([mean_in, rstd_in])), gamma_in=cu(bn_in.weight.detach()), w=cu(w.detach()),
+                scratch=nat.layer_scratch(DEV))
+    if kind == "dw":
+        g_in, dw, coef_in, dgamma, dbeta = nat.dwconv3x3_bwd(cu(nhwc(g), F16), **args)
+    else:
+        g_in, dw, coef_in, dgamma, dbeta = nat.pwconv1x1_bwd(cu(nhwc(g), F16), None, ss_out=None, **args)
+    assert g_in.dtype == F16 and torch.isfinite(g_in).all()
+    gi = g_in.float().cpu().double() / scale
+    ref_gi = nhwc(z_in.grad) / scale
+    tol = EPS_F16 * (3 if kind == "pw" else 1)
+    print(f"fp16 conv bwd {kind} {B}x{H}x{W} x{scale:g}: g_in={((gi - ref_gi).abs().max() / ref_gi.abs().max()).item():.2e} "
+          f"dw={rel_err(dw.cpu().reshape(-1) / scale, w.grad.reshape(-1) / scale):.2e}")
+    assert (gi - ref_gi).abs().max() <= tol * ref_gi.abs().max()
+    # pointwise: dy and relu(bn(y_in)) rounded to fp16 for the MFMA, two roundings (measured 5.6e-4); depthwise: fp32 operands
+    assert rel_err(dw.cpu().reshape(-1) / scale, w.grad.reshape(-1) / scale) < (2 * EPS_F16 if kind == "pw" else 2e-6)
+    yhat_in = (nhwc(y_in) - mean_in) * rstd_in
+    assert rel_err(dbeta.cpu() / scale, gi.sum(dim=(0, 1, 2))) < 1e-4
+    assert rel_err(dgamma.cpu() / scale, (gi * yhat_in).sum(dim=(0, 1, 2))) < 1e-4
+
+
+@pytest.mark.parametrize("kind", ["dw", "pw"])
+def test_conv_fwd_fp16_rounding_edges(kind):
+    """The fp16 storage of the conv layers (Act<ww_f16>::round2 / st2 in the depthwise kernel, st4 in the pointwise one, both
+    through pack2) at the edges of its contract: RNE, subnormals kept, overflow to inf -- never 65504 or NaN.  BN-apply is the
+    identity (scale 1, shift 0) and the filter is diagonal (pointwise) or its centre tap only (depthwise), so y[p][c] =
+    a_p w_c: a product of two fp16 values, exact in fp32.  The stored fp16 must equal torch's ``fp32_result.to(float16)`` bit
+    for bit (signed zeros included) over all 64 x 64 products, among them ties (3 x 683 = 2049 -> 2048, 7 x 293 = 2051 ->
+    2052), subnormal results and ties (1.5 x 2^-24 -> 2^-23, 0.5 x 2^-24 -> 0), 152 x 431 = 65512 -> 65504 and
+    1365 x 48 = 65520, 255 x 257 -> inf."""
+    from wakeword_trainer_home_amd import _native as nat
+    from tests.test_hip_kernels import cu, _bn_tensors
+    q = 2.0 ** -24
+    g = torch.Generator().manual_seed(3)
+    a_vals = [3.0, 7.0, 152.0, 1365.0, 255.0, 2.0 ** -14, q, 3 * q, 1.0, 2.0 ** -10, 65504.0, 0.5, 1.5, 2.0 ** -7]
+    w_vals = [683.0, 293.0, 431.0, 48.0, 257.0, 2.0 ** -5, 0.5, -0.5, 1.0, -1.0, 2.0, 2.0 ** -12, -683.0, 1.0 + 2.0 ** -10,
+              0.75, 65504.0, -2.0 ** -12]
+    a = torch.tensor(a_vals + (torch.rand(64 - len(a_vals), generator=g) * 8).half().tolist(), dtype=torch.float64)
+    w = torch.tensor(w_vals + (torch.randn(64 - len(w_vals), generator=g) * 300).half().tolist(), dtype=torch.float64)
+    y_in = a.reshape(1, 8, 8, 1).expand(1, 8, 8, 64).contiguous()                 # NHWC: pixel p holds a_p in every channel
+    ss_in = torch.cat([torch.ones(64, dtype=torch.float64), torch.zeros(64, dtype=torch.float64)])
+    if kind == "dw":
+        wt = torch.zeros(64, 1, 3, 3, dtype=torch.float64)
+        wt[:, 0, 1, 1] = w
+    else:
+        wt = torch.diag(w).reshape(64, 64, 1, 1)
+    exact = a[:, None] * w[None, :]                                               # (pixel, channel)
+    assert torch.equal(exact.float().double(), exact) and torch.equal(a.half().double(), a) and torch.equal(w.half().double(), w)
+    want = exact.float().half()
+    gamma, beta, rm, rv = _bn_tensors(2)
+    ga, be, rm_g, rv_g = cu(gamma), cu(beta), cu(rm), cu(rv)          # (the BN struct holds raw pointers: keep them alive)
+    bn = nat.make_bn(ga, be, rm_g, rv_g)
+    fn = nat.dwconv3x3_fwd if kind == "dw" else nat.pwconv1x1_fwd
+    y, _, _ = fn(cu(y_in, torch.float16), cu(ss_in), cu(wt), bn, nat.layer_scratch(DEV))
+    got = y.cpu().reshape(64, 64)
+    bad = got.view(torch.int16) != want.view(torch.int16)
+    assert not bad.any(), [(exact[i, j].item(), got[i, j].item(), want[i, j].item()) for i, j in bad.nonzero()[:8].tolist()]
+    A, W = {v: i for i, v in enumerate(a_vals)}, {v: i for i, v in enumerate(w_vals)}
+    assert got[A[3.0], W[683.0]].item() == 2048.0 and got[A[7.0], W[293.0]].item() == 2052.0
+    assert got[A[3 * q], W[0.5]].item() == 2 * q and got[A[q], W[0.5]].item() == 0.0 and got[A[2.0 ** -14], W[2.0 ** -5]].item() == 2.0 ** -19
+    assert got[A[152.0], W[431.0]].item() == 65504.0 and got[A[1365.0], W[48.0]].item() == float("inf")
+    assert got[A[255.0], W[257.0]].item() == float("inf") and got[A[65504.0], W[-683.0]].item() == float("-inf")
+    assert not torch.isnan(got).any()

@@ -383,3 +383,230 @@ def test_async_autograd_step_skips_nonfinite_batch_on_device(tmp_path):
     changed2 = any(not torch.equal(snaps[2][k], after[k]) for k in after)
     assert changed01 and same12 and changed2
     assert abs(avg - (seen[0][1] + seen[1][1]) / 3) < 1e-6
+
+
+# ------------------------------------------------------------------------------------------ layers against the restated reference
+# oracle/gru.py:gru_restated rounds exactly what the device rounds to the matrix type (x, W_ih, each step's h_{t-1} and W_hh,
+# dGi / dGh, the operands of the dW and dX products) and nothing else, so only fp32 accumulation order, the fast gate functions of
+# the 16-bit modes (gate_sigmoid<true>, ~2e-7) and the rare 16-bit rounding that flips because the device's fp32 operand differs
+# from the float64 one in its last bits stay between the two.  Error measures: y, h_n and dh0 absolute (all O(1)); dx and the four
+# parameter gradients relative to each tensor's largest entry.  In the 16-bit modes a flip does not stay alone: it moves the next
+# step's operands by ~1e-5, which flips more of them, so the errors settle at the level where the reference itself moves when its
+# inputs are perturbed by 2e-7 (measured on the CPU: up to 2.4e-3 for bf16 gradients at B=7, T=13).  The forward stays well
+# inside the mode's own error (restated vs exact GRU: bf16 3e-3..5e-3, fp16 3e-4..6e-4 on y).  Measured on the MI355X, largest
+# over both workgroup shapes and every case of a mode (y|h_n, dh0, gradients): fp32 7.6e-7, 7.3e-7, 1.1e-6; bf16 2.7e-4,
+# 7.8e-4, 2.4e-3; fp16 3.9e-5, 1.1e-4, 1.9e-4.  Bounds: 2-3x those in bf16 and fp16, 7-9x in fp32 (the device sums in a fixed
+# order: the results repeat).
+_MT = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}
+_GRU_BOUND = {"fp32": (5e-6, 5e-6, 1e-5), "bf16": (8e-4, 2e-3, 5e-3), "fp16": (1e-4, 3e-4, 5e-4)}     # (y|h_n, dh0, gradients)
+_REF_CACHE = {}
+
+# Single-direction cases (ww_gru_fwd / ww_gru_bwd), with the host branch each one reaches:
+#   t1_b1       B = 1, T = 1, I = 9: one step, one batch row, the k_gemm projection (I % 64 != 0)
+#   b7_i64      B = 7 (< 8 rows), I = 64, B*T = 91 >= 35: the ww_gemm16_nt_bias projection (16-bit modes)
+#   b9_i64_kg   B = 9 (> 8 rows), I = 64, B*T = 27 < 35: the 16-bit copies do not fit the dGh region -> k_gemm
+#   b17_i256    B = 17 (> 16 rows), I = 256, B*T = 204 >= 192: ww_gemm16_nt_bias
+#   b19_i256_kg I = 256, B*T = 190 < 192: k_gemm
+#   x_ld67      x a column view with row stride 67 (ldx % 4 != 0): k_gemm although B*T = 54 would fit gemm16; vecA/vecB = 0 in dW_ih
+#   y_off1      y / dy column views at a 4-byte offset of rows of 132 floats: y_vec = dy_vec = 0 from the pointer alone
+#   dy_none     no dy, only dh_n
+#   split       B = 64, T = 80: B*T = 5120 >= 4096 -> the dW_hh / dW_ih products split K 64 ways (k_splitk_sum)
+# every case has an h0 and asks for dh0.
+_DIR_CASES = {
+    "t1_b1": dict(B=1, T=1, I=9, reverse=False),
+    "b7_i64": dict(B=7, T=13, I=64, reverse=True),
+    "b9_i64_kg": dict(B=9, T=3, I=64, reverse=False),
+    "b17_i256": dict(B=17, T=12, I=256, reverse=False),
+    "b19_i256_kg": dict(B=19, T=10, I=256, reverse=True),
+    "x_ld67": dict(B=9, T=6, I=64, reverse=True, ldx=67),
+    "y_off1": dict(B=17, T=5, I=64, reverse=False, yoff=1),
+    "dy_none": dict(B=8, T=7, I=40, reverse=True, no_dy=True),
+    "split": dict(B=64, T=80, I=64, reverse=False),
+}
+
+
+def _gru_inputs(B, T, I, seed, nd):
+    """fp32-representable float64 inputs: nn.GRU's initialisation, x ~ N(0,1), h0 ~ 0.3 N(0,1), dy / dh_n ~ N(0,1)."""
+    g = torch.Generator().manual_seed(seed)
+    H, k = 128, 128 ** -0.5
+    q = lambda t: t.float().double()
+    P = [[q((torch.rand(*s, generator=g, dtype=torch.float64) * 2 - 1) * k) for s in ((3 * H, I), (3 * H, H), (3 * H,), (3 * H,))]
+         for _ in range(nd)]
+    x = q(torch.randn(B, T, I, generator=g, dtype=torch.float64))
+    h0 = [q(0.3 * torch.randn(B, H, generator=g, dtype=torch.float64)) for _ in range(nd)]
+    dy = q(torch.randn(B, T, nd * H, generator=g, dtype=torch.float64))
+    dhn = [q(torch.randn(B, H, generator=g, dtype=torch.float64)) for _ in range(nd)]
+    return P, x, h0, dy, dhn
+
+
+def _check_restated(tag, mode, got, ref):
+    """got / ref: dicts of the same keys.  Prints the measured errors (-s) and checks them against the mode's bounds."""
+    b_fwd, b_dh0, b_rel = _GRU_BOUND[mode]
+    errs = {}
+    for k, r in ref.items():
+        a = got[k].detach().cpu().double()
+        errs[k] = (a - r).abs().max().item() if k.startswith(("y", "h_n", "dh0")) else _rel(a, r)
+    print(f"restated-gru {tag} {mode}: " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
+    for k, e in errs.items():
+        assert e <= (b_fwd if k.startswith(("y", "h_n")) else b_dh0 if k.startswith("dh0") else b_rel), (tag, mode, k, e)
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("case", list(_DIR_CASES))
+def test_gru_direction_matches_restated_reference(case, mode, gru_rows):
+    """ww_gru_fwd / ww_gru_bwd in each matrix mode against oracle/gru.py:gru_restated (bounds and the branch each case
+    reaches: see _GRU_BOUND / _DIR_CASES above): y, h_n, dx, dW_ih, dW_hh, db_ih, db_hh and dh0; nothing written outside y."""
+    from wakeword_trainer_home_amd import _native as nat
+    from oracle.gru import gru_restated
+    c = _DIR_CASES[case]
+    B, T, I, rev, H = c["B"], c["T"], c["I"], c["reverse"], 128
+    P, x, h0, dy, dhn = _gru_inputs(B, T, I, 1 + list(_DIR_CASES).index(case), 1)
+    P, h0, dhn, dy = P[0], h0[0], dhn[0], (None if c.get("no_dy") else dy)
+    key = ("dir", case, mode)
+    if key not in _REF_CACHE:
+        _REF_CACHE[key] = gru_restated(x, *P, h0=h0, dy=dy, dh_n=dhn, mtype=_MT[mode], reverse=rev)
+    ref = _REF_CACHE[key]
+    f = lambda t: t.float().to(DEV)
+    if c.get("ldx"):
+        xd = torch.zeros(B, T, c["ldx"], device=DEV)[:, :, :I]
+        xd.copy_(f(x))
+    else:
+        xd = f(x)
+    off = c.get("yoff", 0)
+    ld = H + 4 if off else H
+    ybuf = torch.full((B, T, ld), 7.0, device=DEV)
+    y = ybuf[:, :, off:off + H]
+    assert (y.data_ptr() % 16 != 0) == bool(off)
+    md = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[mode]
+    ws = nat.gru_workspace(B, T, I, H, DEV)
+    Pd = [f(p) for p in P]
+    h_n = nat.gru_fwd(xd, *Pd, y, ws, h0=f(h0), reverse=rev, mode=md)
+    if off:
+        assert torch.equal(ybuf[:, :, :off], torch.full_like(ybuf[:, :, :off], 7.0))
+        assert torch.equal(ybuf[:, :, off + H:], torch.full_like(ybuf[:, :, off + H:], 7.0))
+    dyd = None
+    if dy is not None:
+        dybuf = torch.full((B, T, ld), float("nan"), device=DEV)       # columns outside the view must never be read
+        dyd = dybuf[:, :, off:off + H]
+        dyd.copy_(f(dy))
+    dx = torch.zeros(B, T, I, device=DEV)
+    dw_ih, dw_hh, db_ih, db_hh, dh0 = nat.gru_bwd(xd, Pd[0], Pd[1], dyd, f(dhn), ws, reverse=rev, dx=dx, want_dh0=True, mode=md)
+    got = dict(y=y, h_n=h_n, dh0=dh0, dx=dx, dw_ih=dw_ih, dw_hh=dw_hh, db_ih=db_ih, db_hh=db_hh)
+    _check_restated(f"{case}/rows{gru_rows}", mode, got, {k: ref[k] for k in got})
+
+
+# Bidirectional cases (ww_gru_bidir_fwd / _bwd, both directions in one recurrent launch, dX as one ww_gemm_seg2 product):
+#   t1_b1     B = 1, T = 1, I = 9: k_gemm projections
+#   b9_i64    B = 9, B*T = 54: ww_gemm16_nt_bias, the second direction reusing the first one's 16-bit x (xh_shared)
+#   b7_i256   B = 7, B*T = 35 < 192: k_gemm
+#   y_off1    y / dy column views at a 4-byte offset (rows of 260 floats): y_vec = dy_vec = 0
+#   dy_none   no dy, only dh_n of both directions
+#   split     B = 64, T = 80: split-K dW products of both directions
+_BIDIR_CASES = {
+    "t1_b1": dict(B=1, T=1, I=9),
+    "b9_i64": dict(B=9, T=6, I=64),
+    "b7_i256": dict(B=7, T=5, I=256),
+    "y_off1": dict(B=17, T=4, I=40, yoff=1),
+    "dy_none": dict(B=16, T=5, I=64, no_dy=True),
+    "split": dict(B=64, T=80, I=64),
+}
+
+
+def _bidir_ref(case, mode):
+    from oracle.gru import gru_restated
+    c = _BIDIR_CASES[case]
+    B, T, I, H = c["B"], c["T"], c["I"], 128
+    P, x, h0, dy, dhn = _gru_inputs(B, T, I, 101 + list(_BIDIR_CASES).index(case), 2)
+    dy = None if c.get("no_dy") else dy
+    key = ("bidir", case, mode)
+    if key not in _REF_CACHE:
+        o = [gru_restated(x, *P[d], h0=h0[d], dy=None if dy is None else dy[:, :, d * H:(d + 1) * H], dh_n=dhn[d],
+                          mtype=_MT[mode], reverse=(d == 1)) for d in range(2)]
+        ref = {"y": torch.cat([o[0]["y"], o[1]["y"]], 2), "dx": o[0]["dx"] + o[1]["dx"]}
+        for d in range(2):
+            for k in ("h_n", "dh0", "dw_ih", "dw_hh", "db_ih", "db_hh"):
+                ref[f"{k}{d}"] = o[d][k]
+        _REF_CACHE[key] = ref
+    return c, (P, x, h0, dy, dhn), _REF_CACHE[key]
+
+
+def _bidir_run(c, inputs, mode, outs=None, defer=False):
+    from wakeword_trainer_home_amd import _native as nat
+    P, x, h0, dy, dhn = inputs
+    B, T, I, H = c["B"], c["T"], c["I"], 128
+    f = lambda t: t.float().to(DEV)
+    md = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[mode]
+    off = c.get("yoff", 0)
+    ld = 2 * H + 4 if off else 2 * H
+    ybuf = torch.full((B, T, ld), 7.0, device=DEV)
+    y = ybuf[:, :, off:off + 2 * H]
+    params = [[f(p) for p in P[d]] for d in range(2)]
+    ws = [nat.gru_workspace(B, T, I, H, DEV) for _ in range(2)]
+    xd = f(x)
+    h_n = nat.gru_bidir_fwd(xd, params, y, ws, mode=md, h0=[f(h0[0]), f(h0[1])])
+    if off:
+        assert torch.equal(ybuf[:, :, :off], torch.full_like(ybuf[:, :, :off], 7.0))
+        assert torch.equal(ybuf[:, :, off + 2 * H:], torch.full_like(ybuf[:, :, off + 2 * H:], 7.0))
+    dyd = None
+    if dy is not None:
+        dybuf = torch.full((B, T, ld), float("nan"), device=DEV)
+        dyd = dybuf[:, :, off:off + 2 * H]
+        dyd.copy_(f(dy))
+    dx = torch.zeros(B, T, I, device=DEV)
+    dh0 = [torch.empty(B, H, device=DEV) for _ in range(2)]
+    grads = nat.gru_bidir_bwd(xd, params, dyd, [f(dhn[0]), f(dhn[1])], ws, dx=dx, mode=md, outs=outs, defer=defer, dh0=dh0)
+    got = {"y": y, "dx": dx}
+    for d in range(2):
+        got[f"h_n{d}"], got[f"dh0{d}"] = h_n[d], dh0[d]
+        for k, g in zip(("dw_ih", "dw_hh", "db_ih", "db_hh"), grads[d]):
+            got[f"{k}{d}"] = g
+    return got
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("case", list(_BIDIR_CASES))
+def test_gru_bidirectional_matches_restated_reference(case, mode, gru_rows):
+    """ww_gru_bidir_fwd / _bwd in each matrix mode against two restated directions (bounds and the branch each case reaches:
+    see _GRU_BOUND / _BIDIR_CASES above): y (both halves), both h_n and dh0, the summed dx, all eight parameter gradients."""
+    c, inputs, ref = _bidir_ref(case, mode)
+    got = _bidir_run(c, inputs, mode)
+    _check_restated(f"bidir-{case}/rows{gru_rows}", mode, got, ref)
+
+
+@pytest.mark.parametrize("mode", ["fp32", "bf16", "fp16"])
+def test_gru_split_dw_deferred_equals_immediate(mode):
+    """B*T = 5120: the split-K weight-gradient products under ww_ctx_set_deferred_reduce keep dW_hh and dW_ih partials in the
+    two halves of the partial region and queue one 768-column bias item per direction (db_ih | db_hh adjacent in a flat
+    bucket, nn.GRU's parameter order): 6 queued items, one flush.  Deferred == immediate to round-off (the flush sums in
+    double, the immediate kernels in float: measured 2.9e-7 rel, bound 2e-6 as for the linear layers), and the deferred
+    gradients also meet the restated reference."""
+    from wakeword_trainer_home_amd import _native as nat
+    c, inputs, ref = _bidir_ref("split", mode)
+    now = _bidir_run(c, inputs, mode)
+    I, H = c["I"], 128
+    sizes = [3 * H * I, 3 * H * H, 3 * H, 3 * H]
+    bucket = torch.full((2 * sum(sizes),), float("nan"), device=DEV)
+    outs, o = [], 0
+    for d in range(2):
+        slots = []
+        for s, shape in zip(sizes, ((3 * H, I), (3 * H, H), (3 * H,), (3 * H,))):
+            slots.append(bucket[o:o + s].view(shape))
+            o += s
+        outs.append(tuple(slots))
+    lib, cx = nat.load(), nat.ctx(DEV)
+    assert lib.ww_deferred_reduce_pending(cx) == 0
+    later = _bidir_run(c, inputs, mode, outs=outs, defer=True)
+    assert lib.ww_deferred_reduce_pending(cx) == 6
+    nat.deferred_flush(DEV)
+    assert lib.ww_deferred_reduce_pending(cx) == 0
+    torch.cuda.synchronize()
+    assert not torch.isnan(bucket).any()
+    worst = 0.0
+    for d in range(2):
+        for k in ("dw_ih", "dw_hh", "db_ih", "db_hh"):
+            e = _rel(later[f"{k}{d}"].double(), now[f"{k}{d}"].double())
+            worst = max(worst, e)
+            assert e <= 2e-6, (k, d, e)
+    print(f"restated-gru deferred-vs-immediate {mode}: {worst:.2e}")
+    _check_restated("bidir-split-deferred", mode, {k: v for k, v in later.items() if k.startswith(("dw", "db"))},
+                    {k: v for k, v in ref.items() if k.startswith(("dw", "db"))})

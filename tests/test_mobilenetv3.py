@@ -340,3 +340,100 @@ def test_backward_that_raises_midway_leaves_no_stale_deferred_sums():
     assert nat.load().ww_deferred_reduce_pending(nat.ctx(DEV)) == 0
     for a, b, c in zip(got, clean2, ref):
         assert torch.equal(a, b)
+
+
+# ------------------------------------------------------------------------------------------ fp16 matrix mode
+# The pieces that take a matrix mode, in fp16 (operands rounded to fp16, fp32 accumulation), against float64 restatements of
+# that mode (oracle/rounding.py:mround); the squeeze-excitation and direct-stem kernels take no mode.  Bounds <= 10x the values
+# measured on the MI355X, which each test's docstring gives.
+def _r16(t):
+    from oracle.rounding import mround
+    return mround(t, torch.float16)
+
+
+@pytest.mark.parametrize("M,K,N,act", [(7680, 40, 240, 1), (1000, 16, 72, 2), (300, 9, 16, 1), (24320, 72, 24, 0)])
+def test_conv1x1_bn_act_fp16_mode(M, K, N, act):
+    """ww_conv1x1_bn_act_fwd in fp16 mode (statistics from the GEMM epilogue) against float64 BatchNorm of the product of
+    the fp16-rounded operands.  Measured: y 1.6e-7, a 1.9e-7, running statistics 7.6e-8 (relative to each tensor's largest
+    entry); bounds 1e-6, 1.5e-6, 5e-7."""
+    from wakeword_trainer_home_amd import _native as nat
+    g = torch.Generator().manual_seed(M + N + 1)
+    x = torch.randn(M, K, generator=g, dtype=torch.float64)
+    w = torch.randn(N, K, generator=g, dtype=torch.float64) * 0.3
+    gamma, beta = torch.rand(N, generator=g, dtype=torch.float64) + 0.5, torch.randn(N, generator=g, dtype=torch.float64) * 0.3
+    rm, rv = torch.randn(N, generator=g, dtype=torch.float64) * 0.1, torch.rand(N, generator=g, dtype=torch.float64) + 0.5
+    y_ref = _r16(x) @ _r16(w).T
+    rm_ref, rv_ref = rm.clone(), rv.clone()
+    a_ref = ACTS[act](Fn.batch_norm(y_ref, rm_ref, rv_ref, gamma, beta, training=True, momentum=0.01, eps=1e-3))
+    f = lambda t: t.float().to(DEV).contiguous()
+    xd, wd, gm, bt, rm1, rv1 = f(x), f(w), f(gamma), f(beta), f(rm), f(rv)
+    y, a, ss, mr = nat.conv1x1_bn_act_fwd(xd, wd, nat.make_bn(gm, bt, rm1, rv1, momentum=0.01, eps=1e-3, training=True), act,
+                                          mode=torch.float16)
+    e = dict(y=_rel(y.cpu().double(), y_ref), a=_rel(a.cpu().double(), a_ref),
+             rs=max(_rel(rm1.cpu().double(), rm_ref), _rel(rv1.cpu().double(), rv_ref)))
+    print(f"fp16 conv1x1 {M}x{K}x{N}: " + " ".join(f"{k}={v:.2e}" for k, v in e.items()))
+    assert e["y"] <= 1e-6 and e["a"] <= 1.5e-6 and e["rs"] <= 5e-7, e
+
+
+def test_stem_im2col_products_fp16_mode():
+    """The im2col stem's two products in fp16 mode (what _StemIm2col runs when the direct stem does not apply): patches (M, 9)
+    @ W^T (the shallow K = 9 stage) and dW = dY^T patches split over M, against the fp16-rounded operands in float64.
+    Measured: y 7.9e-8, dW 1.1e-7 relative; bounds 5e-7, 1e-6."""
+    from wakeword_trainer_home_amd import _native as nat
+    g = torch.Generator().manual_seed(8)
+    img = torch.randn(6, 1, 41, 151, generator=g)
+    cols = nat.im2col3x3s2(img[:, 0].contiguous().to(DEV))
+    w = torch.randn(16, 9, generator=g) * 0.3
+    cref = Fn.unfold(img, 3, padding=1, stride=2).transpose(1, 2).reshape(-1, 9).double()
+    assert torch.equal(cols.cpu().double(), cref)
+    y = nat.linear_mfma_fwd(cols, w.to(DEV), None, mode=torch.float16)
+    dy = torch.randn(cols.shape[0], 16, generator=g)
+    _, dw, _ = nat.linear_mfma_bwd(cols, w.to(DEV), None, dy.to(DEV), mode=torch.float16, need_dx=False, need_db=False)
+    ey = _rel(y.cpu().double(), _r16(cref) @ _r16(w.double()).T)
+    ew = _rel(dw.cpu().double(), _r16(dy.double()).T @ _r16(cref))
+    print(f"fp16 stem im2col: y={ey:.2e} dw={ew:.2e}")
+    assert ey <= 5e-7 and ew <= 1e-6, (ey, ew)
+
+
+def test_mobilenetv3_fp16_mode_step_matches_oracle():
+    """create_model('mobilenetv3', mode='fp16'): one training step at B = 16 against the float64 MobileNetV3Oracle, checked
+    like config 3's bf16 mode (tests/test_config_sizes.py).  Measured: logits 3.2e-4 of their scale, loss 3.1e-7, gradient
+    1 - cos 3.0e-4, running means 6.5e-4 of a standard deviation, eval logits 3.7e-6; bounds 3e-3, 3e-6, 1 - cos 3e-3, 6e-3,
+    3.5e-5."""
+    from wakeword_trainer_home_amd.models import create_model
+    from oracle.mobilenetv3 import MobileNetV3Oracle
+    from tests.golden_util import make_inputs
+    B = 16
+    torch.manual_seed(12)
+    model = create_model("mobilenetv3", dropout=0.3, dropout_seed=2, mode="fp16").to(DEV)
+    oracle = MobileNetV3Oracle(dropout=0.3, seed=2)
+    oracle.load_state_dict({k: v.cpu().double() if v.is_floating_point() else v.cpu() for k, v in model.state_dict().items()})
+    x, y = make_inputs(9, B)
+    model.train()
+    oracle.train()
+    out = model(x.to(DEV))
+    loss = Fn.cross_entropy(out, y.to(DEV))
+    loss.backward()
+    ref = oracle(x, step=0, training=True)
+    lo = Fn.cross_entropy(ref, y)
+    lo.backward()
+    derr = (out.detach().cpu().double() - ref.detach()).abs().max().item() / max(ref.abs().max().item(), 1.0)
+    lerr = abs(loss.item() - lo.item())
+    gd = torch.cat([p.grad.flatten().cpu().double() for p in model.parameters()])
+    go = torch.cat([p.grad.flatten() for p in oracle.parameters()])
+    cos = (gd @ go / (gd.norm() * go.norm())).item()
+    assert torch.isfinite(gd).all()
+    worst_rs = 0.0
+    ob = dict(oracle.named_buffers())
+    for n, b in model.named_buffers():        # running means in units of the channel's batch standard deviation (as config 3)
+        if not n.endswith("running_mean"):
+            continue
+        var_b = ((ob[n.replace("running_mean", "running_var")].double() - 0.99) / 0.01).clamp_min(1e-12)
+        worst_rs = max(worst_rs, ((b.cpu().double() - ob[n].double()).abs() / 0.01 / var_b.sqrt()).max().item())
+    model.eval()
+    oracle.eval()
+    with torch.no_grad():
+        ev_ref = oracle(x, training=False)
+        eerr = (model(x.to(DEV)).cpu().double() - ev_ref).abs().max().item() / max(ev_ref.abs().max().item(), 1.0)
+    print(f"fp16 mobilenetv3 B={B}: logits {derr:.2e} loss {lerr:.2e} cos {cos:.6f} running means {worst_rs:.2e} eval {eerr:.2e}")
+    assert derr <= 3e-3 and lerr <= 3e-6 and 1 - cos <= 3e-3 and worst_rs <= 6e-3 and eerr <= 3.5e-5, (derr, lerr, cos, worst_rs, eerr)

@@ -863,39 +863,47 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def gru_bidir_fwd(x, params, y, ws, mode=torch.float32):
+def gru_bidir_fwd(x, params, y, ws, mode=torch.float32, h0=None):
     """Both directions of a bidirectional layer, ONE recurrent launch: x (B,T,I); params = [(w_ih, w_hh, b_ih, b_hh)] x 2
-    (forward, reverse); y (B,T,2H) written; ws = two gru_workspace tensors.  -> [h_n forward, h_n reverse], each (B,H)."""
-    dev = _dev(*params[0], *params[1], ws[0], ws[1])
+    (forward, reverse); y (B,T,2H) written; ws = two gru_workspace tensors; h0 = [(B,H) | None] x 2 (None: zeros).
+    -> [h_n forward, h_n reverse], each (B,H)."""
+    h0 = h0 or (None, None)
+    dev = _dev(*params[0], *params[1], ws[0], ws[1], *h0)
     _dev_rows(x, y)
     B, T, I = x.shape
     H = params[0][1].shape[1]
     ldx, ldy = _bt_rows(x, "x"), _bt_rows(y, "y")
     if tuple(y.shape) != (B, T, 2 * H) or any(tuple(p[0].shape) != (3 * H, I) or tuple(p[1].shape) != (3 * H, H) for p in params):
         raise ValueError("GRU parameter / output shapes do not match (w_ih (3H,I), w_hh (3H,H), y (B,T,2H))")
+    if any(t is not None and (tuple(t.shape) != (B, H) or t.dtype != torch.float32) for t in h0):
+        raise ValueError("GRU h0 must be float32 (B,H) per direction")
     h_n = [torch.empty((B, H), dtype=torch.float32, device=dev) for _ in range(2)]
     keep = [[t.contiguous() for t in p] for p in params]
     dirs = (GruDir * 2)()
     for k in range(2):
         dirs[k].w_ih, dirs[k].w_hh, dirs[k].b_ih, dirs[k].b_hh = (t.data_ptr() for t in keep[k])
-        dirs[k].h_n, dirs[k].ws = h_n[k].data_ptr(), ws[k].data_ptr()
+        dirs[k].h_n, dirs[k].ws, dirs[k].h0 = h_n[k].data_ptr(), ws[k].data_ptr(), _ptr(h0[k])
     with _guard(dev):
         _check(load().ww_gru_bidir_fwd(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), B, T, I, H, _p(y), ldy,
                                        min(ws[0].numel(), ws[1].numel()) * 4, _stream(dev)), "ww_gru_bidir_fwd")
     return h_n
 
 
-def gru_bidir_bwd(x, params, dy, dh_n, ws, dx=None, mode=torch.float32, outs=None, defer=False):
+def gru_bidir_bwd(x, params, dy, dh_n, ws, dx=None, mode=torch.float32, outs=None, defer=False, dh0=None):
     """Backward of gru_bidir_fwd: dy (B,T,2H) or None, dh_n = [(B,H) | None] x 2; dx (B,T,I) written when given.
     -> [(dw_ih, dw_hh, db_ih, db_hh)] x 2.  outs: the same structure of tensors to write the gradients into (bucket slots);
-    defer: queue the sums of the weight-gradient / bias partials (valid after deferred_flush; ``ws`` is kept until then)."""
-    dev = _dev(params[0][0], params[1][0], ws[0], ws[1])
+    defer: queue the sums of the weight-gradient / bias partials (valid after deferred_flush; ``ws`` is kept until then);
+    dh0 = [(B,H) | None] x 2: where to write the gradient of each direction's h0."""
+    dh0 = dh0 or (None, None)
+    dev = _dev(params[0][0], params[1][0], ws[0], ws[1], *dh0)
     _dev_rows(x, dy, dx)
     B, T, I = x.shape
     H = params[0][1].shape[1]
     ldx = _bt_rows(x, "x")
     ldy = _bt_rows(dy, "dy") if dy is not None else 2 * H
     lddx = _bt_rows(dx, "dx") if dx is not None else I
+    if any(t is not None and (tuple(t.shape) != (B, H) or t.dtype != torch.float32) for t in dh0):
+        raise ValueError("GRU dh0 outputs must be float32 (B,H) per direction")
     keep = [[p[0].contiguous(), p[1].contiguous()] for p in params]
     if outs is None:
         outs = [(None, None, None, None)] * 2
@@ -904,7 +912,7 @@ def gru_bidir_bwd(x, params, dy, dh_n, ws, dx=None, mode=torch.float32, outs=Non
     dirs = (GruDir * 2)()
     for k in range(2):
         dirs[k].w_ih, dirs[k].w_hh = keep[k][0].data_ptr(), keep[k][1].data_ptr()
-        dirs[k].ws, dirs[k].dh_n = ws[k].data_ptr(), _ptr(dh_n[k])
+        dirs[k].ws, dirs[k].dh_n, dirs[k].dh0 = ws[k].data_ptr(), _ptr(dh_n[k]), _ptr(dh0[k])
         dirs[k].dw_ih, dirs[k].dw_hh, dirs[k].db_ih, dirs[k].db_hh = (g.data_ptr() for g in grads[k])
     with _guard(dev), (_deferring(dev, ws[0], ws[1]) if defer else contextlib.nullcontext()):
         _check(load().ww_gru_bidir_bwd(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), _p(dy), ldy, B, T, I, H,
