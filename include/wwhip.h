@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define WW_ABI_VERSION 14
+#define WW_ABI_VERSION 15
 
 #define WW_OK 0
 #define WW_E_INVALID (-1)     /* bad argument (shape, null pointer, unsupported size) */
@@ -444,6 +444,37 @@ int ww_gru_bidir_fwd(ww_ctx *ctx, int mode, const float *x, long ldx, const ww_g
                      float *y, long ldy, size_t ws_bytes, ww_stream_t stream);
 int ww_gru_bidir_bwd(ww_ctx *ctx, int mode, const float *x, long ldx, const ww_gru_dir *dir /* [2] */, const float *dy, long ldy,
                      int B, int T, int I, int H, size_t ws_bytes, float *dx, long lddx, ww_stream_t stream);
+
+/* ------------------------------------------------------------------ LSTM layer (the reference's LSTMWakeword)
+ * torch.nn.LSTM's cell and parameter layout (gate order i|f|g|o; w_ih (4H,I), w_hh (4H,H), b_ih, b_hh (4H)) -- what the
+ * reference's LSTMWakeword wraps (src/models/architectures.py: nn.LSTM(input, 128, num_layers, batch_first=True,
+ * bidirectional)).  Same conventions as the GRU entry points above: x (B,T,I) with row stride ldx, y (B,T,H) with row stride
+ * ldy, reverse != 0 runs t = T-1..0, H = 128 only, ws (ww_lstm_workspace_bytes, 256-byte aligned) kept from ww_lstm_fwd to the
+ * ww_lstm_bwd of the same (layer, direction).  h0 / c0 nullable (zeros); h_n / c_n (B,H) outputs, nullable.  ww_lstm_bwd: dy,
+ * dh_n and dc_n are nullable (at least one given); dx is written, or added to when accumulate_dx != 0; dh0 / dc0 nullable. */
+size_t ww_lstm_workspace_bytes(int B, int T, int I, int H);
+int ww_lstm_fwd(ww_ctx *ctx, int mode, const float *x, long ldx, const float *w_ih, const float *w_hh, const float *b_ih,
+                const float *b_hh, const float *h0, const float *c0, int B, int T, int I, int H, int reverse, float *y, long ldy,
+                float *h_n, float *c_n, void *ws, size_t ws_bytes, ww_stream_t stream);
+int ww_lstm_bwd(ww_ctx *ctx, int mode, const float *x, long ldx, const float *w_ih, const float *w_hh, const float *dy, long ldy,
+                const float *dh_n, const float *dc_n, int B, int T, int I, int H, int reverse, void *ws, size_t ws_bytes, float *dx,
+                long lddx, int accumulate_dx, float *dw_ih, float *dw_hh, float *db_ih, float *db_hh, float *dh0, float *dc0,
+                ww_stream_t stream);
+/* Both directions of a bidirectional layer with ONE recurrent launch per pass (as ww_gru_bidir_*): y / dy (B,T,2H) with row
+ * stride ldy >= 2H, direction d owns columns [d*H, (d+1)*H); one workspace per direction; dx = sum over both directions.   */
+typedef struct ww_lstm_dir {
+    const float *w_ih, *w_hh, *b_ih, *b_hh;      /* nn.LSTM layout: (4H,I), (4H,H), (4H), (4H); gate order i|f|g|o */
+    const float *h0, *c0;                        /* (B,H) initial states or NULL (zeros) */
+    float *h_n, *c_n;                            /* (B,H) final states out, or NULL */
+    void *ws;
+    const float *dh_n, *dc_n;                    /* backward: gradients of h_n / c_n, or NULL */
+    float *dw_ih, *dw_hh, *db_ih, *db_hh;        /* backward: parameter gradients (written) */
+    float *dh0, *dc0;                            /* backward: gradients of h0 / c0 out, or NULL */
+} ww_lstm_dir;
+int ww_lstm_bidir_fwd(ww_ctx *ctx, int mode, const float *x, long ldx, const ww_lstm_dir *dir /* [2] */, int B, int T, int I, int H,
+                      float *y, long ldy, size_t ws_bytes, ww_stream_t stream);
+int ww_lstm_bidir_bwd(ww_ctx *ctx, int mode, const float *x, long ldx, const ww_lstm_dir *dir /* [2] */, const float *dy, long ldy,
+                      int B, int T, int I, int H, size_t ws_bytes, float *dx, long lddx, ww_stream_t stream);
 
 /* Deferred partial sums.  The parameter-gradient kernels of the generic layers (ww_linear_mfma_bwd's split-K dW product,
  * ww_dwconv_nhwc_bwd, ww_stem3x3s2_bwd_dw) end in "sum the per-block partials into the gradient" -- a 4-5 us launch each that

@@ -14,7 +14,7 @@ import torch
 from wakeword_trainer_home_amd import _native as nat
 from wakeword_trainer_home_amd.config import get_preset
 from wakeword_trainer_home_amd.data import make_synthetic_batch
-from wakeword_trainer_home_amd.models import create_model
+from wakeword_trainer_home_amd.models import create_model, LSTMWakeword
 from wakeword_trainer_home_amd.training import Trainer
 
 dev = "cuda:0"
@@ -22,7 +22,7 @@ CONFIGS = (("crnn", 512, "bf16"), ("crnn", 4096, "bf16"), ("gru", 4096, "fp32"),
            ("mobilenetv3", 2048, "bf16"))
 GRAPH = "--graph" in sys.argv                 # replay the step as a captured HIP graph (Trainer hip_graph mode)
 argv = [a for a in sys.argv[1:] if a != "--graph"]
-if argv:                                      # e.g.  bench_models.py crnn 4096 fp16 [--graph]
+if argv:                                      # e.g.  bench_models.py crnn 4096 fp16 [--graph]  |  lstm 512 fp32
     CONFIGS = ((argv[0], int(argv[1]), argv[2]),)
 for arch, B, act in CONFIGS:
     cfg = get_preset("cnn_small_logmel40")
@@ -30,13 +30,14 @@ for arch, B, act in CONFIGS:
     cfg.training.hip_graph, cfg.training.hip_graph_auto = GRAPH, False       # the eager line is eager for every model
     torch.manual_seed(0)
     kw = {"act_dtype": act} if arch == "crnn" else {"mode": act}
-    model = create_model(arch, dropout=0.3, **kw)
+    # (the factory does not offer "lstm" yet: the reference's LSTMWakeword is built directly)
+    model = LSTMWakeword(dropout=0.3, **kw) if arch == "lstm" else create_model(arch, dropout=0.3, **kw)
     with contextlib.redirect_stdout(sys.stderr):
         tr = Trainer(model, [], [], cfg, checkpoint_dir=Path(tempfile.mkdtemp()), device=dev)
     tr.model.train()
     pool = [make_synthetic_batch(B, 24000, seed=i, device=dev) for i in range(2)]
     classes = ["logmel_specaug", "conv_stem_fwd", "dwconv3x3_fwd", "pwconv1x1_fwd", "pwconv1x1_bwd", "dwconv3x3_bwd", "conv_stem_bwd",
-               "finalize", "gru", "linear_mfma", "nhwc_layers"]
+               "finalize", "gru", "linear_mfma", "nhwc_layers", "lstm"]
 
     def step(i):
         (tr._step_autograd_async if tr._async_autograd else tr._step_generic)(*pool[i % 2], i)

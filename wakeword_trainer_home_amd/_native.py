@@ -15,7 +15,7 @@ _LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libwwhip.so"
 _lib = None
 _ctx = {}
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 BWD_ALL, BWD_LATE, BWD_EARLY = 0, 1, 2
 ACT_F32, ACT_BF16, ACT_F16 = 0, 1, 2
 LOSS_CE, LOSS_FOCAL = 0, 1
@@ -66,6 +66,12 @@ class GruDir(C.Structure):
     """ww_gru_dir: one direction of a bidirectional GRU layer (include/wwhip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "h0", "h_n", "ws", "dh_n", "dw_ih", "dw_hh", "db_ih",
                                           "db_hh", "dh0")]
+
+
+class LstmDir(C.Structure):
+    """ww_lstm_dir: one direction of a bidirectional LSTM layer (include/wwhip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "h0", "c0", "h_n", "c_n", "ws", "dh_n", "dc_n", "dw_ih",
+                                          "dw_hh", "db_ih", "db_hh", "dh0", "dc0")]
 
 
 class StepCtl(C.Structure):
@@ -154,6 +160,13 @@ _SIGS = {
     "ww_gru_bidir_bwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _vp, C.c_long, _i, _i, _i, _i, _sz, _vp, C.c_long, _vp]),
     "ww_gru_bwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _vp, _vp, C.c_long, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, C.c_long, _i,
                              _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ww_lstm_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ww_lstm_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_long, _vp, _vp, _vp,
+                              _sz, _vp]),
+    "ww_lstm_bwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _vp, _vp, C.c_long, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, C.c_long,
+                              _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ww_lstm_bidir_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _i, _i, _i, _i, _vp, C.c_long, _sz, _vp]),
+    "ww_lstm_bidir_bwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _vp, C.c_long, _i, _i, _i, _i, _sz, _vp, C.c_long, _vp]),
     "ww_clip_optim_step": (C.c_int, [_vp, C.POINTER(OptimCfg), _vp, _vp, _vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ww_layer_scratch_bytes": (_sz, []),
     "ww_conv_stem_fwd": (C.c_int, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, C.POINTER(BN), _vp, _vp, _vp, _vp]),
@@ -917,6 +930,119 @@ def gru_bidir_bwd(x, params, dy, dh_n, ws, dx=None, mode=torch.float32, outs=Non
     with _guard(dev), (_deferring(dev, ws[0], ws[1]) if defer else contextlib.nullcontext()):
         _check(load().ww_gru_bidir_bwd(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), _p(dy), ldy, B, T, I, H,
                                        min(ws[0].numel(), ws[1].numel()) * 4, _p(dx), lddx, _stream(dev)), "ww_gru_bidir_bwd")
+    return grads
+
+
+# ---- LSTM layers (include/wwhip.h ww_lstm_*): the gru_* wrappers' shapes, plus the cell states c0 / c_n and their gradients
+def lstm_workspace(B, T, I, H, dev):
+    n = load().ww_lstm_workspace_bytes(B, T, I, H)
+    if n == 0:
+        raise NativeError(f"LSTM shape B={B} T={T} I={I} H={H} is not implemented (hidden size 128 only)")
+    return torch.empty(n // 4, dtype=torch.float32, device=dev)
+
+
+def _state_ok(ts, B, H, what):
+    if any(t is not None and (tuple(t.shape) != (B, H) or t.dtype != torch.float32 or not t.is_contiguous()) for t in ts):
+        raise ValueError(f"LSTM {what} must be contiguous float32 (B,H)")
+
+
+def lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, y, ws, h0=None, c0=None, reverse=False, mode=torch.float32):
+    """One LSTM direction: x (B,T,I) -> writes y (B,T,H) (may be a column slice of a (B,T,2H) buffer); returns (h_n, c_n)."""
+    dev = _dev(w_ih, w_hh, b_ih, b_hh, ws, h0, c0)
+    _dev_rows(x, y)
+    B, T, I = x.shape
+    H = w_hh.shape[1]
+    ldx, ldy = _bt_rows(x, "x"), _bt_rows(y, "y")
+    if tuple(w_ih.shape) != (4 * H, I) or tuple(w_hh.shape) != (4 * H, H) or tuple(y.shape) != (B, T, H):
+        raise ValueError("LSTM parameter / output shapes do not match (w_ih (4H,I), w_hh (4H,H), y (B,T,H))")
+    _state_ok((h0, c0), B, H, "h0 / c0")
+    h_n = torch.empty((B, H), dtype=torch.float32, device=dev)
+    c_n = torch.empty((B, H), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_lstm_fwd(ctx(dev), act_code(mode), _p(x), ldx, _p(w_ih.contiguous()), _p(w_hh.contiguous()), _p(b_ih),
+                                  _p(b_hh), _p(h0), _p(c0), B, T, I, H, int(reverse), _p(y), ldy, _p(h_n), _p(c_n), _p(ws),
+                                  ws.numel() * 4, _stream(dev)), "ww_lstm_fwd")
+    return h_n, c_n
+
+
+def lstm_bwd(x, w_ih, w_hh, dy, dh_n, dc_n, ws, reverse=False, dx=None, accumulate_dx=False, want_dh0=False, mode=torch.float32):
+    """Backward of the lstm_fwd that filled ``ws``: -> (dw_ih, dw_hh, db_ih, db_hh, dh0 | None, dc0 | None); dx written or
+    accumulated in place."""
+    dev = _dev(w_ih, w_hh, dh_n, dc_n, ws)
+    _dev_rows(x, dy, dx)
+    B, T, I = x.shape
+    H = w_hh.shape[1]
+    ldx = _bt_rows(x, "x")
+    ldy = _bt_rows(dy, "dy") if dy is not None else H
+    lddx = _bt_rows(dx, "dx") if dx is not None else I
+    _state_ok((dh_n, dc_n), B, H, "dh_n / dc_n")
+    dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
+    db_ih = torch.empty(4 * H, dtype=torch.float32, device=dev)
+    db_hh = torch.empty(4 * H, dtype=torch.float32, device=dev)
+    dh0 = torch.empty((B, H), dtype=torch.float32, device=dev) if want_dh0 else None
+    dc0 = torch.empty((B, H), dtype=torch.float32, device=dev) if want_dh0 else None
+    with _guard(dev):
+        _check(load().ww_lstm_bwd(ctx(dev), act_code(mode), _p(x), ldx, _p(w_ih.contiguous()), _p(w_hh.contiguous()), _p(dy), ldy,
+                                  _p(dh_n), _p(dc_n), B, T, I, H, int(reverse), _p(ws), ws.numel() * 4, _p(dx), lddx,
+                                  int(accumulate_dx), _p(dw_ih), _p(dw_hh), _p(db_ih), _p(db_hh), _p(dh0), _p(dc0), _stream(dev)),
+               "ww_lstm_bwd")
+    return dw_ih, dw_hh, db_ih, db_hh, dh0, dc0
+
+
+def lstm_bidir_fwd(x, params, y, ws, mode=torch.float32, h0=None, c0=None):
+    """Both directions of a bidirectional layer, ONE recurrent launch: x (B,T,I); params = [(w_ih, w_hh, b_ih, b_hh)] x 2
+    (forward, reverse); y (B,T,2H) written; ws = two lstm_workspace tensors; h0 / c0 = [(B,H) | None] x 2 (None: zeros).
+    -> ([h_n forward, h_n reverse], [c_n forward, c_n reverse]), each (B,H)."""
+    h0, c0 = h0 or (None, None), c0 or (None, None)
+    dev = _dev(*params[0], *params[1], ws[0], ws[1], *h0, *c0)
+    _dev_rows(x, y)
+    B, T, I = x.shape
+    H = params[0][1].shape[1]
+    ldx, ldy = _bt_rows(x, "x"), _bt_rows(y, "y")
+    if tuple(y.shape) != (B, T, 2 * H) or any(tuple(p[0].shape) != (4 * H, I) or tuple(p[1].shape) != (4 * H, H) for p in params):
+        raise ValueError("LSTM parameter / output shapes do not match (w_ih (4H,I), w_hh (4H,H), y (B,T,2H))")
+    _state_ok(tuple(h0) + tuple(c0), B, H, "h0 / c0")
+    h_n = [torch.empty((B, H), dtype=torch.float32, device=dev) for _ in range(2)]
+    c_n = [torch.empty((B, H), dtype=torch.float32, device=dev) for _ in range(2)]
+    keep = [[t.contiguous() for t in p] for p in params]
+    dirs = (LstmDir * 2)()
+    for k in range(2):
+        dirs[k].w_ih, dirs[k].w_hh, dirs[k].b_ih, dirs[k].b_hh = (t.data_ptr() for t in keep[k])
+        dirs[k].h_n, dirs[k].c_n, dirs[k].ws = h_n[k].data_ptr(), c_n[k].data_ptr(), ws[k].data_ptr()
+        dirs[k].h0, dirs[k].c0 = _ptr(h0[k]), _ptr(c0[k])
+    with _guard(dev):
+        _check(load().ww_lstm_bidir_fwd(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), B, T, I, H, _p(y), ldy,
+                                        min(ws[0].numel(), ws[1].numel()) * 4, _stream(dev)), "ww_lstm_bidir_fwd")
+    return h_n, c_n
+
+
+def lstm_bidir_bwd(x, params, dy, dh_n, ws, dx=None, mode=torch.float32, outs=None, defer=False, dh0=None, dc_n=None, dc0=None):
+    """Backward of lstm_bidir_fwd: dy (B,T,2H) or None, dh_n / dc_n = [(B,H) | None] x 2; dx (B,T,I) written when given.
+    -> [(dw_ih, dw_hh, db_ih, db_hh)] x 2.  outs / defer as in gru_bidir_bwd; dh0 / dc0 = [(B,H) | None] x 2: where to write
+    the gradients of each direction's initial states."""
+    dh0, dc0, dc_n = dh0 or (None, None), dc0 or (None, None), dc_n or (None, None)
+    dev = _dev(params[0][0], params[1][0], ws[0], ws[1], *dh0, *dc0)
+    _dev_rows(x, dy, dx)
+    B, T, I = x.shape
+    H = params[0][1].shape[1]
+    ldx = _bt_rows(x, "x")
+    ldy = _bt_rows(dy, "dy") if dy is not None else 2 * H
+    lddx = _bt_rows(dx, "dx") if dx is not None else I
+    _state_ok(tuple(dh0) + tuple(dc0) + tuple(dh_n) + tuple(dc_n), B, H, "state gradients")
+    keep = [[p[0].contiguous(), p[1].contiguous()] for p in params]
+    if outs is None:
+        outs = [(None, None, None, None)] * 2
+    grads = [(_out(o[0], tuple(p[0].shape), dev), _out(o[1], tuple(p[1].shape), dev), _out(o[2], (4 * H,), dev),
+              _out(o[3], (4 * H,), dev)) for p, o in zip(params, outs)]
+    dirs = (LstmDir * 2)()
+    for k in range(2):
+        dirs[k].w_ih, dirs[k].w_hh = keep[k][0].data_ptr(), keep[k][1].data_ptr()
+        dirs[k].ws, dirs[k].dh_n, dirs[k].dc_n = ws[k].data_ptr(), _ptr(dh_n[k]), _ptr(dc_n[k])
+        dirs[k].dh0, dirs[k].dc0 = _ptr(dh0[k]), _ptr(dc0[k])
+        dirs[k].dw_ih, dirs[k].dw_hh, dirs[k].db_ih, dirs[k].db_hh = (g.data_ptr() for g in grads[k])
+    with _guard(dev), (_deferring(dev, ws[0], ws[1]) if defer else contextlib.nullcontext()):
+        _check(load().ww_lstm_bidir_bwd(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), _p(dy), ldy, B, T, I, H,
+                                        min(ws[0].numel(), ws[1].numel()) * 4, _p(dx), lddx, _stream(dev)), "ww_lstm_bidir_bwd")
     return grads
 
 

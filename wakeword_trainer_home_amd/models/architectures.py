@@ -404,3 +404,7 @@ def create_model(architecture: str, num_classes: int = 2, pretrained: bool = Fal
         raise ValueError(f"Architecture '{architecture}' exists in the reference but is outside this build's "
                          f"HIP hot path (DESIGN.md 'Out of scope'). Supported: {_SUPPORTED}")
     raise ValueError(f"Unknown architecture: {architecture}. Supported: {_SUPPORTED}")
+
+
+# the reference's LSTMWakeword, importable from its own module path (the factory entry is not switched on yet)
+from .lstm import LSTMWakeword  # noqa: E402,F401
