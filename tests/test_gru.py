@@ -130,6 +130,27 @@ def test_gru_argument_checks():
         nat.gru_fwd(x, w_ih, w_hh, b, b, torch.zeros(4, 5, 128, device=DEV), ws[:100])       # workspace too small
     with pytest.raises(ValueError):
         nat.gru_fwd(x.transpose(0, 1), w_ih, w_hh, b, b, torch.zeros(5, 4, 128, device=DEV), ws)
+    y = torch.zeros(4, 5, 128, device=DEV)
+    with pytest.raises(ValueError):                                        # h0 of the wrong batch size
+        nat.gru_fwd(x, w_ih, w_hh, b, b, y, ws, h0=torch.zeros(3, 128, device=DEV))
+    with pytest.raises(ValueError):                                        # h0 not float32
+        nat.gru_fwd(x, w_ih, w_hh, b, b, y, ws, h0=torch.zeros(4, 128, device=DEV, dtype=torch.bfloat16))
+    with pytest.raises(ValueError):                                        # dh_n of the wrong shape
+        nat.gru_bwd(x, w_ih, w_hh, y, torch.zeros(4, 64, device=DEV), ws)
+    # the C entry points themselves (WW_E_INVALID = -1), before any launch
+    import ctypes as C
+    lib, cx, p = nat.load(), nat.ctx(DEV), lambda t: C.c_void_p(t.data_ptr())
+    B, T, I, H = 4, 5, 8, 128
+    assert lib.ww_gru_bwd(cx, 0, p(x), I, p(w_ih), p(w_hh), p(y), H - 4, None, B, T, I, H, 0, p(ws), ws.numel() * 4, None, I, 0,
+                          p(w_ih), p(w_hh), p(b), p(b), None, None) == -1           # dy row stride smaller than H
+    gw, gb = torch.zeros(384, 8, device=DEV), torch.zeros(384, device=DEV)
+    dirs = (nat.GruDir * 2)()
+    for k in range(2):
+        dirs[k].w_ih, dirs[k].w_hh, dirs[k].ws = w_ih.data_ptr(), w_hh.data_ptr(), ws.data_ptr()       # one workspace for both
+        dirs[k].dw_ih, dirs[k].dw_hh, dirs[k].db_ih, dirs[k].db_hh = gw.data_ptr(), w_hh.data_ptr(), gb.data_ptr(), b.data_ptr()
+    y2 = torch.zeros(B, T, 2 * H, device=DEV)
+    assert lib.ww_gru_bidir_bwd(cx, 0, p(x), I, C.byref(dirs), p(y2), 2 * H, B, T, I, H, ws.numel() * 4, None, I, None) == -1
+    torch.cuda.synchronize()
 
 
 # ------------------------------------------------------------------------------------------ model level

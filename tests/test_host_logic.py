@@ -313,6 +313,21 @@ def test_library_exports_the_whole_c_abi():
         assert _native.prob_threshold(float(np.float32(p))) == prob_threshold(p)
 
 
+@pytest.mark.parametrize("B,T,I,gru,lstm", [(1, 1, 1, 25174528, 33564160), (7, 5, 8, 25366016, 33755648),
+                                             (33, 13, 100, 27597312, 35991040), (512, 76, 64, 244514816, 252968960),
+                                             (512, 76, 256, 269680640, 286523392), (512, 151, 40, 460783616, 469237760),
+                                             (4096, 151, 40, 3510108160, 3519021056), (4096, 76, 256, 1805123584, 1822425088)])
+def test_recurrent_workspace_sizes_are_pinned(B, T, I, gru, lstm):
+    """The GRU and LSTM share one workspace layout (csrc/ww_rnn.h) parameterised by the cell; these byte counts are the ones
+    each cell's own layout returned before they were merged (H = 128; any other hidden size is refused with 0)."""
+    from wakeword_trainer_home_amd import _native
+    lib = _native.load()
+    assert lib.ww_gru_workspace_bytes(B, T, I, 128) == gru
+    assert lib.ww_lstm_workspace_bytes(B, T, I, 128) == lstm
+    assert lib.ww_gru_workspace_bytes(B, T, I, 64) == 0
+    assert lib.ww_lstm_workspace_bytes(B, T, I, 64) == 0
+
+
 @pytest.mark.parametrize("kw", [dict(), dict(n_mels=64), dict(n_mels=128), dict(n_mels=13), dict(n_mels=3), dict(n_mels=80, f_min=20.0),
                                 dict(n_mels=23, f_max=3800.0), dict(n_mels=1), dict(n_mels=40, sample_rate=8000),
                                 dict(n_mels=40, n_fft=512), dict(n_mels=64, n_fft=256), dict(n_mels=40, n_fft=2048)])

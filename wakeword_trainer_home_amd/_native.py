@@ -828,78 +828,150 @@ def add_f32(a, b):
     return y
 
 
-def gru_workspace(B, T, I, H, dev):
-    n = load().ww_gru_workspace_bytes(B, T, I, H)
+# ---- recurrent layers (include/wwhip.h ww_gru_* / ww_lstm_*): one implementation, parameterised by the cell's gate count,
+# C entry points, per-direction struct and recurrent states (GRU: h; LSTM: h, c).  x (B,T,I) and y / dy (B,T,nd*H) may be
+# row-strided views; the states and their gradients are contiguous float32 (B,H) or None (zeros / not wanted).
+class _Cell:
+    def __init__(self, name, gates, prefix, dir_struct, states):
+        self.name, self.gates, self.prefix, self.dir_struct, self.states = name, gates, prefix, dir_struct, states
+
+
+_GRU = _Cell("GRU", 3, "ww_gru", GruDir, ("h",))
+_LSTM = _Cell("LSTM", 4, "ww_lstm", LstmDir, ("h", "c"))
+
+
+def _rnn_workspace(cell, B, T, I, H, dev):
+    n = getattr(load(), cell.prefix + "_workspace_bytes")(B, T, I, H)
     if n == 0:
-        raise NativeError(f"GRU shape B={B} T={T} I={I} H={H} is not implemented (hidden size 128 only)")
+        raise NativeError(f"{cell.name} shape B={B} T={T} I={I} H={H} is not implemented (hidden size 128 only)")
     return torch.empty(n // 4, dtype=torch.float32, device=dev)
 
 
-def gru_fwd(x, w_ih, w_hh, b_ih, b_hh, y, ws, h0=None, reverse=False, mode=torch.float32):
-    """One GRU direction: x (B,T,I) -> writes y (B,T,H) (may be a column slice of a (B,T,2H) buffer); returns h_n (B,H)."""
-    dev = _dev(w_ih, w_hh, b_ih, b_hh, ws, h0)
-    _dev_rows(x, y)
+def _state_ok(cell, ts, B, H, what):
+    if any(t is not None and (tuple(t.shape) != (B, H) or t.dtype != torch.float32 or not t.is_contiguous()) for t in ts):
+        raise ValueError(f"{cell.name} {what} must be contiguous float32 (B,H)")
+
+
+def _rnn_shapes(cell, x, params, y, nd):
     B, T, I = x.shape
-    H = w_hh.shape[1]
+    H = params[0][1].shape[1]
+    G = cell.gates * H
+    if tuple(y.shape) != (B, T, nd * H) or any(tuple(p[0].shape) != (G, I) or tuple(p[1].shape) != (G, H) for p in params):
+        raise ValueError(f"{cell.name} parameter / output shapes do not match (w_ih ({cell.gates}H,I), w_hh ({cell.gates}H,H), "
+                         f"y (B,T,{nd if nd > 1 else ''}H))")
+    return B, T, I, H
+
+
+def _rnn_fwd(cell, x, w_ih, w_hh, b_ih, b_hh, y, ws, s0, reverse, mode):
+    """One direction; s0: the initial states.  -> the final states."""
+    dev = _dev(w_ih, w_hh, b_ih, b_hh, ws, *s0)
+    _dev_rows(x, y)
     ldx, ldy = _bt_rows(x, "x"), _bt_rows(y, "y")
-    if tuple(w_ih.shape) != (3 * H, I) or tuple(w_hh.shape) != (3 * H, H) or tuple(y.shape) != (B, T, H):
-        raise ValueError("GRU parameter / output shapes do not match (w_ih (3H,I), w_hh (3H,H), y (B,T,H))")
-    h_n = torch.empty((B, H), dtype=torch.float32, device=dev)
+    B, T, I, H = _rnn_shapes(cell, x, [(w_ih, w_hh)], y, 1)
+    _state_ok(cell, s0, B, H, " / ".join(s + "0" for s in cell.states))
+    s_n = [torch.empty((B, H), dtype=torch.float32, device=dev) for _ in cell.states]
+    fn = cell.prefix + "_fwd"
     with _guard(dev):
-        _check(load().ww_gru_fwd(ctx(dev), act_code(mode), _p(x), ldx, _p(w_ih.contiguous()), _p(w_hh.contiguous()), _p(b_ih), _p(b_hh), _p(h0),
-                                 B, T, I, H, int(reverse), _p(y), ldy, _p(h_n), _p(ws), ws.numel() * 4, _stream(dev)),
-               "ww_gru_fwd")
-    return h_n
+        _check(getattr(load(), fn)(ctx(dev), act_code(mode), _p(x), ldx, _p(w_ih.contiguous()), _p(w_hh.contiguous()), _p(b_ih),
+                                   _p(b_hh), *map(_p, s0), B, T, I, H, int(reverse), _p(y), ldy, *map(_p, s_n), _p(ws),
+                                   ws.numel() * 4, _stream(dev)), fn)
+    return s_n
 
 
-def gru_bwd(x, w_ih, w_hh, dy, dh_n, ws, reverse=False, dx=None, accumulate_dx=False, want_dh0=False, mode=torch.float32):
-    """Backward of the gru_fwd that filled ``ws``: -> (dw_ih, dw_hh, db_ih, db_hh, dh0 | None); dx written/accumulated in place."""
-    dev = _dev(w_ih, w_hh, dh_n, ws)
+def _rnn_bwd(cell, x, w_ih, w_hh, dy, ds_n, ws, reverse, dx, accumulate_dx, want_ds0, mode):
+    """Backward of the one-direction _rnn_fwd that filled ``ws``: -> (dw_ih, dw_hh, db_ih, db_hh, *ds0)."""
+    dev = _dev(w_ih, w_hh, ws, *ds_n)
     _dev_rows(x, dy, dx)
     B, T, I = x.shape
     H = w_hh.shape[1]
     ldx = _bt_rows(x, "x")
     ldy = _bt_rows(dy, "dy") if dy is not None else H
     lddx = _bt_rows(dx, "dx") if dx is not None else I
+    _state_ok(cell, ds_n, B, H, " / ".join(f"d{s}_n" for s in cell.states))
     dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-    db_ih = torch.empty(3 * H, dtype=torch.float32, device=dev)
-    db_hh = torch.empty(3 * H, dtype=torch.float32, device=dev)
-    dh0 = torch.empty((B, H), dtype=torch.float32, device=dev) if want_dh0 else None
+    db_ih, db_hh = (torch.empty(cell.gates * H, dtype=torch.float32, device=dev) for _ in range(2))
+    ds0 = [torch.empty((B, H), dtype=torch.float32, device=dev) if want_ds0 else None for _ in cell.states]
+    fn = cell.prefix + "_bwd"
     with _guard(dev):
-        _check(load().ww_gru_bwd(ctx(dev), act_code(mode), _p(x), ldx, _p(w_ih.contiguous()), _p(w_hh.contiguous()), _p(dy), ldy, _p(dh_n),
-                                 B, T, I, H, int(reverse), _p(ws), ws.numel() * 4, _p(dx), lddx, int(accumulate_dx),
-                                 _p(dw_ih), _p(dw_hh), _p(db_ih), _p(db_hh), _p(dh0), _stream(dev)), "ww_gru_bwd")
-    return dw_ih, dw_hh, db_ih, db_hh, dh0
+        _check(getattr(load(), fn)(ctx(dev), act_code(mode), _p(x), ldx, _p(w_ih.contiguous()), _p(w_hh.contiguous()), _p(dy), ldy,
+                                   *map(_p, ds_n), B, T, I, H, int(reverse), _p(ws), ws.numel() * 4, _p(dx), lddx,
+                                   int(accumulate_dx), _p(dw_ih), _p(dw_hh), _p(db_ih), _p(db_hh), *map(_p, ds0), _stream(dev)), fn)
+    return (dw_ih, dw_hh, db_ih, db_hh, *ds0)
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+def _rnn_bidir_fwd(cell, x, params, y, ws, s0, mode):
+    """Both directions, ONE recurrent launch; s0[j] = [(B,H) | None] x 2 for state j.  -> s_n[j] = [forward, reverse]."""
+    dev = _dev(*params[0], *params[1], ws[0], ws[1], *(t for s in s0 for t in s))
+    _dev_rows(x, y)
+    ldx, ldy = _bt_rows(x, "x"), _bt_rows(y, "y")
+    B, T, I, H = _rnn_shapes(cell, x, params, y, 2)
+    _state_ok(cell, [t for s in s0 for t in s], B, H, " / ".join(s + "0" for s in cell.states))
+    s_n = [[torch.empty((B, H), dtype=torch.float32, device=dev) for _ in range(2)] for _ in cell.states]
+    keep = [[t.contiguous() for t in p] for p in params]
+    dirs = (cell.dir_struct * 2)()
+    for k in range(2):
+        dirs[k].w_ih, dirs[k].w_hh, dirs[k].b_ih, dirs[k].b_hh = (t.data_ptr() for t in keep[k])
+        dirs[k].ws = ws[k].data_ptr()
+        for j, s in enumerate(cell.states):
+            setattr(dirs[k], s + "0", _p(s0[j][k]))
+            setattr(dirs[k], s + "_n", s_n[j][k].data_ptr())
+    fn = cell.prefix + "_bidir_fwd"
+    with _guard(dev):
+        _check(getattr(load(), fn)(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), B, T, I, H, _p(y), ldy,
+                                   min(ws[0].numel(), ws[1].numel()) * 4, _stream(dev)), fn)
+    return s_n
+
+
+def _rnn_bidir_bwd(cell, x, params, dy, ds_n, ws, dx, mode, outs, defer, ds0):
+    """Backward of _rnn_bidir_fwd; ds_n[j] / ds0[j] = [(B,H) | None] x 2 for state j.  -> [(dw_ih, dw_hh, db_ih, db_hh)] x 2."""
+    dev = _dev(params[0][0], params[1][0], ws[0], ws[1], *(t for s in ds0 for t in s))
+    _dev_rows(x, dy, dx)
+    B, T, I = x.shape
+    H = params[0][1].shape[1]
+    ldx = _bt_rows(x, "x")
+    ldy = _bt_rows(dy, "dy") if dy is not None else 2 * H
+    lddx = _bt_rows(dx, "dx") if dx is not None else I
+    _state_ok(cell, [t for s in ds0 + ds_n for t in s], B, H, "state gradients")
+    keep = [[p[0].contiguous(), p[1].contiguous()] for p in params]
+    if outs is None:
+        outs = [(None, None, None, None)] * 2
+    G = cell.gates * H
+    grads = [(_out(o[0], tuple(p[0].shape), dev), _out(o[1], tuple(p[1].shape), dev), _out(o[2], (G,), dev), _out(o[3], (G,), dev))
+             for p, o in zip(params, outs)]
+    dirs = (cell.dir_struct * 2)()
+    for k in range(2):
+        dirs[k].w_ih, dirs[k].w_hh = keep[k][0].data_ptr(), keep[k][1].data_ptr()
+        dirs[k].ws = ws[k].data_ptr()
+        for j, s in enumerate(cell.states):
+            setattr(dirs[k], f"d{s}_n", _p(ds_n[j][k]))
+            setattr(dirs[k], f"d{s}0", _p(ds0[j][k]))
+        dirs[k].dw_ih, dirs[k].dw_hh, dirs[k].db_ih, dirs[k].db_hh = (g.data_ptr() for g in grads[k])
+    fn = cell.prefix + "_bidir_bwd"
+    with _guard(dev), (_deferring(dev, ws[0], ws[1]) if defer else contextlib.nullcontext()):
+        _check(getattr(load(), fn)(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), _p(dy), ldy, B, T, I, H,
+                                   min(ws[0].numel(), ws[1].numel()) * 4, _p(dx), lddx, _stream(dev)), fn)
+    return grads
+
+
+def gru_workspace(B, T, I, H, dev):
+    return _rnn_workspace(_GRU, B, T, I, H, dev)
+
+
+def gru_fwd(x, w_ih, w_hh, b_ih, b_hh, y, ws, h0=None, reverse=False, mode=torch.float32):
+    """One GRU direction: x (B,T,I) -> writes y (B,T,H) (may be a column slice of a (B,T,2H) buffer); returns h_n (B,H)."""
+    return _rnn_fwd(_GRU, x, w_ih, w_hh, b_ih, b_hh, y, ws, (h0,), reverse, mode)[0]
+
+
+def gru_bwd(x, w_ih, w_hh, dy, dh_n, ws, reverse=False, dx=None, accumulate_dx=False, want_dh0=False, mode=torch.float32):
+    """Backward of the gru_fwd that filled ``ws``: -> (dw_ih, dw_hh, db_ih, db_hh, dh0 | None); dx written/accumulated in place."""
+    return _rnn_bwd(_GRU, x, w_ih, w_hh, dy, (dh_n,), ws, reverse, dx, accumulate_dx, want_dh0, mode)
 
 
 def gru_bidir_fwd(x, params, y, ws, mode=torch.float32, h0=None):
     """Both directions of a bidirectional layer, ONE recurrent launch: x (B,T,I); params = [(w_ih, w_hh, b_ih, b_hh)] x 2
     (forward, reverse); y (B,T,2H) written; ws = two gru_workspace tensors; h0 = [(B,H) | None] x 2 (None: zeros).
     -> [h_n forward, h_n reverse], each (B,H)."""
-    h0 = h0 or (None, None)
-    dev = _dev(*params[0], *params[1], ws[0], ws[1], *h0)
-    _dev_rows(x, y)
-    B, T, I = x.shape
-    H = params[0][1].shape[1]
-    ldx, ldy = _bt_rows(x, "x"), _bt_rows(y, "y")
-    if tuple(y.shape) != (B, T, 2 * H) or any(tuple(p[0].shape) != (3 * H, I) or tuple(p[1].shape) != (3 * H, H) for p in params):
-        raise ValueError("GRU parameter / output shapes do not match (w_ih (3H,I), w_hh (3H,H), y (B,T,2H))")
-    if any(t is not None and (tuple(t.shape) != (B, H) or t.dtype != torch.float32) for t in h0):
-        raise ValueError("GRU h0 must be float32 (B,H) per direction")
-    h_n = [torch.empty((B, H), dtype=torch.float32, device=dev) for _ in range(2)]
-    keep = [[t.contiguous() for t in p] for p in params]
-    dirs = (GruDir * 2)()
-    for k in range(2):
-        dirs[k].w_ih, dirs[k].w_hh, dirs[k].b_ih, dirs[k].b_hh = (t.data_ptr() for t in keep[k])
-        dirs[k].h_n, dirs[k].ws, dirs[k].h0 = h_n[k].data_ptr(), ws[k].data_ptr(), _ptr(h0[k])
-    with _guard(dev):
-        _check(load().ww_gru_bidir_fwd(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), B, T, I, H, _p(y), ldy,
-                                       min(ws[0].numel(), ws[1].numel()) * 4, _stream(dev)), "ww_gru_bidir_fwd")
-    return h_n
+    return _rnn_bidir_fwd(_GRU, x, params, y, ws, [h0 or (None, None)], mode)[0]
 
 
 def gru_bidir_bwd(x, params, dy, dh_n, ws, dx=None, mode=torch.float32, outs=None, defer=False, dh0=None):
@@ -907,143 +979,37 @@ def gru_bidir_bwd(x, params, dy, dh_n, ws, dx=None, mode=torch.float32, outs=Non
     -> [(dw_ih, dw_hh, db_ih, db_hh)] x 2.  outs: the same structure of tensors to write the gradients into (bucket slots);
     defer: queue the sums of the weight-gradient / bias partials (valid after deferred_flush; ``ws`` is kept until then);
     dh0 = [(B,H) | None] x 2: where to write the gradient of each direction's h0."""
-    dh0 = dh0 or (None, None)
-    dev = _dev(params[0][0], params[1][0], ws[0], ws[1], *dh0)
-    _dev_rows(x, dy, dx)
-    B, T, I = x.shape
-    H = params[0][1].shape[1]
-    ldx = _bt_rows(x, "x")
-    ldy = _bt_rows(dy, "dy") if dy is not None else 2 * H
-    lddx = _bt_rows(dx, "dx") if dx is not None else I
-    if any(t is not None and (tuple(t.shape) != (B, H) or t.dtype != torch.float32) for t in dh0):
-        raise ValueError("GRU dh0 outputs must be float32 (B,H) per direction")
-    keep = [[p[0].contiguous(), p[1].contiguous()] for p in params]
-    if outs is None:
-        outs = [(None, None, None, None)] * 2
-    grads = [(_out(o[0], tuple(p[0].shape), dev), _out(o[1], tuple(p[1].shape), dev), _out(o[2], (3 * H,), dev),
-              _out(o[3], (3 * H,), dev)) for p, o in zip(params, outs)]
-    dirs = (GruDir * 2)()
-    for k in range(2):
-        dirs[k].w_ih, dirs[k].w_hh = keep[k][0].data_ptr(), keep[k][1].data_ptr()
-        dirs[k].ws, dirs[k].dh_n, dirs[k].dh0 = ws[k].data_ptr(), _ptr(dh_n[k]), _ptr(dh0[k])
-        dirs[k].dw_ih, dirs[k].dw_hh, dirs[k].db_ih, dirs[k].db_hh = (g.data_ptr() for g in grads[k])
-    with _guard(dev), (_deferring(dev, ws[0], ws[1]) if defer else contextlib.nullcontext()):
-        _check(load().ww_gru_bidir_bwd(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), _p(dy), ldy, B, T, I, H,
-                                       min(ws[0].numel(), ws[1].numel()) * 4, _p(dx), lddx, _stream(dev)), "ww_gru_bidir_bwd")
-    return grads
+    return _rnn_bidir_bwd(_GRU, x, params, dy, [dh_n], ws, dx, mode, outs, defer, [dh0 or (None, None)])
 
 
-# ---- LSTM layers (include/wwhip.h ww_lstm_*): the gru_* wrappers' shapes, plus the cell states c0 / c_n and their gradients
 def lstm_workspace(B, T, I, H, dev):
-    n = load().ww_lstm_workspace_bytes(B, T, I, H)
-    if n == 0:
-        raise NativeError(f"LSTM shape B={B} T={T} I={I} H={H} is not implemented (hidden size 128 only)")
-    return torch.empty(n // 4, dtype=torch.float32, device=dev)
-
-
-def _state_ok(ts, B, H, what):
-    if any(t is not None and (tuple(t.shape) != (B, H) or t.dtype != torch.float32 or not t.is_contiguous()) for t in ts):
-        raise ValueError(f"LSTM {what} must be contiguous float32 (B,H)")
+    return _rnn_workspace(_LSTM, B, T, I, H, dev)
 
 
 def lstm_fwd(x, w_ih, w_hh, b_ih, b_hh, y, ws, h0=None, c0=None, reverse=False, mode=torch.float32):
     """One LSTM direction: x (B,T,I) -> writes y (B,T,H) (may be a column slice of a (B,T,2H) buffer); returns (h_n, c_n)."""
-    dev = _dev(w_ih, w_hh, b_ih, b_hh, ws, h0, c0)
-    _dev_rows(x, y)
-    B, T, I = x.shape
-    H = w_hh.shape[1]
-    ldx, ldy = _bt_rows(x, "x"), _bt_rows(y, "y")
-    if tuple(w_ih.shape) != (4 * H, I) or tuple(w_hh.shape) != (4 * H, H) or tuple(y.shape) != (B, T, H):
-        raise ValueError("LSTM parameter / output shapes do not match (w_ih (4H,I), w_hh (4H,H), y (B,T,H))")
-    _state_ok((h0, c0), B, H, "h0 / c0")
-    h_n = torch.empty((B, H), dtype=torch.float32, device=dev)
-    c_n = torch.empty((B, H), dtype=torch.float32, device=dev)
-    with _guard(dev):
-        _check(load().ww_lstm_fwd(ctx(dev), act_code(mode), _p(x), ldx, _p(w_ih.contiguous()), _p(w_hh.contiguous()), _p(b_ih),
-                                  _p(b_hh), _p(h0), _p(c0), B, T, I, H, int(reverse), _p(y), ldy, _p(h_n), _p(c_n), _p(ws),
-                                  ws.numel() * 4, _stream(dev)), "ww_lstm_fwd")
-    return h_n, c_n
+    return tuple(_rnn_fwd(_LSTM, x, w_ih, w_hh, b_ih, b_hh, y, ws, (h0, c0), reverse, mode))
 
 
 def lstm_bwd(x, w_ih, w_hh, dy, dh_n, dc_n, ws, reverse=False, dx=None, accumulate_dx=False, want_dh0=False, mode=torch.float32):
     """Backward of the lstm_fwd that filled ``ws``: -> (dw_ih, dw_hh, db_ih, db_hh, dh0 | None, dc0 | None); dx written or
     accumulated in place."""
-    dev = _dev(w_ih, w_hh, dh_n, dc_n, ws)
-    _dev_rows(x, dy, dx)
-    B, T, I = x.shape
-    H = w_hh.shape[1]
-    ldx = _bt_rows(x, "x")
-    ldy = _bt_rows(dy, "dy") if dy is not None else H
-    lddx = _bt_rows(dx, "dx") if dx is not None else I
-    _state_ok((dh_n, dc_n), B, H, "dh_n / dc_n")
-    dw_ih, dw_hh = torch.empty_like(w_ih), torch.empty_like(w_hh)
-    db_ih = torch.empty(4 * H, dtype=torch.float32, device=dev)
-    db_hh = torch.empty(4 * H, dtype=torch.float32, device=dev)
-    dh0 = torch.empty((B, H), dtype=torch.float32, device=dev) if want_dh0 else None
-    dc0 = torch.empty((B, H), dtype=torch.float32, device=dev) if want_dh0 else None
-    with _guard(dev):
-        _check(load().ww_lstm_bwd(ctx(dev), act_code(mode), _p(x), ldx, _p(w_ih.contiguous()), _p(w_hh.contiguous()), _p(dy), ldy,
-                                  _p(dh_n), _p(dc_n), B, T, I, H, int(reverse), _p(ws), ws.numel() * 4, _p(dx), lddx,
-                                  int(accumulate_dx), _p(dw_ih), _p(dw_hh), _p(db_ih), _p(db_hh), _p(dh0), _p(dc0), _stream(dev)),
-               "ww_lstm_bwd")
-    return dw_ih, dw_hh, db_ih, db_hh, dh0, dc0
+    return _rnn_bwd(_LSTM, x, w_ih, w_hh, dy, (dh_n, dc_n), ws, reverse, dx, accumulate_dx, want_dh0, mode)
 
 
 def lstm_bidir_fwd(x, params, y, ws, mode=torch.float32, h0=None, c0=None):
     """Both directions of a bidirectional layer, ONE recurrent launch: x (B,T,I); params = [(w_ih, w_hh, b_ih, b_hh)] x 2
     (forward, reverse); y (B,T,2H) written; ws = two lstm_workspace tensors; h0 / c0 = [(B,H) | None] x 2 (None: zeros).
     -> ([h_n forward, h_n reverse], [c_n forward, c_n reverse]), each (B,H)."""
-    h0, c0 = h0 or (None, None), c0 or (None, None)
-    dev = _dev(*params[0], *params[1], ws[0], ws[1], *h0, *c0)
-    _dev_rows(x, y)
-    B, T, I = x.shape
-    H = params[0][1].shape[1]
-    ldx, ldy = _bt_rows(x, "x"), _bt_rows(y, "y")
-    if tuple(y.shape) != (B, T, 2 * H) or any(tuple(p[0].shape) != (4 * H, I) or tuple(p[1].shape) != (4 * H, H) for p in params):
-        raise ValueError("LSTM parameter / output shapes do not match (w_ih (4H,I), w_hh (4H,H), y (B,T,2H))")
-    _state_ok(tuple(h0) + tuple(c0), B, H, "h0 / c0")
-    h_n = [torch.empty((B, H), dtype=torch.float32, device=dev) for _ in range(2)]
-    c_n = [torch.empty((B, H), dtype=torch.float32, device=dev) for _ in range(2)]
-    keep = [[t.contiguous() for t in p] for p in params]
-    dirs = (LstmDir * 2)()
-    for k in range(2):
-        dirs[k].w_ih, dirs[k].w_hh, dirs[k].b_ih, dirs[k].b_hh = (t.data_ptr() for t in keep[k])
-        dirs[k].h_n, dirs[k].c_n, dirs[k].ws = h_n[k].data_ptr(), c_n[k].data_ptr(), ws[k].data_ptr()
-        dirs[k].h0, dirs[k].c0 = _ptr(h0[k]), _ptr(c0[k])
-    with _guard(dev):
-        _check(load().ww_lstm_bidir_fwd(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), B, T, I, H, _p(y), ldy,
-                                        min(ws[0].numel(), ws[1].numel()) * 4, _stream(dev)), "ww_lstm_bidir_fwd")
-    return h_n, c_n
+    return tuple(_rnn_bidir_fwd(_LSTM, x, params, y, ws, [h0 or (None, None), c0 or (None, None)], mode))
 
 
 def lstm_bidir_bwd(x, params, dy, dh_n, ws, dx=None, mode=torch.float32, outs=None, defer=False, dh0=None, dc_n=None, dc0=None):
     """Backward of lstm_bidir_fwd: dy (B,T,2H) or None, dh_n / dc_n = [(B,H) | None] x 2; dx (B,T,I) written when given.
     -> [(dw_ih, dw_hh, db_ih, db_hh)] x 2.  outs / defer as in gru_bidir_bwd; dh0 / dc0 = [(B,H) | None] x 2: where to write
     the gradients of each direction's initial states."""
-    dh0, dc0, dc_n = dh0 or (None, None), dc0 or (None, None), dc_n or (None, None)
-    dev = _dev(params[0][0], params[1][0], ws[0], ws[1], *dh0, *dc0)
-    _dev_rows(x, dy, dx)
-    B, T, I = x.shape
-    H = params[0][1].shape[1]
-    ldx = _bt_rows(x, "x")
-    ldy = _bt_rows(dy, "dy") if dy is not None else 2 * H
-    lddx = _bt_rows(dx, "dx") if dx is not None else I
-    _state_ok(tuple(dh0) + tuple(dc0) + tuple(dh_n) + tuple(dc_n), B, H, "state gradients")
-    keep = [[p[0].contiguous(), p[1].contiguous()] for p in params]
-    if outs is None:
-        outs = [(None, None, None, None)] * 2
-    grads = [(_out(o[0], tuple(p[0].shape), dev), _out(o[1], tuple(p[1].shape), dev), _out(o[2], (4 * H,), dev),
-              _out(o[3], (4 * H,), dev)) for p, o in zip(params, outs)]
-    dirs = (LstmDir * 2)()
-    for k in range(2):
-        dirs[k].w_ih, dirs[k].w_hh = keep[k][0].data_ptr(), keep[k][1].data_ptr()
-        dirs[k].ws, dirs[k].dh_n, dirs[k].dc_n = ws[k].data_ptr(), _ptr(dh_n[k]), _ptr(dc_n[k])
-        dirs[k].dh0, dirs[k].dc0 = _ptr(dh0[k]), _ptr(dc0[k])
-        dirs[k].dw_ih, dirs[k].dw_hh, dirs[k].db_ih, dirs[k].db_hh = (g.data_ptr() for g in grads[k])
-    with _guard(dev), (_deferring(dev, ws[0], ws[1]) if defer else contextlib.nullcontext()):
-        _check(load().ww_lstm_bidir_bwd(ctx(dev), act_code(mode), _p(x), ldx, C.byref(dirs), _p(dy), ldy, B, T, I, H,
-                                        min(ws[0].numel(), ws[1].numel()) * 4, _p(dx), lddx, _stream(dev)), "ww_lstm_bidir_bwd")
-    return grads
+    return _rnn_bidir_bwd(_LSTM, x, params, dy, [dh_n, dc_n or (None, None)], ws, dx, mode, outs, defer,
+                          [dh0 or (None, None), dc0 or (None, None)])
 
 
 def step_ctl_new(dev, step=0, lr=0.0, parity=0):
