@@ -170,3 +170,14 @@ def test_trainer_bf16_tracks_reference_trace(golden_dir, tmp_path):
     d = np.abs(np.array(losses) - tr["step_loss"])
     assert d.max() < 5e-4, d
     print(f"bf16 storage: max |loss - ref| = {d.max():.2e}")
+
+
+@pytest.mark.parametrize("p", [0.0, 0.3])
+@pytest.mark.parametrize("B,Fd,T", [(4, 40, 151), (6, 13, 50), (5, 8, 12)])
+def test_cnn_small_bf16_per_tensor_matches_restatement(nat, B, Fd, T, p):
+    """cnn_small in bf16 storage against the restated conv stack (oracle/conv_stack.py) with the device's ReLU decisions:
+    logits, all 29 gradients and 18 running statistics, each tensor on its own (tests/test_cnn_front.py:check_cnn_small).
+    (40, 151) and (13, 50) take the WIDE_IMG / pooled-gradient variant of k_pw_bwd_bf16 (HW >= 64; at 1520 and 175 pixels
+    per image tiles straddle two images); (8, 12) has 4 x 6 maps, smaller than one 64-pixel tile."""
+    from tests.test_cnn_front import check_cnn_small
+    check_cnn_small(nat, "bf16", B, Fd, T, p, seed=B + Fd)

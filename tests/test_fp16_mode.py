@@ -284,3 +284,13 @@ def test_conv_fwd_fp16_rounding_edges(kind):
     assert got[A[152.0], W[431.0]].item() == 65504.0 and got[A[1365.0], W[48.0]].item() == float("inf")
     assert got[A[255.0], W[257.0]].item() == float("inf") and got[A[65504.0], W[-683.0]].item() == float("-inf")
     assert not torch.isnan(got).any()
+
+
+@pytest.mark.parametrize("p", [0.0, 0.3])
+@pytest.mark.parametrize("B,Fd,T", [(4, 40, 151), (6, 13, 50), (5, 8, 12)])
+def test_cnn_small_fp16_per_tensor_matches_restatement(B, Fd, T, p):
+    """tests/test_bf16_mode.py:test_cnn_small_bf16_per_tensor_matches_restatement in fp16 storage, at GradScaler's 65536 loss
+    scale."""
+    from wakeword_trainer_home_amd import _native as nat
+    from tests.test_cnn_front import check_cnn_small
+    check_cnn_small(nat, "fp16", B, Fd, T, p, seed=B + Fd)

@@ -464,28 +464,37 @@ def _native_model_run(nat, sd, x, dlogits, dropout_p, seed, step, training=True)
     return logits.cpu(), dict(zip(names, params)), dict(zip(names, grads))
 
 
-def _device_relu_masks(nat, model, x):
-    """ReLU decisions the device takes for this model/input: run the conv stack layer by layer through the
-    C-ABI and evaluate z = fma(y, scale, shift) > 0 exactly as the kernels do (fp32, single rounding)."""
+def _device_conv_chain(nat, model, x, act=torch.float32, momentum=0.1, eps=1e-5, training=True):
+    """The conv stack run layer by layer through the C-ABI (conv_stem_fwd / dwconv3x3_fwd / pwconv1x1_fwd) with ``act``
+    storage, starting from copies of the model's running statistics, and the ReLU decisions the device takes on it: z =
+    fma(y, scale, shift) > 0 evaluated exactly as the kernels do (fp32, single rounding).  -> dict of per-layer lists: mask
+    (NCHW bool, CPU), y (NHWC device tensors), ss, mr, running_mean, running_var (device tensors, updated by the chain)."""
     convs = [model.stem.conv] + [c for blk in model.blocks for c in (blk.dw, blk.pw)]
     bns = [model.stem.bn] + [c for blk in model.blocks for c in (blk.dw_bn, blk.pw_bn)]
     scratch = nat.layer_scratch(DEV)
-    keep, masks = [], []
+    out = {k: [] for k in ("mask", "y", "ss", "mr", "running_mean", "running_var", "keep")}
     y_prev = ss_prev = None
     for l, (conv, bn) in enumerate(zip(convs, bns)):
-        t = [cu(bn.weight.detach()), cu(bn.bias.detach()), torch.zeros(64, device=DEV), torch.ones(64, device=DEV)]
-        keep.append(t)
-        h = nat.make_bn(*t)
+        t = [cu(bn.weight.detach()), cu(bn.bias.detach()), cu(bn.running_mean), cu(bn.running_var)]
+        out["keep"].append(t)                            # (the BN struct holds raw pointers: keep them alive)
+        h = nat.make_bn(*t, momentum=momentum, eps=eps, training=training)
         if l == 0:
-            y, ss, _ = nat.conv_stem_fwd(cu(x), cu(conv.weight.detach()), h, scratch)
+            y, ss, mr = nat.conv_stem_fwd(cu(x), cu(conv.weight.detach()), h, scratch, act=act)
         else:
             fn = nat.dwconv3x3_fwd if l % 2 == 1 else nat.pwconv1x1_fwd
-            y, ss, _ = fn(y_prev, ss_prev, cu(conv.weight.detach()), h, scratch)
+            y, ss, mr = fn(y_prev, ss_prev, cu(conv.weight.detach()), h, scratch)
         yc, sc = y.cpu().double(), ss.cpu().double()
-        z32 = (yc * sc[:64] + sc[64:]).float()          # product+sum exact in float64 -> one rounding == fmaf
-        masks.append((z32 > 0).permute(0, 3, 1, 2).contiguous())
+        z32 = (yc * sc[:64] + sc[64:]).float()          # product exact in float64, sum rounded once: the sign of fmaf
+        for k, v in zip(("mask", "y", "ss", "mr", "running_mean", "running_var"),
+                        ((z32 > 0).permute(0, 3, 1, 2).contiguous(), y, ss, mr, t[2], t[3])):
+            out[k].append(v)
         y_prev, ss_prev = y, ss
-    return masks
+    return out
+
+
+def _device_relu_masks(nat, model, x, act=torch.float32):
+    """ReLU decisions the device takes for this model/input (NCHW bool per layer); see _device_conv_chain."""
+    return _device_conv_chain(nat, model, x, act=act)["mask"]
 
 
 def _oracle_with_masks(model, x, masks, keep_mask, p):

@@ -101,3 +101,131 @@ def test_head_oracle_matrix_type():
     ref = r(torch.nn.functional.hardswish(r(x) @ r(l0.weight).t() + l0.bias)) @ r(l3.weight).t() + l3.bias
     assert (o(x, training=False, mtype=torch.float16) - ref).abs().max().item() <= 1e-12
     assert not torch.equal(o(x, training=False, mtype=torch.float16), o(x, training=False))
+
+
+# ---------------------------------------------------------------------------------------------------------- the conv stack
+def _conv_model(seed, p=0.0, mom=0.1, eps=1e-5):
+    """CNNSmallOracle with random BatchNorm affine parameters and running statistics (at the default init the stem's and the
+    pointwise BNs' dgamma are structurally ~0) and the given momentum / eps on every BatchNorm."""
+    from oracle.cnn_small import CNNSmallOracle
+    torch.manual_seed(seed)
+    model = CNNSmallOracle(dropout=p, dropout_seed=11).double()
+    with torch.no_grad():
+        for m in model.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.normal_(0, 0.2)
+                m.running_mean.normal_(0, 0.1)
+                m.running_var.uniform_(0.5, 1.5)
+                m.momentum, m.eps = mom, eps
+    return model
+
+
+def _capture(model):
+    """forward hooks: every conv output y_l and every BatchNorm output z_l (its .grad is dL/dz_l after a backward)."""
+    convs = [model.stem.conv] + [c for blk in model.blocks for c in (blk.dw, blk.pw)]
+    bns = [model.stem.bn] + [c for blk in model.blocks for c in (blk.dw_bn, blk.pw_bn)]
+    ys, zs = [], []
+
+    def keep_z(m, i, o):
+        o.retain_grad()
+        zs.append(o)
+
+    for c in convs:
+        c.register_forward_hook(lambda m, i, o: ys.append(o.detach()))
+    for b in bns:
+        b.register_forward_hook(keep_z)
+    return ys, zs
+
+
+@pytest.mark.parametrize("head,B,Fd,T,p", [("freq", 3, 13, 17, 0.0), ("freq", 4, 2, 9, 0.0), ("gap", 3, 11, 14, 0.0),
+                                           ("gap", 5, 7, 9, 0.4)])
+def test_unrounded_conv_stack_restatement_is_autograd(head, B, Fd, T, p):
+    """Without rounding and masks, oracle/conv_stack.py IS autograd of CNNSmallOracle (GAP head, dropout included) and of
+    CRNNOracle.front + mean over frequency: y_l, z_l's gradient, running statistics, the head's output and every gradient to
+    ~1e-12, at a non-default momentum and eps."""
+    from oracle.cnn_small import dropout_keep_mask
+    from oracle.conv_stack import conv_stack_restated, cnn_params, grad_names, NL
+    mom, eps = 0.25, 1e-3
+    model = _conv_model(B * 10 + Fd, p=p, mom=mom, eps=eps)
+    params = cnn_params(model)
+    model.dropout_step = 3
+    g = torch.Generator().manual_seed(Fd * T)
+    x = torch.randn(B, 1, Fd, T, generator=g, dtype=torch.float64) * 2 - 4
+    ys, zs = _capture(model)
+    model.train()
+    if head == "freq":
+        from oracle.crnn import CRNNOracle
+        crnn = CRNNOracle(dropout=0.0)
+        crnn.front = f = model                       # CRNNOracle.forward's front-end, up to the GRU
+        h = torch.relu(f.stem.bn(f.stem.conv(x)))
+        for blk in f.blocks:
+            h = blk(h)
+        ref = h.mean(dim=2).transpose(1, 2)
+        dout = torch.randn(ref.shape, generator=g, dtype=torch.float64)
+        keep = None
+    else:
+        ref = model(x)
+        dout = torch.randn(ref.shape, generator=g, dtype=torch.float64)
+        keep = dropout_keep_mask(B, 64, p, 11, 3) if p > 0 else None
+        assert keep is None or not keep.all()
+    (ref * dout).sum().backward()
+    o = conv_stack_restated(params, x, momentum=mom, eps=eps, head=head, dout=dout, keep=keep, dropout_p=p)
+    err = lambda a, b: (a - b).abs().max().item() / max(b.abs().max().item(), 1e-300)
+    assert err(o["seq" if head == "freq" else "logits"], ref.detach()) <= 1e-12
+    bns = [model.stem.bn] + [c for blk in model.blocks for c in (blk.dw_bn, blk.pw_bn)]
+    for l in range(NL):
+        assert err(o["y"][l], ys[l]) <= 1e-12, l
+        assert err(o["g"][l], zs[l].grad) <= 1e-11, l
+        assert err(o["running_mean"][l], bns[l].running_mean) <= 1e-12, l
+        assert err(o["running_var"][l], bns[l].running_var) <= 1e-12, l
+    names = grad_names(head)
+    assert sorted(o["grads"]) == sorted(names)
+    ref_grads = dict(model.named_parameters())
+    for n in names:
+        assert err(o["grads"][n], ref_grads[n].grad) <= 1e-10, n
+
+
+@pytest.mark.parametrize("mt", [None, "bf16", "fp16"])
+@pytest.mark.parametrize("head", ["freq", "gap"])
+def test_conv_stack_restatement_own_masks_and_rounding(mt, head):
+    """Handed its own ReLU decisions, the restatement computes exactly what it computes without masks; in a 16-bit mode every
+    stored y_l and g_l is a value of the storage type, and the rounding changes the result (it is not silently skipped)."""
+    from oracle.conv_stack import conv_stack_restated, cnn_params, NL
+    mtype = MT.get(mt)
+    model = _conv_model(7)
+    g = torch.Generator().manual_seed(2)
+    B, Fd, T = 3, 9, 15
+    x = torch.randn(B, 1, Fd, T, generator=g, dtype=torch.float64) * 2 - 4
+    dout = torch.randn((B, 8, 64) if head == "freq" else (B, 2), generator=g, dtype=torch.float64) * 1000
+    kw = dict(mtype=mtype, head=head, dout=dout, momentum=0.2, eps=1e-4)
+    a = conv_stack_restated(cnn_params(model), x, **kw)
+    b = conv_stack_restated(cnn_params(model), x, masks=a["mask"], **kw)
+    for k in ("y", "g", "scale", "shift", "running_mean", "running_var"):
+        assert all(torch.equal(u, v) for u, v in zip(a[k], b[k])), k
+    assert all(torch.equal(a["grads"][n], b["grads"][n]) for n in a["grads"])
+    if mtype is None:
+        return
+    for l in range(NL):
+        assert torch.equal(mround(a["y"][l], mtype), a["y"][l]), l
+        if head == "freq" or l < 8:                  # GAP's layer-8 gradient is the fp32 pooled gradient
+            assert torch.equal(mround(a["g"][l], mtype), a["g"][l]), l
+    c = conv_stack_restated(cnn_params(model), x, masks=a["mask"], **{**kw, "mtype": None})
+    assert not torch.equal(c["grads"]["blocks.3.pw.weight"], a["grads"]["blocks.3.pw.weight"])
+
+
+def test_conv_stack_restatement_eval_mode():
+    """training=False: scale / shift from the running statistics, which stay as they are; the output is the module's in
+    eval mode."""
+    from oracle.conv_stack import conv_stack_restated, cnn_params, NL
+    model = _conv_model(3, mom=0.3, eps=1e-2)
+    x = torch.randn(2, 1, 10, 12, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
+    model.eval()
+    ref = model(x).detach()
+    o = conv_stack_restated(cnn_params(model), x, training=False, eps=1e-2, head="gap")
+    assert (o["logits"] - ref).abs().max().item() <= 1e-12 * ref.abs().max().item()
+    bns = [model.stem.bn] + [c for blk in model.blocks for c in (blk.dw_bn, blk.pw_bn)]
+    for l in range(NL):
+        assert torch.equal(o["running_mean"][l], bns[l].running_mean) and torch.equal(o["running_var"][l], bns[l].running_var)
+    with pytest.raises(ValueError):
+        conv_stack_restated(cnn_params(model), x, training=False, head="gap", dout=torch.zeros(2, 2, dtype=torch.float64))
