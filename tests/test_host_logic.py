@@ -507,6 +507,80 @@ def test_flat_bucket_gradient_slots_are_adopted_by_autograd_and_owner_checked():
     assert s.data_ptr() == twin._fb_views[0].data_ptr() != m._fb_views[0].data_ptr()
 
 
+def test_flat_bucket_slots_only_where_autograd_adopts_them_after_the_pass():
+    """grad_slot inside a backward pass: no slot under ``create_graph`` (autograd stores a clone at once), for a parameter with a
+    tensor hook or an unmarked post-accumulate hook (they see the gradient before the pass's end, where a deferred sum is not
+    yet valid), or in ``torch.autograd.grad`` (which would return the slot itself: a view of the bucket the next backward
+    overwrites).  The gradients are right in every case; a plain backward still adopts every slot."""
+    import torch.nn as nn
+    from wakeword_trainer_home_amd.models.flat_buckets import FlatBuckets, grad_slot
+    handed = []
+
+    class Fn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, w):
+            ctx.save_for_backward(x, w)
+            ctx.w = w
+            return x @ w.T
+
+        @staticmethod
+        def backward(ctx, g):
+            x, w = ctx.saved_tensors
+            dw, out = g.T @ x, grad_slot(ctx.w)
+            handed.append(out is not None)
+            if out is not None:
+                out.copy_(dw)
+                dw = out
+            return g @ w, dw
+
+    class M(FlatBuckets, nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.a, self.b = nn.Parameter(torch.randn(3, 4)), nn.Parameter(torch.randn(2, 3))
+
+        def forward(self, x):
+            return Fn.apply(Fn.apply(x, self.a), self.b)
+
+    torch.manual_seed(1)
+    m, x, x2 = M(), torch.randn(5, 4), torch.randn(5, 4)
+    ref = torch.autograd.grad((x @ m.a.T @ m.b.T).sum(), [m.a, m.b])
+    _ = m.flat_grad                                              # builds the bucket and the slots
+    in_bucket = lambda t: m.flat_grad.data_ptr() <= t.data_ptr() < m.flat_grad.data_ptr() + 4 * m.flat_grad.numel()
+    m(x).sum().backward()
+    assert handed == [True, True] and all(in_bucket(p.grad) for p in m.parameters())
+    m.zero_grad(set_to_none=True)
+    handed.clear()
+    got = torch.autograd.grad(m(x).sum(), [m.a, m.b])
+    assert handed == [False, False] and not any(in_bucket(t) for t in got)
+    kept = [t.clone() for t in got]
+    m(x2).sum().backward()                                      # a later backward leaves them alone
+    assert all(torch.equal(a, b) and torch.allclose(a, r) for a, b, r in zip(got, kept, ref))
+    m.zero_grad(set_to_none=True)
+    handed.clear()
+    m(x).sum().backward(create_graph=True)
+    assert handed == [False, False] and all(torch.allclose(p.grad, r) for p, r in zip(m.parameters(), ref))
+    assert torch.allclose(m.gather_grads(), torch.cat([r.flatten() for r in ref]))
+    m.zero_grad(set_to_none=True)
+    handed.clear()
+    seen = []
+    h = m.a.register_hook(lambda g: seen.append(g.clone()))
+    m(x).sum().backward()
+    h.remove()
+    assert handed == [True, False] and torch.allclose(seen[0], ref[0]) and torch.allclose(m.a.grad, ref[0])
+    m.zero_grad(set_to_none=True)
+    handed.clear()
+
+    def flushing(p):
+        pass
+    flushing.ww_flushes_deferred = True
+    h1 = m.b.register_post_accumulate_grad_hook(flushing)
+    h2 = m.a.register_post_accumulate_grad_hook(lambda p: None)
+    m(x).sum().backward()
+    h1.remove()
+    h2.remove()
+    assert handed == [True, False]                              # b's hook is marked as flushing; a's is not
+
+
 def test_pending_batch_counts_do_not_survive_a_load_and_modules_pickle():
     """BatchNorm's num_batches_tracked is counted on the host between state reads (no kernel per layer per step).  Loading a
     state dict makes the loaded value the truth -- a count pending from earlier steps must not be added to it -- and the hooks

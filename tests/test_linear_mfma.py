@@ -103,6 +103,75 @@ def test_mobilenetv3_head_matches_oracle(B, mode):
     assert eerr <= {"fp32": 5e-6, "bf16": 2e-3, "fp16": 2.5e-4}[mode]
 
 
+_EDGE = np.array([0.0, 3.0, -3.0, np.nextafter(np.float32(3), np.float32(4)), np.nextafter(np.float32(3), np.float32(0)),
+                  np.nextafter(np.float32(-3), np.float32(-4)), np.nextafter(np.float32(-3), np.float32(0)),
+                  np.finfo(np.float32).tiny, -np.finfo(np.float32).tiny], dtype=np.float32)
+
+
+@pytest.mark.parametrize("M,K,N", [(96, 40, 72), (1500, 24, 130)])
+@pytest.mark.parametrize("mode", ["fp32", "bf16", "fp16"])
+@pytest.mark.parametrize("p", [0.0, 0.3])
+@pytest.mark.parametrize("act", ["relu", "hardswish", "hardsigmoid"])
+def test_linear_epilogue_activation_edges(act, p, mode, M, K, N):
+    """linear_mfma_fwd(want_pre=True) / linear_mfma_bwd(pre=...) with a ReLU / Hardswish / Hardsigmoid epilogue, with and without
+    dropout, against float64 restated operands.  The first rows of x are zero, so there the pre-activation IS the bias, which
+    carries 0, +-3, one fp32 ulp to either side of +-3 and the smallest normal of either sign: torch's conventions at the kinks
+    (relu'(0) = 0, hardswish'(-3) = 0 and (3) = 1, hardsigmoid'(+-3) = 0) are pinned exactly there.  The reference's
+    activation decisions elsewhere are taken at the device's own fp32 pre-activations, and its dpre is formed in fp32 as
+    k_linear_dpre forms it, so that the 16-bit modes round the same values."""
+    import torch.nn.functional as Fn
+    from oracle.cnn_small import dropout_keep_mask
+    from wakeword_trainer_home_amd import _native as nat
+    code = {"relu": nat.LIN_RELU, "hardswish": nat.LIN_HARDSWISH, "hardsigmoid": nat.LIN_HARDSIGMOID}[act]
+    f64 = {"relu": torch.relu, "hardswish": Fn.hardswish, "hardsigmoid": Fn.hardsigmoid}[act]
+    md = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[mode]
+    g = torch.Generator().manual_seed(M + N + int(10 * p))
+    Z = 4                                                   # zero rows
+    x = torch.randn(M, K, generator=g)
+    x[:Z] = 0
+    w = torch.randn(N, K, generator=g) * (3 / K ** 0.5)
+    b = torch.randn(N, generator=g) * 2
+    b[:len(_EDGE)] = torch.from_numpy(_EDGE)
+    dy = torch.randn(M, N, generator=g)
+    seed, step, off = 9, 5, 3
+    y, pre = nat.linear_mfma_fwd(x.to(DEV), w.to(DEV), b.to(DEV), act=code, dropout_p=p, seed=seed, step=step, sample_offset=off,
+                                 mode=md, want_pre=True)
+    dx, dw, db = nat.linear_mfma_bwd(x.to(DEV), w.to(DEV), pre, dy.to(DEV), act=code, dropout_p=p, seed=seed, step=step,
+                                     sample_offset=off, mode=md)
+    y, pre, dx, dw, db = (t.cpu().double() for t in (y, pre, dx, dw, db))
+    r = (lambda t: t.to(md).double()) if mode != "fp32" else (lambda t: t.double())
+    pre_ref = r(x) @ r(w).t() + b.double()
+    assert torch.equal(pre[:Z], b.double().expand(Z, N))    # zero rows: exactly the bias
+    keep = torch.from_numpy(dropout_keep_mask(M, N, p, seed, step, off).astype(np.float64))
+    scale = float(np.float32(1.0 / (1.0 - float(np.float32(p))))) if p > 0 else 1.0
+    z = pre.clone().requires_grad_(True)                    # the device's fp32 pre-activations, in float64
+    h = f64(z) * keep * scale
+    (h * dy.double()).sum().backward()
+    y_ref = h.detach()
+    # dpre as k_linear_dpre forms it in fp32 (dy * scale, then * act'), so that its 16-bit rounding is the device's
+    slope = (z.grad / (dy.double() * keep * scale)).where(keep > 0, torch.zeros(()))   # torch's act'(pre)
+    if act == "hardswish":                                  # the device's z * fp32(1/3) + 0.5, rounded once
+        inner = (pre > -3) & (pre < 3)
+        slope = torch.where(inner, (pre * float(np.float32(1 / 3)) + 0.5).float().double(), slope)
+    g32 = torch.where(keep > 0, dy * np.float32(scale), torch.zeros(())) if p > 0 else dy.clone()
+    dpre = (g32 * slope.float()).double()
+    dx_ref, dw_ref, db_ref = r(dpre) @ r(w), r(dpre).t() @ r(x), dpre.sum(0)
+    tol = {"fp32": 2e-6, "bf16": 2e-5, "fp16": 4e-6}[mode]
+    errs = {"pre": _rel(pre, pre_ref), "y": _rel(y, y_ref), "y_edge": _rel(y[:Z], y_ref[:Z]), "dx": _rel(dx, dx_ref),
+            "dx_edge": _rel(dx[:Z], dx_ref[:Z]), "dw": _rel(dw, dw_ref), "db": _rel(db, db_ref)}
+    print(f"linear {act} p={p} {mode} {M}x{K}x{N}: " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
+    bad = {k: v for k, v in errs.items() if not v <= tol}
+    assert not bad, bad
+    # the planted columns' derivative in the REFERENCE is torch's convention at the kinks, which it relies on (the device's own
+    # derivative there is pinned through dx_edge and db above: the zero rows' dpre is all they are made of)
+    kink = slope[:Z, :len(_EDGE)]
+    want = {"relu": [0, 1, 0, 1, 1, 0, 0, 1, 0], "hardswish": [0.5, 1, 0, 1, 1.5, 0, -0.5, 0.5, 0.5],
+            "hardsigmoid": [1 / 6, 0, 0, 0, 1 / 6, 0, 1 / 6, 1 / 6, 1 / 6]}[act]
+    for j, v in enumerate(want):
+        kept = keep[:Z, j] > 0
+        assert torch.allclose(kink[kept, j], torch.full_like(kink[kept, j], float(v)), rtol=1e-6, atol=1e-6), (act, _EDGE[j])
+
+
 def test_linear_argument_checks():
     from wakeword_trainer_home_amd import _native as nat
     from wakeword_trainer_home_amd.models.heads import MFMALinear

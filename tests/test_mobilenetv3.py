@@ -46,6 +46,39 @@ def test_bn_act_layer(M, C, act, training):
     assert _rel(dg.cpu().double(), gamma.grad) <= 5e-5 and _rel(db.cpu().double(), beta.grad) <= 5e-5
 
 
+@pytest.mark.parametrize("act", [1, 2, 3])
+@pytest.mark.parametrize("training", [True, False])
+def test_bn_act_backward_at_the_activation_kinks(act, training):
+    """ww_bn_act_bwd with the activation's input planted EXACTLY at its kinks: channels whose input is all zero normalise to
+    z = beta whatever the statistics, and beta carries 0, +-3 and one fp32 ulp to either side of +-3.  torch's conventions
+    (relu'(0) = 0, hardswish'(-3) = 0 and (3) = 1, hardsigmoid'(+-3) = 0) must hold in dx, dgamma and dbeta."""
+    from wakeword_trainer_home_amd import _native as nat
+    edge = np.array([0.0, 3.0, -3.0, np.nextafter(np.float32(3), np.float32(4)), np.nextafter(np.float32(3), np.float32(0)),
+                     np.nextafter(np.float32(-3), np.float32(-4)), np.nextafter(np.float32(-3), np.float32(0))], dtype=np.float32)
+    M, C = 300, 24
+    g = torch.Generator().manual_seed(act + 10 * training)
+    x = (torch.randn(M, C, generator=g) * 2 + 1).double()
+    x[:, :len(edge)] = 0
+    gamma = (torch.rand(C, generator=g) + 0.5).double()
+    beta = (torch.randn(C, generator=g) * 0.3).double()
+    beta[:len(edge)] = torch.from_numpy(edge).double()
+    rm, rv = (torch.randn(C, generator=g) * 0.1).double(), (torch.rand(C, generator=g) + 0.5).double()
+    rm[:len(edge)] = 0
+    da = torch.randn(M, C, generator=g, dtype=torch.float64)
+    xr, gr, br = (t.clone().requires_grad_(True) for t in (x, gamma, beta))
+    z = Fn.batch_norm(xr, rm.clone(), rv.clone(), gr, br, training=training, momentum=0.01, eps=1e-3)
+    assert torch.equal(z.detach()[:, :len(edge)], beta[:len(edge)].expand(M, len(edge)))
+    (ACTS[act](z) * da).sum().backward()
+    f = lambda t: t.detach().float().to(DEV).contiguous()
+    rmd, rvd, gm, bt, xd = f(rm), f(rv), f(gamma), f(beta), f(x)
+    bn = nat.make_bn(gm, bt, rmd, rvd, momentum=0.01, eps=1e-3, training=training)
+    _, ss, mr = nat.bn_act_fwd(xd, bn, act, C)
+    dx, dg, db = nat.bn_act_bwd(xd, f(da), ss, mr, act, training, C)
+    E = len(edge)
+    for got, want in ((dx[:, :E], xr.grad[:, :E]), (db[:E], br.grad[:E]), (dx, xr.grad), (db, br.grad), (dg, gr.grad)):
+        assert _rel(got.cpu().double(), want) <= 5e-5, (act, training)
+
+
 @pytest.mark.parametrize("B,H,W,C,k,s", [(3, 20, 76, 16, 3, 2), (2, 10, 38, 72, 3, 2), (2, 5, 19, 96, 5, 2), (2, 3, 10, 240, 5, 1),
                                          (1, 2, 5, 576, 5, 1), (2, 7, 9, 10, 3, 1), (5, 5, 19, 88, 3, 1), (9, 3, 10, 288, 5, 2),
                                          (21, 2, 5, 24, 5, 1), (3, 11, 11, 40, 3, 2)])
@@ -407,7 +440,8 @@ def test_mobilenetv3_fp16_mode_step_matches_oracle():
     torch.manual_seed(12)
     model = create_model("mobilenetv3", dropout=0.3, dropout_seed=2, mode="fp16").to(DEV)
     oracle = MobileNetV3Oracle(dropout=0.3, seed=2)
-    oracle.load_state_dict({k: v.cpu().double() if v.is_floating_point() else v.cpu() for k, v in model.state_dict().items()})
+    state0 = {k: v.cpu().double() if v.is_floating_point() else v.cpu() for k, v in model.state_dict().items()}
+    oracle.load_state_dict(state0)
     x, y = make_inputs(9, B)
     model.train()
     oracle.train()
@@ -437,3 +471,6 @@ def test_mobilenetv3_fp16_mode_step_matches_oracle():
         eerr = (model(x.to(DEV)).cpu().double() - ev_ref).abs().max().item() / max(ev_ref.abs().max().item(), 1.0)
     print(f"fp16 mobilenetv3 B={B}: logits {derr:.2e} loss {lerr:.2e} cos {cos:.6f} running means {worst_rs:.2e} eval {eerr:.2e}")
     assert derr <= 3e-3 and lerr <= 3e-6 and 1 - cos <= 3e-3 and worst_rs <= 6e-3 and eerr <= 3.5e-5, (derr, lerr, cos, worst_rs, eerr)
+    # and per tensor, against the restatement of fp16 mode (tests/test_mobilenetv3_tensors.py; unscaled loss, as above)
+    from tests.test_mobilenetv3_tensors import _report_and_check, restated_grad_errors
+    _report_and_check("fp16_step", "fp16", f"fp16 mobilenetv3 B={B} per tensor", restated_grad_errors(model, state0, x, y, "fp16", 2))

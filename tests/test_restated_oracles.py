@@ -229,3 +229,93 @@ def test_conv_stack_restatement_eval_mode():
         assert torch.equal(o["running_mean"][l], bns[l].running_mean) and torch.equal(o["running_var"][l], bns[l].running_var)
     with pytest.raises(ValueError):
         conv_stack_restated(cnn_params(model), x, training=False, head="gap", dout=torch.zeros(2, 2, dtype=torch.float64))
+
+
+def _mnv3(seed):
+    """float64 MobileNetV3Oracle with random BatchNorm affine parameters and running statistics, SE and head biases."""
+    from oracle.mobilenetv3 import MobileNetV3Oracle
+    torch.manual_seed(seed)
+    m = MobileNetV3Oracle(2, dropout=0.3, seed=6)
+    with torch.no_grad():
+        for mod in m.modules():
+            if isinstance(mod, torch.nn.BatchNorm2d):
+                mod.weight.uniform_(0.5, 1.5)
+                mod.bias.normal_(0, 0.2)
+                mod.running_mean.normal_(0, 0.1)
+                mod.running_var.uniform_(0.5, 1.5)
+            elif isinstance(mod, (torch.nn.Conv2d, torch.nn.Linear)) and mod.bias is not None:
+                mod.bias.normal_(0, 0.2)
+    return m
+
+
+@pytest.mark.parametrize("se_rounded", [False, True])
+def test_unrounded_mobilenetv3_restatement_is_autograd(se_rounded):
+    """mtype None: the rounding-aware walk (RoundedLinear GEMMs, the composed SE with se_rounded) is the plain float64 model --
+    logits, every gradient, the running statistics after the step and the eval logits, to ~1e-12 per tensor."""
+    import copy
+    import torch.nn.functional as Fn
+    a = _mnv3(2)
+    b = copy.deepcopy(a)
+    x = torch.randn(3, 1, 24, 30, generator=torch.Generator().manual_seed(1), dtype=torch.float64) * 2 - 4
+    y = torch.tensor([0, 1, 1])
+    outs = []
+    for m, kw in ((a, {}), (b, {"restate": True, "se_rounded": se_rounded})):
+        m.train()
+        out = m(x, step=2, **kw)
+        Fn.cross_entropy(out, y).backward()
+        m.eval()
+        with torch.no_grad():
+            outs.append((out.detach(), m(x, training=False, **kw)))
+    err = lambda u, v: (u - v).abs().max().item() / max(v.abs().max().item(), 1e-300)
+    assert err(outs[1][0], outs[0][0]) <= 1e-12 and err(outs[1][1], outs[0][1]) <= 1e-12
+    grads = list(b.named_parameters())
+    assert len(grads) == 142
+    scale = max(q.grad.abs().max().item() for q in a.parameters())
+    for (n, p), q in zip(grads, a.parameters()):
+        # (the projection BatchNorms' dbeta is structurally zero -- a 1x1 conv + BatchNorm follows -- hence the floor)
+        assert (p.grad - q.grad).abs().max().item() <= 1e-11 * max(q.grad.abs().max().item(), 1e-4 * scale), n
+    for (n, u), v in zip(b.named_buffers(), a.buffers()):
+        assert torch.equal(u, v) if not u.is_floating_point() else err(u, v) <= 1e-12, n
+
+
+@pytest.mark.parametrize("mt", ["bf16", "fp16"])
+def test_rounded_linear_rounds_dpre_w_and_x(mt):
+    """RoundedLinear: forward R(x) R(W)^T + b; backward dX = R(dpre) R(W), dW = R(dpre)^T R(x), db = colsum(dpre) -- against an
+    explicit computation, and differing from the unrounded one (the rounding is really applied)."""
+    from oracle.mobilenetv3 import RoundedLinear
+    mtype = MT[mt]
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn(7, 5, generator=g, dtype=torch.float64).requires_grad_(True)
+    w = torch.randn(3, 5, generator=g, dtype=torch.float64).requires_grad_(True)
+    b = torch.randn(3, generator=g, dtype=torch.float64).requires_grad_(True)
+    dpre = torch.randn(7, 3, generator=g, dtype=torch.float64)
+    R = lambda t: mround(t.detach(), mtype)
+    y = RoundedLinear.apply(x, w, b, mtype)
+    assert torch.equal(y.detach(), R(x) @ R(w).t() + b.detach())
+    y.backward(dpre)
+    assert torch.equal(x.grad, R(dpre) @ R(w))
+    assert torch.equal(w.grad, R(dpre).t() @ R(x))
+    assert torch.equal(b.grad, dpre.sum(0))
+    assert not torch.equal(x.grad, dpre @ w.detach()) and not torch.equal(w.grad, dpre.t() @ x.detach())
+
+
+@pytest.mark.parametrize("mt", ["bf16", "fp16"])
+def test_mobilenetv3_restatement_rounding_takes_effect(mt):
+    """A matrix type moves the restated model, the eval stem rounds its operands, and se_rounded changes the result (the
+    composed SE rounds its FCs)."""
+    import copy
+    mtype = MT[mt]
+    m = _mnv3(3)
+    x = torch.randn(2, 1, 16, 20, generator=torch.Generator().manual_seed(5), dtype=torch.float64) * 2 - 4
+    err = lambda u, v: (u - v).abs().max().item() / max(v.abs().max().item(), 1e-300)
+    outs = {}
+    for kw in ({}, {"mtype": mtype}, {"mtype": mtype, "se_rounded": True}):
+        mm = copy.deepcopy(m).train()
+        outs[len(kw)] = mm(x, restate=True, **kw).detach()
+    assert err(outs[1], outs[0]) > 0
+    assert err(outs[2], outs[1]) > 0
+    mm = copy.deepcopy(m).eval()
+    mm.mobilenet.features[0][0].weight.data += 1e-3          # the eval stem GEMM sees its operands rounded: a change far
+    e0 = mm(x, training=False, restate=True, mtype=mtype)     # below the rounding quantum of most weights moves nothing
+    mm.mobilenet.features[0][0].weight.data += 1e-9
+    assert torch.equal(e0, mm(x, training=False, restate=True, mtype=mtype))

@@ -523,7 +523,10 @@ def defer_begin(dev):
 
 def defer_reset(dev):
     """Start of a forward pass: whatever a previous backward pass left queued or armed is stale (that pass raised before its
-    end-of-backward callback ran) -- forget it, so the next backward arms a fresh flush."""
+    end-of-backward callback ran) -- forget it, so the next backward arms a fresh flush.  A forward that runs INSIDE a backward
+    pass (a checkpointed region's recompute) leaves the queue alone: it belongs to the running pass, whose callback flushes it."""
+    if torch._C._current_graph_task_id() >= 0:
+        return
     st = _defer.get(torch.device(dev))
     if st is not None and (st["armed"] or st["keep"]):
         _check(load().ww_deferred_reduce_discard(ctx(torch.device(dev))), "ww_deferred_reduce_discard")

@@ -21,7 +21,7 @@ __device__ __forceinline__ float act_fwd(int act, float z) {
 }
 __device__ __forceinline__ float act_grad(int act, float z) {
     if (act == WW_LIN_RELU) return z > 0.f ? 1.f : 0.f;
-    if (act == WW_LIN_HARDSWISH) return z < -3.f ? 0.f : (z <= 3.f ? z * (1.f / 3.f) + 0.5f : 1.f);
+    if (act == WW_LIN_HARDSWISH) return z <= -3.f ? 0.f : (z < 3.f ? z * (1.f / 3.f) + 0.5f : 1.f);   // 0 at -3, 1 at 3
     if (act == WW_LIN_HARDSIGMOID) return (z > -3.f && z < 3.f) ? (1.f / 6.f) : 0.f;
     return 1.f;
 }

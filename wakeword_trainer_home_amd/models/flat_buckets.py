@@ -15,9 +15,16 @@ def grad_slot(param):
     gradient -- or None (no bucket, or the parameter already holds a gradient that this backward must be added to).  autograd
     adopts a returned gradient tensor as ``param.grad`` without copying when nothing else references it and its layout is the
     parameter's, so the gradient is born in the bucket and ``gather_grads`` has nothing to move (it was three multi-tensor copy
-    launches per step, 142 tensors)."""
+    launches per step, 142 tensors).
+
+    Inside a backward pass a slot is only handed out where autograd adopts it as it is, after the pass: a backward node may
+    defer the slot's final sum to the end of the pass (``_native.defer_begin``), and a slot that is read or kept before that
+    holds partial values, or aliases the bucket past the next backward.  So no slot while grad mode is on (``create_graph``:
+    autograd stores a clone of it at once), for a parameter with hooks (they see the gradient before the end of the pass;
+    post-accumulate hooks marked ``ww_flushes_deferred`` run the flush themselves), or in a pass that does not accumulate the
+    gradients into ``.grad`` (``torch.autograd.grad`` would return the slot itself)."""
     slot = getattr(param, "_ww_grad_slot", None)
-    if slot is None or param.grad is not None:
+    if slot is None or param.grad is not None or not _adopting_pass(param):
         return None
     ref, idx, off = slot
     mod = ref()
@@ -25,6 +32,40 @@ def grad_slot(param):
     if mod is None or mod._fb_plist is None or idx >= len(mod._fb_plist) or mod._fb_plist[idx] is not param:
         return None
     return mod._fb_grad[off:off + param.numel()].view_as(param)
+
+
+def _hooked(param):
+    if param._backward_hooks:
+        return True
+    post = getattr(param, "_post_accumulate_grad_hooks", None)
+    return bool(post) and not all(getattr(h, "ww_flushes_deferred", False) for h in post.values())
+
+
+_passes = {}         # graph task id -> whether that backward pass adopts slots (keyed: concurrent passes do not share a decision)
+
+
+def _adopting_pass(param):
+    """Outside a backward pass: True (the caller's business).  Inside one: grad mode off, no hooks on ``param``, and the pass
+    accumulates into ``.grad`` -- decided once per pass (one engine query costs ~9 us) on the FIRST parameter asked about.
+    ``torch.autograd.grad`` (which captures the gradients instead, and refuses the query for a captured leaf) gets no slots at
+    all, nor does a ``backward(inputs=...)`` that leaves that first parameter out.  A ``backward(inputs=...)`` that includes it
+    hands slots to every parameter, and an excluded one's slot is written but never adopted: its ``.grad`` stays None, and
+    ``gather_grads`` refuses a bucket with a missing gradient."""
+    task = torch._C._current_graph_task_id()
+    if task < 0:
+        return True
+    if torch.is_grad_enabled() or _hooked(param):
+        return False
+    ok = _passes.get(task)
+    if ok is None:
+        try:
+            ok = bool(torch._C._will_engine_execute_node(torch.autograd.graph.get_gradient_edge(param).node))
+        except RuntimeError:
+            ok = False
+        if len(_passes) >= 64:              # task ids only grow: forget old passes (one still running is asked again)
+            _passes.clear()
+        _passes[task] = ok
+    return ok
 
 
 class FlatBuckets:

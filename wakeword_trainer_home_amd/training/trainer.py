@@ -368,6 +368,7 @@ class Trainer:
                         for v, q in todo:
                             q.grad = v                            # gather_grads() after the backward must not copy them again
                 _ov["handles"].append(_self._reduce_start(ext[_ov["cut"]:]))     # incl. the found_inf slot behind the bucket
+        hook.ww_flushes_deferred = True       # reads no gradient before its flush: the tail keeps its slots (grad_slot)
         for q in plist[first:]:
             ov["hooks"].append(q.register_post_accumulate_grad_hook(hook))
         self._ov = ov
