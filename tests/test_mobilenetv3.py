@@ -19,9 +19,27 @@ def _rel(a, b):
 ACTS = {0: lambda z: z, 1: Fn.hardswish, 2: torch.relu, 3: Fn.hardsigmoid}
 
 
-@pytest.mark.parametrize("M,C,act,training", [(1000, 16, 1, True), (333, 72, 2, True), (64, 576, 1, True), (50, 24, 0, True),
-                                              (200, 40, 3, True), (300, 88, 2, False)])
-def test_bn_act_layer(M, C, act, training):
+def _misaligned(t):
+    """A contiguous device copy of ``t`` that starts one float into a larger buffer: 4-byte aligned, never 16-byte aligned
+    (torch's allocations are), so a call that is handed it cannot take its float4 kernels."""
+    buf = torch.empty(t.numel() + 1, dtype=torch.float32, device=DEV)
+    v = buf[1:].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+def _cases(aligned, misaligned=()):
+    """Cases with a trailing ``misaligned`` flag; an aligned case keeps the id pytest gives it without the flag."""
+    case = lambda c, m: pytest.param(*c, m, id="-".join(map(str, c)) + ("-misaligned" if m else ""))
+    return [case(c, False) for c in aligned] + [case(c, True) for c in misaligned]
+
+
+@pytest.mark.parametrize("M,C,act,training,misaligned", _cases(
+    [(1000, 16, 1, True), (333, 72, 2, True), (64, 576, 1, True), (50, 24, 0, True), (200, 40, 3, True), (300, 88, 2, False),
+     (129, 7, 3, True), (257, 10, 1, True)],                        # C % 4 != 0: the one-float forms of the elementwise passes
+    [(333, 72, 2, True), (300, 88, 2, False)]))                     # x / da off the 16-byte grid: the same forms at C % 4 == 0
+def test_bn_act_layer(M, C, act, training, misaligned):
     from wakeword_trainer_home_amd import _native as nat
     g = torch.Generator().manual_seed(M + C)
     x = (torch.randn(M, C, generator=g, dtype=torch.float64) * 2 + 1).requires_grad_(True)
@@ -37,11 +55,11 @@ def test_bn_act_layer(M, C, act, training):
     rmd, rvd = f(rm), f(rv)
     gm, bt = f(gamma), f(beta)
     bn = nat.make_bn(gm, bt, rmd, rvd, momentum=0.01, eps=1e-3, training=training)
-    xd = f(x)
+    xd, dad = (_misaligned(f(t)) for t in (x, da)) if misaligned else (f(x), f(da))
     y, ss, mr = nat.bn_act_fwd(xd, bn, act, C)
     assert _rel(y.cpu().double(), y_ref.detach()) <= 2e-5
     assert _rel(rmd.cpu().double(), rm_ref) <= 1e-5 and _rel(rvd.cpu().double(), rv_ref) <= 1e-5
-    dx, dg, db = nat.bn_act_bwd(xd, f(da), ss, mr, act, training, C)
+    dx, dg, db = nat.bn_act_bwd(xd, dad, ss, mr, act, training, C)
     assert _rel(dx.cpu().double(), x.grad) <= 5e-5
     assert _rel(dg.cpu().double(), gamma.grad) <= 5e-5 and _rel(db.cpu().double(), beta.grad) <= 5e-5
 
@@ -79,10 +97,15 @@ def test_bn_act_backward_at_the_activation_kinks(act, training):
         assert _rel(got.cpu().double(), want) <= 5e-5, (act, training)
 
 
-@pytest.mark.parametrize("B,H,W,C,k,s", [(3, 20, 76, 16, 3, 2), (2, 10, 38, 72, 3, 2), (2, 5, 19, 96, 5, 2), (2, 3, 10, 240, 5, 1),
-                                         (1, 2, 5, 576, 5, 1), (2, 7, 9, 10, 3, 1), (5, 5, 19, 88, 3, 1), (9, 3, 10, 288, 5, 2),
-                                         (21, 2, 5, 24, 5, 1), (3, 11, 11, 40, 3, 2)])
-def test_depthwise_layer(B, H, W, C, k, s):
+@pytest.mark.parametrize("B,H,W,C,k,s,misaligned", _cases(
+    [(3, 20, 76, 16, 3, 2), (2, 10, 38, 72, 3, 2), (2, 5, 19, 96, 5, 2), (2, 3, 10, 240, 5, 1), (1, 2, 5, 576, 5, 1),
+     (2, 7, 9, 10, 3, 1), (5, 5, 19, 88, 3, 1), (9, 3, 10, 288, 5, 2), (21, 2, 5, 24, 5, 1), (3, 11, 11, 40, 3, 2),
+     # C % 4 != 0 (one channel per thread): k = 5 at stride 2; a weight-gradient block wider than the float4 form's 512
+     # threads; a map of more than 128 pixels
+     (2, 7, 9, 10, 5, 2), (1, 3, 4, 514, 3, 1), (2, 12, 13, 6, 3, 2)],
+    # x / dy off the 16-byte grid: an LDS-path shape and a gather-path shape, which must take the one-channel form instead
+    [(5, 5, 19, 88, 3, 1), (3, 20, 76, 16, 3, 2)]))
+def test_depthwise_layer(B, H, W, C, k, s, misaligned):
     from wakeword_trainer_home_amd import _native as nat
     g = torch.Generator().manual_seed(H * W + C)
     x = torch.randn(B, C, H, W, generator=g, dtype=torch.float64, requires_grad=True)
@@ -91,9 +114,10 @@ def test_depthwise_layer(B, H, W, C, k, s):
     dy = torch.randn_like(y_ref)
     (y_ref * dy).sum().backward()
     nhwc = lambda t: t.detach().permute(0, 2, 3, 1).float().contiguous().to(DEV)
-    y = nat.dwconv_nhwc_fwd(nhwc(x), w.detach().float().to(DEV), k, s)
+    xd, dyd = (_misaligned(nhwc(t)) for t in (x, dy)) if misaligned else (nhwc(x), nhwc(dy))
+    y = nat.dwconv_nhwc_fwd(xd, w.detach().float().to(DEV), k, s)
     assert y.shape == nhwc(y_ref).shape and _rel(y.cpu().double(), nhwc(y_ref).cpu().double()) <= 2e-6
-    dx, dw = nat.dwconv_nhwc_bwd(nhwc(x), w.detach().float().to(DEV), nhwc(dy), k, s)
+    dx, dw = nat.dwconv_nhwc_bwd(xd, w.detach().float().to(DEV), dyd, k, s)
     assert _rel(dx.cpu().double(), nhwc(x.grad).cpu().double()) <= 2e-6
     assert _rel(dw.cpu().double(), w.grad) <= 2e-5
 
@@ -101,18 +125,20 @@ def test_depthwise_layer(B, H, W, C, k, s):
 def test_se_pieces_and_stem_patches():
     from wakeword_trainer_home_amd import _native as nat
     g = torch.Generator().manual_seed(5)
-    B, HW, C = 6, 50, 72
-    x = torch.randn(B, HW, C, generator=g)
-    gate = torch.rand(B, C, generator=g)
-    dy = torch.randn(B, HW, C, generator=g)
-    dpool = torch.randn(B, C, generator=g)
-    xd, gd, dyd, dpd = (t.to(DEV) for t in (x, gate, dy, dpool))
-    assert _rel(nat.pool_hw_fwd(xd).cpu(), x.mean(1)) <= 1e-6
-    assert torch.equal(nat.scale_bc_fwd(xd, gd).cpu(), x * gate[:, None, :])
-    assert _rel(nat.scale_bc_bwd_gate(xd, dyd).cpu(), (x * dy).sum(1)) <= 1e-6
-    assert _rel(nat.scale_pool_bwd(dyd, gd, dpd, (B, HW, C)).cpu(), dy * gate[:, None, :] + dpool[:, None, :] / HW) <= 1e-6
-    assert _rel(nat.scale_pool_bwd(None, None, dpd, (B, HW, C)).cpu(), (dpool[:, None, :] / HW).expand(B, HW, C)) <= 1e-6
-    assert torch.equal(nat.add_f32(xd, dyd).cpu(), x + dy)
+    for B, HW, C in ((6, 50, 72), (3, 11, 10)):                     # C % 4 == 0 and C % 4 != 0
+        x = torch.randn(B, HW, C, generator=g)
+        gate = torch.rand(B, C, generator=g)
+        dy = torch.randn(B, HW, C, generator=g)
+        dpool = torch.randn(B, C, generator=g)
+        xd, gd, dyd, dpd = (t.to(DEV) for t in (x, gate, dy, dpool))
+        assert _rel(nat.pool_hw_fwd(xd).cpu(), x.mean(1)) <= 1e-6
+        assert torch.equal(nat.scale_bc_fwd(xd, gd).cpu(), x * gate[:, None, :])
+        assert _rel(nat.scale_bc_bwd_gate(xd, dyd).cpu(), (x * dy).sum(1)) <= 1e-6
+        assert _rel(nat.scale_pool_bwd(dyd, gd, dpd, (B, HW, C)).cpu(), dy * gate[:, None, :] + dpool[:, None, :] / HW) <= 1e-6
+        assert _rel(nat.scale_pool_bwd(None, None, dpd, (B, HW, C)).cpu(), (dpool[:, None, :] / HW).expand(B, HW, C)) <= 1e-6
+        assert torch.equal(nat.add_f32(xd, dyd).cpu(), x + dy)
+    u, v = torch.randn(1001, generator=g), torch.randn(1001, generator=g)      # a length that is no multiple of 4
+    assert torch.equal(nat.add_f32(u.to(DEV), v.to(DEV)).cpu(), u + v)
     img = torch.randn(3, 1, 41, 151, generator=g)
     cols = nat.im2col3x3s2(img[:, 0].contiguous().to(DEV)).cpu()
     ref = Fn.unfold(img, 3, padding=1, stride=2).transpose(1, 2).reshape(-1, 9)

@@ -621,6 +621,25 @@ def nhwc_scratch(Cn, dev):
     return buf
 
 
+def _partials_scratch(Cn, dev, defer):
+    """Scratch for a weight-gradient call: a buffer of its own when the sum of the partials is deferred (it must outlive the
+    next layer call, which overwrites the cached one), else the cached per-(C, device) scratch."""
+    if defer:
+        return torch.empty(load().ww_nhwc_scratch_bytes(Cn) // 4, dtype=torch.float32, device=dev)
+    return nhwc_scratch(Cn, dev)
+
+
+def _conv_bn_act_outs(shape, dev):
+    """(y pre-BN, a, ss (2C), mr (2C)) of a conv + BatchNorm + activation call whose output has `shape` = (..., C)."""
+    new = lambda *sh: torch.empty(sh, dtype=torch.float32, device=dev)
+    return new(*shape), new(*shape), new(2 * shape[-1]), new(2 * shape[-1])
+
+
+def _dw_out_hw(H, W, k, stride):
+    """Output size of a k x k convolution with padding k // 2."""
+    return (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
+
+
 def bn_act_fwd(x, bn: BN, act, Cn):
     """x (..., C) -> (y, ss (2C), mr (2C))."""
     dev = _dev(x)
@@ -652,10 +671,7 @@ def conv1x1_bn_act_fwd(x, w, bn: BN, act, mode=torch.float32, residual=None):
     dev = _dev(x, w, residual)
     M, K = x.shape
     N = w.shape[0]
-    y = torch.empty((M, N), dtype=torch.float32, device=dev)
-    a = torch.empty_like(y)
-    ss = torch.empty(2 * N, dtype=torch.float32, device=dev)
-    mr = torch.empty(2 * N, dtype=torch.float32, device=dev)
+    y, a, ss, mr = _conv_bn_act_outs((M, N), dev)
     scratch = nhwc_scratch(N, dev)
     if scratch.numel() < ((M + 63) // 64) * 2 * N:          # very tall and narrow: a scratch of its own size
         scratch = torch.empty(((M + 63) // 64) * 2 * N, dtype=torch.float32, device=dev)
@@ -669,11 +685,7 @@ def dwconv_bn_act_fwd(x, w, k, stride, bn: BN, act):
     """Depthwise conv + BatchNorm + activation -> (y pre-BN, a, ss, mr); the LDS kernel takes the statistics where it applies."""
     dev = _dev(x, w)
     B, H, W, Cn = x.shape
-    Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
-    y = torch.empty((B, Ho, Wo, Cn), dtype=torch.float32, device=dev)
-    a = torch.empty_like(y)
-    ss = torch.empty(2 * Cn, dtype=torch.float32, device=dev)
-    mr = torch.empty(2 * Cn, dtype=torch.float32, device=dev)
+    y, a, ss, mr = _conv_bn_act_outs((B, *_dw_out_hw(H, W, k, stride), Cn), dev)
     with _guard(dev):
         _check(load().ww_dwconv_bn_act_fwd(ctx(dev), _p(x), _p(w), B, H, W, Cn, k, stride, C.byref(bn), act, _p(y), _p(a), _p(ss),
                                            _p(mr), _p(nhwc_scratch(Cn, dev)), _stream(dev)), "ww_dwconv_bn_act_fwd")
@@ -683,21 +695,19 @@ def dwconv_bn_act_fwd(x, w, k, stride, bn: BN, act):
 def dwconv_nhwc_fwd(x, w, k, stride):
     dev = _dev(x, w)
     B, H, W, Cn = x.shape
-    Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
-    y = torch.empty((B, Ho, Wo, Cn), dtype=torch.float32, device=dev)
+    y = torch.empty((B, *_dw_out_hw(H, W, k, stride), Cn), dtype=torch.float32, device=dev)
     with _guard(dev):
         _check(load().ww_dwconv_nhwc_fwd(ctx(dev), _p(x), _p(w), B, H, W, Cn, k, stride, _p(y), _stream(dev)), "ww_dwconv_nhwc_fwd")
     return y
 
 
 def dwconv_nhwc_bwd(x, w, dy, k, stride, need_dx=True, dw_out=None, defer=False):
-    """defer: queue the sum of the weight-gradient partials (dw valid after deferred_flush); the partials then get a buffer of
-    their own instead of the per-(C, device) scratch the next layer call would overwrite."""
+    """defer: queue the sum of the weight-gradient partials (dw valid after deferred_flush)."""
     dev = _dev(x, w, dy)
     B, H, W, Cn = x.shape
     dx = torch.empty_like(x) if need_dx else None
     dw = _out(dw_out, tuple(w.shape), dev)
-    scratch = torch.empty(load().ww_nhwc_scratch_bytes(Cn) // 4, dtype=torch.float32, device=dev) if defer else nhwc_scratch(Cn, dev)
+    scratch = _partials_scratch(Cn, dev, defer)
     with _guard(dev), (_deferring(dev, scratch) if defer else contextlib.nullcontext()):
         _check(load().ww_dwconv_nhwc_bwd(ctx(dev), _p(x), _p(w), _p(dy), B, H, W, Cn, k, stride, _p(dx), _p(dw),
                                          _p(scratch), _stream(dev)), "ww_dwconv_nhwc_bwd")
@@ -791,10 +801,7 @@ def stem3x3s2_bn_act_fwd(x, w, bn: BN, act):
     dev = _dev(x, w)
     B, H, W = x.shape
     Cn = w.shape[0]
-    y = torch.empty((B, (H + 1) // 2, (W + 1) // 2, Cn), dtype=torch.float32, device=dev)
-    a = torch.empty_like(y)
-    ss = torch.empty(2 * Cn, dtype=torch.float32, device=dev)
-    mr = torch.empty(2 * Cn, dtype=torch.float32, device=dev)
+    y, a, ss, mr = _conv_bn_act_outs((B, (H + 1) // 2, (W + 1) // 2, Cn), dev)
     with _guard(dev):
         _check(load().ww_stem3x3s2_bn_act_fwd(ctx(dev), _p(x), _p(w), B, H, W, Cn, C.byref(bn), act, _p(y), _p(a), _p(ss), _p(mr),
                                               _p(nhwc_scratch(Cn, dev)), _stream(dev)), "ww_stem3x3s2_bn_act_fwd")
@@ -806,7 +813,7 @@ def stem3x3s2_bwd_dw(x, dy, w_shape, dw_out=None, defer=False):
     B, H, W = x.shape
     Cn = dy.shape[-1]
     dw = _out(dw_out, tuple(w_shape), dev)
-    scratch = torch.empty(load().ww_nhwc_scratch_bytes(Cn) // 4, dtype=torch.float32, device=dev) if defer else nhwc_scratch(Cn, dev)
+    scratch = _partials_scratch(Cn, dev, defer)
     with _guard(dev), (_deferring(dev, scratch) if defer else contextlib.nullcontext()):
         _check(load().ww_stem3x3s2_bwd_dw(ctx(dev), _p(x), _p(dy), B, H, W, Cn, _p(dw), _p(scratch), _stream(dev)),
                "ww_stem3x3s2_bwd_dw")

@@ -49,18 +49,6 @@ struct Epilogue {
     float *stat_part;           // nullable: per row tile [sum (N) | sum of squares (N)] of the stored outputs (BatchNorm partials)
 };
 
-__device__ __forceinline__ float lin_act(int act, float z) {
-    if (act == WW_LIN_HARDSWISH) return z * fminf(fmaxf(z + 3.f, 0.f), 6.f) * (1.f / 6.f);
-    if (act == WW_LIN_RELU) return z < 0.f ? 0.f : z;
-    if (act == WW_LIN_HARDSIGMOID) return fminf(fmaxf(z + 3.f, 0.f), 6.f) * (1.f / 6.f);
-    return z;
-}
-__device__ __forceinline__ float lin_act_grad(int act, float z) {      // torch's hardswish / hardsigmoid / relu backward
-    if (act == WW_LIN_HARDSWISH) return z <= -3.f ? 0.f : (z < 3.f ? z * (1.f / 3.f) + 0.5f : 1.f);   // 0 at -3, 1 at 3
-    if (act == WW_LIN_RELU) return z > 0.f ? 1.f : 0.f;
-    if (act == WW_LIN_HARDSIGMOID) return (z > -3.f && z < 3.f) ? (1.f / 6.f) : 0.f;
-    return 1.f;
-}
 // The launch-constant Philox inputs of a dropout epilogue (resolved step, seed).  k_gemm keeps them in VECTOR registers on purpose
 // (dropout_ctx_vgpr): as wave-uniform values the compiler hoists the whole 10-round key schedule into ~20 SGPRs, which on top of the
 // GEMM's live kernel arguments overflowed the scalar file (20-60 spilled SGPRs and a scratch segment in the r02 build).

@@ -1,34 +1,46 @@
 // Generic channels-last (NHWC, fp32) layers for bodies whose channel counts vary layer to layer -- the MobileNetV3-small body
 // of BASELINE config 3 (torchvision's mobilenet_v3_small as the reference instantiates it,
-// src/models/architectures.py:91-102).  Unlike the 64-channel cnn_small kernels (BatchNorm folded into producers and
-// consumers) these are plain, unfused building blocks: an activation tensor is a row-major (M = B*H*W, C) matrix, so
-//   * every 1x1 convolution and every squeeze-excitation FC is ww_gemm / ww_linear_mfma_* on the matrix cores;
-//   * BatchNorm(+activation) is a statistics pass (chunked column sums, fixed-order fp64 finish) and an apply pass;
-//   * depthwise k x k (3 or 5, stride 1 or 2) is a per-(pixel, 4-channel) gather;
-//   * squeeze-excitation is pool -> FC+ReLU -> FC+Hardsigmoid -> scale.
-// First version: correctness and the reference's layer semantics; fusion of these passes is the next step.
+// src/models/architectures.py:91-102).  An activation tensor is a row-major (M = B*H*W, C) matrix, so every 1x1 convolution is a
+// matrix-core GEMM (ww_linear.hip) and the squeeze-excitation block has kernels of its own (ww_se.hip).  This file holds the rest:
+//   * BatchNorm(+activation), forward and backward.  The statistics are per-chunk partial sums -- from k_colstats /
+//     k_bnact_bwd_stats, or left by the producer (the GEMM epilogue, k_dwl_conv, k_stem3x3s2_fwd) -- finished in fixed order in
+//     fp64 either by the apply pass itself (k_bn_act_apply_fin, k_bnact_bwd_apply_fin: small layers) or by a finish launch;
+//   * depthwise k x k (3 or 5, stride 1 or 2): whole images staged in LDS for maps of <= 128 pixels (k_dwl_*), a per-(pixel,
+//     channel vector) gather otherwise (k_dwg_*);
+//   * the one-channel 3x3 stride-2 stem as a direct convolution that leaves its BatchNorm partials and weight-gradient partials;
+//   * the pieces of the composed squeeze-excitation path and of the eval stem (pooling, gating, im2col, add).
+// Elementwise and gather kernels are templated on the vector width V: 4 floats per access where C % 4 == 0 and every base
+// pointer is 16-byte aligned (every MobileNetV3 layer), else 1 -- the same arithmetic per element in the same order, the same bits.
 #include "ww_internal.h"
 #include "ww_layers.h"
 #include <algorithm>
+#include <type_traits>
 
 namespace {
-
-__device__ __forceinline__ float act_fwd(int act, float z) {
-    if (act == WW_LIN_RELU) return z < 0.f ? 0.f : z;
-    if (act == WW_LIN_HARDSWISH) return z * fminf(fmaxf(z + 3.f, 0.f), 6.f) * (1.f / 6.f);
-    if (act == WW_LIN_HARDSIGMOID) return fminf(fmaxf(z + 3.f, 0.f), 6.f) * (1.f / 6.f);
-    return z;
-}
-__device__ __forceinline__ float act_grad(int act, float z) {
-    if (act == WW_LIN_RELU) return z > 0.f ? 1.f : 0.f;
-    if (act == WW_LIN_HARDSWISH) return z <= -3.f ? 0.f : (z < 3.f ? z * (1.f / 3.f) + 0.5f : 1.f);   // 0 at -3, 1 at 3
-    if (act == WW_LIN_HARDSIGMOID) return (z > -3.f && z < 3.f) ? (1.f / 6.f) : 0.f;
-    return 1.f;
-}
 
 constexpr int NCHUNK = 256;     // max row chunks of the column reductions (one workgroup each)
 constexpr int NCHUNK_DW = 1024; // max pixel chunks of the depthwise weight-gradient kernel
 
+// V consecutive floats moved by one load / store: V = 4 is a float4 (16-byte aligned), V = 1 a float.  An elementwise kernel
+// indexes its vectors with Idx<V>: 32 bits at V = 4, where a thread pays one 32-bit remainder per FOUR elements (vec4_ok is what
+// guarantees the range), 64 bits at V = 1.
+template <int V> struct alignas(4 * V) Vf { float e[V]; };
+template <int V> using Idx = std::conditional_t<V == 4, uint32_t, long>;
+template <int V> __device__ __forceinline__ Vf<V> ldv(const float *p) { return *reinterpret_cast<const Vf<V> *>(p); }
+template <int V> __device__ __forceinline__ void stv(float *p, const Vf<V> &v) { *reinterpret_cast<Vf<V> *>(p) = v; }
+
+// end of a column-reduction block (C*R threads, thread = (column c, row lane r)): fixed-order sum of the R lanes' two fp64
+// accumulators through LDS (red: 2*R*C doubles) -> part_row[c], part_row[C + c]
+__device__ __forceinline__ void col_reduce_store(double *red, int C, int R, int c, int r, double s, double q, float *__restrict__ part_row) {
+    red[r * C + c] = s; red[(R + r) * C + c] = q;
+    __syncthreads();
+    if (r == 0) {
+        double a = 0.0, b = 0.0;
+        for (int i = 0; i < R; ++i) { a += red[i * C + c]; b += red[(R + i) * C + c]; }
+        part_row[c] = (float)a;
+        part_row[C + c] = (float)b;
+    }
+}
 // Column reductions over a tall (M, C) matrix with ANY C <= 1024: a block has C*R threads, thread t owns column t % C and rows
 // r0 + t / C (+R, +2R, ...), so consecutive threads read consecutive addresses whatever C is (a 64-column tiling would
 // leave 3/4 of the lanes idle at C = 16); one block per row chunk, partials finished in fixed order afterwards.
@@ -49,14 +61,7 @@ __global__ __launch_bounds__(1024) void k_colstats(const float *__restrict__ x, 
         for (int u = 0; u < 8; ++u)
             if (rb + (long)u * R < r1) { const double d = v[u]; s += d; q += d * d; }
     }
-    red[r * C + c] = s; red[(R + r) * C + c] = q;
-    __syncthreads();
-    if (r == 0) {
-        double a = 0.0, b = 0.0;
-        for (int i = 0; i < R; ++i) { a += red[i * C + c]; b += red[(R + i) * C + c]; }
-        part[(long)blockIdx.x * 2 * C + c] = (float)a;
-        part[(long)blockIdx.x * 2 * C + C + c] = (float)b;
-    }
+    col_reduce_store(red, C, R, c, r, s, q, part + (long)blockIdx.x * 2 * C);
 }
 // fixed-order sum of the chunk partials of 64 columns by 16 row lanes: tot0/tot1 valid in the threads with p == 0.  A lane's
 // <= 16 partial rows (chunks <= NCHUNK = 256) are loaded in ONE batch before the first add: as a load -> add loop the finish
@@ -85,6 +90,27 @@ __device__ __forceinline__ void chunk_sums(const float *__restrict__ part, int c
         for (int i = 0; i < 16; ++i) { tot0 += sh[0][i][c]; tot1 += sh[1][i][c]; }
     }
 }
+// Per-channel BatchNorm finalisation in fp64: batch mean and clamped variance from the channel's sums s, q over M rows (training)
+// or the running statistics (eval), rstd, scale = gamma * rstd and shift = beta - mean * scale.  The passes use
+// y = x * scale + shift and xhat = (x - mean) * rstd.
+struct BnStat { double mean, var, rstd, scale; };
+__device__ __forceinline__ BnStat bn_stat(const ww_bn_t &bn, bool training, long M, double s, double q, float g_c, float rm_c, float rv_c) {
+    BnStat k = {rm_c, rv_c, 0.0, 0.0};
+    if (training) {
+        k.mean = s / (double)M;
+        k.var = q / (double)M - k.mean * k.mean;
+        if (k.var < 0.0) k.var = 0.0;
+    }
+    k.rstd = 1.0 / sqrt(k.var + (double)bn.eps);
+    k.scale = (double)g_c * k.rstd;
+    return k;
+}
+// torch's running-statistics update (momentum, unbiased variance); rm_c, rv_c: the values before it
+__device__ __forceinline__ void bn_update_running(const ww_bn_t &bn, int c, long M, const BnStat &k, float rm_c, float rv_c) {
+    const double m = bn.momentum, unb = M > 1 ? k.var * (double)M / (double)(M - 1) : k.var;
+    bn.running_mean[c] = (float)((1.0 - m) * (double)rm_c + m * k.mean);
+    bn.running_var[c] = (float)((1.0 - m) * (double)rv_c + m * unb);
+}
 // BatchNorm2d statistics -> scale|shift (ss) and mean|rstd (mr); torch semantics for the running statistics.
 // grid ceil(C/64), block 1024 (64 columns x 16 chunk lanes)
 __global__ __launch_bounds__(1024) void k_bn_finish(const float *__restrict__ part, int chunks, long M, int C, ww_bn_t bn,
@@ -100,69 +126,52 @@ __global__ __launch_bounds__(1024) void k_bn_finish(const float *__restrict__ pa
     double s = 0.0, q = 0.0;
     if (bn.training) chunk_sums(part, chunks, C, c, p, cl, sh, s, q);
     if (p != 0 || c >= C) return;
-    double mean, var;
-    if (bn.training) {
-        mean = s / (double)M;
-        var = q / (double)M - mean * mean;
-        if (var < 0.0) var = 0.0;
-        if (bn.running_mean) {
-            const double m = bn.momentum, unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
-            bn.running_mean[c] = (float)((1.0 - m) * (double)rm_c + m * mean);
-            bn.running_var[c] = (float)((1.0 - m) * (double)rv_c + m * unb);
-        }
-    } else {
-        mean = rm_c;
-        var = rv_c;
-    }
-    const double rstd = 1.0 / sqrt(var + (double)bn.eps), scale = (double)g_c * rstd;
-    ss[c] = (float)scale;
-    ss[C + c] = (float)((double)b_c - mean * scale);
-    mr[c] = (float)mean;
-    mr[C + c] = (float)rstd;
+    const BnStat k = bn_stat(bn, bn.training, M, s, q, g_c, rm_c, rv_c);
+    if (bn.training && bn.running_mean) bn_update_running(bn, c, M, k, rm_c, rv_c);
+    ss[c] = (float)k.scale; ss[C + c] = (float)((double)b_c - k.mean * k.scale);
+    mr[c] = (float)k.mean; mr[C + c] = (float)k.rstd;
 }
-__global__ __launch_bounds__(256) void k_bn_act_apply(const float *__restrict__ x, const float *__restrict__ ss, long n, int C,
+// y = act(x * scale[c] + shift[c]) over nv vectors of V floats
+template <int V>
+__global__ __launch_bounds__(256) void k_bn_act_apply(Idx<V> nv, const float *__restrict__ x, const float *__restrict__ ss, int C,
                                                       int act, float *__restrict__ y) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % C);
-        y[i] = act_fwd(act, fmaf(x[i], ss[c], ss[C + c]));
-    }
-}
-// the elementwise passes for C % 4 == 0 (every MobileNetV3 layer): a thread moves float4s, the channel index comes from a 32-bit
-// remainder per FOUR elements (the scalar forms pay a 64-bit one per element); same arithmetic per element, same bits
-__global__ __launch_bounds__(256) void k_bn_act_apply4(const float4 *__restrict__ x, const float *__restrict__ ss, uint32_t n4,
-                                                       int C, int act, float4 *__restrict__ y) {
-    const uint32_t C4 = (uint32_t)C >> 2;
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
-        const int c = (int)(i % C4) * 4;
-        const float4 v = x[i], sc = *reinterpret_cast<const float4 *>(ss + c), sf = *reinterpret_cast<const float4 *>(ss + C + c);
-        y[i] = make_float4(act_fwd(act, fmaf(v.x, sc.x, sf.x)), act_fwd(act, fmaf(v.y, sc.y, sf.y)),
-                           act_fwd(act, fmaf(v.z, sc.z, sf.z)), act_fwd(act, fmaf(v.w, sc.w, sf.w)));
+    typedef Idx<V> I;
+    const I CV = (I)C / V;
+    for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < nv; i += (I)gridDim.x * 256) {
+        const int c = (int)(i % CV) * V;
+        const Vf<V> v = ldv<V>(x + (size_t)i * V), sc = ldv<V>(ss + c), sf = ldv<V>(ss + C + c);
+        Vf<V> o;
+#pragma unroll
+        for (int e = 0; e < V; ++e) o.e[e] = lin_act(act, fmaf(v.e[e], sc.e[e], sf.e[e]));
+        stv<V>(y + (size_t)i * V, o);
     }
 }
 __device__ __forceinline__ float bnact_bwd_one(float xv, float dav, float sc, float sf, float mu, float rs, float s1, float s2,
                                                float invM, int act, int training) {
-    const float dz = dav * act_grad(act, fmaf(xv, sc, sf));
+    const float dz = dav * lin_act_grad(act, fmaf(xv, sc, sf));
     if (!training) return sc * dz;
     const float xh = (xv - mu) * rs;
     return sc * (dz - s1 * invM - xh * s2 * invM);
 }
-__global__ __launch_bounds__(256) void k_bnact_bwd_apply4(const float4 *__restrict__ x, const float4 *__restrict__ da,
-                                                          const float *__restrict__ ss, const float *__restrict__ mr,
-                                                          const float *__restrict__ sums, long M, uint32_t n4, int C, int act,
-                                                          int training, float4 *__restrict__ dx) {
-    const uint32_t C4 = (uint32_t)C >> 2;
+// backward pass 2: dx = gamma*rstd*(dz - mean(dz) - xhat*mean(dz*xhat))   (training);  eval: dx = scale*dz
+template <int V>
+__global__ __launch_bounds__(256) void k_bnact_bwd_apply(Idx<V> nv, const float *__restrict__ x, const float *__restrict__ da,
+                                                         const float *__restrict__ ss, const float *__restrict__ mr,
+                                                         const float *__restrict__ sums, long M, int C, int act, int training,
+                                                         float *__restrict__ dx) {
+    typedef Idx<V> I;
+    const I CV = (I)C / V;
     const float invM = 1.0f / (float)M;
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
-        const int c = (int)(i % C4) * 4;
-        const float4 xv = x[i], dv = da[i];
-        const float4 sc = *reinterpret_cast<const float4 *>(ss + c), sf = *reinterpret_cast<const float4 *>(ss + C + c);
-        const float4 mu = *reinterpret_cast<const float4 *>(mr + c), rs = *reinterpret_cast<const float4 *>(mr + C + c);
-        float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
-        if (training) { s1 = *reinterpret_cast<const float4 *>(sums + c); s2 = *reinterpret_cast<const float4 *>(sums + C + c); }
-        dx[i] = make_float4(bnact_bwd_one(xv.x, dv.x, sc.x, sf.x, mu.x, rs.x, s1.x, s2.x, invM, act, training),
-                            bnact_bwd_one(xv.y, dv.y, sc.y, sf.y, mu.y, rs.y, s1.y, s2.y, invM, act, training),
-                            bnact_bwd_one(xv.z, dv.z, sc.z, sf.z, mu.z, rs.z, s1.z, s2.z, invM, act, training),
-                            bnact_bwd_one(xv.w, dv.w, sc.w, sf.w, mu.w, rs.w, s1.w, s2.w, invM, act, training));
+    for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < nv; i += (I)gridDim.x * 256) {
+        const int c = (int)(i % CV) * V;
+        const Vf<V> xv = ldv<V>(x + (size_t)i * V), dv = ldv<V>(da + (size_t)i * V);
+        const Vf<V> sc = ldv<V>(ss + c), sf = ldv<V>(ss + C + c), mu = ldv<V>(mr + c), rs = ldv<V>(mr + C + c);
+        Vf<V> s1 = {}, s2 = {}, o;
+        if (training) { s1 = ldv<V>(sums + c); s2 = ldv<V>(sums + C + c); }
+#pragma unroll
+        for (int e = 0; e < V; ++e)
+            o.e[e] = bnact_bwd_one(xv.e[e], dv.e[e], sc.e[e], sf.e[e], mu.e[e], rs.e[e], s1.e[e], s2.e[e], invM, act, training);
+        stv<V>(dx + (size_t)i * V, o);
     }
 }
 // backward pass 1: dz = da * act'(z); partial sums of dz and dz*xhat (same thread layout as k_colstats)
@@ -184,19 +193,12 @@ __global__ __launch_bounds__(1024) void k_bnact_bwd_stats(const float *__restric
 #pragma unroll
         for (int u = 0; u < 8; ++u)
             if (rb + (long)u * R < r1) {
-                const float dz = dv[u] * act_grad(act, fmaf(xv[u], sc, sf));
+                const float dz = dv[u] * lin_act_grad(act, fmaf(xv[u], sc, sf));
                 s1 += dz;
                 s2 += (double)dz * (double)((xv[u] - mu) * rs);
             }
     }
-    red[r * C + c] = s1; red[(R + r) * C + c] = s2;
-    __syncthreads();
-    if (r == 0) {
-        double a = 0.0, b = 0.0;
-        for (int i = 0; i < R; ++i) { a += red[i * C + c]; b += red[(R + i) * C + c]; }
-        part[(long)blockIdx.x * 2 * C + c] = (float)a;
-        part[(long)blockIdx.x * 2 * C + C + c] = (float)b;
-    }
+    col_reduce_store(red, C, R, c, r, s1, s2, part + (long)blockIdx.x * 2 * C);
 }
 __global__ __launch_bounds__(1024) void k_bnact_bwd_finish(const float *__restrict__ part, int chunks, int C,
                                                            float *__restrict__ sums, float *__restrict__ dgamma,
@@ -208,25 +210,6 @@ __global__ __launch_bounds__(1024) void k_bnact_bwd_finish(const float *__restri
     if (p != 0 || c >= C) return;
     sums[c] = (float)s1; sums[C + c] = (float)s2;
     dgamma[c] = (float)s2; dbeta[c] = (float)s1;
-}
-// backward pass 2: dx = gamma*rstd*(dz - mean(dz) - xhat*mean(dz*xhat))   (training);  eval: dx = scale*dz
-__global__ __launch_bounds__(256) void k_bnact_bwd_apply(const float *__restrict__ x, const float *__restrict__ da,
-                                                         const float *__restrict__ ss, const float *__restrict__ mr,
-                                                         const float *__restrict__ sums, long M, int C, int act, int training,
-                                                         float *__restrict__ dx) {
-    const long n = M * C;
-    const float invM = 1.0f / (float)M;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % C);
-        const float xv = x[i], sc = ss[c];
-        const float dz = da[i] * act_grad(act, fmaf(xv, sc, ss[C + c]));
-        if (training) {
-            const float xh = (xv - mr[c]) * mr[C + c];
-            dx[i] = sc * (dz - sums[c] * invM - xh * sums[C + c] * invM);
-        } else {
-            dx[i] = sc * dz;
-        }
-    }
 }
 
 // ---- BatchNorm apply pass that FINISHES the statistics itself, for layers whose PRODUCER (the 1x1-convolution GEMM's epilogue,
@@ -286,21 +269,14 @@ __global__ __launch_bounds__(256) void k_bn_act_apply_fin(const float *__restric
     }
     bn_group_totals(part, chunks, C, c0, t.CG4, tot, redd);
     if (fin) {
-        const int c = c0 + threadIdx.x;
-        const double mean = tot[threadIdx.x] / (double)M;
-        double var = tot[CG + threadIdx.x] / (double)M - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const double rstd = 1.0 / sqrt(var + (double)bn.eps), scale = (double)g_c * rstd;
-        const float scf = (float)scale, shf = (float)((double)b_c - mean * scale);
+        const BnStat k = bn_stat(bn, true, M, tot[threadIdx.x], tot[CG + threadIdx.x], g_c, rm_c, rv_c);
+        const float scf = (float)k.scale, shf = (float)((double)b_c - k.mean * k.scale);
         scsh[threadIdx.x] = scf; scsh[CG + threadIdx.x] = shf;
         if (rc == 0) {
+            const int c = c0 + threadIdx.x;
             ss[c] = scf; ss[C + c] = shf;
-            mr[c] = (float)mean; mr[C + c] = (float)rstd;
-            if (bn.running_mean) {
-                const double m = bn.momentum, unb = M > 1 ? var * (double)M / (double)(M - 1) : var;
-                bn.running_mean[c] = (float)((1.0 - m) * (double)rm_c + m * mean);
-                bn.running_var[c] = (float)((1.0 - m) * (double)rv_c + m * unb);
-            }
+            mr[c] = (float)k.mean; mr[C + c] = (float)k.rstd;
+            if (bn.running_mean) bn_update_running(bn, c, M, k, rm_c, rv_c);
         }
     }
     __syncthreads();
@@ -321,8 +297,8 @@ __global__ __launch_bounds__(256) void k_bn_act_apply_fin(const float *__restric
         for (int u = 0; u < 4; ++u)
             if (rb + (long)u * t.R < r1)
                 *reinterpret_cast<float4 *>(y + (size_t)(rb + (long)u * t.R) * C + col) =
-                    make_float4(act_fwd(act, fmaf(v[u].x, sc.x, sf.x)) + rv[u].x, act_fwd(act, fmaf(v[u].y, sc.y, sf.y)) + rv[u].y,
-                                act_fwd(act, fmaf(v[u].z, sc.z, sf.z)) + rv[u].z, act_fwd(act, fmaf(v[u].w, sc.w, sf.w)) + rv[u].w);
+                    make_float4(lin_act(act, fmaf(v[u].x, sc.x, sf.x)) + rv[u].x, lin_act(act, fmaf(v[u].y, sc.y, sf.y)) + rv[u].y,
+                                lin_act(act, fmaf(v[u].z, sc.z, sf.z)) + rv[u].z, lin_act(act, fmaf(v[u].w, sc.w, sf.w)) + rv[u].w);
     }
 }
 
@@ -374,135 +350,45 @@ __global__ __launch_bounds__(256) void k_bnact_bwd_apply_fin(const float *__rest
     }
 }
 
-// ---- depthwise k x k, stride s, padding k/2.  thread = (output pixel, 4 channels); w (C,1,k,k) as in nn.Conv2d
-struct DwG { int B, H, W, C, k, s, Ho, Wo; };
+// ---- depthwise k x k, stride s, padding k/2; w (C,1,k,k) as in nn.Conv2d.  Gather kernels: thread = (pixel, V channels),
+// templated on the kernel size K and the vector width V; the layer's weights sit in LDS transposed to [tap][C] (one LDS read
+// per tap).  Every tap's vector is loaded UNCONDITIONALLY from clamped coordinates and an out-of-range tap is dropped by the
+// accumulation only: a guarded load (a `continue` per tap) compiles to a branch and a wait around every load -- up to 25
+// dependent L2 round trips per output, 20-40 us for tensors of a few MB; this way a thread has all k*k loads in flight at once.
+// Tensors have < 2^31 elements (host check): 32-bit index arithmetic.
+struct DwG { int B, H, W, C, s, Ho, Wo; };
+template <int K>
+__device__ __forceinline__ void dwg_stage_weights(const float *__restrict__ w, int C, float *wl) {
+    for (int i = threadIdx.x; i < C * K * K; i += 256) wl[(i % (K * K)) * C + i / (K * K)] = w[i];
+    __syncthreads();
+}
+template <int K, int V>
 __global__ __launch_bounds__(256) void k_dwg_fwd(const float *__restrict__ x, const float *__restrict__ w, DwG g,
                                                  float *__restrict__ y) {
-    extern __shared__ __align__(16) float wl[];      // the layer's weights, transposed to [tap][C]: one ds_read_b128 per tap
-    const int c4n = (g.C + 3) / 4, pad = g.k / 2, kk = g.k * g.k;
-    const bool vec = (g.C & 3) == 0;
-    for (int i = threadIdx.x; i < g.C * kk; i += 256) wl[(i % kk) * g.C + i / kk] = w[i];
-    __syncthreads();
-    const uint32_t n = (uint32_t)g.B * g.Ho * g.Wo * c4n;      // < 2^31 (host check): 32-bit index arithmetic
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-        uint32_t p = i / (uint32_t)c4n;
-        const int cq = (int)(i - p * c4n);
-        uint32_t q = p / (uint32_t)g.Wo;
-        const int wo = (int)(p - q * g.Wo);
-        const int b = (int)(q / (uint32_t)g.Ho);
-        const int ho = (int)(q - (uint32_t)b * g.Ho);
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int kh = 0; kh < g.k; ++kh) {
-            const int hi = ho * g.s + kh - pad;
-            if (hi < 0 || hi >= g.H) continue;
-            for (int kw = 0; kw < g.k; ++kw) {
-                const int wi = wo * g.s + kw - pad;
-                if (wi < 0 || wi >= g.W) continue;
-                const float *xp = x + (((size_t)b * g.H + hi) * g.W + wi) * g.C + 4 * cq;
-                if (vec) {
-                    const float4 xv = *reinterpret_cast<const float4 *>(xp);
-                    const float4 wv = *reinterpret_cast<const float4 *>(wl + (kh * g.k + kw) * g.C + 4 * cq);
-                    acc[0] = fmaf(xv.x, wv.x, acc[0]); acc[1] = fmaf(xv.y, wv.y, acc[1]);
-                    acc[2] = fmaf(xv.z, wv.z, acc[2]); acc[3] = fmaf(xv.w, wv.w, acc[3]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (4 * cq + e < g.C) acc[e] = fmaf(xp[e], wl[(kh * g.k + kw) * g.C + 4 * cq + e], acc[e]);
-                }
-            }
-        }
-        float *yp = y + (((size_t)b * g.Ho + ho) * g.Wo + wo) * g.C + 4 * cq;
-        if (vec) {
-            *reinterpret_cast<float4 *>(yp) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (4 * cq + e < g.C) yp[e] = acc[e];
-        }
-    }
-}
-// dx[b,hi,wi,c] = sum over taps with (hi + pad - kh) divisible by s of w[c,kh,kw] * dy[b,(hi+pad-kh)/s,(wi+pad-kw)/s,c]
-__global__ __launch_bounds__(256) void k_dwg_bwd_dx(const float *__restrict__ dy, const float *__restrict__ w, DwG g,
-                                                    float *__restrict__ dx) {
-    extern __shared__ __align__(16) float wl[];      // weights as [tap][C]
-    const int c4n = (g.C + 3) / 4, pad = g.k / 2, kk = g.k * g.k;
-    const bool vec = (g.C & 3) == 0;
-    for (int i = threadIdx.x; i < g.C * kk; i += 256) wl[(i % kk) * g.C + i / kk] = w[i];
-    __syncthreads();
-    const uint32_t n = (uint32_t)g.B * g.H * g.W * c4n;        // < 2^31 (host check): 32-bit index arithmetic
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-        uint32_t p = i / (uint32_t)c4n;
-        const int cq = (int)(i - p * c4n);
-        uint32_t q = p / (uint32_t)g.W;
-        const int wi = (int)(p - q * g.W);
-        const int b = (int)(q / (uint32_t)g.H);
-        const int hi = (int)(q - (uint32_t)b * g.H);
-        float acc[4] = {0.f, 0.f, 0.f, 0.f};
-        for (int kh = 0; kh < g.k; ++kh) {
-            const int th = hi + pad - kh;
-            if (th < 0 || th % g.s) continue;
-            const int ho = th / g.s;
-            if (ho >= g.Ho) continue;
-            for (int kw = 0; kw < g.k; ++kw) {
-                const int tw = wi + pad - kw;
-                if (tw < 0 || tw % g.s) continue;
-                const int wo = tw / g.s;
-                if (wo >= g.Wo) continue;
-                const float *dp = dy + (((size_t)b * g.Ho + ho) * g.Wo + wo) * g.C + 4 * cq;
-                if (vec) {
-                    const float4 dv = *reinterpret_cast<const float4 *>(dp);
-                    const float4 wv = *reinterpret_cast<const float4 *>(wl + (kh * g.k + kw) * g.C + 4 * cq);
-                    acc[0] = fmaf(dv.x, wv.x, acc[0]); acc[1] = fmaf(dv.y, wv.y, acc[1]);
-                    acc[2] = fmaf(dv.z, wv.z, acc[2]); acc[3] = fmaf(dv.w, wv.w, acc[3]);
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (4 * cq + e < g.C) acc[e] = fmaf(dp[e], wl[(kh * g.k + kw) * g.C + 4 * cq + e], acc[e]);
-                }
-            }
-        }
-        float *xp = dx + (((size_t)b * g.H + hi) * g.W + wi) * g.C + 4 * cq;
-        if (vec) {
-            *reinterpret_cast<float4 *>(xp) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (4 * cq + e < g.C) xp[e] = acc[e];
-        }
-    }
-}
-// C % 4 == 0 forms of the two gathers, templated on the kernel size: every tap's float4 is loaded UNCONDITIONALLY from clamped
-// coordinates and an out-of-range tap is zeroed by a select afterwards.  The guarded form above (a `continue` per tap) compiles
-// to a branch and a wait around every load -- up to 25 dependent L2 round trips per output, 20-40 us for tensors of a few MB;
-// this way a thread has all k*k loads in flight at once.  Same products in the same (kh, kw) order: the same bits.
-template <int K>
-__global__ __launch_bounds__(256) void k_dwg_fwd4(const float *__restrict__ x, const float *__restrict__ w, DwG g,
-                                                  float *__restrict__ y) {
     extern __shared__ __align__(16) float wl[];      // [tap][C]
     constexpr int KK = K * K, PAD = K / 2;
-    const int c4n = g.C >> 2;
-    for (int i = threadIdx.x; i < g.C * KK; i += 256) wl[(i % KK) * g.C + i / KK] = w[i];
-    __syncthreads();
-    const uint32_t n = (uint32_t)g.B * g.Ho * g.Wo * c4n;
+    const int cvn = g.C / V;
+    dwg_stage_weights<K>(w, g.C, wl);
+    const uint32_t n = (uint32_t)g.B * g.Ho * g.Wo * cvn;
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-        uint32_t p = i / (uint32_t)c4n;
-        const int cq = (int)(i - p * c4n);
+        uint32_t p = i / (uint32_t)cvn;
+        const int cq = (int)(i - p * cvn);
         uint32_t q = p / (uint32_t)g.Wo;
         const int wo = (int)(p - q * g.Wo);
         const int b = (int)(q / (uint32_t)g.Ho);
         const int ho = (int)(q - (uint32_t)b * g.Ho);
-        const float *xb = x + (size_t)b * g.H * g.W * g.C + 4 * cq;
-        float4 xv[KK];
+        const float *xb = x + (size_t)b * g.H * g.W * g.C + V * cq;
+        Vf<V> xv[KK];
 #pragma unroll
         for (int kh = 0; kh < K; ++kh) {
             const int hi = min(max(ho * g.s + kh - PAD, 0), g.H - 1);
 #pragma unroll
             for (int kw = 0; kw < K; ++kw) {
                 const int wi = min(max(wo * g.s + kw - PAD, 0), g.W - 1);
-                xv[kh * K + kw] = *reinterpret_cast<const float4 *>(xb + (uint32_t)((hi * g.W + wi) * g.C));
+                xv[kh * K + kw] = ldv<V>(xb + (uint32_t)((hi * g.W + wi) * g.C));
             }
         }
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        Vf<V> acc = {};
 #pragma unroll
         for (int kh = 0; kh < K; ++kh) {
             const int hi = ho * g.s + kh - PAD;
@@ -510,34 +396,33 @@ __global__ __launch_bounds__(256) void k_dwg_fwd4(const float *__restrict__ x, c
             for (int kw = 0; kw < K; ++kw) {
                 const int wi = wo * g.s + kw - PAD;
                 if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) {
-                    const float4 wv = *reinterpret_cast<const float4 *>(wl + (kh * K + kw) * g.C + 4 * cq);
-                    const float4 v = xv[kh * K + kw];
-                    acc.x = fmaf(v.x, wv.x, acc.x); acc.y = fmaf(v.y, wv.y, acc.y);
-                    acc.z = fmaf(v.z, wv.z, acc.z); acc.w = fmaf(v.w, wv.w, acc.w);
+                    const Vf<V> wv = ldv<V>(wl + (kh * K + kw) * g.C + V * cq), v = xv[kh * K + kw];
+#pragma unroll
+                    for (int e = 0; e < V; ++e) acc.e[e] = fmaf(v.e[e], wv.e[e], acc.e[e]);
                 }
             }
         }
-        *reinterpret_cast<float4 *>(y + (size_t)p * g.C + 4 * cq) = acc;
+        stv<V>(y + (size_t)p * g.C + V * cq, acc);
     }
 }
-template <int K>
-__global__ __launch_bounds__(256) void k_dwg_bwd_dx4(const float *__restrict__ dy, const float *__restrict__ w, DwG g,
-                                                     float *__restrict__ dx) {
+// dx[b,hi,wi,c] = sum over taps with (hi + pad - kh) divisible by s of w[c,kh,kw] * dy[b,(hi+pad-kh)/s,(wi+pad-kw)/s,c]
+template <int K, int V>
+__global__ __launch_bounds__(256) void k_dwg_bwd_dx(const float *__restrict__ dy, const float *__restrict__ w, DwG g,
+                                                    float *__restrict__ dx) {
     extern __shared__ __align__(16) float wl[];      // [tap][C]
     constexpr int KK = K * K, PAD = K / 2;
-    const int c4n = g.C >> 2;
-    for (int i = threadIdx.x; i < g.C * KK; i += 256) wl[(i % KK) * g.C + i / KK] = w[i];
-    __syncthreads();
-    const uint32_t n = (uint32_t)g.B * g.H * g.W * c4n;
+    const int cvn = g.C / V;
+    dwg_stage_weights<K>(w, g.C, wl);
+    const uint32_t n = (uint32_t)g.B * g.H * g.W * cvn;
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-        uint32_t p = i / (uint32_t)c4n;
-        const int cq = (int)(i - p * c4n);
+        uint32_t p = i / (uint32_t)cvn;
+        const int cq = (int)(i - p * cvn);
         uint32_t q = p / (uint32_t)g.W;
         const int wi = (int)(p - q * g.W);
         const int b = (int)(q / (uint32_t)g.H);
         const int hi = (int)(q - (uint32_t)b * g.H);
-        const float *db = dy + (size_t)b * g.Ho * g.Wo * g.C + 4 * cq;
-        float4 dv[KK];
+        const float *db = dy + (size_t)b * g.Ho * g.Wo * g.C + V * cq;
+        Vf<V> dv[KK];
         uint32_t ok = 0;
 #pragma unroll
         for (int kh = 0; kh < K; ++kh) {
@@ -549,19 +434,19 @@ __global__ __launch_bounds__(256) void k_dwg_bwd_dx4(const float *__restrict__ d
                 const int tw = wi + PAD - kw, wo = g.s == 2 ? tw >> 1 : tw;
                 const bool okw = tw >= 0 && (g.s == 1 || !(tw & 1)) && wo < g.Wo;
                 const int woc = min(max(wo, 0), g.Wo - 1);
-                dv[kh * K + kw] = *reinterpret_cast<const float4 *>(db + (uint32_t)((hoc * g.Wo + woc) * g.C));
+                dv[kh * K + kw] = ldv<V>(db + (uint32_t)((hoc * g.Wo + woc) * g.C));
                 ok |= (uint32_t)(okh && okw) << (kh * K + kw);
             }
         }
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        Vf<V> acc = {};
 #pragma unroll
         for (int t = 0; t < KK; ++t)
             if (ok & (1u << t)) {
-                const float4 wv = *reinterpret_cast<const float4 *>(wl + t * g.C + 4 * cq);
-                acc.x = fmaf(dv[t].x, wv.x, acc.x); acc.y = fmaf(dv[t].y, wv.y, acc.y);
-                acc.z = fmaf(dv[t].z, wv.z, acc.z); acc.w = fmaf(dv[t].w, wv.w, acc.w);
+                const Vf<V> wv = ldv<V>(wl + t * g.C + V * cq);
+#pragma unroll
+                for (int e = 0; e < V; ++e) acc.e[e] = fmaf(dv[t].e[e], wv.e[e], acc.e[e]);
             }
-        *reinterpret_cast<float4 *>(dx + (size_t)p * g.C + 4 * cq) = acc;
+        stv<V>(dx + (size_t)p * g.C + V * cq, acc);
     }
 }
 // ---- small feature maps (H*W <= 128 pixels: the 5x19, 3x10 and 2x5 stages of MobileNetV3 at 40 x 151 inputs, 9 of its 11 depthwise
@@ -587,6 +472,24 @@ __device__ __forceinline__ void dwl_stage(const float *__restrict__ src, int B, 
                      "+v"(v[2].x), "+v"(v[2].y), "+v"(v[2].z), "+v"(v[2].w), "+v"(v[3].x), "+v"(v[3].y), "+v"(v[3].z), "+v"(v[3].w));
 #pragma unroll
         for (int u = 0; u < 4; ++u) slab[min(i0 + 256 * u, n - 1)] = v[u];
+    }
+}
+// end of a kernel whose threads = (channel float4 cq, pixel lane) hold float4 sums / sums of squares of their outputs: fixed-order
+// fp64 sum over the `lanes` lanes of a quad (lane l of quad cq is thread l * nq + cq; red: [2][256] float4) by the quad's
+// `owner` thread -> its row of BatchNorm statistics partials: part_row[c:c+4] = sums, part_row[C+c:C+c+4] = sums of squares
+__device__ __forceinline__ void stat_part_store(float4 *red, const float4 &s4, const float4 &q4, int lanes, int nq, int cq, bool owner,
+                                                float *__restrict__ part_row, int c, int C) {
+    red[threadIdx.x] = s4; red[256 + threadIdx.x] = q4;
+    __syncthreads();
+    if (owner) {
+        double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int q = 0; q < lanes; ++q) {
+            const float4 a = red[q * nq + cq], b = red[256 + q * nq + cq];
+            t[0] += a.x; t[1] += a.y; t[2] += a.z; t[3] += a.w; t[4] += b.x; t[5] += b.y; t[6] += b.z; t[7] += b.w;
+        }
+        float *o = part_row + c;
+        *reinterpret_cast<float4 *>(o) = make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
+        *reinterpret_cast<float4 *>(o + C) = make_float4((float)t[4], (float)t[5], (float)t[6], (float)t[7]);
     }
 }
 // BWD = false: y = conv(x);  BWD = true: dx = conv^T(dy).  `in` has (Hi, Wi) pixels per image, `out` (Hq, Wq).
@@ -653,21 +556,9 @@ __global__ __launch_bounds__(256) void k_dwl_conv(const float *__restrict__ in, 
                 q4.z = fmaf(acc.z, acc.z, q4.z); q4.w = fmaf(acc.w, acc.w, q4.w);
             }
         }
-    if (STATS) {
-        float4 *red = slab + (size_t)l.nimg * Hi * Wi * l.CC4;      // [2][256]
-        red[threadIdx.x] = s4; red[256 + threadIdx.x] = q4;
-        __syncthreads();
-        if (lane == 0 && c0q + cq < C4) {
-            double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (int q = 0; q < R; ++q) {
-                const float4 a = red[q * l.CC4 + cq], b = red[256 + q * l.CC4 + cq];
-                t[0] += a.x; t[1] += a.y; t[2] += a.z; t[3] += a.w; t[4] += b.x; t[5] += b.y; t[6] += b.z; t[7] += b.w;
-            }
-            float *o = stat_part + (size_t)grp * 2 * g.C + 4 * (c0q + cq);
-            *reinterpret_cast<float4 *>(o) = make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
-            *reinterpret_cast<float4 *>(o + g.C) = make_float4((float)t[4], (float)t[5], (float)t[6], (float)t[7]);
-        }
-    }
+    if (STATS)
+        stat_part_store(slab + (size_t)l.nimg * Hi * Wi * l.CC4, s4, q4, R, l.CC4, cq, lane == 0 && c0q + cq < C4,
+                        stat_part + (size_t)grp * 2 * g.C, 4 * (c0q + cq), g.C);
 }
 // weight gradient: x and dy slabs of the workgroup's images in LDS, thread = (tap, channel float4) summing over (image, output
 // pixel) in fixed order; part[image group][C*k*k], summed over the groups by the column-sum launch that follows.
@@ -705,108 +596,71 @@ __global__ __launch_bounds__(256) void k_dwl_dw(const float *__restrict__ x, con
     }
 }
 
-// dw[c][tap] partials over a chunk of output pixels (thread layout of k_colstats): part[chunk][C*k*k]
-__global__ __launch_bounds__(1024) void k_dwg_bwd_dw(const float *__restrict__ x, const float *__restrict__ dy, DwG g, int R,
-                                                     long px_per_chunk, float *__restrict__ part) {
-    extern __shared__ float redf[];           // [R][C]
-    const int c = threadIdx.x % g.C, r = threadIdx.x / g.C, pad = g.k / 2, kk = g.k * g.k;
-    const long P = (long)g.B * g.Ho * g.Wo;
-    const long p0 = (long)blockIdx.x * px_per_chunk, p1 = min(P, p0 + px_per_chunk);
-    float acc[25];
-#pragma unroll
-    for (int t = 0; t < 25; ++t) acc[t] = 0.f;
-    for (long p = p0 + r; p < p1; p += R) {
-        const int wo = (int)(p % g.Wo);
-        const long q = p / g.Wo;
-        const int ho = (int)(q % g.Ho), b = (int)(q / g.Ho);
-        const float d = dy[(size_t)p * g.C + c];
-#pragma unroll
-        for (int kh = 0; kh < 5; ++kh) {
-            const int hi = ho * g.s + kh - pad;
-            if (kh >= g.k || hi < 0 || hi >= g.H) continue;
-#pragma unroll
-            for (int kw = 0; kw < 5; ++kw) {
-                const int wi = wo * g.s + kw - pad;
-                if (kw >= g.k || wi < 0 || wi >= g.W) continue;
-                acc[kh * 5 + kw] = fmaf(d, x[(((size_t)b * g.H + hi) * g.W + wi) * g.C + c], acc[kh * 5 + kw]);
-            }
-        }
-    }
-    for (int kh = 0; kh < g.k; ++kh)
-        for (int kw = 0; kw < g.k; ++kw) {
-            __syncthreads();
-            float v = 0.f;                    // acc is indexed with compile-time constants only (no scratch)
-#pragma unroll
-            for (int a5 = 0; a5 < 25; ++a5) v = (a5 == kh * 5 + kw) ? acc[a5] : v;
-            redf[r * g.C + c] = v;
-            __syncthreads();
-            if (r == 0) {
-                float t = 0.f;
-                for (int i = 0; i < R; ++i) t += redf[i * g.C + c];
-                part[(size_t)blockIdx.x * g.C * kk + (size_t)c * kk + kh * g.k + kw] = t;
-            }
-        }
-}
-
-// the same for C % 4 == 0: a thread owns FOUR channels (float4 loads) and rows r, r+R, ...: block = (C/4)*R <= 512 threads.
-// Up to NCHUNK_DW blocks; 32-bit pixel arithmetic; the row lanes of a block are summed through LDS T taps at a time
-// (T * R * C floats <= 48 KB), each (tap, channel quad) by one thread in fixed order.  Templated on the kernel size; the k*k
-// input float4s of a pixel are loaded unconditionally from clamped coordinates (a guarded tap load is a branch + a wait: 25
-// dependent round trips per pixel in the first form) and out-of-range taps are skipped by the accumulation only.
-template <int K>
-__global__ __launch_bounds__(512) void k_dwg_bwd_dw4(const float *__restrict__ x, const float *__restrict__ dy, DwG g, int R,
-                                                     uint32_t px_per_chunk, int T, float *__restrict__ part) {
+// weight gradient of the gather path: dw[c][tap] partials over a chunk of output pixels, part[chunk][C*k*k] (summed over the
+// chunks by the column-sum launch that follows).  A thread owns V channels and the chunk's pixels r, r+R, ...: block = (C/V)*R
+// threads, <= 512 at V = 4 (100 accumulator registers per thread), <= 1024 at V = 1, where C itself may be up to 1024.  32-bit
+// pixel arithmetic; the row lanes of a block are summed through LDS T taps at a time (T * R * C floats <= 48 KB), each (tap,
+// channel vector) by one thread in fixed order.  The k*k input vectors of a pixel are loaded unconditionally from clamped
+// coordinates and out-of-range taps are skipped by the accumulation only.
+template <int K, int V>
+__global__ __launch_bounds__(V == 4 ? 512 : 1024) void k_dwg_bwd_dw(const float *__restrict__ x, const float *__restrict__ dy, DwG g,
+                                                                    int R, uint32_t px_per_chunk, int T, float *__restrict__ part) {
     extern __shared__ __align__(16) float redf[];           // [T][R][C]
     constexpr int KK = K * K, PAD = K / 2;
-    const int C4 = g.C / 4, cq = threadIdx.x % C4, r = threadIdx.x / C4;
+    const int CV = g.C / V, cq = threadIdx.x % CV, r = threadIdx.x / CV;
     const uint32_t P = (uint32_t)g.B * g.Ho * g.Wo;
     const uint32_t p0 = blockIdx.x * px_per_chunk, p1 = min(P, p0 + px_per_chunk);
-    float ax[KK], ay[KK], az[KK], aw[KK];       // plain arrays: an array of HIP float4 structs is not promoted to registers
+    float acc[V][KK];                           // plain arrays: an array of vector structs is not promoted to registers
 #pragma unroll
-    for (int t = 0; t < KK; ++t) { ax[t] = 0.f; ay[t] = 0.f; az[t] = 0.f; aw[t] = 0.f; }
+    for (int e = 0; e < V; ++e)
+#pragma unroll
+        for (int t = 0; t < KK; ++t) acc[e][t] = 0.f;
     for (uint32_t p = p0 + r; p < p1; p += R) {
         const uint32_t q = p / (uint32_t)g.Wo;
         const int wo = (int)(p - q * g.Wo);
         const uint32_t b = q / (uint32_t)g.Ho;
         const int ho = (int)(q - b * g.Ho);
-        const float4 d = *reinterpret_cast<const float4 *>(dy + (size_t)p * g.C + 4 * cq);
-        const float *xb = x + (size_t)b * g.H * g.W * g.C + 4 * cq;
+        const Vf<V> d = ldv<V>(dy + (size_t)p * g.C + V * cq);
+        const float *xb = x + (size_t)b * g.H * g.W * g.C + V * cq;
 #pragma unroll
         for (int kh = 0; kh < K; ++kh) {
             const int hi = ho * g.s + kh - PAD, hic = min(max(hi, 0), g.H - 1);
-            float4 xv[K];
+            Vf<V> xv[K];
 #pragma unroll
             for (int kw = 0; kw < K; ++kw) {
                 const int wic = min(max(wo * g.s + kw - PAD, 0), g.W - 1);
-                xv[kw] = *reinterpret_cast<const float4 *>(xb + (uint32_t)((hic * g.W + wic) * g.C));
+                xv[kw] = ldv<V>(xb + (uint32_t)((hic * g.W + wic) * g.C));
             }
 #pragma unroll
             for (int kw = 0; kw < K; ++kw) {
                 const int wi = wo * g.s + kw - PAD;
                 if (hi >= 0 && hi < g.H && wi >= 0 && wi < g.W) {
-                    const int t = kh * K + kw;
-                    ax[t] = fmaf(d.x, xv[kw].x, ax[t]); ay[t] = fmaf(d.y, xv[kw].y, ay[t]);
-                    az[t] = fmaf(d.z, xv[kw].z, az[t]); aw[t] = fmaf(d.w, xv[kw].w, aw[t]);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) acc[e][kh * K + kw] = fmaf(d.e[e], xv[kw].e[e], acc[e][kh * K + kw]);
                 }
             }
         }
     }
     int slot = 0, base = 0;                     // taps base .. base + slot - 1 (in (kh, kw) order) sit in LDS
-    float *outp = part + (size_t)blockIdx.x * g.C * KK + (size_t)(4 * cq) * KK;
+    float *outp = part + (size_t)blockIdx.x * g.C * KK + (size_t)(V * cq) * KK;
 #pragma unroll
     for (int t5 = 0; t5 < KK; ++t5) {           // compile-time: the accumulators are read by constant index
-        *reinterpret_cast<float4 *>(redf + ((size_t)slot * R + r) * g.C + 4 * cq) = make_float4(ax[t5], ay[t5], az[t5], aw[t5]);
+        Vf<V> a;
+#pragma unroll
+        for (int e = 0; e < V; ++e) a.e[e] = acc[e][t5];
+        stv<V>(redf + ((size_t)slot * R + r) * g.C + V * cq, a);
         ++slot;
         if (slot == T || t5 == KK - 1) {
             __syncthreads();
             for (int sl = r; sl < slot; sl += R) {
-                float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+                Vf<V> t = {};
                 for (int i = 0; i < R; ++i) {
-                    const float4 u = *reinterpret_cast<const float4 *>(redf + ((size_t)sl * R + i) * g.C + 4 * cq);
-                    t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w;
+                    const Vf<V> u = ldv<V>(redf + ((size_t)sl * R + i) * g.C + V * cq);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) t.e[e] += u.e[e];
                 }
-                float *o = outp + base + sl;
-                o[0] = t.x; o[KK] = t.y; o[2 * KK] = t.z; o[3 * KK] = t.w;
+#pragma unroll
+                for (int e = 0; e < V; ++e) outp[base + sl + e * KK] = t.e[e];
             }
             __syncthreads();
             base += slot;
@@ -837,49 +691,54 @@ __global__ __launch_bounds__(1024) void k_pool_fwd(const float *__restrict__ x, 
         s[(size_t)b * C + c] = (float)(t / HW);
     }
 }
-// y = x * g[b][c]
-__global__ __launch_bounds__(256) void k_scale_fwd(const float *__restrict__ x, const float *__restrict__ gte, int B, int HW, int C,
-                                                   float *__restrict__ y) {
-    const long n = (long)B * HW * C;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % C);
-        const long b = i / ((long)HW * C);
-        y[i] = x[i] * gte[b * C + c];
+// y = x * g[b][c]     (HWCV: vectors per image)
+template <int V>
+__global__ __launch_bounds__(256) void k_scale_fwd(Idx<V> nv, const float *__restrict__ x, const float *__restrict__ gte, Idx<V> HWCV,
+                                                   int C, float *__restrict__ y) {
+    typedef Idx<V> I;
+    const I CV = (I)C / V;
+    for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < nv; i += (I)gridDim.x * 256) {
+        const I b = i / HWCV, c = (i % CV) * V;
+        const Vf<V> v = ldv<V>(x + (size_t)i * V), g = ldv<V>(gte + (size_t)b * C + c);
+        Vf<V> o;
+#pragma unroll
+        for (int e = 0; e < V; ++e) o.e[e] = v.e[e] * g.e[e];
+        stv<V>(y + (size_t)i * V, o);
     }
 }
-__global__ __launch_bounds__(256) void k_scale_fwd4(const float4 *__restrict__ x, const float *__restrict__ gte, uint32_t n4,
-                                                    uint32_t HWC4, int C, float4 *__restrict__ y) {
-    const uint32_t C4 = (uint32_t)C >> 2;
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
-        const uint32_t b = i / HWC4, c = (i % C4) * 4;
-        const float4 v = x[i], g = *reinterpret_cast<const float4 *>(gte + (size_t)b * C + c);
-        y[i] = make_float4(v.x * g.x, v.y * g.y, v.z * g.z, v.w * g.w);
-    }
-}
-__global__ __launch_bounds__(256) void k_scale_pool_bwd4(const float4 *__restrict__ dy, const float *__restrict__ gte,
-                                                         const float *__restrict__ dpool, uint32_t n4, uint32_t HWC4, int HW, int C,
-                                                         float4 *__restrict__ dx) {
-    const uint32_t C4 = (uint32_t)C >> 2;
+// dx = dy * g[b][c] + dpool[b][c] / HW     (dy nullable: plain pooling backward; dpool nullable: plain scaling backward)
+template <int V>
+__global__ __launch_bounds__(256) void k_scale_pool_bwd(Idx<V> nv, const float *__restrict__ dy, const float *__restrict__ gte,
+                                                        const float *__restrict__ dpool, Idx<V> HWCV, int HW, int C,
+                                                        float *__restrict__ dx) {
+    typedef Idx<V> I;
+    const I CV = (I)C / V;
     const float inv = 1.0f / (float)HW;
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
-        const uint32_t b = i / HWC4, c = (i % C4) * 4;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < nv; i += (I)gridDim.x * 256) {
+        const I b = i / HWCV, c = (i % CV) * V;
+        Vf<V> v = {};
         if (dy) {
-            const float4 d = dy[i], g = *reinterpret_cast<const float4 *>(gte + (size_t)b * C + c);
-            v = make_float4(d.x * g.x, d.y * g.y, d.z * g.z, d.w * g.w);
+            const Vf<V> d = ldv<V>(dy + (size_t)i * V), g = ldv<V>(gte + (size_t)b * C + c);
+#pragma unroll
+            for (int e = 0; e < V; ++e) v.e[e] = d.e[e] * g.e[e];
         }
         if (dpool) {
-            const float4 dp = *reinterpret_cast<const float4 *>(dpool + (size_t)b * C + c);
-            v = make_float4(fmaf(dp.x, inv, v.x), fmaf(dp.y, inv, v.y), fmaf(dp.z, inv, v.z), fmaf(dp.w, inv, v.w));
+            const Vf<V> dp = ldv<V>(dpool + (size_t)b * C + c);
+#pragma unroll
+            for (int e = 0; e < V; ++e) v.e[e] = fmaf(dp.e[e], inv, v.e[e]);
         }
-        dx[i] = v;
+        stv<V>(dx + (size_t)i * V, v);
     }
 }
-__global__ __launch_bounds__(256) void k_add4(const float4 *__restrict__ a, const float4 *__restrict__ b, uint32_t n4,
-                                              float4 *__restrict__ y) {
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n4; i += gridDim.x * 256u) {
-        const float4 u = a[i], v = b[i];
-        y[i] = make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w);
+template <int V>
+__global__ __launch_bounds__(256) void k_add(Idx<V> nv, const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ y) {
+    typedef Idx<V> I;
+    for (I i = (I)blockIdx.x * 256 + threadIdx.x; i < nv; i += (I)gridDim.x * 256) {
+        const Vf<V> u = ldv<V>(a + (size_t)i * V), v = ldv<V>(b + (size_t)i * V);
+        Vf<V> o;
+#pragma unroll
+        for (int e = 0; e < V; ++e) o.e[e] = u.e[e] + v.e[e];
+        stv<V>(y + (size_t)i * V, o);
     }
 }
 // dg[b][c] = sum_hw dy * x   (same thread map as k_pool_fwd)
@@ -901,20 +760,6 @@ __global__ __launch_bounds__(1024) void k_scale_bwd_gate(const float *__restrict
 #pragma unroll
         for (int i = 0; i < 16; ++i) t += sh[i][cl];
         dg[(size_t)b * C + c] = (float)t;
-    }
-}
-// dx = dy * g[b][c] + dpool[b][c] / HW     (dy nullable: plain pooling backward; dpool nullable: plain scaling backward)
-__global__ __launch_bounds__(256) void k_scale_pool_bwd(const float *__restrict__ dy, const float *__restrict__ gte,
-                                                        const float *__restrict__ dpool, int B, int HW, int C,
-                                                        float *__restrict__ dx) {
-    const long n = (long)B * HW * C;
-    const float inv = 1.0f / (float)HW;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int c = (int)(i % C);
-        const long b = i / ((long)HW * C);
-        float v = dy ? dy[i] * gte[b * C + c] : 0.f;
-        if (dpool) v = fmaf(dpool[b * C + c], inv, v);
-        dx[i] = v;
     }
 }
 // ---- the one-channel 3x3 stride-2 stem (Conv2d(1, C, 3, 2, 1), the first layer of MobileNetV3Wakeword) as a direct convolution.
@@ -943,7 +788,7 @@ __device__ __forceinline__ void stem_patch(const float *__restrict__ xb, const S
 // 256/C4 pixel lanes.  y (B,Ho,Wo,C); stat_part[block][2C] (nullable).
 __global__ __launch_bounds__(256) void k_stem3x3s2_fwd(const float *__restrict__ x, const float *__restrict__ w, StemG g,
                                                        float *__restrict__ y, float *__restrict__ stat_part) {
-    __shared__ __align__(16) float4 red[2][256];
+    __shared__ __align__(16) float4 red[2 * 256];
     const int C4 = g.C >> 2, cq = threadIdx.x % C4, lane = threadIdx.x / C4, L = 256 / C4;
     float wr[4][9];
 #pragma unroll
@@ -980,18 +825,7 @@ __global__ __launch_bounds__(256) void k_stem3x3s2_fwd(const float *__restrict__
             }
         }
     if (!stat_part) return;
-    red[0][threadIdx.x] = s4; red[1][threadIdx.x] = q4;
-    __syncthreads();
-    if (lane == 0) {
-        double t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int q = 0; q < L; ++q) {
-            const float4 a = red[0][q * C4 + cq], b = red[1][q * C4 + cq];
-            t[0] += a.x; t[1] += a.y; t[2] += a.z; t[3] += a.w; t[4] += b.x; t[5] += b.y; t[6] += b.z; t[7] += b.w;
-        }
-        float *o = stat_part + (size_t)blockIdx.x * 2 * g.C + 4 * cq;
-        *reinterpret_cast<float4 *>(o) = make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
-        *reinterpret_cast<float4 *>(o + g.C) = make_float4((float)t[4], (float)t[5], (float)t[6], (float)t[7]);
-    }
+    stat_part_store(red, s4, q4, L, C4, cq, lane == 0, stat_part + (size_t)blockIdx.x * 2 * g.C, 4 * cq, g.C);
 }
 // dW[c][t] = sum_p dy[p][c] * patch[p][t]: part[block][C*9] (summed over the blocks by the column-sum launch that follows)
 __global__ __launch_bounds__(256) void k_stem3x3s2_dw(const float *__restrict__ x, const float *__restrict__ dy, StemG g,
@@ -1053,24 +887,42 @@ __global__ __launch_bounds__(256) void k_im2col3x3s2(const float *__restrict__ x
         cols[i] = (hi >= 0 && hi < H && wi >= 0 && wi < W) ? x[((size_t)b * H + hi) * W + wi] : 0.f;
     }
 }
-__global__ __launch_bounds__(256) void k_add(const float *__restrict__ a, const float *__restrict__ b, long n, float *__restrict__ y) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) y[i] = a[i] + b[i];
-}
 
 inline int egrid(long n) { return (int)std::min<long>((n + 255) / 256, 256 * 32); }
+inline bool aligned16(std::initializer_list<const void *> ptrs) {            // every (non-null) pointer on the 16-byte grid
+    uintptr_t bits = 0;
+    for (const void *p : ptrs) bits |= (uintptr_t)p;
+    return (bits & 15) == 0;
+}
 // float4 form usable: channel count a multiple of 4, every base pointer 16-byte aligned, index fits 32 bits
 inline bool vec4_ok(long n, int C, std::initializer_list<const void *> ptrs) {
-    if ((C & 3) || (n & 3) || n / 4 >= (1L << 31)) return false;
-    for (const void *p : ptrs)
-        if ((uintptr_t)p & 15) return false;
-    return true;
+    return !(C & 3) && !(n & 3) && n / 4 < (1L << 31) && aligned16(ptrs);
 }
 inline int rows_r(int C) { return std::max(1, 1024 / C); }                       // row lanes R of a C*R-thread block
 inline int chunks_for(long M, int C) { return (int)std::max<long>(1, std::min<long>(NCHUNK, M / (4L * rows_r(C)))); }
 }  // namespace
 
+// an elementwise kernel template over n floats: kern<4> over n / 4 float4s when v4 (vec4_ok), else kern<1> over n floats
+#define WW_LAUNCH_EW(kern, v4, n, st, ...)                                                                                   \
+    do {                                                                                                                     \
+        if (v4) hipLaunchKernelGGL(kern<4>, dim3(egrid((n) / 4)), dim3(256), 0, st, (uint32_t)((n) / 4), __VA_ARGS__);       \
+        else hipLaunchKernelGGL(kern<1>, dim3(egrid(n)), dim3(256), 0, st, (long)(n), __VA_ARGS__);                         \
+    } while (0)
+// the instance of a depthwise kernel template for the layer's k (3 or 5: make_dwg); the other template arguments follow
+#define WW_DW_K(k, kern, ...) ((k) == 3 ? kern<3, __VA_ARGS__> : kern<5, __VA_ARGS__>)
+
 // scratch of one layer call: chunk partials (BatchNorm: 2C per chunk, depthwise weight gradient: up to 25C per chunk) + 2C sums
 extern "C" size_t ww_nhwc_scratch_bytes(int C) { return (size_t)(NCHUNK_DW * 25 + 2) * std::max(C, 1) * sizeof(float); }
+
+// `chunks` rows of statistics partials -> ss, mr (finish launch), then y = act(bn(x)) (apply launch)
+static int bn_finish_apply(const float *part, int chunks, const float *x, long M, int C, const ww_bn_t *bn, int act, float *y,
+                           float *ss, float *mr, hipStream_t st) {
+    hipLaunchKernelGGL(k_bn_finish, dim3((C + 63) / 64), dim3(1024), 0, st, part, chunks, M, C, *bn, ss, mr);
+    WW_LAUNCH_CHECK();
+    WW_LAUNCH_EW(k_bn_act_apply, vec4_ok(M * C, C, {x, y, ss}), M * C, st, x, (const float *)ss, C, act, y);
+    WW_LAUNCH_CHECK();
+    return WW_OK;
+}
 
 extern "C" int ww_bn_act_fwd(ww_ctx *ctx, const float *x, long M, int C, const ww_bn_t *bn, int act, float *y, float *ss,
                              float *mr, void *scratch, ww_stream_t stream) {
@@ -1089,15 +941,7 @@ extern "C" int ww_bn_act_fwd(ww_ctx *ctx, const float *x, long M, int C, const w
                            (M + chunks - 1) / chunks, part);
         WW_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(k_bn_finish, dim3((C + 63) / 64), dim3(1024), 0, st, part, chunks, M, C, *bn, ss, mr);
-    WW_LAUNCH_CHECK();
-    if (vec4_ok(M * C, C, {x, y, ss}))
-        hipLaunchKernelGGL(k_bn_act_apply4, dim3(egrid(M * C / 4)), dim3(256), 0, st, (const float4 *)x, ss, (uint32_t)(M * C / 4), C,
-                           act, (float4 *)y);
-    else
-        hipLaunchKernelGGL(k_bn_act_apply, dim3(egrid(M * C)), dim3(256), 0, st, x, ss, M * C, C, act, y);
-    WW_LAUNCH_CHECK();
-    return WW_OK;
+    return bn_finish_apply(part, chunks, x, M, C, bn, act, y, ss, mr, st);
 }
 
 // (row chunk, channel group) tiling of k_bn_act_apply_fin: the widest group (16, 8 or 4 channel float4s) whose re-read of the
@@ -1120,24 +964,16 @@ static BnTile bn_tile(long M, int C, int chunks) {
 int ww_bn_act_from_partials(ww_ctx *ctx, const float *x, long M, int C, const ww_bn_t *bn, int act, float *y, float *ss, float *mr,
                             const float *part, int chunks, const float *res, hipStream_t st) {
     WW_REQUIRE(C <= 1024 && chunks >= 1, WW_E_UNSUPPORTED, "ww_bn_act_from_partials: C=%d > 1024", C);
-    const bool v4 = vec4_ok(M * C, C, {x, y, part, res});
-    const BnTile t = v4 ? bn_tile(M, C, chunks) : BnTile{0, 0, 0, 0};
+    const BnTile t = vec4_ok(M * C, C, {x, y, part, res}) ? bn_tile(M, C, chunks) : BnTile{0, 0, 0, 0};
     if (t.CG4) {
         const int blocks = (int)((M + t.rows_per_block - 1) / t.rows_per_block) * t.G_c;
         hipLaunchKernelGGL(k_bn_act_apply_fin, dim3(blocks), dim3(256), 0, st, x, part, chunks, M, C, t, *bn, act, y, ss, mr, res);
         WW_LAUNCH_CHECK();
         return WW_OK;
     }
-    hipLaunchKernelGGL(k_bn_finish, dim3((C + 63) / 64), dim3(1024), 0, st, part, chunks, M, C, *bn, ss, mr);
-    WW_LAUNCH_CHECK();
-    if (v4)
-        hipLaunchKernelGGL(k_bn_act_apply4, dim3(egrid(M * C / 4)), dim3(256), 0, st, (const float4 *)x, ss, (uint32_t)(M * C / 4), C,
-                           act, (float4 *)y);
-    else
-        hipLaunchKernelGGL(k_bn_act_apply, dim3(egrid(M * C)), dim3(256), 0, st, x, ss, M * C, C, act, y);
-    WW_LAUNCH_CHECK();
-    if (res) return ww_add_f32(ctx, y, res, (size_t)(M * C), y, (ww_stream_t)st);      // tall layers: the add stays its own pass (in place)
-    return WW_OK;
+    const int rc = bn_finish_apply(part, chunks, x, M, C, bn, act, y, ss, mr, st);
+    if (rc || !res) return rc;
+    return ww_add_f32(ctx, y, res, (size_t)(M * C), y, (ww_stream_t)st);      // tall layers: the add stays its own pass (in place)
 }
 
 extern "C" int ww_bn_act_bwd(ww_ctx *ctx, const float *x, const float *da, long M, int C, const float *ss, const float *mr, int act,
@@ -1168,11 +1004,8 @@ extern "C" int ww_bn_act_bwd(ww_ctx *ctx, const float *x, const float *da, long 
     }
     hipLaunchKernelGGL(k_bnact_bwd_finish, dim3((C + 63) / 64), dim3(1024), 0, st, part, chunks, C, sums, dgamma, dbeta);
     WW_LAUNCH_CHECK();
-    if (vec4_ok(M * C, C, {x, da, dx, ss, mr, sums}))
-        hipLaunchKernelGGL(k_bnact_bwd_apply4, dim3(egrid(M * C / 4)), dim3(256), 0, st, (const float4 *)x, (const float4 *)da, ss,
-                           mr, sums, M, (uint32_t)(M * C / 4), C, act, training, (float4 *)dx);
-    else
-        hipLaunchKernelGGL(k_bnact_bwd_apply, dim3(egrid(M * C)), dim3(256), 0, st, x, da, ss, mr, sums, M, C, act, training, dx);
+    WW_LAUNCH_EW(k_bnact_bwd_apply, vec4_ok(M * C, C, {x, da, dx, ss, mr, sums}), M * C, st, x, da, ss, mr, (const float *)sums, M, C, act,
+                 training, dx);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
@@ -1194,7 +1027,7 @@ static bool dwl_plan(const DwG &g, size_t bytes_per_img_cc4, size_t budget, DwL 
 static int make_dwg(const char *who, int B, int H, int W, int C, int k, int s, DwG *g) {
     WW_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1, WW_E_INVALID, "%s: bad shape", who);
     WW_REQUIRE((k == 3 || k == 5) && (s == 1 || s == 2), WW_E_UNSUPPORTED, "%s: kernel %d stride %d not implemented", who, k, s);
-    g->B = B; g->H = H; g->W = W; g->C = C; g->k = k; g->s = s;
+    g->B = B; g->H = H; g->W = W; g->C = C; g->s = s;
     g->Ho = (H + 2 * (k / 2) - k) / s + 1;
     g->Wo = (W + 2 * (k / 2) - k) / s + 1;
     return WW_OK;
@@ -1209,18 +1042,15 @@ extern "C" int ww_dwconv_nhwc_fwd(ww_ctx *ctx, const float *x, const float *w, i
     const size_t wbytes = (size_t)C * k * k * sizeof(float);
     WW_REQUIRE(wbytes <= 64 * 1024, WW_E_UNSUPPORTED, "ww_dwconv_nhwc_fwd: C*k*k = %d weights do not fit the LDS cache", C * k * k);
     WW_REQUIRE((long)B * H * W * C < (1L << 31), WW_E_UNSUPPORTED, "ww_dwconv_nhwc_fwd: tensor too large for 32-bit indices");
-    const dim3 grid(egrid((long)B * g.Ho * g.Wo * ((C + 3) / 4)));
+    const bool v4 = (C & 3) == 0 && aligned16({x, y});
     DwL l;
-    if ((((uintptr_t)x | (uintptr_t)y) & 15) == 0 && dwl_plan(g, (size_t)H * W * 16, 40 * 1024, &l)) {
+    if (v4 && dwl_plan(g, (size_t)H * W * 16, 40 * 1024, &l)) {
         const dim3 lg((unsigned)((B + l.nimg - 1) / l.nimg) * l.G_c);
         const size_t lds = ((size_t)k * k * l.CC4 + (size_t)l.nimg * H * W * l.CC4) * 16;
-        if (k == 3) hipLaunchKernelGGL((k_dwl_conv<3, false, false>), lg, dim3(256), lds, (hipStream_t)stream, x, w, g, l, y, (float *)nullptr);
-        else hipLaunchKernelGGL((k_dwl_conv<5, false, false>), lg, dim3(256), lds, (hipStream_t)stream, x, w, g, l, y, (float *)nullptr);
-    } else if ((C & 3) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
-        if (k == 3) hipLaunchKernelGGL(k_dwg_fwd4<3>, grid, dim3(256), wbytes, (hipStream_t)stream, x, w, g, y);
-        else hipLaunchKernelGGL(k_dwg_fwd4<5>, grid, dim3(256), wbytes, (hipStream_t)stream, x, w, g, y);
+        hipLaunchKernelGGL(WW_DW_K(k, k_dwl_conv, false, false), lg, dim3(256), lds, (hipStream_t)stream, x, w, g, l, y, (float *)nullptr);
     } else {
-        hipLaunchKernelGGL(k_dwg_fwd, grid, dim3(256), wbytes, (hipStream_t)stream, x, w, g, y);
+        const dim3 grid(egrid((long)B * g.Ho * g.Wo * (C / (v4 ? 4 : 1))));
+        hipLaunchKernelGGL(v4 ? WW_DW_K(k, k_dwg_fwd, 4) : WW_DW_K(k, k_dwg_fwd, 1), grid, dim3(256), wbytes, (hipStream_t)stream, x, w, g, y);
     }
     WW_LAUNCH_CHECK();
     return WW_OK;
@@ -1235,15 +1065,14 @@ extern "C" int ww_dwconv_bn_act_fwd(ww_ctx *ctx, const float *x, const float *w,
     hipStream_t st = (hipStream_t)stream;
     const long M = (long)B * g.Ho * g.Wo;
     DwL l;
-    if (bn->training && (((uintptr_t)x | (uintptr_t)y | (uintptr_t)scratch) & 15) == 0 && dwl_plan(g, (size_t)H * W * 16, 40 * 1024, &l)) {
+    if (bn->training && aligned16({x, y, scratch}) && dwl_plan(g, (size_t)H * W * 16, 40 * 1024, &l)) {
         // the LDS kernel leaves one row of statistics partials per image group: conv + (finishing) apply = 2 launches
         ww_prof_scope ps_(ctx, WW_K_NHWC, st);
         const int groups = (B + l.nimg - 1) / l.nimg;
         const dim3 lg((unsigned)groups * l.G_c);
         const size_t lds = ((size_t)k * k * l.CC4 + (size_t)l.nimg * H * W * l.CC4 + 512) * 16;
         float *part = (float *)scratch;
-        if (k == 3) hipLaunchKernelGGL((k_dwl_conv<3, false, true>), lg, dim3(256), lds, st, x, w, g, l, y, part);
-        else hipLaunchKernelGGL((k_dwl_conv<5, false, true>), lg, dim3(256), lds, st, x, w, g, l, y, part);
+        hipLaunchKernelGGL(WW_DW_K(k, k_dwl_conv, false, true), lg, dim3(256), lds, st, x, w, g, l, y, part);
         WW_LAUNCH_CHECK();
         return ww_bn_act_from_partials(ctx, y, M, C, bn, act, a, ss, mr, part, groups, nullptr, st);
     }
@@ -1262,18 +1091,15 @@ extern "C" int ww_dwconv_nhwc_bwd(ww_ctx *ctx, const float *x, const float *w, c
         const size_t wbytes = (size_t)C * k * k * sizeof(float);
         WW_REQUIRE(wbytes <= 64 * 1024, WW_E_UNSUPPORTED, "ww_dwconv_nhwc_bwd: C*k*k = %d weights do not fit the LDS cache", C * k * k);
         WW_REQUIRE((long)B * H * W * C < (1L << 31), WW_E_UNSUPPORTED, "ww_dwconv_nhwc_bwd: tensor too large for 32-bit indices");
-        const dim3 grid(egrid((long)B * H * W * ((C + 3) / 4)));
+        const bool v4 = (C & 3) == 0 && aligned16({dy, dx});
         DwL l;
-        if ((((uintptr_t)dy | (uintptr_t)dx) & 15) == 0 && dwl_plan(g, (size_t)g.Ho * g.Wo * 16, 40 * 1024, &l)) {
+        if (v4 && dwl_plan(g, (size_t)g.Ho * g.Wo * 16, 40 * 1024, &l)) {
             const dim3 lg((unsigned)((B + l.nimg - 1) / l.nimg) * l.G_c);
             const size_t lds = ((size_t)k * k * l.CC4 + (size_t)l.nimg * g.Ho * g.Wo * l.CC4) * 16;
-            if (k == 3) hipLaunchKernelGGL((k_dwl_conv<3, true, false>), lg, dim3(256), lds, st, dy, w, g, l, dx, (float *)nullptr);
-            else hipLaunchKernelGGL((k_dwl_conv<5, true, false>), lg, dim3(256), lds, st, dy, w, g, l, dx, (float *)nullptr);
-        } else if ((C & 3) == 0 && (((uintptr_t)dy | (uintptr_t)dx) & 15) == 0) {
-            if (k == 3) hipLaunchKernelGGL(k_dwg_bwd_dx4<3>, grid, dim3(256), wbytes, st, dy, w, g, dx);
-            else hipLaunchKernelGGL(k_dwg_bwd_dx4<5>, grid, dim3(256), wbytes, st, dy, w, g, dx);
+            hipLaunchKernelGGL(WW_DW_K(k, k_dwl_conv, true, false), lg, dim3(256), lds, st, dy, w, g, l, dx, (float *)nullptr);
         } else {
-            hipLaunchKernelGGL(k_dwg_bwd_dx, grid, dim3(256), wbytes, st, dy, w, g, dx);
+            const dim3 grid(egrid((long)B * H * W * (C / (v4 ? 4 : 1))));
+            hipLaunchKernelGGL(v4 ? WW_DW_K(k, k_dwg_bwd_dx, 4) : WW_DW_K(k, k_dwg_bwd_dx, 1), grid, dim3(256), wbytes, st, dy, w, g, dx);
         }
         WW_LAUNCH_CHECK();
     }
@@ -1282,28 +1108,20 @@ extern "C" int ww_dwconv_nhwc_bwd(ww_ctx *ctx, const float *x, const float *w, c
     float *part = (float *)scratch;
     int chunks;
     DwL l;
-    if ((((uintptr_t)x | (uintptr_t)dy) & 15) == 0 && dwl_plan(g, (size_t)(H * W + g.Ho * g.Wo) * 16, 56 * 1024, &l) &&
-        (B + l.nimg - 1) / l.nimg <= NCHUNK_DW) {
+    const bool v4 = (C & 3) == 0 && aligned16({x, dy});
+    if (v4 && dwl_plan(g, (size_t)(H * W + g.Ho * g.Wo) * 16, 56 * 1024, &l) && (B + l.nimg - 1) / l.nimg <= NCHUNK_DW) {
         chunks = (B + l.nimg - 1) / l.nimg;
         const size_t lds = (size_t)l.nimg * (H * W + g.Ho * g.Wo) * l.CC4 * 16;
         if (k == 3) hipLaunchKernelGGL(k_dwl_dw<3>, dim3((unsigned)chunks * l.G_c), dim3(256), lds, st, x, dy, g, l, part);
         else hipLaunchKernelGGL(k_dwl_dw<5>, dim3((unsigned)chunks * l.G_c), dim3(256), lds, st, x, dy, g, l, part);
-    } else if ((C & 3) == 0) {
-        const int R4 = std::max(1, std::min(32, 512 / (C / 4)));      // <= 512 threads: 100 accumulator registers per thread
-        WW_REQUIRE(P < (1L << 31) && (long)H * W * C < (1L << 31), WW_E_UNSUPPORTED, "ww_dwconv_nhwc_bwd: tensor too large for 32-bit pixel indices");
-        chunks = (int)std::max<long>(1, std::min<long>(NCHUNK_DW, P / (4L * R4)));
-        const int T = std::max(1, std::min(k * k, 12288 / (R4 * C)));   // taps per LDS round: <= 48 KB
-        if (k == 3)
-            hipLaunchKernelGGL(k_dwg_bwd_dw4<3>, dim3(chunks), dim3((C / 4) * R4), (size_t)T * R4 * C * sizeof(float), st, x, dy, g, R4,
-                               (uint32_t)((P + chunks - 1) / chunks), T, part);
-        else
-            hipLaunchKernelGGL(k_dwg_bwd_dw4<5>, dim3(chunks), dim3((C / 4) * R4), (size_t)T * R4 * C * sizeof(float), st, x, dy, g, R4,
-                               (uint32_t)((P + chunks - 1) / chunks), T, part);
     } else {
-        const int R = rows_r(C);
-        chunks = chunks_for(P, C);
-        hipLaunchKernelGGL(k_dwg_bwd_dw, dim3(chunks), dim3(C * R), (size_t)R * C * sizeof(float), st, x, dy, g, R,
-                           (P + chunks - 1) / chunks, part);
+        // row lanes and pixel chunks: (C/4)*R <= 512 threads and up to NCHUNK_DW chunks at V = 4; the column-reduction layout at V = 1
+        const int V = v4 ? 4 : 1, R = v4 ? std::max(1, std::min(32, 512 / (C / 4))) : rows_r(C);
+        WW_REQUIRE(P < (1L << 31) && (long)H * W * C < (1L << 31), WW_E_UNSUPPORTED, "ww_dwconv_nhwc_bwd: tensor too large for 32-bit pixel indices");
+        chunks = v4 ? (int)std::max<long>(1, std::min<long>(NCHUNK_DW, P / (4L * R))) : chunks_for(P, C);
+        const int T = std::max(1, std::min(k * k, 12288 / (R * C)));   // taps per LDS round: <= 48 KB
+        hipLaunchKernelGGL(v4 ? WW_DW_K(k, k_dwg_bwd_dw, 4) : WW_DW_K(k, k_dwg_bwd_dw, 1), dim3(chunks), dim3((C / V) * R),
+                           (size_t)T * R * C * sizeof(float), st, x, dy, g, R, (uint32_t)((P + chunks - 1) / chunks), T, part);
     }
     WW_LAUNCH_CHECK();
     if (ww_defer(ctx, part, dw, (long)C * k * k, chunks, 0)) return WW_OK;      // (the caller keeps `scratch` until the flush)
@@ -1320,10 +1138,10 @@ extern "C" int ww_scale_bc_fwd(ww_ctx *ctx, const float *x, const float *gate, i
     WW_REQUIRE(ctx && x && gate && y && B >= 1 && HW >= 1 && C >= 1, WW_E_INVALID, "ww_scale_bc_fwd: bad argument");
     const long n = (long)B * HW * C;
     if (vec4_ok(n, C, {x, gate, y}))
-        hipLaunchKernelGGL(k_scale_fwd4, dim3(egrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float4 *)x, gate, (uint32_t)(n / 4),
-                           (uint32_t)((long)HW * C / 4), C, (float4 *)y);
+        hipLaunchKernelGGL(k_scale_fwd<4>, dim3(egrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (uint32_t)(n / 4), x, gate,
+                           (uint32_t)((long)HW * C / 4), C, y);
     else
-        hipLaunchKernelGGL(k_scale_fwd, dim3(egrid(n)), dim3(256), 0, (hipStream_t)stream, x, gate, B, HW, C, y);
+        hipLaunchKernelGGL(k_scale_fwd<1>, dim3(egrid(n)), dim3(256), 0, (hipStream_t)stream, n, x, gate, (long)HW * C, C, y);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
@@ -1339,10 +1157,10 @@ extern "C" int ww_scale_pool_bwd(ww_ctx *ctx, const float *dy, const float *gate
     WW_REQUIRE(ctx && dx && (dy || dpool) && (!dy || gate) && B >= 1 && HW >= 1 && C >= 1, WW_E_INVALID, "ww_scale_pool_bwd: bad argument");
     const long n = (long)B * HW * C;
     if (vec4_ok(n, C, {dy, gate, dpool, dx}))
-        hipLaunchKernelGGL(k_scale_pool_bwd4, dim3(egrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float4 *)dy, gate, dpool,
-                           (uint32_t)(n / 4), (uint32_t)((long)HW * C / 4), HW, C, (float4 *)dx);
+        hipLaunchKernelGGL(k_scale_pool_bwd<4>, dim3(egrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (uint32_t)(n / 4), dy, gate, dpool,
+                           (uint32_t)((long)HW * C / 4), HW, C, dx);
     else
-        hipLaunchKernelGGL(k_scale_pool_bwd, dim3(egrid(n)), dim3(256), 0, (hipStream_t)stream, dy, gate, dpool, B, HW, C, dx);
+        hipLaunchKernelGGL(k_scale_pool_bwd<1>, dim3(egrid(n)), dim3(256), 0, (hipStream_t)stream, n, dy, gate, dpool, (long)HW * C, HW, C, dx);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
@@ -1363,7 +1181,7 @@ extern "C" int ww_stem3x3s2_bn_act_fwd(ww_ctx *ctx, const float *x, const float 
     int rc = make_stem("ww_stem3x3s2_bn_act_fwd", B, H, W, C, &g);
     if (rc) return rc;
     WW_REQUIRE(bn->training, WW_E_INVALID, "ww_stem3x3s2_bn_act_fwd: training-mode statistics only");
-    WW_REQUIRE((((uintptr_t)y | (uintptr_t)scratch) & 15) == 0, WW_E_INVALID, "ww_stem3x3s2_bn_act_fwd: y / scratch must be 16-byte aligned");
+    WW_REQUIRE(aligned16({y, scratch}), WW_E_INVALID, "ww_stem3x3s2_bn_act_fwd: y / scratch must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     ww_prof_scope ps_(ctx, WW_K_NHWC, st);
     const long P = (long)B * g.Ho * g.Wo;
@@ -1379,7 +1197,7 @@ extern "C" int ww_stem3x3s2_bwd_dw(ww_ctx *ctx, const float *x, const float *dy,
     StemG g;
     int rc = make_stem("ww_stem3x3s2_bwd_dw", B, H, W, C, &g);
     if (rc) return rc;
-    WW_REQUIRE(((uintptr_t)dy & 15) == 0, WW_E_INVALID, "ww_stem3x3s2_bwd_dw: dy must be 16-byte aligned");
+    WW_REQUIRE(aligned16({dy}), WW_E_INVALID, "ww_stem3x3s2_bwd_dw: dy must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     ww_prof_scope ps_(ctx, WW_K_NHWC, st);
     const long P = (long)B * g.Ho * g.Wo;
@@ -1399,11 +1217,7 @@ extern "C" int ww_im2col3x3s2(ww_ctx *ctx, const float *x, int B, int H, int W, 
 extern "C" int ww_add_f32(ww_ctx *ctx, const float *a, const float *b, size_t n, float *y, ww_stream_t stream) {
     WW_REQUIRE(ctx && a && b && y, WW_E_INVALID, "ww_add_f32: null argument");
     if (n == 0) return WW_OK;
-    if (vec4_ok((long)n, 4, {a, b, y}))
-        hipLaunchKernelGGL(k_add4, dim3(egrid((long)n / 4)), dim3(256), 0, (hipStream_t)stream, (const float4 *)a, (const float4 *)b,
-                           (uint32_t)(n / 4), (float4 *)y);
-    else
-        hipLaunchKernelGGL(k_add, dim3(egrid((long)n)), dim3(256), 0, (hipStream_t)stream, a, b, (long)n, y);
+    WW_LAUNCH_EW(k_add, vec4_ok((long)n, 4, {a, b, y}), (long)n, (hipStream_t)stream, a, b, y);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }

@@ -15,6 +15,7 @@
 // weight row, up to 10 float4s per lane, xor-butterfly inside the group), row-lane column sums for the transposed products
 // of the backward.  Everything is a fixed-order sum: bit-reproducible, so a replayed HIP graph equals the eager step.
 #include "ww_internal.h"
+#include "ww_layers.h"
 #include <algorithm>
 
 namespace {
@@ -24,8 +25,6 @@ constexpr int SE_MAXC = 1024;    // channel bounds (LDS vectors, thread maps)
 constexpr int SE_MAXCS = 256;
 constexpr int SE_Q = 10;         // float4s of a weight row per lane (row dots)
 
-__device__ __forceinline__ float hsig(float z) { return fminf(fmaxf(z + 3.f, 0.f), 6.f) * (1.f / 6.f); }
-__device__ __forceinline__ float hsig_grad(float z) { return (z > -3.f && z < 3.f) ? (1.f / 6.f) : 0.f; }
 __device__ __forceinline__ float dot4(const float4 &a, const float4 &b, float acc) {
     return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, fmaf(a.x, b.x, acc))));
 }
@@ -208,7 +207,7 @@ __global__ __launch_bounds__(SE_T) void k_se_fwd(const float *__restrict__ x, in
     for (int p = tid; p < IMG * C; p += SE_T) {
         const float pre = gv[p];
         if (p < nimg * C) pre2_out[(size_t)b0 * C + p] = pre;
-        gv[p] = hsig(pre);
+        gv[p] = lin_act(WW_LIN_HARDSIGMOID, pre);
     }
     __syncthreads();
     const uint32_t C4 = (uint32_t)C >> 2, per = (uint32_t)HW * C4, n4 = (uint32_t)nimg * per;
@@ -261,8 +260,8 @@ __global__ __launch_bounds__(SE_T) void k_se_bwd(const float *__restrict__ x, co
         float d = 0.f, g = 0.f;
         if (p < nimg * C) {
             const float z = z2[u];
-            d = dgv[p] * hsig_grad(z);
-            g = hsig(z);
+            d = dgv[p] * lin_act_grad(WW_LIN_HARDSIGMOID, z);
+            g = lin_act(WW_LIN_HARDSIGMOID, z);
             dpre2_out[(size_t)b0 * C + p] = d;
         }
         dgv[p] = d;

@@ -1,11 +1,11 @@
 """``MobileNetV3Wakeword`` (``src/models/architectures.py:68-123``: torchvision's ``mobilenet_v3_small`` with a one-channel
 stem conv and the ``Linear(576,1024) -> Hardswish -> Dropout -> Linear(1024, num_classes)`` classifier) on the native
-channels-last layer library (``ww_bn_act_*``, ``ww_dwconv_nhwc_*``, squeeze-excitation pieces) and the matrix cores
-(``ww_linear_mfma_*`` for every 1x1 convolution, SE FC and the classifier).  The module tree reproduces torchvision's, so the
+channels-last layer library and the matrix cores.  A ``Conv2dNormActivation`` is one autograd node (``_ConvBNActFn``: conv ->
+BatchNorm -> activation, the statistics taken by the convolution kernel where it can) and a squeeze-excitation block is another
+(``_SEFn``: one launch forward, two backward), in fp32 or a 16-bit matrix mode.  The module tree reproduces torchvision's, so the
 ``state_dict`` keys are the reference model's (``mobilenet.features.4.block.2.fc1.weight`` ...).  torchvision itself is not
 available in this build environment: the architecture is restated from its published definition (``oracle/mobilenetv3.py``
-carries the same restatement in plain torch.nn) -- parity with torchvision is unpinned, parity with torch.nn is tested.
-First version: unfused fp32 layers (correctness and coverage before speed)."""
+carries the same restatement in plain torch.nn) -- parity with torchvision is unpinned, parity with torch.nn is tested."""
 import torch
 import torch.nn as nn
 
@@ -27,61 +27,6 @@ def _make_divisible(v, divisor=8):
 
 
 # ------------------------------------------------------------------------------------------ autograd wrappers
-class _PWFn(torch.autograd.Function):          # 1x1 convolution on (B,H,W,Cin) = one GEMM over the pixels
-    @staticmethod
-    def forward(ctx, x, w4, bias, act, mode):
-        shp = x.shape
-        x2 = x.reshape(-1, shp[-1])
-        w2 = w4.reshape(w4.shape[0], -1)
-        need_pre = act != nat.LIN_NONE
-        out = nat.linear_mfma_fwd(x2, w2, bias, act=act, mode=mode, want_pre=need_pre)
-        y, pre = out if need_pre else (out, None)
-        ctx.save_for_backward(x2, w2, pre)
-        ctx.act, ctx.mode, ctx.shp, ctx.wshape, ctx.has_bias = act, mode, shp, w4.shape, bias is not None
-        return y.reshape(*shp[:-1], w2.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        x2, w2, pre = ctx.saved_tensors
-        dx, dw, db = nat.linear_mfma_bwd(x2, w2, pre, dy.reshape(-1, w2.shape[0]).contiguous(), act=ctx.act, mode=ctx.mode,
-                                         need_dx=ctx.needs_input_grad[0], need_db=ctx.has_bias)
-        return (dx.reshape(ctx.shp) if dx is not None else None), dw.reshape(ctx.wshape), db, None, None
-
-
-class _BNActFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gamma, beta, mod, act):
-        Cn = x.shape[-1]
-        bn = nat.make_bn(gamma, beta, mod.running_mean, mod.running_var, momentum=mod.momentum, eps=mod.eps,
-                         training=mod.training)
-        y, ss, mr = nat.bn_act_fwd(x.contiguous(), bn, act, Cn)
-        if mod.training:
-            mod._pending_tracked += 1          # host-side count, folded into the buffer when the state is read
-        ctx.save_for_backward(x, ss, mr)
-        ctx.act, ctx.training, ctx.Cn = act, mod.training, Cn
-        return y
-
-    @staticmethod
-    def backward(ctx, da):
-        x, ss, mr = ctx.saved_tensors
-        dx, dg, db = nat.bn_act_bwd(x.contiguous(), da.contiguous(), ss, mr, ctx.act, ctx.training, ctx.Cn)
-        return dx, dg, db, None, None
-
-
-class _DWFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, w, k, stride):
-        ctx.save_for_backward(x, w)
-        ctx.k, ctx.stride = k, stride
-        return nat.dwconv_nhwc_fwd(x.contiguous(), w.contiguous(), k, stride)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        dx, dw = nat.dwconv_nhwc_bwd(x.contiguous(), w.contiguous(), dy.contiguous(), ctx.k, ctx.stride)
-        return dx, dw, None, None
-
-
 class _PoolFn(torch.autograd.Function):       # (B,H,W,C) -> (B,C) mean
     @staticmethod
     def forward(ctx, x):
@@ -93,40 +38,6 @@ class _PoolFn(torch.autograd.Function):       # (B,H,W,C) -> (B,C) mean
     @staticmethod
     def backward(ctx, ds):
         return nat.scale_pool_bwd(None, None, ds.contiguous(), ctx.shp).reshape(ctx.full)
-
-
-class _ScaleFn(torch.autograd.Function):      # y[b,h,w,c] = x[b,h,w,c] * gate[b,c]
-    @staticmethod
-    def forward(ctx, x, gate):
-        B, H, W, Cn = x.shape
-        ctx.save_for_backward(x, gate)
-        return nat.scale_bc_fwd(x.reshape(B, H * W, Cn), gate.contiguous()).reshape(x.shape)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, gate = ctx.saved_tensors
-        B, H, W, Cn = x.shape
-        dy3, x3 = dy.contiguous().reshape(B, H * W, Cn), x.reshape(B, H * W, Cn)
-        dx = nat.scale_pool_bwd(dy3, gate.contiguous(), None, (B, H * W, Cn)).reshape(x.shape)
-        return dx, nat.scale_bc_bwd_gate(x3, dy3)
-
-
-class _StemFn(torch.autograd.Function):       # Conv2d(1, C, 3, stride 2, pad 1): patches + GEMM; (B,1,H,W) -> (B,Ho,Wo,C)
-    @staticmethod
-    def forward(ctx, x, w4, mode):
-        B, _, H, W = x.shape
-        cols = nat.im2col3x3s2(x.reshape(B, H, W).contiguous())
-        w2 = w4.reshape(w4.shape[0], 9)
-        ctx.save_for_backward(cols, w2)
-        ctx.mode, ctx.wshape = mode, w4.shape
-        return nat.linear_mfma_fwd(cols, w2, None, mode=mode).reshape(B, (H + 1) // 2, (W + 1) // 2, w4.shape[0])
-
-    @staticmethod
-    def backward(ctx, dy):
-        cols, w2 = ctx.saved_tensors
-        _, dw, _ = nat.linear_mfma_bwd(cols, w2, None, dy.reshape(-1, w2.shape[0]).contiguous(), mode=ctx.mode, need_dx=False,
-                                       need_db=False)
-        return None, dw.reshape(ctx.wshape), None
 
 
 class _ConvBNActFn(torch.autograd.Function):
