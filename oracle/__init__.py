@@ -11,6 +11,9 @@ Pinning status (see DESIGN.md "Oracle"):
     generated in the build container by importing the reference's own modules
     (tests/golden/make_golden.py -> tests/golden/*.npz|json).
   * Philox4x32-10: PINNED against the Random123 known-answer vectors.
+  * clip / optimizer update / loss-scale rule (optim.py): PINNED against what the
+    reference instantiates -- torch.optim, clip_grad_norm_, torch.amp.GradScaler --
+    in float64 on the CPU (tests/test_optim_oracle.py).
   * log-mel / MFCC / SpecAugment / cnn_small: the reference ships no source
     for ``src/data`` and has no ``cnn_small``, so these
     follow the build's own written spec -- **parity unpinned** with respect to

@@ -140,8 +140,9 @@ def test_state_dict_is_torch_compatible(kind):
 
 
 def test_large_bucket_path_and_argument_checks():
-    """n > 32768 takes the two-launch path (block partial sums of squares + a grid-wide clip/update that reduces them in
-    every block): same numbers as torch; a non-finite gradient skips the update and leaves the step count alone."""
+    """n > 4096 takes the two-launch path (block partial sums of squares + a grid-wide clip/update that reduces them in
+    every block), from n = 65536 on with a float4 body: same numbers as torch; a non-finite gradient skips the update and
+    leaves the step count alone."""
     from wakeword_trainer_home_amd import _native as nat
     n = (1 << 17) + 12345
     g = torch.Generator().manual_seed(4)

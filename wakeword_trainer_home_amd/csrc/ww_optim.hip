@@ -65,7 +65,8 @@ __device__ __forceinline__ void bias_terms(const OptimArgs &a, long long t, floa
     bc2_sqrt = (float)sqrt(bc2);
 }
 
-// single block, the whole gradient bucket held in registers (n <= 32 * 1024): norm -> clip -> found_inf -> update.
+// single block, the whole gradient bucket held in registers (room for 32 * 1024; the host sends it n <= 4 096 unless
+// WW_OPTIM_SMALL_MAX says otherwise): norm -> clip -> found_inf -> update.
 // Loads are issued in unrolled batches so their latencies overlap -- one block has no other way to hide them.
 constexpr int OPT_EPT = 32;
 __global__ __launch_bounds__(1024) void k_clip_optim_small(OptimArgs a, float *__restrict__ p, float *__restrict__ g,
