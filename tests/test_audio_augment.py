@@ -1,19 +1,20 @@
 """Waveform augmentation: oracle self-checks on CPU, HIP parity on the GPU.
 The law is the build's own spec (reference source absent -> parity unpinned w.r.t. the reference); what is checked here
-is device == oracle: Philox choices bit-exact, waveform within 1e-4 absolute (fp32 direct convolution vs float64)."""
+is device == oracle: Philox choices bit-exact, waveform within max(m * e32, 16 * 2**-24) absolute per call, the former
+flat 1e-4 as ceiling (tests/input_stage.py; tests/test_input_stage_bounds.py shows on the CPU that these bounds
+discriminate).  e32 is the error of the fp32 restatement of the law (every array and scalar in float32, on the CPU)
+against the float64 oracle on the same inputs; m = 8 for the direct convolution and 32 for the overlap-save form.  For
+the direct form e32 is the larger of that restatement and the one whose convolution is one running fp32 sum over the
+taps, the device's own order: every dense-RIR direct case rests on the second (1200 taps: 1.3e-6 against numpy's blocked
+1.2e-7; 8192 taps: 4.3e-6 against 1.4e-7; the device measured 1.3e-6 and 4.3e-6)."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import audio_augment as oa
+from tests import input_stage as S
 
-
-def _banks(rng, R=3, L=1200, K=2, Nn=40000):
-    t = np.arange(L)
-    rirs = (rng.standard_normal((R, L)) * np.exp(-t / (L / 6.0))).astype(np.float32)
-    rirs[:, 0] = 1.0
-    noises = (0.1 * rng.standard_normal((K, Nn))).astype(np.float32)
-    return rirs, noises
+_banks = S.banks
 
 
 def test_oracle_choices_ranges_and_rates():
@@ -62,30 +63,82 @@ def _run_device(x, rirs, noises, fft=False, **kw):
     return out.cpu().numpy(), ch.cpu().numpy()
 
 
-def _check(x, rirs, noises, rir_prob, noise_prob, smin, smax, seed=0, step=0, sample_offset=0, atol=1e-4, fft=False):
+def _check(x, rirs, noises, rir_prob, noise_prob, smin, smax, seed=0, step=0, sample_offset=0, atol=None, fft=False, ref=None,
+           tag="augment"):
+    """Device against the float64 oracle (or a closed-form ``ref``) within input_stage.waveform_bound; choices bit-exact."""
     out, ch = _run_device(x, rirs, noises, fft=fft, rir_prob=rir_prob, noise_prob=noise_prob, snr_min_db=smin, snr_max_db=smax,
                           seed=seed, step=step, sample_offset=sample_offset)
-    ref, rch = oa.audio_augment(x, rirs, noises, rir_prob, noise_prob, smin, smax, seed, step, sample_offset)
+    oref, rch = oa.audio_augment(x, rirs, noises, rir_prob, noise_prob, smin, smax, seed, step, sample_offset)
+    f32, _ = oa.audio_augment(x, rirs, noises, rir_prob, noise_prob, smin, smax, seed, step, sample_offset, dtype=np.float32)
+    e32 = float(np.abs(f32 - oref).max())
+    yard = e32
+    if atol is None:
+        c = S.aug_call(x, rirs, noises, rir_prob, noise_prob, smin, smax, seed, step, sample_offset)
+        yard = e32 if fft else max(e32, S.aug_e_seq(c, oref))
+        atol = S.waveform_bound(e32, fft, yard)
     assert np.array_equal(ch[:, 0], rch["rir"]) and np.array_equal(ch[:, 1], rch["noise"])
     assert np.array_equal(ch[:, 2], rch["offset"])
     assert np.allclose(ch[:, 3].copy().view(np.float32), rch["snr_db"], rtol=0, atol=2e-6)
     assert np.isfinite(out).all() and np.abs(out).max() <= 1.0
-    err = np.abs(out - ref).max()
-    assert err <= atol, err
+    err = np.abs(out - (oref if ref is None else ref)).max()
+    S.measured(f"{tag} {'fft' if fft else 'direct'}", err, yard, atol)
+    assert err <= atol, (err, atol, e32)
     return out, ch
+
+
+def _check_call(c, fft, **kw):
+    return _check(c["x"], c["rirs"], c["noises"], c["rir_prob"], c["noise_prob"], c["smin"], c["smax"], c["seed"], c["step"],
+                  c["sample_offset"], fft=fft, **kw)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("fft", [False, True], ids=["direct", "fft"])
-@pytest.mark.parametrize("B,N,L", [(6, 24000, 1200), (3, 2048, 8), (5, 5000, 1), (2, 24000, 8192), (4, 1000, 3001),
-                                   (3, 24000, 4000), (2, 40000, 5000)])
+@pytest.mark.parametrize("B,N,L", S.MATCH_SHAPES)
 def test_device_matches_oracle(B, N, L, fft):
     """Both forms of the convolution: direct time-domain, and overlap-save FFT (1, 2 and 3+ segments per clip)."""
-    rng = np.random.default_rng(B * 1000 + L)
-    rirs, noises = _banks(rng, R=3, L=L, K=2, Nn=N + 777)
-    x = (0.2 * rng.standard_normal((B, N))).astype(np.float32)
-    _check(x, rirs, noises, 0.6, 0.6, 5.0, 20.0, seed=5, step=3, sample_offset=17, fft=fft)
-    _check(x, rirs, noises, 1.0, 1.0, 0.0, 0.0, seed=6, fft=fft)
+    for c in S.match_calls(B, N, L):
+        _check_call(c, fft)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fft", [False, True], ids=["direct", "fft"])
+@pytest.mark.parametrize("N", S.TWO_TAP_N)
+@pytest.mark.parametrize("L", S.TWO_TAP_L)
+def test_convolution_alone_matches_closed_form(N, L, fft):
+    """A two-tap bank h[0] = 1, h[L-1] = 0.5 and no noise: the reference is y[t] = x[t] + 0.5 x[t-L+1] and the loudness scale
+    (the oracle equals it exactly, test_input_stage_bounds.py).  A seam one sample off -- a tile's history, a segment's head,
+    the padded tail of a length that is no multiple of 8 -- moves a full-size sample here."""
+    c = S.two_tap_call(N, L)
+    _check_call(c, fft, ref=S.two_tap_closed_form(c["x"], L), tag=f"two-tap N={N} L={L}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fft", [False, True], ids=["direct", "fft"])
+def test_mix_alone_on_a_planted_noise_bank(fft):
+    """No RIR (the FFT form then copies), every clip mixed; a sample of +3 sits just before and one of -3 just after each clip's
+    noise segment, so noise statistics over a window one sample off move the output by 1e-2 and more."""
+    out, ch = _check_call(S.mix_alone_call(), fft, tag="mix alone")
+    assert (ch[:, 0] == -1).all() and (ch[:, 1] >= 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fft", [False, True], ids=["direct", "fft"])
+def test_saturating_mix(fft):
+    """Loud clips under loud noise, both effects on: a fifth of the samples end on the rails, the others do not, and both kinds
+    are under the bound (with quiet inputs |out| <= 1 holds trivially)."""
+    c = S.saturation_call()
+    out, _ = _check_call(c, fft, tag="saturation")
+    ref, _ = S.aug_oracle(c)
+    share = float(np.mean(np.abs(ref) == 1.0))
+    assert 0.1 <= share <= 0.5, share
+    assert abs(float(np.mean(np.abs(out) == 1.0)) - share) < 1e-3
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fft", [False, True], ids=["direct", "fft"])
+def test_wide_philox_words(fft):
+    """Seed, step and sample offset beyond 32 bits: choices bit-exact, waveform within the bound."""
+    _check_call(S.wide_philox_call(), fft, tag="wide philox")
 
 
 @pytest.mark.gpu
@@ -110,24 +163,19 @@ def test_fft_and_direct_forms_agree_at_full_batch():
 
 @pytest.mark.gpu
 def test_device_edge_cases():
-    rng = np.random.default_rng(9)
-    rirs, noises = _banks(rng, R=2, L=400, K=3, Nn=24000)       # Nn == N: the only offset is 0
-    x = (0.3 * rng.standard_normal((8, 24000))).astype(np.float32)
-    out, ch = _check(x, rirs, noises, 0.5, 0.5, 5.0, 20.0, seed=2)
+    calls = S.edge_case_calls()
+    first = calls[0][0]                                         # Nn == N: the only offset is 0
+    out, ch = _check_call(first, False)
     assert (ch[:, 2] == 0).all()
     # effects off / banks absent: clipped copy, bit-exact
+    x, rirs, noises = first["x"], first["rirs"], first["noises"]
     for args in ((rirs, noises, 0.0, 0.0), (None, None, 1.0, 1.0)):
         o, c = _run_device(x * 5, args[0], args[1], rir_prob=args[2], noise_prob=args[3], snr_min_db=5.0, snr_max_db=20.0)
         assert np.array_equal(o, np.clip(x * 5, -1, 1)) and (c[:, :2] == -1).all()
-    # silent clip and silent noise: no NaN from 0/0
-    x[0] = 0
-    noises[:] = 0
-    _check(x, rirs, noises, 1.0, 1.0, 5.0, 20.0, seed=4)
-    _check(x, rirs, noises, 1.0, 1.0, 5.0, 20.0, seed=4, fft=True)
-    # only one of the banks
-    _check(x, rirs, None, 1.0, 1.0, 5.0, 20.0, seed=4)
-    _check(x, rirs, None, 1.0, 1.0, 5.0, 20.0, seed=4, fft=True)
-    _check(x, None, _banks(rng, K=2, Nn=30000)[1], 1.0, 1.0, 5.0, 20.0, seed=4)
+    # silent clip and silent noise (no NaN from 0/0); only one of the banks
+    for c, forms in calls[1:]:
+        for fft in forms:
+            _check_call(c, fft)
 
 
 @pytest.mark.gpu
