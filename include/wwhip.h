@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define WW_ABI_VERSION 15
+#define WW_ABI_VERSION 16
 
 #define WW_OK 0
 #define WW_E_INVALID (-1)     /* bad argument (shape, null pointer, unsupported size) */
@@ -509,6 +509,45 @@ int ww_clip_optim_step(ww_ctx *ctx, const ww_optim_cfg *cfg, float *flat_params,
                        ww_step_stats *stats_host_alt /* nullable; see ww_step_ctl */,
                        const float *found_inf_extra /* nullable: != 0 -> skip (another rank's verdict) */,
                        ww_loss_scale *loss_scale /* nullable: fp16 mode, slot = parity */, ww_stream_t stream);
+
+/* ------------------------------------------------------------------ evaluation: the score stage after the logits
+ * Replaces, per batch, what the reference's evaluator does on the host after copying the logits back: softmax and the
+ * positive-class confidence (src/evaluation/evaluator.py:136-137, 220-221, 305-306, 379-380), the threshold decision
+ * (:138, :222, :307; src/evaluation/inference.py:209-210), the 100-threshold ROC loop (evaluator.py:389-408) and the argmax
+ * confusion counts MetricsCalculator.calculate takes from the collected logits (evaluator.py:321-324, src/training/metrics.py:
+ * 105-116).  One launch per batch, no host synchronisation; the caller reads everything back once per dataset.
+ *   scores      WW_SCORE_LOGITS: fp32 (B,2);  WW_SCORE_CONF: fp32 (B), already the positive-class confidence
+ *   targets     int64 (B), nullable (nothing is counted per class then)
+ *   thresholds  fp64 (K) on the device, ascending, 1 <= K <= WW_EVAL_MAX_THRESHOLDS;  decision: one fp64 threshold, not NaN
+ * Per sample i, written at index offset + i of the dataset-long buffers conf / pred / bin (bin nullable):
+ *   conf  fp32: exp(l1-m) / (exp(l0-m) + exp(l1-m)), m = max(l0,l1), or the copied score
+ *   pred  uint8: (double)conf >= decision
+ *   bin   int32: number of table entries t with (double)conf >= t  (NaN -> 0)
+ * Accumulators, added to and never reset here: hist uint64 [2][K+1] indexed [target][bin] (targets 0 and 1 only) and the
+ * counters below.  tp/tn/fp/fn compare the target with torch.argmax of the logits (a tie goes to class 0, a NaN logit wins,
+ * the first NaN wins when both are); with WW_SCORE_CONF the predicted class is pred.  Every comparison is fp64 on the fp32
+ * value, so the reference's three comparison semantics differ only in the table the host passes (DESIGN.md "Evaluation").
+ * Counting is integer only (LDS partial histogram, then one atomic add per non-empty counter per workgroup): reproducible. */
+#define WW_SCORE_LOGITS 0
+#define WW_SCORE_CONF 1
+#define WW_EVAL_MAX_THRESHOLDS 1024
+typedef struct {
+    uint64_t tp, tn, fp, fn;   /* argmax confusion counts over the samples whose target is 0 or 1 */
+    uint64_t count;            /* samples seen */
+    uint64_t bad_target;       /* targets outside {0,1} */
+    uint64_t nan_score;        /* samples whose confidence is NaN */
+    uint64_t reserved;
+} ww_eval_counters;
+int ww_eval_accumulate(ww_ctx *ctx, const float *scores, int score_kind, const int64_t *targets, int B,
+                       const double *thresholds, int K, double decision, float *conf, uint8_t *pred, int32_t *bin,
+                       size_t offset, uint64_t *hist, ww_eval_counters *counters, ww_stream_t stream);
+/* The chunking of MicrophoneInference's buffer loop (src/evaluation/inference.py:150-153) applied to a whole recording
+ * wave (S) fp32 on the device: window w = wave[w*(chunk/2) .. +chunk), W = 0 if S < chunk else (S - chunk)/(chunk/2) + 1 (host
+ * only: the first function below); out (W,chunk), peaks (W).  Each window is divided by its own peak max|x| when that is > 0
+ * (:190-191) with a correctly rounded division -- bit-equal to NumPy's float32 x / peak; an all-zero window stays zero, a window
+ * holding a NaN is copied unscaled (np.max returns the NaN and NaN > 0 is false) and its peak is NaN.  W must be the rule's. */
+long ww_wave_num_windows(long S, int chunk);
+int ww_wave_windows(ww_ctx *ctx, const float *wave, long S, int chunk, int W, float *out, float *peaks, ww_stream_t stream);
 
 /* ------------------------------------------------------------------ collectives: deliberately NOT in this ABI
  * SURVEY.md §8b sketched two more entry points, `ww_comm_init` (ctx, nccl_unique_id, rank, world) and `ww_allreduce_f32`

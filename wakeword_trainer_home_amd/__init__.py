@@ -3,7 +3,8 @@
 
 The package layout mirrors the reference's ``src/`` tree for the hot path only:
 ``config`` (dataclasses the Trainer reads), ``data`` (FeatureExtractor / SpecAugment),
-``models`` (create_model / create_loss_function), ``training`` (Trainer and its glue).
+``models`` (create_model / create_loss_function), ``training`` (Trainer and its glue),
+``evaluation`` (ModelEvaluator / load_model_for_evaluation / RecordingScanner).
 All device work goes through ``_native`` -> ``csrc/libwwhip.so`` (hand-written HIP, gfx950).
 """
 import os as _os
@@ -16,3 +17,14 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 __version__ = "0.2.0"
+
+_SUBPACKAGES = ("config", "data", "models", "training", "evaluation")
+
+
+def __getattr__(name):
+    """``wakeword_trainer_home_amd.evaluation`` (and the other sub-packages) on first use: importing the package itself stays
+    as light as it was."""
+    if name in _SUBPACKAGES:
+        import importlib
+        return importlib.import_module(f"{__name__}.{name}")
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

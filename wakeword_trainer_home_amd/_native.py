@@ -15,7 +15,7 @@ _LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libwwhip.so"
 _lib = None
 _ctx = {}
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 BWD_ALL, BWD_LATE, BWD_EARLY = 0, 1, 2
 ACT_F32, ACT_BF16, ACT_F16 = 0, 1, 2
 LOSS_CE, LOSS_FOCAL = 0, 1
@@ -188,6 +188,9 @@ _SIGS = {
                                    _vp, _sz, _i, _vp]),
     "ww_ce2_loss_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "ww_grad_norm_clip": (C.c_int, [_vp, _vp, _sz, _f, _vp, _vp, _vp]),
+    "ww_eval_accumulate": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ww_wave_num_windows": (C.c_long, [C.c_long, _i]),
+    "ww_wave_windows": (C.c_int, [_vp, _vp, C.c_long, _i, _i, _vp, _vp, _vp]),
     "ww_prof_num_classes": (C.c_int, []),
     "ww_prof_class_name": (C.c_char_p, [_i]),
     "ww_ctx_set_deferred_reduce": (C.c_int, [_vp, _i]),
@@ -1278,6 +1281,60 @@ def grad_norm_clip_(flat, max_norm, norm_out=None, stats=None):
 
 
 FOUND_INF_FLOAT_INDEX = StepStats.found_inf.offset // 4
+
+SCORE_LOGITS, SCORE_CONF = 0, 1
+EVAL_MAX_THRESHOLDS = 1024
+EVAL_COUNTERS = ("tp", "tn", "fp", "fn", "count", "bad_target", "nan_score", "reserved")   # ww_eval_counters: 8 x uint64
+
+
+def eval_accumulate(scores, targets, thresholds, decision, conf, pred, bins, offset, hist, counters):
+    """One batch of the score stage (ww_eval_accumulate), launched on the current stream; nothing is read back.
+    scores (B,2) f32 logits or (B,) f32 confidences; targets (B,) i64 or None; thresholds (K,) f64 ascending;
+    conf f32 / pred u8 / bins i32|None are dataset-long and written at [offset, offset+B); hist i64 (2,K+1) and
+    counters i64 (8,) (EVAL_COUNTERS) are added to."""
+    dev = _dev(scores, targets, thresholds, conf, pred, bins, hist, counters)
+    if scores.dtype != torch.float32 or not (scores.dim() == 1 or (scores.dim() == 2 and scores.shape[1] == 2)):
+        raise ValueError(f"scores must be float32 (B,2) logits or (B,) confidences, got {scores.dtype} {tuple(scores.shape)}")
+    kind = SCORE_LOGITS if scores.dim() == 2 else SCORE_CONF
+    B, K = scores.shape[0], thresholds.numel()
+    if targets is not None and (targets.dtype != torch.int64 or targets.shape != (B,)):
+        raise ValueError("targets must be int64 of shape (B,)")
+    if thresholds.dtype != torch.float64 or thresholds.dim() != 1:
+        raise ValueError("thresholds must be a 1-D float64 tensor")
+    if conf.dtype != torch.float32 or pred.dtype != torch.uint8 or (bins is not None and bins.dtype != torch.int32):
+        raise ValueError("conf / pred / bins must be float32 / uint8 / int32")
+    offset = int(offset)
+    if offset < 0 or any(t is not None and (t.dim() != 1 or t.numel() < offset + B) for t in (conf, pred, bins)):
+        raise ValueError(f"per-sample outputs must be 1-D and hold offset + B = {offset + B} elements")
+    if hist.dtype != torch.int64 or hist.numel() != 2 * (K + 1) or counters.dtype != torch.int64 or counters.numel() != 8:
+        raise ValueError(f"hist must be int64 with 2*(K+1) = {2 * (K + 1)} elements and counters int64 with 8")
+    with _guard(dev):
+        _check(load().ww_eval_accumulate(ctx(dev), _p(scores), kind, _p(targets), B, _p(thresholds), K, float(decision),
+                                         _p(conf), _p(pred), _p(bins), offset, _p(hist), _p(counters), _stream(dev)),
+               "ww_eval_accumulate")
+
+
+def wave_num_windows(n_samples, chunk):
+    return int(load().ww_wave_num_windows(int(n_samples), int(chunk)))
+
+
+def wave_windows(wave, chunk):
+    """wave (S,) f32 cuda -> (out (W,chunk) f32: the 50 %-overlap windows, each divided by its own peak; peaks (W,) f32)."""
+    dev = _dev(wave)
+    if wave.dim() != 1 or wave.dtype != torch.float32:
+        raise ValueError(f"recording must be a 1-D float32 tensor, got {wave.dtype} {tuple(wave.shape)}")
+    chunk = int(chunk)
+    if chunk < 2:
+        raise ValueError("chunk must be at least 2 samples")
+    S = wave.shape[0]
+    W = wave_num_windows(S, chunk)
+    if W >= 2 ** 31:
+        raise ValueError(f"{W} windows: scan the recording in pieces")
+    out = torch.empty((W, chunk), dtype=torch.float32, device=dev)
+    peaks = torch.empty((W,), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_wave_windows(ctx(dev), _p(wave), S, chunk, W, _p(out), _p(peaks), _stream(dev)), "ww_wave_windows")
+    return out, peaks
 
 
 def prof_classes():
