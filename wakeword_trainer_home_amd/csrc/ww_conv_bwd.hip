@@ -12,6 +12,7 @@
 // i.e. reads g_l, y_l, y_{l-1} and writes g_{l-1}: 4 tensor passes per layer.
 // Weight-gradient and statistic partials are per-block slabs summed in double by the
 // finalize kernels (bit-reproducible; no float atomics).
+#include <type_traits>
 #include "ww_internal.h"
 #include <stdlib.h>
 #include "ww_act.h"
@@ -286,15 +287,29 @@ __global__ __launch_bounds__(256, 2) void k_pw_bwd(const T *__restrict__ g, cons
 typedef short short4v __attribute__((ext_vector_type(4)));
 constexpr int PWH_LD = 72;      // 16-bit elements per LDS row (144 B)
 
-// A/B operand of a 32x32x16 MFMA whose K index is the PIXEL: channels c0..c0+31 (lane&31), pixels p0 + 8*(lane>>5) .. +7
-template <typename H>
-__device__ __forceinline__ typename H16<H>::x8 tr_operand(const H *tile, int p0, int c0, int lane) {
+// Lane part of a transposing read's address, loop-invariant: the 16-lane group g = lane>>4 reads the 4-pixel x 16-channel
+// block at pixels half_rows*(g>>1) .. +3, channels 16*(g&1) .. +15, and lane 4q+pp of the group supplies row q, columns 4pp.
+__device__ __forceinline__ int pw_tr_lane(int lane, int half_rows) {
     const int g = lane >> 4, i = lane & 15, q = i >> 2, pp = i & 3;
-    const H *base = tile + (p0 + 8 * (g >> 1) + q) * PWH_LD + c0 + 16 * (g & 1) + 4 * pp;
-    typedef short4v __attribute__((address_space(3))) * lds_p;
-    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(base));
-    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(base + 4 * PWH_LD));
+    return (half_rows * (g >> 1) + q) * PWH_LD + 16 * (g & 1) + 4 * pp;
+}
+typedef short4v __attribute__((address_space(3))) * pw_lds_p;
+typedef uint32_t pw_u32x2 __attribute__((ext_vector_type(2)));
+
+// A/B operand of a 32x32x16 MFMA whose K index is the PIXEL: channels c0..c0+31 (lane&31), pixels p0 + 8*(lane>>5) .. +7;
+// base = tile + p0 * PWH_LD + c0 + pw_tr_lane(lane, 8)
+template <typename H>
+__device__ __forceinline__ typename H16<H>::x8 tr_operand(const H *base) {
+    const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pw_lds_p)(base));
+    const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((pw_lds_p)(base + 4 * PWH_LD));
     return __builtin_bit_cast(typename H16<H>::x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+// Epilogue read in the MFMA D layout: a lane owns channel lane&31 and, in registers 4G .. 4G+3, the four consecutive pixels
+// 8G + 4*(lane>>5) .. +3 -- one transposing read of the [pixel][channel] tile (base = tile + (p0 + 8G) * PWH_LD + c0 +
+// pw_tr_lane(lane, 4)); .x holds pixels 0,1 and .y pixels 2,3 as packed 16-bit pairs
+template <typename H>
+__device__ __forceinline__ pw_u32x2 tr_pixels4(const H *base) {
+    return __builtin_bit_cast(pw_u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((pw_lds_p)(base)));
 }
 
 // The layer's own output y_out is NOT read back: it is recomputed from the a tile with the forward kernel's exact
@@ -302,6 +317,10 @@ __device__ __forceinline__ typename H16<H>::x8 tr_operand(const H *tile, int p0,
 // stored), which trades one activation-tensor read (97 MB at the full batch) for 4 MFMAs per wave and a third barrier.
 // WIDE_IMG: an image has at least one tile of pixels (HW >= 64), so a tile touches at most two images and their pooled
 // gradients are two registers; the per-pixel lookup (a division per element) is compiled only into the other variant.
+// The kernel is bound by the instructions a tile issues, not by HBM, so the tile body is kept lean: the epilogues read
+// their 16-bit tiles four pixels at a time and round / convert in pairs, only the ragged last tile of the tensor carries
+// row masks and clamped addresses (tile<true>), global addresses are a wave-uniform tile base plus a 32-bit lane offset
+// and the walk direction is a signed tile stride.
 template <typename H, bool FROM_POOL, bool WIDE_IMG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_pw_bwd_bf16(const H *__restrict__ g, const float *__restrict__ dpool,
                                                      const float *__restrict__ ss_out,
@@ -311,7 +330,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                                                      H *__restrict__ g_in, float *__restrict__ stat_partials,
                                                      float *__restrict__ dw_partials, int rev) {
     // dy, a = relu(bn(y_in)), and two y_in tiles (even / odd tile of the unrolled loop): g_in overwrites the raw y_in tile
-    // in place and is stored from there while the next tile is staged into the other one.  36.9 KB -> 4 workgroups per CU.
+    // in place and is stored from there while the next tile is staged into the other one.  46 KB -> 3 workgroups per CU.
     // + the 64x64 weights (bf16): both MFMA B operands come from this one copy (row reads forward, transposing reads for dX)
     __shared__ __align__(16) H tiles[5 * PWB_TILE * PWH_LD];
     H *dyt = tiles, *at = tiles + PWB_TILE * PWH_LD, *yit0 = tiles + 2 * PWB_TILE * PWH_LD, *yit1 = tiles + 3 * PWB_TILE * PWH_LD;
@@ -344,71 +363,117 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     floatx16 dwacc = {0.f};
     float st1 = 0.f, st2 = 0.f;
 
-    const long ntiles = (M + PWB_TILE - 1) / PWB_TILE;
-    const long last_img = (M - 1) / HW;
+    // M < 2^31 (checked on the host): tile and pixel indices are 32-bit
+    const int Mi = (int)M, nt = (int)((M + PWB_TILE - 1) / PWB_TILE);
+    const int ragged = (Mi & (PWB_TILE - 1)) ? nt - 1 : -1;      // the one tile that can hold rows past M
+    const int last_img = (Mi - 1) / HW;
+    // lane parts of the LDS offsets (elements); rows, k-steps and register groups add compile-time constants
+    const int o_stage = (tid >> 4) * PWH_LD + 4 * c4;               // staging stores, g_in read-out: + 16i rows
+    const int o_row = (32 * rh + r) * PWH_LD + 8 * h;               // row-read A operands: + 16t channels
+    const int o_w = ch * PWH_LD + 8 * h;                            // forward B operand
+    const int o_trk = pw_tr_lane(lane, 8);                          // K = pixel operands: + 16t rows + first channel
+    const int o_epr = pw_tr_lane(lane, 4) + 32 * rh * PWH_LD + 32 * n;   // epilogue reads: + 8G rows
+    const int o_epw = (32 * rh + 4 * h) * PWH_LD + ch;              // epilogue stores: + (reg&3) + 8G rows
+    // global addresses: wave-uniform tile base + row constant + this 32-bit lane offset (bytes): the 4 channels 4*c4 of row tid>>4
+    const uint32_t o_glb = 4u * (uint32_t)sizeof(H) * (uint32_t)tid;
+    constexpr size_t ROWS16 = 16 * 64 * sizeof(H);
+
     typename A16::raw4 rg0[4], ri0[4];
     float dpA0 = 0.f, dpB0 = 0.f;   // pooled gradient of the (at most two, when HW >= tile) images of a tile
-    auto issue = [&](long ti, typename A16::raw4 (&rg)[4], typename A16::raw4 (&ri)[4], float &ndpA, float &ndpB) {
-        if (ti >= ntiles) return;
-        if (rev) ti = ntiles - 1 - ti;
+    int bnd0 = 0;                   // first pixel of the second of them
+    auto issue = [&](int tt, typename A16::raw4 (&rg)[4], typename A16::raw4 (&ri)[4], float &ndpA, float &ndpB, int &nbnd) {
+        const char *yb = reinterpret_cast<const char *>(y_in + (size_t)tt * (PWB_TILE * 64));      // wave-uniform
+        const char *gb = nullptr;                       // the pooled variants have no gradient tensor (g is null)
+        if (!FROM_POOL) gb = reinterpret_cast<const char *>(g + (size_t)tt * (PWB_TILE * 64));
+        if (tt != ragged) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            long p = ti * PWB_TILE + (tid >> 4) + 16 * i;
-            p = p < M ? p : M - 1;
-            ri[i] = A16::ldraw4(y_in + (size_t)p * 64 + 4 * c4);
-            if (!FROM_POOL) rg[i] = A16::ldraw4_nt(g + (size_t)p * 64 + 4 * c4);
+            for (int i = 0; i < 4; ++i) {
+                ri[i] = A16::ldraw4(reinterpret_cast<const H *>(yb + ROWS16 * i + (size_t)o_glb));
+                if (!FROM_POOL) rg[i] = A16::ldraw4_nt(reinterpret_cast<const H *>(gb + ROWS16 * i + (size_t)o_glb));
+            }
+        } else {
+            int lastrow = Mi - 1 - tt * PWB_TILE;
+            asm volatile("" : "+s"(lastrow));       // computed here, on the one visit, not hoisted into registers held across the loop
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const uint32_t o = ((uint32_t)min((tid >> 4) + 16 * i, lastrow) * 64u + 4u * c4) * (uint32_t)sizeof(H);
+                ri[i] = A16::ldraw4(reinterpret_cast<const H *>(yb + (size_t)o));
+                if (!FROM_POOL) rg[i] = A16::ldraw4_nt(reinterpret_cast<const H *>(gb + (size_t)o));
+            }
         }
         if (FROM_POOL && WIDE_IMG) {
-            const long b0 = (long)((uint32_t)(ti * PWB_TILE) / (uint32_t)HW);   // M < 2^31 (checked on the host): 32-bit division
+            const int b0 = (int)((uint32_t)(tt * PWB_TILE) / (uint32_t)HW);
             ndpA = dpool[(size_t)b0 * 64 + ch];
             ndpB = dpool[(size_t)(b0 < last_img ? b0 + 1 : last_img) * 64 + ch];
+            nbnd = (b0 + 1) * HW;
         }
     };
-    auto tile = [&](long ti, H *yit, typename A16::raw4 (&rg)[4], typename A16::raw4 (&ri)[4], float &ndpA, float &ndpB) {
-        const long p0 = (rev ? ntiles - 1 - ti : ti) * PWB_TILE;
+    // tile walk of this workgroup: tt, tt + dt, ... (dt < 0 walks the tensor backwards), `left` tiles to go
+    const int dt = rev ? -(int)gridDim.x : (int)gridDim.x;
+    auto tile = [&](auto last_c, int tt, bool more, H *yit, typename A16::raw4 (&rg)[4], typename A16::raw4 (&ri)[4],
+                    float &ndpA, float &ndpB, int &nbnd) {
+        constexpr bool LAST = decltype(last_c)::value;
+        int p0 = tt * PWB_TILE;
+        if (LAST) asm volatile("" : "+s"(p0));      // as in issue(): the ragged tile's masks are not loop invariants to keep live
         const float dpA = ndpA, dpB = ndpB;
+        const int bnd = nbnd;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int row = (tid >> 4) + 16 * i;
-            const bool ok = p0 + row < M;
+            const bool ok = !LAST || p0 + (tid >> 4) + 16 * i < Mi;
             const float4 yr = A16::cvt4(ri[i]);
             const float z0 = fmaf(yr.x, si.x, ti4.x), z1 = fmaf(yr.y, si.y, ti4.y);
             const float z2 = fmaf(yr.z, si.z, ti4.z), z3 = fmaf(yr.w, si.w, ti4.w);
             const float a0 = !ok || z0 < 0.f ? 0.f : z0, a1 = !ok || z1 < 0.f ? 0.f : z1;
             const float a2 = !ok || z2 < 0.f ? 0.f : z2, a3 = !ok || z3 < 0.f ? 0.f : z3;
-            *reinterpret_cast<uint2 *>(at + row * PWH_LD + 4 * c4) = make_uint2(A16::pack2(a0, a1), A16::pack2(a2, a3));
-            *reinterpret_cast<uint2 *>(yit + row * PWH_LD + 4 * c4) = ok ? ri[i] : make_uint2(0u, 0u);
-            if (!FROM_POOL) *reinterpret_cast<uint2 *>(dyt + row * PWH_LD + 4 * c4) = ok ? rg[i] : make_uint2(0u, 0u);   // raw dz; dy in place below
+            *reinterpret_cast<uint2 *>(at + o_stage + 16 * i * PWH_LD) = make_uint2(A16::pack2(a0, a1), A16::pack2(a2, a3));
+            *reinterpret_cast<uint2 *>(yit + o_stage + 16 * i * PWH_LD) = ok ? ri[i] : make_uint2(0u, 0u);
+            if (!FROM_POOL) *reinterpret_cast<uint2 *>(dyt + o_stage + 16 * i * PWH_LD) = ok ? rg[i] : make_uint2(0u, 0u);   // raw dz; dy in place below
         }
-        issue(ti + (long)gridDim.x, rg, ri, ndpA, ndpB);
+        if (more) issue(tt + dt, rg, ri, ndpA, ndpB, nbnd);
         __syncthreads();
-        const int rbase = 32 * rh;
         // ---- y = a . W^T as the forward computed it, then dy = A dz + B y + C in place (each element is owned by one lane)
         {
             floatx16 yacc = {0.f};
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const bf16x8 a = *reinterpret_cast<const bf16x8 *>(at + (rbase + r) * PWH_LD + 16 * t + 8 * h);
-                const bf16x8 wf = *reinterpret_cast<const bf16x8 *>(wtile + ch * PWH_LD + 16 * t + 8 * h);
+                const bf16x8 a = *reinterpret_cast<const bf16x8 *>(at + o_row + 16 * t);
+                const bf16x8 wf = *reinterpret_cast<const bf16x8 *>(wtile + o_w + 16 * t);
                 yacc = H16<H>::mfma32(a, wf, yacc);
             }
-            const int p0i = (int)p0, Mi = (int)M;
-            const int bnd = FROM_POOL ? (int)(((uint32_t)p0 / (uint32_t)HW + 1u) * (uint32_t)HW) : 0;
 #pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int prow = rbase + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                const int p = p0i + prow;                      // M < 2^31 (host check)
-                const float okf = p < Mi ? 1.f : 0.f;          // a factor, not a select: keeps the 16 LDS reads branch-free
-                const float yv = A16::round1(yacc[reg]);       // (rows >= M hold dz = 0, a = 0 -> y = 0: the product is finite)
-                float dz;
-                if (FROM_POOL) {
-                    const float dp = WIDE_IMG ? (p >= bnd ? dpB : dpA) : dpool[(size_t)((uint32_t)min(p, Mi - 1) / (uint32_t)HW) * 64 + ch];
-                    dz = fmaf(yv, so, to) > 0.f ? dp : 0.f;
-                } else {
-                    dz = (float)dyt[prow * PWH_LD + ch];
+            for (int G = 0; G < 4; ++G) {
+                pw_u32x2 zr = {0u, 0u};
+                if (!FROM_POOL) zr = tr_pixels4(dyt + o_epr + 8 * G * PWH_LD);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int reg = 4 * G + 2 * e;
+                    const int p = p0 + 32 * rh + 4 * h + 8 * G + 2 * e;    // pixel of register reg; reg + 1 holds p + 1
+                    const float2 yv = A16::cvt2(A16::pack2(yacc[reg], yacc[reg + 1]));   // the stored (rounded) y_out
+                    float2 dz;
+                    if (FROM_POOL) {
+                        float dp0, dp1;
+                        if (WIDE_IMG) {
+                            dp0 = p >= bnd ? dpB : dpA;
+                            dp1 = p + 1 >= bnd ? dpB : dpA;
+                        } else {
+                            dp0 = dpool[(size_t)((uint32_t)min(p, Mi - 1) / (uint32_t)HW) * 64 + ch];
+                            dp1 = dpool[(size_t)((uint32_t)min(p + 1, Mi - 1) / (uint32_t)HW) * 64 + ch];
+                        }
+                        dz.x = fmaf(yv.x, so, to) > 0.f ? dp0 : 0.f;
+                        dz.y = fmaf(yv.y, so, to) > 0.f ? dp1 : 0.f;
+                    } else {
+                        dz = A16::cvt2(e ? zr.y : zr.x);
+                    }
+                    float d0 = fmaf(cA, dz.x, fmaf(cB, yv.x, cC)), d1 = fmaf(cA, dz.y, fmaf(cB, yv.y, cC));
+                    if (LAST) {     // rows >= M hold dz = 0, a = 0 -> y = 0: the product is finite
+                        d0 *= p < Mi ? 1.f : 0.f;
+                        d1 *= p + 1 < Mi ? 1.f : 0.f;
+                    }
+                    const uint32_t db = A16::pack2(d0, d1);
+                    H *o = dyt + o_epw + (8 * G + 2 * e) * PWH_LD;
+                    o[0] = __builtin_bit_cast(H, (uint16_t)db);
+                    o[PWH_LD] = __builtin_bit_cast(H, (uint16_t)(db >> 16));
                 }
-                const float d = okf * fmaf(cA, dz, fmaf(cB, yv, cC));
-                dyt[prow * PWH_LD + ch] = (H)d;
             }
         }
         __syncthreads();
@@ -417,40 +482,56 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             floatx16 acc = {0.f};
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const bf16x8 a = *reinterpret_cast<const bf16x8 *>(dyt + (rbase + r) * PWH_LD + 16 * t + 8 * h);
-                const bf16x8 wt = tr_operand(wtile, 16 * t, 32 * n, lane);
+                const bf16x8 a = *reinterpret_cast<const bf16x8 *>(dyt + o_row + 16 * t);
+                const bf16x8 wt = tr_operand(wtile + o_trk + 16 * t * PWH_LD + 32 * n);
                 acc = H16<H>::mfma32(a, wt, acc);
             }
 #pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int prow = rbase + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-                const float yv = (float)yit[prow * PWH_LD + ch];
-                const float d = A16::round1(fmaf(yv, sci, sfi) > 0.f ? acc[reg] : 0.f);
-                yit[prow * PWH_LD + ch] = (H)d;
-                st1 += d;
-                st2 = fmaf(d, (yv - mui) * rsi, st2);
+            for (int G = 0; G < 4; ++G) {
+                const pw_u32x2 yr = tr_pixels4(yit + o_epr + 8 * G * PWH_LD);
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const int reg = 4 * G + 2 * e;
+                    const float2 yv = A16::cvt2(e ? yr.y : yr.x);
+                    const uint32_t db = A16::pack2(fmaf(yv.x, sci, sfi) > 0.f ? acc[reg] : 0.f,
+                                                   fmaf(yv.y, sci, sfi) > 0.f ? acc[reg + 1] : 0.f);
+                    const float2 d = A16::cvt2(db);             // the stored (rounded) g_in
+                    H *o = yit + o_epw + (8 * G + 2 * e) * PWH_LD;
+                    o[0] = __builtin_bit_cast(H, (uint16_t)db);
+                    o[PWH_LD] = __builtin_bit_cast(H, (uint16_t)(db >> 16));
+                    st1 += d.x;
+                    st2 = fmaf(d.x, (yv.x - mui) * rsi, st2);
+                    st1 += d.y;
+                    st2 = fmaf(d.y, (yv.y - mui) * rsi, st2);
+                }
             }
         }
         // ---- dW[j][k] += sum_p dy[p][j] * a[p][k]   (K = the tile's 64 pixels, 4 k-steps, transposing LDS reads)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            const bf16x8 dyop = tr_operand(dyt, 16 * t, 32 * rh, lane);
-            const bf16x8 aop = tr_operand(at, 16 * t, 32 * n, lane);
+            const bf16x8 dyop = tr_operand(dyt + o_trk + 16 * t * PWH_LD + 32 * rh);
+            const bf16x8 aop = tr_operand(at + o_trk + 16 * t * PWH_LD + 32 * n);
             dwacc = H16<H>::mfma32(dyop, aop, dwacc);
         }
         __syncthreads();
+        char *gt = reinterpret_cast<char *>(g_in + (size_t)tt * (PWB_TILE * 64));    // wave-uniform
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int row = (tid >> 4) + 16 * i;
-            if (p0 + row < M)
-                *reinterpret_cast<uint2 *>(g_in + (size_t)(p0 + row) * 64 + 4 * c4) =
-                    *reinterpret_cast<const uint2 *>(yit + row * PWH_LD + 4 * c4);
+            if (!LAST || p0 + (tid >> 4) + 16 * i < Mi)
+                *reinterpret_cast<uint2 *>(gt + ROWS16 * i + (size_t)o_glb) =
+                    *reinterpret_cast<const uint2 *>(yit + o_stage + 16 * i * PWH_LD);
         }
     };
-    issue(blockIdx.x, rg0, ri0, dpA0, dpB0);
-    for (long ti = blockIdx.x; ti < ntiles; ti += 2 * (long)gridDim.x) {
-        tile(ti, yit0, rg0, ri0, dpA0, dpB0);
-        if (ti + gridDim.x < ntiles) tile(ti + gridDim.x, yit1, rg0, ri0, dpA0, dpB0);
+    auto run = [&](int tt, bool more, H *yit) {
+        if (tt != ragged) tile(std::false_type(), tt, more, yit, rg0, ri0, dpA0, dpB0, bnd0);
+        else tile(std::true_type(), tt, more, yit, rg0, ri0, dpA0, dpB0, bnd0);
+    };
+    int left = (int)blockIdx.x < nt ? (nt - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
+    int tt = rev ? nt - 1 - (int)blockIdx.x : (int)blockIdx.x;
+    if (left > 0) issue(tt, rg0, ri0, dpA0, dpB0, bnd0);
+    for (; left > 0; left -= 2, tt += 2 * dt) {
+        run(tt, left > 1, yit0);
+        if (left > 1) run(tt + dt, left > 2, yit1);
     }
     st1 += __shfl_xor(st1, 32);
     st2 += __shfl_xor(st2, 32);
