@@ -31,6 +31,8 @@
 extern "C" {
 #endif
 
+/* 16 still: ww_loader_indices / ww_loader_batch (the loader section below) are purely additive -- no existing signature,
+ * struct or constant changed, so a binding built against 16 keeps working. */
 #define WW_ABI_VERSION 16
 
 #define WW_OK 0
@@ -548,6 +550,34 @@ int ww_eval_accumulate(ww_ctx *ctx, const float *scores, int score_kind, const i
  * holding a NaN is copied unscaled (np.max returns the NaN and NaN > 0 is false) and its peak is NaN.  W must be the rule's. */
 long ww_wave_num_windows(long S, int chunk);
 int ww_wave_windows(ww_ctx *ctx, const float *wave, long S, int chunk, int W, float *out, float *peaks, ww_stream_t stream);
+
+/* ------------------------------------------------------------------ loader: batches from a device-resident clip bank
+ * The reference feeds its trainer from a host DataLoader over WakewordDataset (src/data, absent from the snapshot;
+ * src/training/trainer.py:154-157 unpacks its batches).  Here the clips live on the device and ONE launch per batch draws
+ * the clip of every sample, copies it (crop or zero-pad) and writes targets and clip indices.  Nothing is read back, and no
+ * index tensor exists between the draw and the copy.  The laws are DESIGN.md §4 "Loader"; in short, with
+ * g = rank + world * k the epoch position of this rank's k-th sample and Philox4x32-10 keyed by `seed`:
+ *   WW_SAMPLER_PERM   shuffle != 0: clip = perm(g), a 4-round Feistel permutation of [0, n_clips) that depends on (seed,
+ *                     epoch) alone -- the same on every rank, so the ranks' shards are disjoint; shuffle == 0: clip = g.
+ *                     g must stay below n_clips (WW_E_INVALID otherwise).
+ *   WW_SAMPLER_TABLE  with replacement: clip = first i with cdf[i] > u53(g, epoch) * 2^-53 * cdf[n_cdf-1], at most n_cdf-1;
+ *                     cdf = fp64 inclusive cumulative weights on the device, n_cdf <= n_clips entries (the host cuts the
+ *                     table after the last non-zero weight), last entry > 0.
+ *   bank    int16 [n_clips][L], row stride L;  length int32 [n_clips], 0 <= length <= L (clamped);  label uint8 [n_clips]
+ *   out     int16 (B, n_out), rows n_out apart, any 2-byte alignment: length > n_out -> n_out samples from offset
+ *           mulhi32(philox(g, epoch)[0], length - n_out + 1) when training, 0 otherwise; else the clip, then zeros
+ *   targets int64 (B) = label[clip];  clip_index int32 (B) = clip
+ * k0 is the first sample of the launch (k = k0 .. k0 + B - 1); only the low 32 bits of epoch enter the counters.
+ * ww_loader_indices writes the drawn clips alone, for any k0 / count. */
+#define WW_SAMPLER_PERM 0
+#define WW_SAMPLER_TABLE 1
+int ww_loader_indices(ww_ctx *ctx, int n_clips, int strategy, int shuffle, const double *cdf /* TABLE only */, int n_cdf,
+                      uint64_t seed, uint64_t epoch, int rank, int world, int64_t k0, int count, int32_t *index_out,
+                      ww_stream_t stream);
+int ww_loader_batch(ww_ctx *ctx, const int16_t *bank, const int32_t *length, const uint8_t *label, int n_clips, int L,
+                    int strategy, int shuffle, int training, const double *cdf /* TABLE only */, int n_cdf, uint64_t seed,
+                    uint64_t epoch, int rank, int world, int64_t k0, int B, int n_out, int16_t *out, int64_t *targets,
+                    int32_t *clip_index, ww_stream_t stream);
 
 /* ------------------------------------------------------------------ collectives: deliberately NOT in this ABI
  * SURVEY.md §8b sketched two more entry points, `ww_comm_init` (ctx, nccl_unique_id, rank, world) and `ww_allreduce_f32`

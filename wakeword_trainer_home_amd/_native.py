@@ -191,6 +191,9 @@ _SIGS = {
     "ww_eval_accumulate": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ww_wave_num_windows": (C.c_long, [C.c_long, _i]),
     "ww_wave_windows": (C.c_int, [_vp, _vp, C.c_long, _i, _i, _vp, _vp, _vp]),
+    "ww_loader_indices": (C.c_int, [_vp, _i, _i, _i, _vp, _i, _u64, _u64, _i, _i, C.c_int64, _i, _vp, _vp]),
+    "ww_loader_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _u64, _u64, _i, _i, C.c_int64, _i, _i, _vp, _vp,
+                                  _vp, _vp]),
     "ww_prof_num_classes": (C.c_int, []),
     "ww_prof_class_name": (C.c_char_p, [_i]),
     "ww_ctx_set_deferred_reduce": (C.c_int, [_vp, _i]),
@@ -1335,6 +1338,60 @@ def wave_windows(wave, chunk):
     with _guard(dev):
         _check(load().ww_wave_windows(ctx(dev), _p(wave), S, chunk, W, _p(out), _p(peaks), _stream(dev)), "ww_wave_windows")
     return out, peaks
+
+
+SAMPLER_PERM, SAMPLER_TABLE = 0, 1
+_U64 = (1 << 64) - 1
+
+
+def _loader_table(strategy, cdf, n_clips):
+    if strategy == SAMPLER_PERM:
+        return 0
+    if strategy != SAMPLER_TABLE:
+        raise ValueError(f"unknown sampler strategy code {strategy}")
+    if cdf is None or cdf.dtype != torch.float64 or cdf.dim() != 1 or not 1 <= cdf.numel() <= n_clips:
+        raise ValueError("the table sampler needs a 1-D float64 cumulative table of 1..n_clips entries on the device")
+    return cdf.numel()
+
+
+def loader_indices(n_clips, strategy, shuffle, cdf, seed, epoch, rank, world, k0, count, device=None, out=None):
+    """Clip indices of samples k0 .. k0+count-1 of `rank` in `epoch` (ww_loader_indices) -> int32 (count,) cuda."""
+    if out is None:
+        if cdf is None and device is None:
+            raise ValueError("loader_indices needs a device, an output tensor or a table")
+        out = torch.empty((int(count),), dtype=torch.int32, device=cdf.device if device is None else device)
+    dev = _dev(out, cdf)
+    if out.dtype != torch.int32 or out.numel() != count:
+        raise ValueError("out must be int32 with `count` elements")
+    n_cdf = _loader_table(strategy, cdf, n_clips)
+    with _guard(dev):
+        _check(load().ww_loader_indices(ctx(dev), int(n_clips), int(strategy), int(bool(shuffle)), _p(cdf), n_cdf, int(seed) & _U64,
+                                        int(epoch) & _U64, int(rank), int(world), int(k0), int(count), _p(out), _stream(dev)),
+               "ww_loader_indices")
+    return out
+
+
+def loader_batch(bank, length, label, strategy, shuffle, training, cdf, seed, epoch, rank, world, k0, out, targets, clip_index):
+    """One batch of the loader (ww_loader_batch), launched on the current stream; nothing is read back.  bank (n_clips, L) i16,
+    length (n_clips,) i32, label (n_clips,) u8; out (B, n_out) i16 (rows n_out apart, any 2-byte alignment), targets (B,) i64,
+    clip_index (B,) i32."""
+    dev = _dev(bank, length, label, cdf, out, targets, clip_index)
+    if bank.dtype != torch.int16 or bank.dim() != 2 or out.dtype != torch.int16 or out.dim() != 2:
+        raise ValueError("bank and out must be 2-D int16")
+    n_clips, L = bank.shape
+    B, n_out = out.shape
+    if n_clips >= 2 ** 31 or L >= 2 ** 31 or n_out >= 2 ** 31:
+        raise ValueError("the bank holds at most 2^31-1 clips of 2^31-1 samples")
+    if length.dtype != torch.int32 or length.shape != (n_clips,) or label.dtype != torch.uint8 or label.shape != (n_clips,):
+        raise ValueError("length must be int32 (n_clips,) and label uint8 (n_clips,)")
+    if targets.dtype != torch.int64 or targets.shape != (B,) or clip_index.dtype != torch.int32 or clip_index.shape != (B,):
+        raise ValueError("targets must be int64 (B,) and clip_index int32 (B,)")
+    n_cdf = _loader_table(strategy, cdf, n_clips)
+    with _guard(dev):
+        _check(load().ww_loader_batch(ctx(dev), _p(bank), _p(length), _p(label), n_clips, L, int(strategy), int(bool(shuffle)),
+                                      int(bool(training)), _p(cdf), n_cdf, int(seed) & _U64, int(epoch) & _U64, int(rank),
+                                      int(world), int(k0), B, n_out, _p(out), _p(targets), _p(clip_index), _stream(dev)),
+               "ww_loader_batch")
 
 
 def prof_classes():

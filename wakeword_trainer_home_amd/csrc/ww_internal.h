@@ -158,6 +158,8 @@ int ww_launch_sumsq_partials(ww_ctx *ctx, const float *g, size_t n, int *parts_o
 // ---- Philox4x32-10 (host + device), must match oracle/philox.py bit for bit
 #define WW_TAG_SPECAUG 0u
 #define WW_TAG_DROPOUT 1u
+// 2 is ww_audio.hip's TAG_AUDIO
+#define WW_TAG_DATA 3u      // ww_data.hip: epoch order, weighted draw, crop offset
 
 __host__ __device__ inline void ww_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                                           uint32_t k1, uint32_t out[4]) {

@@ -427,14 +427,17 @@ class Trainer:
                 out.append(r)
         return out
 
-    def _prepare_native(self, inputs, targets, step_index):
+    def _prepare_native(self, inputs, targets, step_index, after=None):
         """Input stage of a native step on its own HIP stream: H2D (if needed) + fused log-mel/SpecAugment.  It has no
         dependency on the model, so for batch k+1 it runs while step k's conv stack is executing.  The overlap is not free:
         the resident log-mel workgroups take registers / LDS from the conv kernels, which is why the
         kernel is launched with ``input_stage_workgroups`` persistent workgroups here (one per CU) instead of a full-device
-        grid.  Returns (features, targets, ready_event, step_index)."""
+        grid.  ``after``: an event behind the launch that produced ``inputs`` on another stream (a device loader's
+        ``metadata["ready"]``); the side stream waits for it.  Returns (features, targets, ready_event, step_index)."""
         if self._in_stream is None:
             self._in_stream = torch.cuda.Stream(device=self.device)
+        if after is not None:
+            self._in_stream.wait_event(after)
         with torch.cuda.stream(self._in_stream):
             if inputs.dim() == 2:
                 if self.input_stage_workgroups is None:
@@ -914,7 +917,9 @@ class Trainer:
                 if pipelined:
                     index = self.launched_steps
                     self.launched_steps += 1          # the batch owns this Philox step whether or not it survives
-                    prep = self._prepare_native(parsed[0], parsed[1], index)
+                    meta = batch[2] if len(batch) > 2 else None
+                    prep = self._prepare_native(parsed[0], parsed[1], index,
+                                                after=meta.get("ready") if isinstance(meta, dict) else None)
                 return idx, parsed, prep
             except RuntimeError as e:
                 if "out of memory" in str(e).lower() and survivable(e):
@@ -1018,6 +1023,10 @@ class Trainer:
         try:
             for epoch in range(start_epoch, epochs):
                 self.state.epoch = epoch
+                # epoch-dependent order (data.loader.DeviceBatchLoader, a DataLoader over a DistributedSampler-style sampler)
+                for owner in (self.train_loader, getattr(self.train_loader, "sampler", None)):
+                    if callable(getattr(owner, "set_epoch", None)):
+                        owner.set_epoch(epoch)
                 self._call_callbacks("on_epoch_start", epoch)
                 train_loss, train_acc = self.train_epoch(epoch)
                 val_loss, vm = self.validate_epoch(epoch)
