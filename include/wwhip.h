@@ -32,7 +32,9 @@ extern "C" {
 #endif
 
 /* 16 still: ww_loader_indices / ww_loader_batch (the loader section below) are purely additive -- no existing signature,
- * struct or constant changed, so a binding built against 16 keeps working. */
+ * struct or constant changed, so a binding built against 16 keeps working.
+ * 16 still: the weighted loss entry and its WW_REDUCE_* / WW_DIV_* constants (the loss section below) are purely additive
+ * too; the unweighted loss entry keeps its signature and its results. */
 #define WW_ABI_VERSION 16
 
 #define WW_OK 0
@@ -261,7 +263,8 @@ int ww_cnn_small_bwd(ww_ctx *ctx, int act_dtype, void *const *params, void *cons
  * Replaces LabelSmoothingCrossEntropy.forward (src/models/losses.py:66-98), the eps==0
  * nn.CrossEntropyLoss branch (:256) and FocalLoss.forward (:170-197) for C == 2, plus their
  * autograd, plus the per-batch accuracy / confusion counters of
- * src/training/trainer.py:196-200 + src/training/metrics.py:105-116.                     */
+ * src/training/trainer.py:196-200 + src/training/metrics.py:105-116.  Two entries: the unweighted mean
+ * (what the reference Trainer builds, trainer.py:84) and one with per-class weights and mean / sum / none. */
 #define WW_LOSS_CE 0
 #define WW_LOSS_FOCAL 1
 typedef struct {
@@ -300,6 +303,34 @@ int ww_ce2_loss_fwd_bwd(ww_ctx *ctx, const float *logits, const int64_t *targets
                         float label_smoothing, float focal_alpha, float focal_gamma, float *loss_out,
                         float *dlogits, ww_step_stats *stats, float *found_inf_out, const ww_loss_scale *loss_scale,
                         int loss_scale_slot, ww_stream_t stream);
+/* The same kernel layout with per-class weights and a choice of reduction: the `weight` tensor the reference's three losses
+ * take (src/models/losses.py:89-92, :199-202, :256; create_loss_function passes class_weights through, :245-264) and their
+ * reduction argument (:95-102).  l_b, g_b = the per-sample loss and gradient of the entry above before its 1/B,
+ * w_b = class_weight[y_b], s = the loss scale:
+ *
+ *   reduction, mean_divisor        loss                      dlogits[b]
+ *   MEAN, WW_DIV_BATCH             sum w_b l_b / B           s w_b g_b / B          (loss * weight).mean(): smoothed CE, focal
+ *   MEAN, WW_DIV_WEIGHT_SUM        sum w_b l_b / sum w_b     s w_b g_b / sum w_b    nn.CrossEntropyLoss(weight=...), :256
+ *   SUM                            sum w_b l_b               s w_b g_b
+ *   NONE                           loss_vec[b] = w_b l_b     s w_b g_b              the caller applies the upstream gradient
+ *
+ * loss_out and stats->loss hold the reduced value; for NONE the MEAN value under the given mean_divisor (read only for MEAN
+ * and NONE).  class_weight: 2 floats in DEVICE memory, [w_neg, w_pos], read at run time (a captured graph sees a later
+ * in-place change); NULL = ones.  Sums run in double in one fixed order.  The counters ignore the weights; a target outside
+ * [0,2) is clamped and flagged as above and takes the weight of the class it was clamped to.  sum w_b == 0 under
+ * WW_DIV_WEIGHT_SUM gives 0/0 = NaN as torch does: nonfinite and found_inf are set and the step is skipped; under
+ * WW_DIV_BATCH the same batch gives loss 0 and zero gradients.  With class_weight NULL or (1, 1), MEAN is bit-identical to
+ * the entry above under either divisor.  loss_vec: B floats, required for NONE, unused (may be NULL) otherwise. */
+#define WW_REDUCE_MEAN 0
+#define WW_REDUCE_SUM 1
+#define WW_REDUCE_NONE 2
+#define WW_DIV_BATCH 0
+#define WW_DIV_WEIGHT_SUM 1
+int ww_ce2_loss_weighted_fwd_bwd(ww_ctx *ctx, const float *logits, const int64_t *targets, int B, int loss_kind,
+                                 float label_smoothing, float focal_alpha, float focal_gamma, const float *class_weight,
+                                 int reduction, int mean_divisor, float *loss_out, float *loss_vec, float *dlogits,
+                                 ww_step_stats *stats, float *found_inf_out, const ww_loss_scale *loss_scale,
+                                 int loss_scale_slot, ww_stream_t stream);
 /* Replaces clip_gradients -> torch.nn.utils.clip_grad_norm_
  * (src/training/optimizer_factory.py:446-452) on one flat gradient bucket.  max_norm <= 0:
  * only the norm is computed.  norm_out (nullable) receives the pre-clip L2 norm.          */

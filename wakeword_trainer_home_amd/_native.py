@@ -19,6 +19,8 @@ ABI_VERSION = 16
 BWD_ALL, BWD_LATE, BWD_EARLY = 0, 1, 2
 ACT_F32, ACT_BF16, ACT_F16 = 0, 1, 2
 LOSS_CE, LOSS_FOCAL = 0, 1
+REDUCE_MEAN, REDUCE_SUM, REDUCE_NONE = 0, 1, 2
+DIV_BATCH, DIV_WEIGHT_SUM = 0, 1
 WAVE_F32, WAVE_I16 = 0, 1
 CNN_SMALL_NPTR = 47
 
@@ -187,6 +189,8 @@ _SIGS = {
     "ww_cnn_small_bwd": (C.c_int, [_vp, _i, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _i, _i, _i, _f, _u64, _u64, _u64,
                                    _vp, _sz, _i, _vp]),
     "ww_ce2_loss_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "ww_ce2_loss_weighted_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                               _vp]),
     "ww_grad_norm_clip": (C.c_int, [_vp, _vp, _sz, _f, _vp, _vp, _vp]),
     "ww_eval_accumulate": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ww_wave_num_windows": (C.c_long, [C.c_long, _i]),
@@ -1269,6 +1273,35 @@ def ce2_loss_fwd_bwd(logits, targets, kind=LOSS_CE, label_smoothing=0.0, focal_a
                                           int(loss_scale_slot), _stream(dev)),
                "ww_ce2_loss_fwd_bwd")
     return loss, dl, stats
+
+
+def ce2_loss_weighted_fwd_bwd(logits, targets, kind=LOSS_CE, label_smoothing=0.0, focal_alpha=0.25, focal_gamma=2.0,
+                              class_weight=None, reduction=REDUCE_MEAN, mean_divisor=DIV_BATCH, stats=None, found_inf_out=None,
+                              loss_scale=None, loss_scale_slot=0):
+    """Per-class weights and mean / sum / none (include/wwhip.h has the table) -> (loss (1,) f32, loss_vec (B,) f32 or None,
+    dlogits (B,2) f32, stats uint8[STEP_STATS_BYTES]).  ``class_weight``: float32 device tensor [w_neg, w_pos], read by the
+    kernel through its pointer; None = ones.  ``loss_vec`` is returned for REDUCE_NONE only; ``loss`` is then the mean under
+    ``mean_divisor``."""
+    dev = _dev(logits, targets, class_weight, stats, found_inf_out, loss_scale)
+    if logits.dim() != 2 or logits.shape[1] != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"native loss needs float32 logits of shape (B,2), got {logits.dtype} {tuple(logits.shape)}")
+    if targets.dim() != 1 or targets.shape[0] != logits.shape[0] or targets.dtype != torch.int64:
+        raise ValueError("targets must be int64 of shape (B,)")
+    if class_weight is not None and (class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (2,)):
+        raise ValueError(f"class_weight must be float32 of shape (2,), got {class_weight.dtype} {tuple(class_weight.shape)}")
+    B = logits.shape[0]
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    loss_vec = torch.empty(B, dtype=torch.float32, device=dev) if reduction == REDUCE_NONE else None
+    dl = torch.empty_like(logits)
+    if stats is None:
+        stats = torch.zeros(STEP_STATS_BYTES, dtype=torch.uint8, device=dev)
+    with _guard(dev):
+        _check(load().ww_ce2_loss_weighted_fwd_bwd(ctx(dev), _p(logits), _p(targets), B, kind, label_smoothing, focal_alpha,
+                                                   focal_gamma, _p(class_weight), int(reduction), int(mean_divisor), _p(loss),
+                                                   _p(loss_vec), _p(dl), _p(stats), _p(found_inf_out), _p(loss_scale),
+                                                   int(loss_scale_slot), _stream(dev)),
+               "ww_ce2_loss_weighted_fwd_bwd")
+    return loss, loss_vec, dl, stats
 
 
 def grad_norm_clip_(flat, max_norm, norm_out=None, stats=None):

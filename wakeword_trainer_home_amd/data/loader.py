@@ -117,6 +117,12 @@ class DeviceClipBank:
     def weights(self, strategy, hard_negative_weight=1.0) -> np.ndarray:
         return sampler_weights(self.labels, self.hard_negative, strategy, hard_negative_weight)
 
+    def class_stats(self) -> dict:
+        """``{"positive": clips labelled 1, "negative": clips labelled 0}``: the ``dataset_stats`` that
+        ``calculate_class_weights`` / ``class_weights_from_config`` take (one host read; call it once, not per step)."""
+        counts = torch.bincount(self.labels.long(), minlength=2).cpu()
+        return {"positive": int(counts[1]), "negative": int(counts[0])}
+
 
 _TAGW = 3 << 24          # WW_TAG_DATA in the top byte of ctr[3]
 _M32 = np.uint64(0xFFFFFFFF)

@@ -1,8 +1,17 @@
 """Loss factory of the hot path: same names, constructor arguments and input validation as
 the reference (``src/models/losses.py:14-270``); the arithmetic (loss, gradient, batch
-counters) is one HIP kernel, ``ww_ce2_loss_fwd_bwd``.  Scope: 2 classes, mean reduction, no
-per-class weights -- what ``Trainer`` actually uses (``src/training/trainer.py:78-86`` passes
-``class_weights=None``)."""
+counters) is one HIP kernel.  Scope: 2 classes; optional per-class ``weight`` (``:89-92``, ``:199-202``, ``:256``) and
+``reduction`` in mean / sum / none (``:95-102``).
+
+Two C-ABI entries.  ``weight=None`` with ``reduction="mean"`` -- what ``Trainer`` builds unless it is handed class weights
+(``src/training/trainer.py:78-86`` passes ``class_weights=None``) -- calls ``ww_ce2_loss_fwd_bwd``; every other combination
+calls ``ww_ce2_loss_weighted_fwd_bwd``.  The weighted mean follows the reference class by class: ``CrossEntropyLoss`` divides
+by the sum of the batch's weights as ``nn.CrossEntropyLoss(weight=...)`` does, ``LabelSmoothingCrossEntropy`` and
+``FocalLoss`` divide by the batch size (``(loss * weight).mean()``).
+
+Data parallel: each rank normalises by its own batch -- by its own sum of weights under ``CrossEntropyLoss`` -- and the ranks'
+gradients are averaged, which is what torch DDP does with a weighted ``nn.CrossEntropyLoss``.  Under that divisor a sharded
+run is therefore not the single-process run on the concatenated batch."""
 from typing import Optional
 
 import torch
@@ -10,36 +19,40 @@ import torch.nn as nn
 
 from .. import _native as nat
 
+_REDUCTIONS = {"mean": nat.REDUCE_MEAN, "sum": nat.REDUCE_SUM, "none": nat.REDUCE_NONE}
+
 
 class _CE2Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets, mod):
-        loss, dl, stats = nat.ce2_loss_fwd_bwd(logits.contiguous(), targets.contiguous(), mod._kind, mod._eps,
-                                               mod._alpha, mod._gamma, stats=mod._stats_for(logits.device),
-                                               found_inf_out=mod.found_inf_out, loss_scale=mod.loss_scale,
-                                               loss_scale_slot=mod.loss_scale_slot)
+        loss, vec, dl, stats = mod._launch(logits.contiguous(), targets.contiguous(), mod.found_inf_out)
         mod.last_stats = stats
         ctx.save_for_backward(dl)
-        return loss.reshape(())
+        ctx.per_sample = vec is not None
+        return vec if ctx.per_sample else loss.reshape(())
 
     @staticmethod
     def backward(ctx, gout):
         (dl,) = ctx.saved_tensors
-        return dl * gout, None, None
+        return dl * (gout[:, None] if ctx.per_sample else gout), None, None
 
 
 class _NativeLoss(nn.Module):
     _kind = nat.LOSS_CE
     _eps, _alpha, _gamma = 0.0, 0.25, 2.0
+    _divisor = nat.DIV_BATCH              # what a weighted 'mean' divides by: (loss * weight).mean() of the reference classes
 
     def __init__(self, weight: Optional[torch.Tensor], reduction: str):
         super().__init__()
-        if weight is not None:
-            raise ValueError("per-class weights are not implemented in the HIP loss kernel "
-                             "(the reference Trainer never passes them: trainer.py:84)")
-        if reduction != "mean":
-            raise ValueError(f"the HIP loss kernel implements reduction='mean', got {reduction!r}")
-        self.weight, self.reduction = weight, reduction
+        if weight is not None and not (torch.is_tensor(weight) and weight.dtype == torch.float32 and tuple(weight.shape) == (2,)):
+            what = f"{weight.dtype} {tuple(weight.shape)}" if torch.is_tensor(weight) else type(weight).__name__
+            raise ValueError(f"weight must be a float32 tensor of shape (2,) [w_neg, w_pos] for the 2-class HIP loss kernel, got {what}")
+        if reduction not in _REDUCTIONS:
+            raise ValueError(f"Invalid reduction: {reduction}")
+        # a buffer, so that criterion.to(device) takes it along; the kernel reads it through its pointer at run time, so an
+        # in-place change of its values holds from the next step on, eager or replayed from a captured graph
+        self.register_buffer("weight", None if weight is None else weight.detach().clone())
+        self.reduction = reduction
         self.validate_targets = True      # reference behaviour: raise at once (costs a host sync)
         self.last_stats = None            # device uint8[48] = ww_step_stats of the last call
         self.found_inf_out = None         # float32[1] device tensor that also receives found_inf (data-parallel bucket slot)
@@ -52,15 +65,32 @@ class _NativeLoss(nn.Module):
             self._stats[dev] = torch.zeros(nat.STEP_STATS_BYTES, dtype=torch.uint8, device=dev)
         return self._stats[dev]
 
+    def _launch(self, logits, targets, found_inf_out):
+        """One kernel launch -> (loss (1,), loss_vec (B,) or None, dlogits, stats): the unweighted mean through the entry it
+        always had, everything else through the weighted one."""
+        stats = self._stats_for(logits.device)
+        if self.reduction == "mean" and self.weight is None:
+            loss, dl, stats = nat.ce2_loss_fwd_bwd(logits, targets, self._kind, self._eps, self._alpha, self._gamma, stats=stats,
+                                                   found_inf_out=found_inf_out, loss_scale=self.loss_scale,
+                                                   loss_scale_slot=self.loss_scale_slot)
+            return loss, None, dl, stats
+        w = self.weight
+        if w is not None and (w.device != logits.device or w.dtype != torch.float32):
+            # no copy here: a host-to-device copy per step would sync, and could not be captured into a graph
+            raise ValueError(f"the loss weight is {w.dtype} on {w.device} but the logits are on {logits.device}: move the "
+                             "criterion with .to(device) (it must stay float32)")
+        return nat.ce2_loss_weighted_fwd_bwd(logits, targets, self._kind, self._eps, self._alpha, self._gamma, class_weight=w,
+                                             reduction=_REDUCTIONS[self.reduction], mean_divisor=self._divisor, stats=stats,
+                                             found_inf_out=found_inf_out, loss_scale=self.loss_scale,
+                                             loss_scale_slot=self.loss_scale_slot)
+
     def native_fwd_bwd(self, logits: torch.Tensor, target: torch.Tensor, found_inf_out=None):
         """Loss kernel without autograd: -> (device ww_step_stats, dL/dlogits).  Target range errors are reported through
-        ``stats.bad_target`` (the caller reads the stats once per step)."""
+        ``stats.bad_target`` (the caller reads the stats once per step).  With ``reduction='none'`` the gradient is that of
+        the per-sample losses' sum and ``stats.loss`` their mean."""
         if logits.dim() != 2 or logits.size(1) != 2 or target.dim() != 1 or logits.size(0) != target.size(0):
             raise ValueError(f"expected logits (B,2) and targets (B,), got {tuple(logits.shape)} and {tuple(target.shape)}")
-        _, dl, stats = nat.ce2_loss_fwd_bwd(logits.contiguous(), target.long().contiguous(), self._kind, self._eps,
-                                            self._alpha, self._gamma, stats=self._stats_for(logits.device),
-                                            found_inf_out=found_inf_out, loss_scale=self.loss_scale,
-                                            loss_scale_slot=self.loss_scale_slot)
+        _, _, dl, stats = self._launch(logits.contiguous(), target.long().contiguous(), found_inf_out)
         self.last_stats = stats
         return stats, dl
 
@@ -94,7 +124,9 @@ class LabelSmoothingCrossEntropy(_NativeLoss):
 
 
 class CrossEntropyLoss(LabelSmoothingCrossEntropy):
-    """label_smoothing == 0 branch (the reference returns nn.CrossEntropyLoss there, losses.py:256)."""
+    """label_smoothing == 0 branch (the reference returns nn.CrossEntropyLoss there, losses.py:256): its weighted mean divides
+    by the sum of the batch's weights, not by the batch size."""
+    _divisor = nat.DIV_WEIGHT_SUM
 
     def __init__(self, weight: Optional[torch.Tensor] = None, reduction: str = "mean"):
         super().__init__(0.0, weight, reduction)
@@ -119,6 +151,8 @@ def create_loss_function(loss_name: str, num_classes: int = 2, label_smoothing: 
                          focal_alpha: float = 0.25, focal_gamma: float = 2.0,
                          class_weights: Optional[torch.Tensor] = None, device: str = "cuda") -> nn.Module:
     name = loss_name.lower()
+    if class_weights is not None:
+        class_weights = class_weights.to(device)
     if num_classes != 2 and name in ("cross_entropy", "focal_loss"):
         raise ValueError(f"the HIP loss kernels implement num_classes == 2, got {num_classes}")
     if name == "cross_entropy":

@@ -10,7 +10,7 @@ counters the loss kernel already produced (``ww_step_stats``); because ``calcula
 """
 import logging
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -171,3 +171,21 @@ def calculate_class_weights(dataset_stats: Dict[str, int], method: str = "balanc
     else:
         raise ValueError(f"Unknown weighting method: {method}")
     return torch.tensor([w_neg, w_pos], device=device)
+
+
+_CLASS_WEIGHT_MODES = ["balanced", "none", "custom"]      # the reference validator's list (src/config/validator.py:387)
+
+
+def class_weights_from_config(config: Any, dataset_stats: Dict[str, int], device: str = "cuda") -> Optional[torch.Tensor]:
+    """``config.loss.class_weights`` -> the tensor ``Trainer(class_weights=...)`` / ``create_loss_function`` take, or None.
+    "balanced": ``calculate_class_weights(dataset_stats, "balanced", device)`` (``DeviceClipBank.class_stats()`` gives the
+    stats); "none": None; "custom" names no values, so it asks for an explicit tensor."""
+    mode = config.loss.class_weights
+    if mode == "balanced":
+        return calculate_class_weights(dataset_stats, "balanced", device)
+    if mode == "none":
+        return None
+    if mode == "custom":
+        raise ValueError("loss.class_weights='custom' carries no values: pass an explicit (2,) float tensor [w_neg, w_pos] as "
+                         "Trainer(class_weights=...) or create_loss_function(class_weights=...)")
+    raise ValueError(f"Invalid class weights: {mode} (valid: {_CLASS_WEIGHT_MODES})")

@@ -78,21 +78,33 @@ class Trainer:
     MAX_GRAPHS = 2
 
     def __init__(self, model: nn.Module, train_loader: DataLoader, val_loader: DataLoader, config: Any,
-                 checkpoint_dir: Optional[Path] = None, device: str = "cuda", criterion: Optional[nn.Module] = None):
+                 checkpoint_dir: Optional[Path] = None, device: str = "cuda", criterion: Optional[nn.Module] = None,
+                 class_weights: Optional[torch.Tensor] = None):
+        """``class_weights`` (extension; the reference Trainer always passes None, trainer.py:84): a (2,) float tensor
+        [w_neg, w_pos] handed to ``create_loss_function`` -- ``class_weights_from_config`` maps ``config.loss.class_weights``
+        to one.  The config field alone switches nothing on.  Data parallel: every rank normalises its loss by its own batch
+        (by its own sum of weights under ``CrossEntropyLoss``) and the gradients are averaged, as torch DDP does with a
+        weighted ``nn.CrossEntropyLoss``; under that divisor the sharded run is not the single-process run on the
+        concatenated batch."""
         enforce_cuda()
         self.device, self.config = device, config
         self.model = model.to(device).to(memory_format=torch.channels_last)
         self.native = isinstance(self.model, CNNSmallWakeword)
         self.train_loader, self.val_loader = train_loader, val_loader
 
+        if criterion is not None and class_weights is not None:
+            raise ValueError("pass either criterion or class_weights, not both: a criterion carries its own weight")
         if criterion is None:
             criterion = create_loss_function(loss_name=config.loss.loss_function, num_classes=config.model.num_classes,
                                              label_smoothing=config.loss.label_smoothing,
                                              focal_alpha=config.loss.focal_alpha, focal_gamma=config.loss.focal_gamma,
-                                             class_weights=None, device=device)
+                                             class_weights=class_weights, device=device)
         self.criterion = criterion.to(device)
         self._native_loss = isinstance(self.criterion, _NativeLoss)
         if self._native_loss:
+            if self.criterion.reduction == "none":
+                raise ValueError("a training step needs a scalar loss: reduction='none' is for per-clip loss ranking, "
+                                 "use 'mean' or 'sum' for the Trainer's criterion")
             self.criterion.validate_targets = False      # checked from the per-step stats read instead
 
         self.optimizer, self.scheduler = create_optimizer_and_scheduler(self.model, config)
@@ -657,14 +669,19 @@ class Trainer:
     def _graph_key(self, shape):
         """Everything a captured step bakes BY VALUE: feature shape, storage / matrix modes, the clip norm, the optimizer's
         hyper-parameters other than lr (lr, the Philox step and the slot parity live in the device control block), the loss
-        hyper-parameters, and where the parameter bucket is.  A change of any of them makes the next step eager and the one
-        after it a fresh capture, exactly as an eager step would honour the change."""
+        hyper-parameters, its reduction, whether it has a class weight and where that weight is (its VALUES are read from
+        device memory at replay, so an in-place change needs no new capture), and where the parameter bucket is.  A change of
+        any of them makes the next step eager and the one after it a fresh capture, exactly as an eager step would honour the
+        change."""
         def plain(d, skip=()):
             return tuple(sorted((k, tuple(v) if isinstance(v, (tuple, list)) else v) for k, v in d.items()
                                 if k not in skip and isinstance(v, (int, float, bool, str, tuple, list, type(None)))))
         groups = tuple(plain(g, skip=("params", "lr", "initial_lr")) for g in self.optimizer.param_groups)
         crit = plain({k: v for k, v in vars(self.criterion).items() if k in ("_eps", "_alpha", "_gamma", "smoothing", "alpha", "gamma")})
         flat = getattr(self.model, "flat_param", None)
+        weight = getattr(self.criterion, "weight", None)
+        crit += (("reduction", getattr(self.criterion, "reduction", None)), ("weight", weight is not None),
+                 ("weight_ptr", weight.data_ptr() if torch.is_tensor(weight) else None))
         return (tuple(shape), self._graph_mode_key(), float(self.gradient_clip), groups, type(self.criterion).__name__, crit,
                 None if flat is None else flat.data_ptr())
 
