@@ -164,6 +164,28 @@ int ww_audio_augment(ww_ctx *ctx, const float *wave_in, float *wave_out, int B, 
                      uint64_t sample_offset, int32_t *choice_out, void *scratch, size_t scratch_bytes,
                      ww_stream_t stream);
 
+/* Time-stretch and pitch-shift of the clean clip (they precede the RIR and the noise): time-domain WSOLA, then a
+ * windowed-sinc resampler; the length N is kept.  Law: DESIGN.md "Time-stretch / pitch-shift spec" (the build's own; draw 2
+ * of the audio Philox stream, draws 0 and 1 are ww_audio_augment's).  0.5 <= rate_min <= rate_max <= 2.0 and
+ * -12 <= semis_min <= semis_max <= 12, else WW_E_INVALID.  A clip with neither effect is a bit-exact copy.
+ * choice_out (nullable): int32 (B,3) = stretched?, float bits of the rate, semitones.  delta_out (nullable): int16
+ * (B, ww_audio_tsm_max_grains(N, semis_max)); entry m-1 of a selected clip holds the search offset d_m of grain m, the
+ * entries past the clip's last grain and the rows of copied clips are left as they were.  scratch holds the WSOLA output of
+ * every clip (ww_audio_tsm_scratch_bytes).  wave_out must not alias wave_in.                                          */
+typedef struct {
+    float stretch_prob;  /* time_stretch_prob */
+    float rate_min;      /* time_stretch_min */
+    float rate_max;      /* time_stretch_max */
+    float pitch_prob;    /* pitch_shift_prob */
+    int32_t semis_min;   /* pitch_shift_min */
+    int32_t semis_max;   /* pitch_shift_max */
+} ww_audio_tsm_cfg;
+int ww_audio_tsm_max_grains(int N, int semis_max);
+size_t ww_audio_tsm_scratch_bytes(int B, int N, int semis_max);
+int ww_audio_tsm(ww_ctx *ctx, const float *wave_in, float *wave_out, int B, int N, const ww_audio_tsm_cfg *cfg, uint64_t seed,
+                 uint64_t step, uint64_t sample_offset, int32_t *choice_out, int16_t *delta_out, void *scratch,
+                 size_t scratch_bytes, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ conv stack layers
  * Replace nn.Conv2d / nn.BatchNorm2d(train) / nn.ReLU as the reference composes them
  * (stem form: src/models/architectures.py:99-102; depthwise-separable blocks are the

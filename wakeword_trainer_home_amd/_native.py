@@ -48,6 +48,11 @@ class AudioAugCfg(C.Structure):
     _fields_ = [("rir_prob", C.c_float), ("noise_prob", C.c_float), ("snr_min_db", C.c_float), ("snr_max_db", C.c_float)]
 
 
+class AudioTsmCfg(C.Structure):
+    _fields_ = [("stretch_prob", C.c_float), ("rate_min", C.c_float), ("rate_max", C.c_float), ("pitch_prob", C.c_float),
+                ("semis_min", C.c_int32), ("semis_max", C.c_int32)]
+
+
 class LinearEpi(C.Structure):
     _fields_ = [("act", C.c_int32), ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64),
                 ("sample_offset", C.c_uint64)]
@@ -132,6 +137,9 @@ _SIGS = {
     "ww_audio_rir_spectra": (C.c_int, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
     "ww_audio_augment": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _i, _i, C.POINTER(AudioAugCfg), _u64, _u64,
                                    _u64, _vp, _vp, _sz, _vp]),
+    "ww_audio_tsm_max_grains": (C.c_int, [_i, _i]),
+    "ww_audio_tsm_scratch_bytes": (_sz, [_i, _i, _i]),
+    "ww_audio_tsm": (C.c_int, [_vp, _vp, _vp, _i, _i, C.POINTER(AudioTsmCfg), _u64, _u64, _u64, _vp, _vp, _vp, _sz, _vp]),
     "ww_gemm16_nt": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, C.c_long, C.c_long, C.c_long, _vp]),
     "ww_linear_mfma_fwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, C.POINTER(LinearEpi), _vp, _vp, _vp]),
     "ww_linear_mfma_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
@@ -461,6 +469,40 @@ def audio_augment(wave, rirs, noises, rir_prob, noise_prob, snr_min_db, snr_max_
         _check(load().ww_audio_augment(ctx(dev), _p(wave), _p(out), B, N, _p(rirs), R, L, _p(rir_spectra), _p(noises), K, Nn, C.byref(cfg),
                                        seed, step, sample_offset, _p(choices), _p(scratch), nbytes, _stream(dev)),
                "ww_audio_augment")
+    return (out, choices) if want_choices else out
+
+
+def audio_tsm_max_grains(N, semis_max):
+    return load().ww_audio_tsm_max_grains(N, semis_max)
+
+
+def audio_tsm(wave, stretch_prob, rate_min, rate_max, pitch_prob, semis_min, semis_max, seed=0, step=0, sample_offset=0,
+              want_choices=False, delta_out=None, out=None, scratch=None):
+    """wave (B,N) f32 cuda -> time-stretched / pitch-shifted copy of the same shape [, choices int32 (B,3): stretched?, float
+    bits of the rate, semitones].  ``delta_out``: int16 (B, audio_tsm_max_grains(N, semis_max)) that receives the search
+    offsets of the selected clips.  ``out`` / ``scratch`` default to fresh tensors."""
+    dev = _dev(wave, delta_out, out, scratch)
+    if wave.dim() != 2 or wave.dtype != torch.float32:
+        raise ValueError(f"waveform batch must be float32 (B,N), got {wave.dtype} {tuple(wave.shape)}")
+    if int(semis_min) != semis_min or int(semis_max) != semis_max:
+        raise ValueError(f"pitch shifts are whole semitones, got ({semis_min}, {semis_max})")
+    B, N = wave.shape
+    semis_min, semis_max = int(semis_min), int(semis_max)
+    if out is None:
+        out = torch.empty_like(wave)
+    elif out.shape != wave.shape or out.dtype != torch.float32:
+        raise ValueError("out must be float32 of the waveform's shape")
+    if delta_out is not None and (delta_out.dtype != torch.int16 or -12 <= semis_max <= 12 and
+                                  tuple(delta_out.shape) != (B, audio_tsm_max_grains(N, semis_max))):
+        raise ValueError("delta_out must be int16 (B, audio_tsm_max_grains(N, semis_max))")
+    if scratch is None:
+        scratch = torch.empty(max(load().ww_audio_tsm_scratch_bytes(B, N, semis_max) // 4, 1), dtype=torch.float32, device=dev)
+    choices = torch.empty((B, 3), dtype=torch.int32, device=dev) if want_choices else None
+    cfg = AudioTsmCfg(stretch_prob, rate_min, rate_max, pitch_prob, semis_min, semis_max)
+    with _guard(dev):
+        _check(load().ww_audio_tsm(ctx(dev), _p(wave), _p(out), B, N, C.byref(cfg), seed, step, sample_offset, _p(choices),
+                                   _p(delta_out), _p(scratch), scratch.numel() * scratch.element_size(), _stream(dev)),
+               "ww_audio_tsm")
     return (out, choices) if want_choices else out
 
 

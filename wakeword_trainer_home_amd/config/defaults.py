@@ -5,8 +5,8 @@ Field names and default values follow the reference's dataclasses
 reads are consumed here (``trainer.py:79-83,92,96,107,112``, ``optimizer_factory.py:351-371``).
 Additions (backward compatible, defaults keep reference behaviour): SpecAugment mask
 geometry and the RNG seed in ``AugmentationConfig`` (the reference keeps them as
-``SpecAugment`` ctor arguments, ``tests/test_training_pipeline.py:252-257``), and
-``TrainingConfig.data_parallel``.
+``SpecAugment`` ctor arguments, ``tests/test_training_pipeline.py:252-257``), the
+application probabilities of time-stretch / pitch-shift, and ``TrainingConfig.data_parallel``.
 """
 from dataclasses import dataclass, field, asdict, fields
 from pathlib import Path
@@ -86,6 +86,9 @@ class AugmentationConfig(_Section):
     n_freq_masks: int = 2
     n_time_masks: int = 2
     seed: int = 2024
+    # time-stretch / pitch-shift are applied with these probabilities over the ranges above (0: the ranges are inert)
+    time_stretch_prob: float = 0.0
+    pitch_shift_prob: float = 0.0
 
 
 @dataclass

@@ -5,7 +5,9 @@ n_freq_masks=2, n_time_masks=2)``, ``__call__((1,F,T)) -> same shape``) and the 
 (DESIGN.md "SpecAugment spec") and runs in ``ww_specaug_apply`` (or fused into ``ww_logmel_fwd``).
 ``AudioAugmentation`` keeps the constructor of ``tests/test_training_pipeline.py:230-236`` and runs the RIR convolution +
 background-noise mix of BASELINE config 4 on the GPU (``ww_audio_augment``; law in DESIGN.md "Audio augmentation spec").
-Time-stretch / pitch-shift are outside the north_star list: the ranges are accepted and stored, nothing is resampled."""
+Time-stretch and pitch-shift run on the GPU as well (``ww_audio_tsm``: time-domain WSOLA, then a windowed-sinc resampler; law in
+DESIGN.md "Time-stretch / pitch-shift spec").  They are opt-in through ``time_stretch_prob`` / ``pitch_shift_prob`` (both 0
+by default: nothing new is launched and every result is what it was), act on the clean clip, and the RIR and the noise follow."""
 import torch
 
 from .. import _native as nat
@@ -19,15 +21,26 @@ class AudioAugmentation:
 
     def __init__(self, sample_rate: int = 16000, device="cuda", time_stretch_range=(0.8, 1.2),
                  pitch_shift_range=(-2, 2), background_noise_prob: float = 0.5, noise_snr_range=(5.0, 20.0),
-                 rir_prob: float = 0.25, rirs=None, noises=None, seed: int = 0, fft_min_taps: int = 129):
-        for name, p in (("background_noise_prob", background_noise_prob), ("rir_prob", rir_prob)):
+                 rir_prob: float = 0.25, rirs=None, noises=None, seed: int = 0, fft_min_taps: int = 129,
+                 time_stretch_prob: float = 0.0, pitch_shift_prob: float = 0.0):
+        for name, p in (("background_noise_prob", background_noise_prob), ("rir_prob", rir_prob),
+                        ("time_stretch_prob", time_stretch_prob), ("pitch_shift_prob", pitch_shift_prob)):
             if not 0.0 <= p <= 1.0:
                 raise ValueError(f"{name} must be in [0, 1], got {p}")
         if noise_snr_range[1] < noise_snr_range[0]:
             raise ValueError("noise_snr_range must be (min, max) with max >= min")
+        time_stretch_range, pitch_shift_range = tuple(time_stretch_range), tuple(pitch_shift_range)
+        if len(time_stretch_range) != 2 or not 0.5 <= time_stretch_range[0] <= time_stretch_range[1] <= 2.0:
+            raise ValueError(f"time_stretch_range must be (min, max) with 0.5 <= min <= max <= 2.0, got {time_stretch_range}")
+        if (len(pitch_shift_range) != 2 or any(int(v) != v for v in pitch_shift_range)
+                or not -12 <= pitch_shift_range[0] <= pitch_shift_range[1] <= 12):
+            raise ValueError("pitch_shift_range must be (min, max) in whole semitones with -12 <= min <= max <= 12, got "
+                             f"{pitch_shift_range}")
         self.sample_rate = sample_rate
         self.device = torch.device(device)
-        self.time_stretch_range, self.pitch_shift_range = tuple(time_stretch_range), tuple(pitch_shift_range)
+        self.time_stretch_range = (float(time_stretch_range[0]), float(time_stretch_range[1]))
+        self.pitch_shift_range = (int(pitch_shift_range[0]), int(pitch_shift_range[1]))
+        self.time_stretch_prob, self.pitch_shift_prob = float(time_stretch_prob), float(pitch_shift_prob)
         self.background_noise_prob, self.rir_prob = float(background_noise_prob), float(rir_prob)
         self.noise_snr_range = (float(noise_snr_range[0]), float(noise_snr_range[1]))
         self.seed = seed
@@ -38,6 +51,19 @@ class AudioAugmentation:
         self.rir_spectra = (nat.audio_rir_spectra(self.rirs)
                             if self.rirs is not None and self.rirs.shape[1] >= fft_min_taps else None)
         self.last_choices = None      # device int32 (B,4): rir|-1, noise|-1, offset, float bits of snr_db
+        self.last_tsm_choices = None  # device int32 (B,3): stretched?, float bits of the rate, semitones
+
+    @classmethod
+    def from_config(cls, config, device="cuda", rirs=None, noises=None, seed: int = 0):
+        """The augmentor ``config.augmentation`` describes (a WakewordConfig, or the section itself)."""
+        a = getattr(config, "augmentation", config)
+        data = getattr(config, "data", None)
+        return cls(sample_rate=getattr(data, "sample_rate", 16000), device=device,
+                   time_stretch_range=(a.time_stretch_min, a.time_stretch_max),
+                   pitch_shift_range=(a.pitch_shift_min, a.pitch_shift_max),
+                   background_noise_prob=a.background_noise_prob, noise_snr_range=(a.noise_snr_min, a.noise_snr_max),
+                   rir_prob=a.rir_prob, rirs=rirs, noises=noises, seed=seed,
+                   time_stretch_prob=getattr(a, "time_stretch_prob", 0.0), pitch_shift_prob=getattr(a, "pitch_shift_prob", 0.0))
 
     def _bank(self, bank, name):
         if bank is None:
@@ -53,7 +79,14 @@ class AudioAugmentation:
         wave = audio.to(self.device, non_blocking=True)
         wave = (wave.float() / 32768.0) if wave.dtype == torch.int16 else wave.float()
         st = self.step if step is None else step
-        res = nat.audio_augment(wave.contiguous(), self.rirs, self.noises, self.rir_prob, self.background_noise_prob,
+        wave = wave.contiguous()
+        if self.time_stretch_prob > 0.0 or self.pitch_shift_prob > 0.0:       # the clean clip first; RIR and noise follow
+            wave = nat.audio_tsm(wave, self.time_stretch_prob, *self.time_stretch_range, self.pitch_shift_prob,
+                                 *self.pitch_shift_range, seed=self.seed, step=st, sample_offset=sample_offset,
+                                 want_choices=return_choices)
+            if return_choices:
+                wave, self.last_tsm_choices = wave
+        res = nat.audio_augment(wave, self.rirs, self.noises, self.rir_prob, self.background_noise_prob,
                                 self.noise_snr_range[0], self.noise_snr_range[1], seed=self.seed, step=st,
                                 sample_offset=sample_offset, want_choices=return_choices, rir_spectra=self.rir_spectra)
         if step is None:
