@@ -459,6 +459,30 @@ int ww_cnn_front_fwd(ww_ctx *ctx, int act_dtype, void *const *params, const floa
 int ww_cnn_front_bwd(ww_ctx *ctx, int act_dtype, void *const *params, void *const *grads, const float *x, const float *dseq,
                      int B, int F, int T, void *ws, size_t ws_bytes, ww_stream_t stream);
 
+/* ------------------------------------------------------------------ causal dilated Conv1d on the matrix cores (TCNWakeword)
+ * The convolution of the reference's TemporalBlock (src/models/architectures.py:323-372: nn.Conv1d(Cin, Cout, k, padding=(k-1)d,
+ * dilation=d), of whose output the first T steps are kept -- on those a causal convolution), channels-last:
+ *   y[b,t,n] = bias[n] + sum_j sum_c x[b, t - (k-1-j) d, c] w[n,c,j]          (steps before t = 0 read as 0)
+ * x (B,T,Cin), y / dy / residual (B,T,Cout), w (Cout,Cin,k) = nn.Conv1d.weight, bias (Cout); all fp32, contiguous, 16-byte
+ * aligned.  mode as ww_linear_mfma_*: WW_ACT_F32 = v_mfma_f32_32x32x2_f32 (parity mode), WW_ACT_BF16 / WW_ACT_F16 = operands rounded
+ * when staged, fp32 accumulation.  1 <= k <= 8, d >= 1 (also (k-1) d >= T), B, T >= 1, Cin and Cout positive multiples of 4;
+ * anything else is WW_E_INVALID before any launch.  scratch: ww_tconv1d_scratch_bytes(B,T,Cin,Cout,k) bytes (WW_E_WORKSPACE).
+ * fwd epilogue: + bias, then + residual (nullable), then ReLU (relu != 0) -- "y = relu(conv + residual)" closes a TemporalBlock.
+ * bwd: dpre = dy * mask_scale where y != 0 and y2 != 0 (both nullable: the layer's saved outputs carry its ReLU and dropout
+ * masks, mask_scale = 1/(1-p) of a dropout that followed); dx (nullable; added to when accumulate_dx != 0), dw (Cout,Cin,k) and
+ * db (Cout) in a fixed summation order: dw as row-range partial products summed in order -- queued instead while
+ * ww_ctx_set_deferred_reduce is in force (the scratch must then live until the flush).                                     */
+size_t ww_tconv1d_scratch_bytes(int B, int T, int Cin, int Cout, int k);
+int ww_tconv1d_fwd(ww_ctx *ctx, int mode, const float *x, const float *w, const float *bias, int B, int T, int Cin, int Cout, int k,
+                   int dilation, int relu, const float *residual /* nullable */, float *y, void *scratch, size_t scratch_bytes,
+                   ww_stream_t stream);
+int ww_tconv1d_bwd(ww_ctx *ctx, int mode, const float *x, const float *w, const float *y /* nullable */, const float *y2 /* nullable */,
+                   float mask_scale, const float *dy, int B, int T, int Cin, int Cout, int k, int dilation, float *dx /* nullable */,
+                   int accumulate_dx, float *dw, float *db, void *scratch, size_t scratch_bytes, ww_stream_t stream);
+/* The identity skip of a TemporalBlock whose channel counts agree: y = relu(a + b), and dx = dy where y != 0                */
+int ww_add_relu_fwd(ww_ctx *ctx, const float *a, const float *b, size_t n, float *y, ww_stream_t stream);
+int ww_relu_mask_bwd(ww_ctx *ctx, const float *dy, const float *y, size_t n, float *dx, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ GRU layer, one direction
  * torch.nn.GRU's cell and parameter layout (gate order r|z|n; w_ih (3H,I), w_hh (3H,H), b_ih, b_hh (3H)) -- what the
  * reference's GRUWakeword wraps (src/models/architectures.py:228-235).  batch_first: x (B,T,I) with row stride ldx

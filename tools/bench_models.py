@@ -14,7 +14,7 @@ import torch
 from wakeword_trainer_home_amd import _native as nat
 from wakeword_trainer_home_amd.config import get_preset
 from wakeword_trainer_home_amd.data import make_synthetic_batch
-from wakeword_trainer_home_amd.models import create_model, LSTMWakeword
+from wakeword_trainer_home_amd.models import create_model, LSTMWakeword, TCNWakeword
 from wakeword_trainer_home_amd.training import Trainer
 
 dev = "cuda:0"
@@ -22,7 +22,7 @@ CONFIGS = (("crnn", 512, "bf16"), ("crnn", 4096, "bf16"), ("gru", 4096, "fp32"),
            ("mobilenetv3", 2048, "bf16"))
 GRAPH = "--graph" in sys.argv                 # replay the step as a captured HIP graph (Trainer hip_graph mode)
 argv = [a for a in sys.argv[1:] if a != "--graph"]
-if argv:                                      # e.g.  bench_models.py crnn 4096 fp16 [--graph]  |  lstm 512 fp32
+if argv:                                      # e.g.  bench_models.py crnn 4096 fp16 [--graph]  |  lstm 512 fp32  |  tcn 512 bf16
     CONFIGS = ((argv[0], int(argv[1]), argv[2]),)
 for arch, B, act in CONFIGS:
     cfg = get_preset("cnn_small_logmel40")
@@ -30,8 +30,10 @@ for arch, B, act in CONFIGS:
     cfg.training.hip_graph, cfg.training.hip_graph_auto = GRAPH, False       # the eager line is eager for every model
     torch.manual_seed(0)
     kw = {"act_dtype": act} if arch == "crnn" else {"mode": act}
-    # (the factory does not offer "lstm" yet: the reference's LSTMWakeword is built directly)
-    model = LSTMWakeword(dropout=0.3, **kw) if arch == "lstm" else create_model(arch, dropout=0.3, **kw)
+    # (the factory does not offer "lstm" and "tcn" yet: the reference's LSTMWakeword / TCNWakeword are built directly; the TCN
+    # sees (B, 1, 40, 151) feature batches: 6 B T 432 640 FLOP per step in its convolutions, timed under "linear_mfma")
+    direct = {"lstm": LSTMWakeword, "tcn": TCNWakeword}
+    model = direct[arch](dropout=0.3, **kw) if arch in direct else create_model(arch, dropout=0.3, **kw)
     with contextlib.redirect_stdout(sys.stderr):
         tr = Trainer(model, [], [], cfg, checkpoint_dir=Path(tempfile.mkdtemp()), device=dev)
     tr.model.train()
@@ -63,6 +65,8 @@ for arch, B, act in CONFIGS:
     print(json.dumps({"model": arch, "batch": B, "conv_storage": act if arch == "crnn" else None, "matrix_mode": act,
                       "hip_graph": tr._graph is not None, "loss_scale": tr.scaler.get_scale() if tr.loss_scale is not None else None,
                       "ms_per_step": round(dt * 1e3, 3),
-                      "samples_per_s": round(B / dt, 1), "class_ms_one_step": prof}))
+                      "samples_per_s": round(B / dt, 1),
+                      **({"conv_tflops": round(6 * B * 151 * 432640 / dt / 1e12, 2)} if arch == "tcn" else {}),
+                      "class_ms_one_step": prof}))
     del tr, model, pool
     torch.cuda.empty_cache()

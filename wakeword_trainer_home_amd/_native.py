@@ -145,6 +145,11 @@ _SIGS = {
     "ww_linear_mfma_bwd_scratch_bytes": (_sz, [_i, _i, _i]),
     "ww_linear_mfma_bwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, C.POINTER(LinearEpi), _vp, _vp, _vp, _vp, _sz,
                                      _vp]),
+    "ww_tconv1d_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "ww_tconv1d_fwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ww_tconv1d_bwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ww_add_relu_fwd": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "ww_relu_mask_bwd": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "ww_dropout_bt": (C.c_int, [_vp, _vp, C.c_long, _i, _i, _i, _f, _u64, _u64, _u64, _i, _vp, C.c_long, _vp]),
     "ww_nhwc_scratch_bytes": (_sz, [_i]),
     "ww_bn_act_fwd": (C.c_int, [_vp, _vp, C.c_long, _i, C.POINTER(BN), _i, _vp, _vp, _vp, _vp, _vp]),
@@ -658,6 +663,73 @@ def dropout_bt(x, p, seed=0, step=0, sample_offset=0, stream_id=0, out=None):
         _check(load().ww_dropout_bt(ctx(dev), _p(x), ldx, B, T, Cc, p, seed, step, sample_offset, stream_id, _p(out),
                                     _bt_rows(out, "out"), _stream(dev)), "ww_dropout_bt")
     return out
+
+
+# ---- causal dilated Conv1d (TCNWakeword); activations are contiguous fp32 (B, T, C) tensors
+def _tconv_check(x, w):
+    if x.dim() != 3 or w.dim() != 3 or x.shape[2] != w.shape[1] or x.dtype != torch.float32 or w.dtype != torch.float32:
+        raise ValueError(f"tconv1d: need float32 x (B,T,Cin) and weight (Cout,Cin,k), got {tuple(x.shape)} and {tuple(w.shape)}")
+
+
+def _tconv_scratch(B, T, Cin, Cout, k, dev):
+    # (0 bytes = a shape the kernels refuse: the call itself reports which argument)
+    return torch.empty(max(load().ww_tconv1d_scratch_bytes(B, T, Cin, Cout, k) // 4, 4), dtype=torch.float32, device=dev)
+
+
+def tconv1d_fwd(x, w, bias, dilation=1, relu=False, residual=None, mode=torch.float32):
+    """y = [relu](causal_conv1d(x, w, dilation) + bias [+ residual]); x (B,T,Cin), w (Cout,Cin,k) -> y (B,T,Cout)."""
+    dev = _dev(x, w, bias, residual)
+    _tconv_check(x, w)
+    B, T, Cin = x.shape
+    Cout, _, k = w.shape
+    if residual is not None and (tuple(residual.shape) != (B, T, Cout) or residual.dtype != torch.float32):
+        raise ValueError(f"tconv1d: residual must be float32 {(B, T, Cout)}, got {tuple(residual.shape)}")
+    y = torch.empty((B, T, Cout), dtype=torch.float32, device=dev)
+    scratch = _tconv_scratch(B, T, Cin, Cout, k, dev)
+    with _guard(dev):
+        _check(load().ww_tconv1d_fwd(ctx(dev), act_code(mode), _p(x), _p(w), _p(bias), B, T, Cin, Cout, k, dilation, int(relu),
+                                     _p(residual), _p(y), _p(scratch), scratch.numel() * 4, _stream(dev)), "ww_tconv1d_fwd")
+    return y
+
+
+def tconv1d_bwd(x, w, dy, dilation=1, y=None, y2=None, mask_scale=1.0, mode=torch.float32, need_dx=True, dx=None, dw_out=None,
+                db_out=None, defer=False):
+    """-> (dx | None, dw, db).  y / y2: saved outputs whose zeros mask dy (times mask_scale).  dx given: the input gradient is
+    ADDED to it.  defer: queue the sum of the dw partials (valid after deferred_flush)."""
+    dev = _dev(x, w, dy, y, y2, dx)
+    _tconv_check(x, w)
+    B, T, Cin = x.shape
+    Cout, _, k = w.shape
+    for t in (dy, y, y2):
+        if t is not None and (tuple(t.shape) != (B, T, Cout) or t.dtype != torch.float32):
+            raise ValueError(f"tconv1d backward: dy / y / y2 must be float32 {(B, T, Cout)}, got {tuple(t.shape)}")
+    accumulate = dx is not None
+    if dx is None and need_dx:
+        dx = torch.empty((B, T, Cin), dtype=torch.float32, device=dev)
+    dw = _out(dw_out, (Cout, Cin, k), dev)
+    db = _out(db_out, (Cout,), dev)
+    scratch = _tconv_scratch(B, T, Cin, Cout, k, dev)
+    with _guard(dev), (_deferring(dev, scratch) if defer else contextlib.nullcontext()):
+        _check(load().ww_tconv1d_bwd(ctx(dev), act_code(mode), _p(x), _p(w), _p(y), _p(y2), mask_scale, _p(dy), B, T, Cin, Cout, k,
+                                     dilation, _p(dx), int(accumulate), _p(dw), _p(db), _p(scratch), scratch.numel() * 4,
+                                     _stream(dev)), "ww_tconv1d_bwd")
+    return dx, dw, db
+
+
+def add_relu_fwd(a, b):
+    dev = _dev(a, b)
+    y = torch.empty_like(a)
+    with _guard(dev):
+        _check(load().ww_add_relu_fwd(ctx(dev), _p(a), _p(b), a.numel(), _p(y), _stream(dev)), "ww_add_relu_fwd")
+    return y
+
+
+def relu_mask_bwd(dy, y):
+    dev = _dev(dy, y)
+    dx = torch.empty_like(dy)
+    with _guard(dev):
+        _check(load().ww_relu_mask_bwd(ctx(dev), _p(dy), _p(y), dy.numel(), _p(dx), _stream(dev)), "ww_relu_mask_bwd")
+    return dx
 
 
 # ---- generic channels-last layers (MobileNetV3 body); activations are contiguous fp32 (M, C) / (B, H, W, C) tensors

@@ -408,3 +408,5 @@ def create_model(architecture: str, num_classes: int = 2, pretrained: bool = Fal
 
 # the reference's LSTMWakeword, importable from its own module path (the factory entry is not switched on yet)
 from .lstm import LSTMWakeword  # noqa: E402,F401
+# likewise the reference's TCNWakeword (causal dilated Conv1d on the matrix cores, models/tcn.py)
+from .tcn import NativeCausalConv1d, TemporalBlock, TemporalConvNet, TCNWakeword  # noqa: E402,F401
