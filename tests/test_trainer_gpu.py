@@ -225,6 +225,89 @@ def test_nonfinite_batch_is_skipped_on_the_device(tmp_path, deferred):
         assert torch.isnan(model2(bad.to(DEV))).any()
 
 
+_UNFUSED_RUNS = {}            # (optim, deferred) -> what _unfused_run saw: each arm runs once, the test's cases share it
+
+
+def _unfused_run(optim, deferred, ckpt_dir):
+    """cnn_small's native step under a torch optimizer over four batches of 8 (clean, NaN input, invalid target, clean):
+    step by step with the parameters snapshotted after every launched step, then one epoch through train_epoch."""
+    if (optim, deferred) in _UNFUSED_RUNS:
+        return _UNFUSED_RUNS[optim, deferred]
+    from wakeword_trainer_home_amd.config import WakewordConfig
+    from wakeword_trainer_home_amd.models import create_model
+    from wakeword_trainer_home_amd.training import Trainer
+    cfg = WakewordConfig()
+    cfg.training.epochs, cfg.optimizer.warmup_epochs = 1, 0
+    cfg.training.deferred_metrics = deferred
+    cfg.model.architecture = "cnn_small"
+    x, y = make_inputs(21, 32)
+    bad = x[8:16].clone()
+    bad[3, 0, 5, 7] = float("nan")
+    badt = y[16:24].clone()
+    badt[2] = 5
+    batches = [(x[0:8], y[0:8]), (bad, y[8:16]), (x[16:24], badt), (x[24:32], y[24:32])]
+
+    def trainer():
+        torch.manual_seed(1)
+        model = create_model("cnn_small", dropout=0.0)
+        t = Trainer(model, batches, batches[:1], cfg, checkpoint_dir=ckpt_dir, device=DEV)
+        if optim == "adam_fused":
+            t.optimizer = torch.optim.Adam(model.parameters(), lr=1e-3, fused=True)
+        else:
+            t.optimizer = torch.optim.SGD(model.parameters(), lr=1e-2, momentum=0.9)
+        t._classify_optimizer()
+        return t
+
+    def params(t):
+        return torch.cat([p.detach().flatten().clone() for p in t.model.parameters()])
+
+    t = trainer()
+    r = {"fused": t._fused_optimizer, "skip_on_device": t._skip_on_device, "deferred": t.deferred_metrics}
+    t.model.train()
+    t.train_metrics_tracker.reset()
+    r["snaps"], r["returned"] = [params(t)], []
+    for i, (xi, yi) in enumerate(batches):
+        r["returned"] += t._step_native(xi, yi, i)
+        torch.cuda.synchronize()
+        r["snaps"].append(params(t))
+    r["returned"] += t._flush_pending()
+    t2, fired = trainer(), []
+
+    class CB:
+        def on_batch_end(self, idx, loss, acc):
+            fired.append((idx, loss, acc))
+    t2.add_callback(CB())
+    t2.train_epoch(0)                                 # ends with its own _flush_pending()
+    r["fired"] = fired
+    _UNFUSED_RUNS[optim, deferred] = r
+    return r
+
+
+@pytest.mark.parametrize("deferred", [True, False])
+@pytest.mark.parametrize("optim", ["adam_fused", "sgd"])
+def test_unfused_native_arms_skip_and_apply(tmp_path, optim, deferred):
+    """The native step under a torch optimizer, the two arms no other GPU test runs: one that takes found_inf on the
+    device (fused Adam: clip kernel, then optimizer.step() with the flag) and one that cannot (SGD: the host reads the
+    stats, then steps or drops the gradients).  The properties of test_nonfinite_batch_is_skipped_on_the_device: a
+    skipped batch changes no parameter and reports nothing, and reading the stats one step late changes no update."""
+    r = _unfused_run(optim, deferred, tmp_path)
+    assert not r["fused"]
+    assert r["skip_on_device"] == (optim == "adam_fused")
+    assert r["deferred"] == (deferred and optim == "adam_fused")       # the host decides for SGD: nothing to defer
+    start, s0, s1, s2, s3 = r["snaps"]
+    assert not torch.equal(start, s0), "the first clean batch must be applied"
+    assert torch.equal(s0, s1), "NaN batch must not change the parameters"
+    assert torch.equal(s1, s2), "invalid-target batch must not change the parameters"
+    assert not torch.equal(s2, s3) and not torch.equal(s0, s3), "the last clean batch must be applied"
+    assert torch.isfinite(s3).all()
+    for what in ("returned", "fired"):               # what the steps handed back / what train_epoch gave on_batch_end
+        assert [d[0] for d in r[what]] == [0, 3], (what, r[what])
+        assert all(np.isfinite(d[1]) for d in r[what]), (what, r[what])
+    if optim == "adam_fused":
+        other = _unfused_run(optim, not deferred, tmp_path)
+        assert torch.equal(s3, other["snaps"][-1]), "reading the stats one step late must not change the update"
+
+
 @pytest.mark.parametrize("poison", [False, True], ids=["clean", "with_a_skipped_batch"])
 def test_native_resume_continues_like_an_uninterrupted_run(tmp_path, poison):
     """Checkpoint after 2 of 4 epochs (native cnn_small, fused clip+optimizer, dropout on), resume in a fresh Trainer: the

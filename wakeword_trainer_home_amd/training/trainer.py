@@ -88,6 +88,7 @@ class Trainer:
         concatenated batch."""
         enforce_cuda()
         self.device, self.config = device, config
+        self._dev_type = torch.device(device).type
         self.model = model.to(device).to(memory_format=torch.channels_last)
         self.native = isinstance(self.model, CNNSmallWakeword)
         self.train_loader, self.val_loader = train_loader, val_loader
@@ -156,10 +157,7 @@ class Trainer:
                 for t in list(self.model.parameters()) + list(self.model.buffers()):
                     self._dist.broadcast(t, src=0)
         self._stats_host = None
-        # native step pipelining (see _launch_native): the optimizer consumes the device-side found_inf flag, so no
-        # host read sits between backward and optimizer.step(); with deferred_metrics a step's 48-byte stats are
-        # resolved while the NEXT step is already running (callbacks fire one step late, same order and content).
-        self._fused_optimizer = isinstance(self.optimizer, FlatFusedOptimizer)    # clip + update = one launch
+        self._classify_optimizer()
         if self._stores_fp16():
             # fp16 storage: gradients travel times a dynamic loss scale; trainer.scaler keeps GradScaler's interface
             if not (self._fused_optimizer and self._native_loss):
@@ -169,14 +167,6 @@ class Trainer:
             self.scaler = DeviceGradScaler(self.device, self.optimizer)
             self.loss_scale = self.scaler.state
             self.criterion.loss_scale = self.loss_scale
-        self._skip_on_device = self._fused_optimizer or bool(getattr(self.optimizer, "_step_supports_amp_scaling", False))
-        # HIP-backed models that go through autograd (gru, crnn, mobilenetv3) get the same sync-free step: native loss stats,
-        # device-side clip and skip decision, one deferred 48-byte read (the reference's step reads loss/acc/grad-norm back
-        # three times per batch, trainer.py:177-209)
-        self._async_autograd = (not self.native and self._native_loss and self._skip_on_device
-                                and bool(getattr(self.model, "hip_backed", False)) and torch.device(device).type == "cuda")
-        self.deferred_metrics = (bool(getattr(config.training, "deferred_metrics", True))
-                                 and (self.native or self._async_autograd) and self._native_loss and self._skip_on_device)
         self._pending = None
         self._dropout_modules = [m for m in self.model.modules() if hasattr(m, "dropout_step")]
         self._dp_voted = False             # the ranks agreed to skip the current batch (reference-style step only)
@@ -199,13 +189,36 @@ class Trainer:
         self._graphs = {}
         self._graph = None                 # the graph used last: captured graph + static buffers + host mirror of the control block
         self._graph_seen = {}              # _graph_key -> eager steps seen (a key is captured when it repeats)
-        self._eager_native_steps = 0
         self.audio_augmentation = None     # data.augmentation.AudioAugmentation; applied to (B,N) training batches
         logger.info("Trainer initialized (device=%s, model=%s, native=%s, optimizer=%s, scheduler=%s, loss=%s, "
                     "world=%d)", device, config.model.architecture, self.native, config.optimizer.optimizer,
                     config.optimizer.scheduler, config.loss.loss_function, self.world_size)
 
     # ------------------------------------------------------------------------------- helpers
+    def _classify_optimizer(self):
+        """Which step arms ``self.optimizer`` allows (call again after replacing it).  Native step pipelining (see
+        _step_native): the optimizer consumes the device-side found_inf flag, so no host read sits between backward and
+        optimizer.step(); with deferred_metrics a step's 48-byte stats are resolved while the NEXT step is already
+        running (callbacks fire one step late, same order and content)."""
+        self._fused_optimizer = isinstance(self.optimizer, FlatFusedOptimizer)    # clip + update = one launch
+        self._skip_on_device = self._fused_optimizer or bool(getattr(self.optimizer, "_step_supports_amp_scaling", False))
+        # HIP-backed models that go through autograd (gru, crnn, mobilenetv3) get the same sync-free step: native loss stats,
+        # device-side clip and skip decision, one deferred 48-byte read (the reference's step reads loss/acc/grad-norm back
+        # three times per batch, trainer.py:177-209)
+        self._async_autograd = (not self.native and self._native_loss and self._skip_on_device
+                                and bool(getattr(self.model, "hip_backed", False)) and self._dev_type == "cuda")
+        self.deferred_metrics = (bool(getattr(self.config.training, "deferred_metrics", True))
+                                 and (self.native or self._async_autograd) and self._native_loss and self._skip_on_device)
+
+    @property
+    def _max_norm(self) -> float:
+        return max(float(self.gradient_clip), 0.0)
+
+    def _set_sample_offset(self, B: int):
+        """First global sample index of this rank's shard: dropout draws per global sample (data parallel)."""
+        if hasattr(self.model, "sample_offset"):
+            self.model.sample_offset = self.rank * B
+
     def _bar(self, loader, desc):
         if tqdm is None or not self.show_progress:
             return loader
@@ -237,13 +250,12 @@ class Trainer:
         wave = inputs.to(self.device, non_blocking=True)
         if wave.dtype not in (torch.float32, torch.int16):
             wave = wave.float()
+        if step is None:
+            step = self.launched_steps
         if training and self.audio_augmentation is not None:
             # RIR + background mix on the device, ahead of the STFT (the reference does this on CPU dataset workers)
-            wave = self.audio_augmentation(wave, step=self._launch_step_index() if step is None else step,
-                                           sample_offset=self.rank * wave.shape[0])
-        return nat.logmel_fwd(wave.contiguous(), cfg, sa, seed=a.seed,
-                              step=self._launch_step_index() if step is None else step,
-                              sample_offset=self.rank * wave.shape[0])
+            wave = self.audio_augmentation(wave, step=step, sample_offset=self.rank * wave.shape[0])
+        return nat.logmel_fwd(wave.contiguous(), cfg, sa, seed=a.seed, step=step, sample_offset=self.rank * wave.shape[0])
 
     def _read_stats(self, stats: torch.Tensor) -> dict:
         """The step's single device->host transfer (48 bytes, pinned)."""
@@ -291,7 +303,7 @@ class Trainer:
 
     def _dp_flag_slot(self):
         """float32[1] device view that travels with the gradients through the all-reduce: any rank's found_inf."""
-        if not self._dist or torch.device(self.device).type != "cuda":
+        if not self._dist or self._dev_type != "cuda":
             return None
         if hasattr(self.model, "flat_grad_ext"):
             if self.native:
@@ -392,17 +404,12 @@ class Trainer:
         collective its peers never enter."""
         if not self._dist:
             return bad
-        dev = self.device if torch.device(self.device).type == "cuda" else "cpu"
+        dev = self.device if self._dev_type == "cuda" else "cpu"
         flag = torch.tensor([1.0 if bad else 0.0], device=dev)
         self._dist.all_reduce(flag, op=self._dist.ReduceOp.MAX)
         return bool(flag.item() > 0)
 
     # ------------------------------------------------------------------------------- inner steps
-    def _launch_step_index(self) -> int:
-        """Counter of the Philox streams (SpecAugment, audio augmentation, dropout): the index of the step being
-        launched -- every launched batch takes one, skipped or not."""
-        return self.launched_steps
-
     def _begin_step(self, index: Optional[int] = None) -> int:
         """Hand the step's Philox counter to every HIP module that draws masks, then advance it."""
         if index is None:
@@ -438,6 +445,64 @@ class Trainer:
             if r is not None:
                 out.append(r)
         return out
+
+    # The tail every sync-free step arm (_step_native, _step_autograd_async, _step_native_graph) ends with
+    def _stats_record(self, pair: bool = False):
+        """The pinned 48-byte record this step writes.  Two of them, alternating, so the deferred read of one step is not
+        overwritten by the next: the fused optimizer's slot parity picks one (the same rule a graph replay follows).
+        ``pair``: both records, for a capture, which bakes the two addresses."""
+        if self._host_bufs is None:
+            self._host_bufs = [torch.empty(nat.STEP_STATS_BYTES, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        if pair:
+            return self._host_bufs
+        buf = self._host_bufs[self.optimizer._parity if self._fused_optimizer else self._buf_i]
+        self._buf_i ^= 1
+        return buf
+
+    def _unfused_update(self, stats, flag):
+        """Clip + update through a torch optimizer (the fused one does all of this in one launch); returns the pinned
+        record the step's stats were copied to."""
+        buf = self._stats_record()
+        sv = stats.view(torch.float32)
+        if flag is not None:                       # some rank's bad batch -> every rank's found_inf
+            sv[nat.FOUND_INF_FLOAT_INDEX] = torch.maximum(sv[nat.FOUND_INF_FLOAT_INDEX], (flag[0] != 0).float())
+        if self.native:
+            nat.grad_norm_clip_(self.model.flat_grad, self._max_norm, stats=stats)
+        elif self.gradient_clip > 0:
+            norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), float(self.gradient_clip), foreach=True)
+            sv[1] = norm                                                               # ww_step_stats.grad_norm
+            sv[nat.FOUND_INF_FLOAT_INDEX] = torch.maximum(sv[nat.FOUND_INF_FLOAT_INDEX], (~torch.isfinite(norm)).float())
+        if self._skip_on_device:
+            # the reference skips a batch whose loss is not finite (trainer.py:177-179) or whose targets are invalid
+            # (losses.py:72) before touching the parameters; here the optimizer gets that decision as a device flag
+            # (the mechanism GradScaler uses), so nothing on the host waits for the GPU.  (An optimizer that cannot
+            # take the flag is stepped by _hand_back, once the host has read the stats.)
+            self.optimizer.grad_scale = None
+            self.optimizer.found_inf = sv[nat.FOUND_INF_FLOAT_INDEX]
+            try:
+                self.optimizer.step()
+            finally:
+                del self.optimizer.grad_scale, self.optimizer.found_inf
+        buf.copy_(stats, non_blocking=True)
+        return buf
+
+    def _hand_back(self, batch_idx, buf):
+        """Mark the end of the launched step on the stream; returns the steps whose results became available: this one
+        when it is resolved at once, else (deferred_metrics) the previous one, while this one is parked."""
+        event = torch.cuda.Event()
+        event.record()
+        launched = (batch_idx, buf, event)
+        if self._skip_on_device and self.deferred_metrics:
+            done = self._flush_pending()           # previous step: finished long ago, no stall
+            self._pending = launched
+            return done
+        r = self._resolve(launched)
+        if not self._skip_on_device:               # optimizer cannot skip on the device: decide on the host
+            if r is None:
+                self.optimizer.zero_grad(set_to_none=True)
+            else:
+                self.optimizer.step()
+        return [] if r is None else [r]
 
     def _prepare_native(self, inputs, targets, step_index, after=None):
         """Input stage of a native step on its own HIP stream: H2D (if needed) + fused log-mel/SpecAugment.  It has no
@@ -479,7 +544,7 @@ class Trainer:
         replayed = self._graph_step_or_capture(inputs, targets, step_index, batch_idx)
         if replayed is not None:
             return replayed
-        self.model.sample_offset = self.rank * inputs.shape[0]
+        self._set_sample_offset(inputs.shape[0])
         self.optimizer.zero_grad(set_to_none=True)
         flag = None
         if self.loss_scale is not None:
@@ -504,51 +569,16 @@ class Trainer:
                 stats = self.model.train_step_native(inputs, targets, self.criterion, found_inf_out=flag)
                 self._reduce_inline(ext)
             self._reduce_finish(handles)
-        if self._host_bufs is None:
-            self._host_bufs = [torch.empty(nat.STEP_STATS_BYTES, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        # two pinned records, alternating: the fused optimizer's slot parity picks one (the same rule a graph replay follows)
-        buf = self._host_bufs[self.optimizer._parity if self._fused_optimizer else self._buf_i]
-        self._buf_i ^= 1
         if self._fused_optimizer:
             # clip_gradients + "skip a non-finite batch" + optimizer.step() (trainer.py:177-193) in ONE launch, which also
             # writes the step's 48-byte record into pinned host memory
-            self.optimizer.step(max_norm=max(float(self.gradient_clip), 0.0), stats=stats, stats_host=buf,
-                                found_inf_extra=flag, loss_scale=self.loss_scale)
+            buf = self._stats_record()
+            self.optimizer.step(max_norm=self._max_norm, stats=stats, stats_host=buf, found_inf_extra=flag,
+                                loss_scale=self.loss_scale)
         else:
-            if flag is not None:                   # some rank's bad batch -> every rank's found_inf
-                sv = stats.view(torch.float32)
-                sv[nat.FOUND_INF_FLOAT_INDEX] = torch.maximum(sv[nat.FOUND_INF_FLOAT_INDEX], (flag[0] != 0).float())
-            nat.grad_norm_clip_(self.model.flat_grad, max(float(self.gradient_clip), 0.0), stats=stats)
-        if self._skip_on_device and not self._fused_optimizer:
-            # the reference skips a batch whose loss is not finite (trainer.py:177-179) or whose targets are invalid
-            # (losses.py:72) before touching the parameters; here the fused optimizer gets that decision as a
-            # device flag (the mechanism GradScaler uses), so nothing on the host waits for the GPU
-            self.optimizer.grad_scale = None
-            self.optimizer.found_inf = stats.view(torch.float32)[nat.FOUND_INF_FLOAT_INDEX]
-            try:
-                self.optimizer.step()
-            finally:
-                del self.optimizer.grad_scale, self.optimizer.found_inf
-        if not self._fused_optimizer:
-            buf.copy_(stats, non_blocking=True)
-        event = torch.cuda.Event()
-        event.record()
-        launched = (batch_idx, buf, event)
-        self._eager_native_steps += 1
+            buf = self._unfused_update(stats, flag)
         self._graph_after_eager(inputs)
-        if not self._skip_on_device:               # optimizer cannot skip on the device: decide on the host
-            r = self._resolve(launched)
-            if r is None:
-                self.optimizer.zero_grad(set_to_none=True)
-                return []
-            self.optimizer.step()
-            return [r]
-        if not self.deferred_metrics:
-            r = self._resolve(launched)
-            return [] if r is None else [r]
-        done = self._flush_pending()               # previous step: finished long ago, no stall
-        self._pending = launched
-        return done
+        return self._hand_back(batch_idx, buf)
 
     # ------------------------------------------------------------------------------- HIP graph replay of the native step
     def _graph_capture(self, feats):
@@ -579,17 +609,16 @@ class Trainer:
         forked = [m for m in self.model.modules() if getattr(m, "overlap_directions", False)]
         for m in forked:
             m.overlap_directions = False
+        records = self._stats_record(pair=True)    # a replay writes the one its slot parity picks
         graph = torch.cuda.CUDAGraph()
         torch.cuda.synchronize(dev)
         nat.bind_step_ctl(dev, g["ctl"])           # launches issued while bound read step / lr / parity from the block
-        max_norm = max(float(self.gradient_clip), 0.0)
         try:
             with torch.cuda.graph(graph):
                 nat.step_ctl_advance(dev)
                 for m in self._dropout_modules:
                     m.dropout_step = 0             # an OFFSET while the block is bound
-                if hasattr(self.model, "sample_offset"):
-                    self.model.sample_offset = self.rank * B
+                self._set_sample_offset(B)
                 self.optimizer.zero_grad(set_to_none=True)
                 flag = self.model.flat_grad_ext[-1:] if self._dist else None
                 if self.native:
@@ -601,9 +630,8 @@ class Trainer:
                     self.model.gather_grads()
                 if self._dist:
                     self._reduce_inline(self.model.flat_grad_ext)
-                self.optimizer.step(max_norm=max_norm, stats=stats, stats_host=self._host_bufs[0],
-                                    stats_host_alt=self._host_bufs[1], found_inf_extra=flag, gathered=not self.native,
-                                    loss_scale=self.loss_scale)
+                self.optimizer.step(max_norm=self._max_norm, stats=stats, stats_host=records[0], stats_host_alt=records[1],
+                                    found_inf_extra=flag, gathered=not self.native, loss_scale=self.loss_scale)
         finally:
             nat.bind_step_ctl(dev, None)
             for m in forked:
@@ -617,7 +645,7 @@ class Trainer:
                     p_.grad = self.model._grad_views[id(p_)]
         g["graph"] = graph
         # buffers the graph's nodes point at but that were allocated outside its memory pool: keep them alive with it
-        g["keepalive"] = [self.model.flat_grad_ext, self.model.flat_param, self.criterion.last_stats] + self._host_bufs
+        g["keepalive"] = [self.model.flat_grad_ext, self.model.flat_param, self.criterion.last_stats] + records
         g["keepalive"] += [slot["buf"] for m in self.model.modules() if hasattr(m, "_ws") for slot in m._ws.values()]
         self._graphs[g["key"]] = g
         self._graph = g
@@ -641,19 +669,11 @@ class Trainer:
             g["lr"] = lr
         g["graph"].replay()
         g["step"], g["parity"] = idx & 0xFFFFFFFFFFFFFFFF, self.optimizer._parity
-        buf = self._host_bufs[self.optimizer._parity]
+        buf = self._stats_record()                 # by the parity the replay ran with
         self.optimizer._parity ^= 1
         for m, d in g["tracked"]:
             m._pending_tracked += d
-        event = torch.cuda.Event()
-        event.record()
-        launched = (batch_idx, buf, event)
-        if not self.deferred_metrics:
-            r = self._resolve(launched)
-            return [] if r is None else [r]
-        done = self._flush_pending()
-        self._pending = launched
-        return done
+        return self._hand_back(batch_idx, buf)
 
     def _stores_fp16(self) -> bool:
         # (`act` is the storage code of the conv stack only -- the generic layers of MobileNetV3 use that name for their
@@ -737,8 +757,7 @@ class Trainer:
             replayed = self._graph_step_or_capture(inputs.contiguous(), targets, step_index, batch_idx)
             if replayed is not None:
                 return replayed
-        if hasattr(self.model, "sample_offset"):
-            self.model.sample_offset = self.rank * inputs.shape[0]
+        self._set_sample_offset(inputs.shape[0])
         self.optimizer.zero_grad(set_to_none=True)
         flag = self._dp_flag_slot()                # the loss kernel drops its skip flag behind the gradient bucket
         self.criterion.found_inf_out = flag
@@ -753,11 +772,6 @@ class Trainer:
             if ov is not None:
                 ov["armed"] = False
         stats = self.criterion.last_stats
-        if self._host_bufs is None:
-            self._host_bufs = [torch.empty(nat.STEP_STATS_BYTES, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        # two pinned records, alternating: the fused optimizer's slot parity picks one (the same rule a graph replay follows)
-        buf = self._host_bufs[self.optimizer._parity if self._fused_optimizer else self._buf_i]
-        self._buf_i ^= 1
         if self._fused_optimizer:
             # flat buckets (models/flat_buckets.py): gather the autograd gradients, ONE all-reduce, then clip + skip +
             # update + the 48-byte statistics record in one launch -- as the native cnn_small step does
@@ -770,55 +784,32 @@ class Trainer:
                 else:
                     self._reduce_inline(self.model.flat_grad_ext)
                     self.last_collective = "in-stream"
-            self.optimizer.step(max_norm=max(float(self.gradient_clip), 0.0), stats=stats, stats_host=buf, gathered=True,
-                                found_inf_extra=flag, loss_scale=self.loss_scale)
+            buf = self._stats_record()
+            self.optimizer.step(max_norm=self._max_norm, stats=stats, stats_host=buf, gathered=True, found_inf_extra=flag,
+                                loss_scale=self.loss_scale)
         else:
             self._allreduce_grads()
-            sv = stats.view(torch.float32)
-            if flag is not None:
-                sv[nat.FOUND_INF_FLOAT_INDEX] = torch.maximum(sv[nat.FOUND_INF_FLOAT_INDEX], (flag[0] != 0).float())
-            if self.gradient_clip > 0:
-                norm = torch.nn.utils.clip_grad_norm_(self.model.parameters(), float(self.gradient_clip), foreach=True)
-                sv[1] = norm                                                               # ww_step_stats.grad_norm
-                sv[nat.FOUND_INF_FLOAT_INDEX] = torch.maximum(sv[nat.FOUND_INF_FLOAT_INDEX],
-                                                              (~torch.isfinite(norm)).float())
-            self.optimizer.grad_scale = None
-            self.optimizer.found_inf = sv[nat.FOUND_INF_FLOAT_INDEX]
-            try:
-                self.optimizer.step()
-            finally:
-                del self.optimizer.grad_scale, self.optimizer.found_inf
-            buf.copy_(stats, non_blocking=True)
-        event = torch.cuda.Event()
-        event.record()
-        launched = (batch_idx, buf, event)
+            buf = self._unfused_update(stats, flag)
         if inputs.dim() == 4 and inputs.is_cuda:
             self._graph_after_eager(inputs)
-        if not self.deferred_metrics:
-            r = self._resolve(launched)
-            return [] if r is None else [r]
-        done = self._flush_pending()
-        self._pending = launched
-        return done
+        return self._hand_back(batch_idx, buf)
 
     def _to_model_input(self, inputs, training, step=None):
         """(B,N) waveforms go through the native front end (log-mel/MFCC [+SpecAugment, audio augmentation]); feature
         batches are moved as the reference does (channels_last, trainer.py:160)."""
-        if inputs.dim() == 2 and torch.device(self.device).type == "cuda":
+        if inputs.dim() == 2 and self._dev_type == "cuda":
             return self._features(inputs, training=training, step=step)
         return inputs.to(self.device, non_blocking=True, memory_format=torch.channels_last)
 
     def _step_generic(self, inputs, targets, batch_idx):
         step_index = self._begin_step()
         self.optimizer.zero_grad(set_to_none=True)
-        dev_type = torch.device(self.device).type
         failure = None
         try:
             inputs = self._to_model_input(inputs, training=True, step=step_index)
             targets = targets.to(self.device, non_blocking=True)
-            if hasattr(self.model, "sample_offset"):
-                self.model.sample_offset = self.rank * inputs.shape[0]
-            with torch.autocast(dev_type, enabled=self._autocast and dev_type == "cuda"):
+            self._set_sample_offset(inputs.shape[0])
+            with torch.autocast(self._dev_type, enabled=self._autocast and self._dev_type == "cuda"):
                 outputs = self.model(inputs)
                 loss = self.criterion(outputs, targets)
             finite = bool(torch.isfinite(loss))
@@ -854,7 +845,7 @@ class Trainer:
             inputs = self._features(inputs, training=False) if inputs.dim() == 2 else inputs.to(self.device,
                                                                                               non_blocking=True)
             targets = targets.to(self.device, non_blocking=True)
-            self.model.sample_offset = self.rank * inputs.shape[0]
+            self._set_sample_offset(inputs.shape[0])
             self.criterion(self.model(inputs), targets)
             s = self._read_stats(self.criterion.last_stats)
             if s["bad_target"]:
@@ -865,8 +856,7 @@ class Trainer:
             return s["loss"]
         inputs = self._to_model_input(inputs, training=False)
         targets = targets.to(self.device, non_blocking=True)
-        dev_type = torch.device(self.device).type
-        with torch.autocast(dev_type, enabled=self._autocast and dev_type == "cuda"):
+        with torch.autocast(self._dev_type, enabled=self._autocast and self._dev_type == "cuda"):
             outputs = self.model(inputs)
             loss = self.criterion(outputs, targets)
         if not torch.isfinite(loss):
@@ -878,7 +868,7 @@ class Trainer:
         """Data parallel: every rank sees the epoch's global counters / mean loss."""
         if not self._dist:
             return loss_sum, n_batches
-        dev = self.device if torch.device(self.device).type == "cuda" else "cpu"
+        dev = self.device if self._dev_type == "cuda" else "cpu"
         t = torch.tensor(tracker._c + [n_batches], dtype=torch.float64, device=dev)
         ls = torch.tensor([loss_sum], dtype=torch.float64, device=dev)
         self._dist.all_reduce(t)
@@ -923,6 +913,18 @@ class Trainer:
             voted, self._dp_voted = self._dp_voted, False
             return voted
 
+        def failed(e, idx) -> bool:
+            """A batch's exception (trainer.py:214-226): True = logged and the batch skipped, False = the caller re-raises."""
+            if isinstance(e, RuntimeError):
+                if "out of memory" in str(e).lower() and survivable(e):
+                    logger.error("GPU OOM at batch %d. Clearing cache and skipping batch.", idx)
+                    torch.cuda.empty_cache()
+                    return True
+                logger.exception("Runtime error at batch %d: %s", idx, e)
+                return False
+            logger.exception("Unexpected error at batch %d: %s", idx, e)
+            return survivable(e)
+
         def stage(item):
             """fetch-side work for one loader item: validate, and (native) enqueue its input stage on the side stream"""
             idx, batch = item
@@ -938,16 +940,8 @@ class Trainer:
                     prep = self._prepare_native(parsed[0], parsed[1], index,
                                                 after=meta.get("ready") if isinstance(meta, dict) else None)
                 return idx, parsed, prep
-            except RuntimeError as e:
-                if "out of memory" in str(e).lower() and survivable(e):
-                    logger.error("GPU OOM at batch %d. Clearing cache and skipping batch.", idx)
-                    torch.cuda.empty_cache()
-                    return None
-                logger.exception("Runtime error at batch %d: %s", idx, e)
-                raise
-            except Exception as e:
-                logger.exception("Unexpected error at batch %d: %s", idx, e)
-                if not survivable(e):
+            except Exception as e:                 # noqa: BLE001
+                if not failed(e, idx):
                     raise
                 return None
 
@@ -971,18 +965,9 @@ class Trainer:
                     account(self._step_native(None, None, batch_idx, prepared=prep))
                 else:
                     account(step(parsed[0], parsed[1], batch_idx))
-            except RuntimeError as e:
-                if "out of memory" in str(e).lower() and survivable(e):
-                    logger.error("GPU OOM at batch %d. Clearing cache and skipping batch.", batch_idx)
-                    torch.cuda.empty_cache()
-                    continue
-                logger.exception("Runtime error at batch %d: %s", batch_idx, e)
-                raise
-            except Exception as e:
-                logger.exception("Unexpected error at batch %d: %s", batch_idx, e)
-                if not survivable(e):
+            except Exception as e:                 # noqa: BLE001
+                if not failed(e, batch_idx):
                     raise
-                continue
         account(self._flush_pending())            # the last step's deferred results
         epoch_loss, num_batches = self._epoch_reduce(self.train_metrics_tracker, epoch_loss, num_batches)
         avg_loss = epoch_loss / max(num_batches, 1)
