@@ -483,6 +483,39 @@ int ww_tconv1d_bwd(ww_ctx *ctx, int mode, const float *x, const float *w, const 
 int ww_add_relu_fwd(ww_ctx *ctx, const float *a, const float *b, size_t n, float *y, ww_stream_t stream);
 int ww_relu_mask_bwd(ww_ctx *ctx, const float *dy, const float *y, size_t n, float *dx, ww_stream_t stream);
 
+/* ------------------------------------------------------------------ dense Conv2d on the matrix cores (ResNet18Wakeword)
+ * nn.Conv2d(Cin, Cout, k, stride, padding = k/2, bias=False), channels-last, as an implicit GEMM (M = pixels, K = k*k*Cin, N = Cout;
+ * no patch matrix in memory):
+ *   y[b,ho,wo,n] = sum_{r,s,c} x[b, ho*stride + r - k/2, wo*stride + s - k/2, c] w[n,c,r,s]      (pixels outside the image read as 0)
+ * x / dx (B,H,W,Cin), y / dy (B,Ho,Wo,Cout) with Ho = (H + 2(k/2) - k)/stride + 1 (Wo likewise), w / dw (Cout,Cin,k,k) =
+ * nn.Conv2d.weight; all fp32, contiguous, 16-byte aligned.  mode as ww_tconv1d_*: WW_ACT_F32 = v_mfma_f32_32x32x2_f32 (parity mode),
+ * WW_ACT_BF16 / WW_ACT_F16 = operands rounded when staged, fp32 accumulation.  k odd in 1..7, stride 1 or 2, B, H, W >= 1, Cin and
+ * Cout positive multiples of 4; anything else is WW_E_INVALID before any launch.  scratch: ww_conv2d_scratch_bytes(...) bytes
+ * (WW_E_WORKSPACE; 0 for a shape the kernels refuse).
+ * bwd: dx (nullable; added to when accumulate_dx != 0, else EVERY pixel is written -- also those no output read, as zeros) and dw
+ * in a fixed summation order: pixel-range partial products summed in order -- queued instead while ww_ctx_set_deferred_reduce is
+ * in force (the scratch must then live until the flush).                                                                      */
+size_t ww_conv2d_scratch_bytes(int B, int H, int W, int Cin, int Cout, int k, int stride);
+int ww_conv2d_fwd(ww_ctx *ctx, int mode, const float *x, const float *w, int B, int H, int W, int Cin, int Cout, int k, int stride,
+                  float *y, void *scratch, size_t scratch_bytes, ww_stream_t stream);
+int ww_conv2d_bwd(ww_ctx *ctx, int mode, const float *x, const float *w, const float *dy, int B, int H, int W, int Cin, int Cout, int k,
+                  int stride, float *dx /* nullable */, int accumulate_dx, float *dw, void *scratch, size_t scratch_bytes,
+                  ww_stream_t stream);
+/* The one-channel stem nn.Conv2d(1, C, k, stride, k/2, bias=False) (the reference replaces resnet18's conv1 by Conv2d(1,64,7,2,3)) as
+ * a direct fp32 convolution: x (B,H,W) -> y (B,Ho,Wo,C), w (C,1,k,k); k odd in 1..7, stride 1 or 2, C a multiple of 4 in 4..128.
+ * The image may be smaller than the kernel.  ww_conv2d_stem_bwd_dw is its weight gradient (the input needs none), summed in a fixed
+ * order or queued as above; scratch: ww_conv2d_stem_scratch_bytes(C, k).                                                      */
+size_t ww_conv2d_stem_scratch_bytes(int C, int k);
+int ww_conv2d_stem_fwd(ww_ctx *ctx, const float *x, const float *w, int B, int H, int W, int C, int k, int stride, float *y,
+                       ww_stream_t stream);
+int ww_conv2d_stem_bwd_dw(ww_ctx *ctx, const float *x, const float *dy, int B, int H, int W, int C, int k, int stride, float *dw,
+                          void *scratch, size_t scratch_bytes, ww_stream_t stream);
+/* nn.MaxPool2d(3, 2, 1) on (B,H,W,C) -> (B,(H-1)/2+1,(W-1)/2+1,C), C a positive multiple of 4.  Padding never wins; the gradient goes
+ * to the FIRST maximal element of a window in row-major order (torch's rule), recomputed from x: a gather per input pixel over the
+ * at most 4 windows that contain it, no atomics.                                                                              */
+int ww_maxpool3x3s2_fwd(ww_ctx *ctx, const float *x, int B, int H, int W, int C, float *y, ww_stream_t stream);
+int ww_maxpool3x3s2_bwd(ww_ctx *ctx, const float *x, const float *dy, int B, int H, int W, int C, float *dx, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ GRU layer, one direction
  * torch.nn.GRU's cell and parameter layout (gate order r|z|n; w_ih (3H,I), w_hh (3H,H), b_ih, b_hh (3H)) -- what the
  * reference's GRUWakeword wraps (src/models/architectures.py:228-235).  batch_first: x (B,T,I) with row stride ldx

@@ -14,7 +14,7 @@ import torch
 from wakeword_trainer_home_amd import _native as nat
 from wakeword_trainer_home_amd.config import get_preset
 from wakeword_trainer_home_amd.data import make_synthetic_batch
-from wakeword_trainer_home_amd.models import create_model, LSTMWakeword, TCNWakeword
+from wakeword_trainer_home_amd.models import create_model, LSTMWakeword, ResNet18Wakeword, TCNWakeword
 from wakeword_trainer_home_amd.training import Trainer
 
 dev = "cuda:0"
@@ -23,21 +23,25 @@ CONFIGS = (("crnn", 512, "bf16"), ("crnn", 4096, "bf16"), ("gru", 4096, "fp32"),
 GRAPH = "--graph" in sys.argv                 # replay the step as a captured HIP graph (Trainer hip_graph mode)
 argv = [a for a in sys.argv[1:] if a != "--graph"]
 if argv:                                      # e.g.  bench_models.py crnn 4096 fp16 [--graph]  |  lstm 512 fp32  |  tcn 512 bf16
-    CONFIGS = ((argv[0], int(argv[1]), argv[2]),)
+    CONFIGS = ((argv[0], int(argv[1]), argv[2]),)          # | resnet18 128 bf16 [N_MELS N_SAMPLES: 128 40000 = the preset's features]
+N_MELS, N_SAMPLES = (int(argv[3]), int(argv[4])) if len(argv) > 4 else (40, 24000)
 for arch, B, act in CONFIGS:
     cfg = get_preset("cnn_small_logmel40")
     cfg.training.batch_size = B
+    cfg.data.n_mels = N_MELS
     cfg.training.hip_graph, cfg.training.hip_graph_auto = GRAPH, False       # the eager line is eager for every model
     torch.manual_seed(0)
     kw = {"act_dtype": act} if arch == "crnn" else {"mode": act}
     # (the factory does not offer "lstm" and "tcn" yet: the reference's LSTMWakeword / TCNWakeword are built directly; the TCN
     # sees (B, 1, 40, 151) feature batches: 6 B T 432 640 FLOP per step in its convolutions, timed under "linear_mfma")
-    direct = {"lstm": LSTMWakeword, "tcn": TCNWakeword}
+    # resnet18 likewise: its convolutions' own 6 M K N FLOP (tools/bench_torch_resnet18.conv_flop) give conv_tflops, and the step of
+    # the plain-torch formulation (nn.Conv2d / BatchNorm2d / max_pool2d, channels-last, same dtype) is timed in the same run
+    direct = {"lstm": LSTMWakeword, "tcn": TCNWakeword, "resnet18": ResNet18Wakeword}
     model = direct[arch](dropout=0.3, **kw) if arch in direct else create_model(arch, dropout=0.3, **kw)
     with contextlib.redirect_stdout(sys.stderr):
         tr = Trainer(model, [], [], cfg, checkpoint_dir=Path(tempfile.mkdtemp()), device=dev)
     tr.model.train()
-    pool = [make_synthetic_batch(B, 24000, seed=i, device=dev) for i in range(2)]
+    pool = [make_synthetic_batch(B, N_SAMPLES, seed=i, device=dev) for i in range(2)]
     classes = ["logmel_specaug", "conv_stem_fwd", "dwconv3x3_fwd", "pwconv1x1_fwd", "pwconv1x1_bwd", "dwconv3x3_bwd", "conv_stem_bwd",
                "finalize", "gru", "linear_mfma", "nhwc_layers", "lstm"]
 
@@ -62,11 +66,20 @@ for arch, B, act in CONFIGS:
     torch.cuda.synchronize()
     prof = {k: round(v[0], 3) for k, v in nat.prof_collect(dev).items()}
     nat.prof_enable(dev, [])
+    extra = {}
+    if arch == "resnet18":
+        from bench_torch_resnet18 import conv_flop, torch_step_ms
+        F_, T_ = N_MELS, nat.num_frames(N_SAMPLES, cfg.data.hop_length)
+        pool = []                              # (the native step's clips make room for the torch model's activations)
+        torch.cuda.empty_cache()
+        t_ms = torch_step_ms(B, act, F_, T_)
+        extra = {"features": [1, F_, T_], "conv_tflops": round(3 * B * conv_flop(F_, T_) / dt / 1e12, 2),
+                 "torch_ms_per_step_no_front_end": round(t_ms, 3), "native_over_torch": round(dt * 1e3 / t_ms, 3)}
     print(json.dumps({"model": arch, "batch": B, "conv_storage": act if arch == "crnn" else None, "matrix_mode": act,
                       "hip_graph": tr._graph is not None, "loss_scale": tr.scaler.get_scale() if tr.loss_scale is not None else None,
                       "ms_per_step": round(dt * 1e3, 3),
                       "samples_per_s": round(B / dt, 1),
-                      **({"conv_tflops": round(6 * B * 151 * 432640 / dt / 1e12, 2)} if arch == "tcn" else {}),
+                      **({"conv_tflops": round(6 * B * 151 * 432640 / dt / 1e12, 2)} if arch == "tcn" else {}), **extra,
                       "class_ms_one_step": prof}))
     del tr, model, pool
     torch.cuda.empty_cache()

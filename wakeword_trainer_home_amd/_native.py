@@ -150,6 +150,14 @@ _SIGS = {
     "ww_tconv1d_bwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "ww_add_relu_fwd": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "ww_relu_mask_bwd": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "ww_conv2d_scratch_bytes": (_sz, [_i] * 7),
+    "ww_conv2d_fwd": (C.c_int, [_vp, _i, _vp, _vp] + [_i] * 7 + [_vp, _vp, _sz, _vp]),
+    "ww_conv2d_bwd": (C.c_int, [_vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_vp, _i, _vp, _vp, _sz, _vp]),
+    "ww_conv2d_stem_scratch_bytes": (_sz, [_i, _i]),
+    "ww_conv2d_stem_fwd": (C.c_int, [_vp, _vp, _vp] + [_i] * 6 + [_vp, _vp]),
+    "ww_conv2d_stem_bwd_dw": (C.c_int, [_vp, _vp, _vp] + [_i] * 6 + [_vp, _vp, _sz, _vp]),
+    "ww_maxpool3x3s2_fwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ww_maxpool3x3s2_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ww_dropout_bt": (C.c_int, [_vp, _vp, C.c_long, _i, _i, _i, _f, _u64, _u64, _u64, _i, _vp, C.c_long, _vp]),
     "ww_nhwc_scratch_bytes": (_sz, [_i]),
     "ww_bn_act_fwd": (C.c_int, [_vp, _vp, C.c_long, _i, C.POINTER(BN), _i, _vp, _vp, _vp, _vp, _vp]),
@@ -729,6 +737,112 @@ def relu_mask_bwd(dy, y):
     dx = torch.empty_like(dy)
     with _guard(dev):
         _check(load().ww_relu_mask_bwd(ctx(dev), _p(dy), _p(y), dy.numel(), _p(dx), _stream(dev)), "ww_relu_mask_bwd")
+    return dx
+
+
+# ---- dense Conv2d, the one-channel stem and MaxPool2d(3, 2, 1) (ResNet18Wakeword); contiguous fp32 (B, H, W, C) activations
+def _conv2d_check(x, w):
+    if (x.dim() != 4 or w.dim() != 4 or x.shape[3] != w.shape[1] or w.shape[2] != w.shape[3] or x.dtype != torch.float32
+            or w.dtype != torch.float32):
+        raise ValueError(f"conv2d: need float32 x (B,H,W,Cin) and weight (Cout,Cin,k,k), got {tuple(x.shape)} and {tuple(w.shape)}")
+
+
+def _conv2d_scratch(B, H, W, Cin, Cout, k, stride, dev):
+    # (0 bytes = a shape the kernels refuse: the call itself reports which argument)
+    return torch.empty(max(load().ww_conv2d_scratch_bytes(B, H, W, Cin, Cout, k, stride) // 4, 4), dtype=torch.float32, device=dev)
+
+
+def conv2d_fwd(x, w, stride=1, mode=torch.float32):
+    """y = conv2d(x, w, stride, padding=k//2); x (B,H,W,Cin), w (Cout,Cin,k,k) -> y (B,Ho,Wo,Cout)."""
+    dev = _dev(x, w)
+    _conv2d_check(x, w)
+    B, H, W, Cin = x.shape
+    Cout, _, k, _ = w.shape
+    y = torch.empty((B, *_dw_out_hw(H, W, k, max(stride, 1)), Cout), dtype=torch.float32, device=dev)
+    scratch = _conv2d_scratch(B, H, W, Cin, Cout, k, stride, dev)
+    with _guard(dev):
+        _check(load().ww_conv2d_fwd(ctx(dev), act_code(mode), _p(x), _p(w), B, H, W, Cin, Cout, k, stride, _p(y), _p(scratch),
+                                    scratch.numel() * 4, _stream(dev)), "ww_conv2d_fwd")
+    return y
+
+
+def conv2d_bwd(x, w, dy, stride=1, mode=torch.float32, need_dx=True, dx=None, dw_out=None, defer=False, accumulate=True):
+    """-> (dx | None, dw).  dx given: the input gradient is ADDED to it (accumulate=False: written over it); else every pixel of
+    a fresh dx is written.  defer: queue the sum of the dw partials (valid after deferred_flush)."""
+    dev = _dev(x, w, dy, dx)
+    _conv2d_check(x, w)
+    B, H, W, Cin = x.shape
+    Cout, _, k, _ = w.shape
+    oshape = (B, *_dw_out_hw(H, W, k, max(stride, 1)), Cout)
+    if tuple(dy.shape) != oshape or dy.dtype != torch.float32:
+        raise ValueError(f"conv2d backward: dy must be float32 {oshape}, got {tuple(dy.shape)}")
+    if dx is not None and (tuple(dx.shape) != tuple(x.shape) or dx.dtype != torch.float32):
+        raise ValueError(f"conv2d backward: dx must be float32 {tuple(x.shape)}, got {tuple(dx.shape)}")
+    accumulate = bool(accumulate) and dx is not None
+    if dx is None and need_dx:
+        dx = torch.empty((B, H, W, Cin), dtype=torch.float32, device=dev)
+    dw = _out(dw_out, (Cout, Cin, k, k), dev)
+    scratch = _conv2d_scratch(B, H, W, Cin, Cout, k, stride, dev)
+    with _guard(dev), (_deferring(dev, scratch) if defer else contextlib.nullcontext()):
+        _check(load().ww_conv2d_bwd(ctx(dev), act_code(mode), _p(x), _p(w), _p(dy), B, H, W, Cin, Cout, k, stride, _p(dx),
+                                    int(accumulate), _p(dw), _p(scratch), scratch.numel() * 4, _stream(dev)), "ww_conv2d_bwd")
+    return dx, dw
+
+
+def _stem_check(x, w):
+    if x.dim() != 3 or w.dim() != 4 or w.shape[1] != 1 or w.shape[2] != w.shape[3] or x.dtype != torch.float32 or w.dtype != torch.float32:
+        raise ValueError(f"conv2d stem: need float32 x (B,H,W) and weight (C,1,k,k), got {tuple(x.shape)} and {tuple(w.shape)}")
+
+
+def conv2d_stem_fwd(x, w, stride=2):
+    """x (B,H,W) one-channel images, w (C,1,k,k) -> y (B,Ho,Wo,C): Conv2d(1, C, k, stride, k//2, bias=False), direct."""
+    dev = _dev(x, w)
+    _stem_check(x, w)
+    B, H, W = x.shape
+    Cn, k = w.shape[0], w.shape[2]
+    y = torch.empty((B, *_dw_out_hw(H, W, k, max(stride, 1)), Cn), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_conv2d_stem_fwd(ctx(dev), _p(x), _p(w), B, H, W, Cn, k, stride, _p(y), _stream(dev)), "ww_conv2d_stem_fwd")
+    return y
+
+
+def conv2d_stem_bwd_dw(x, dy, w_shape, stride=2, dw_out=None, defer=False):
+    """dw (C,1,k,k) of conv2d_stem_fwd.  defer: queue the sum of the partials (valid after deferred_flush)."""
+    dev = _dev(x, dy)
+    B, H, W = x.shape
+    Cn, _, k, _ = w_shape
+    oshape = (B, *_dw_out_hw(H, W, k, max(stride, 1)), Cn)
+    if x.dtype != torch.float32 or tuple(dy.shape) != oshape or dy.dtype != torch.float32:
+        raise ValueError(f"conv2d stem backward: dy must be float32 {oshape}, got {tuple(dy.shape)}")
+    dw = _out(dw_out, tuple(w_shape), dev)
+    scratch = torch.empty(max(load().ww_conv2d_stem_scratch_bytes(Cn, k) // 4, 4), dtype=torch.float32, device=dev)
+    with _guard(dev), (_deferring(dev, scratch) if defer else contextlib.nullcontext()):
+        _check(load().ww_conv2d_stem_bwd_dw(ctx(dev), _p(x), _p(dy), B, H, W, Cn, k, stride, _p(dw), _p(scratch), scratch.numel() * 4,
+                                            _stream(dev)), "ww_conv2d_stem_bwd_dw")
+    return dw
+
+
+def maxpool3x3s2_fwd(x):
+    """MaxPool2d(3, 2, 1) on x (B,H,W,C) -> (B,(H-1)//2+1,(W-1)//2+1,C)."""
+    dev = _dev(x)
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f"maxpool3x3s2: need float32 x (B,H,W,C), got {tuple(x.shape)}")
+    B, H, W, Cn = x.shape
+    y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cn), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_maxpool3x3s2_fwd(ctx(dev), _p(x), B, H, W, Cn, _p(y), _stream(dev)), "ww_maxpool3x3s2_fwd")
+    return y
+
+
+def maxpool3x3s2_bwd(x, dy):
+    """dx of maxpool3x3s2_fwd: dy goes to the first maximal element of each window (row-major), recomputed from x."""
+    dev = _dev(x, dy)
+    B, H, W, Cn = x.shape
+    if tuple(dy.shape) != (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cn) or dy.dtype != torch.float32 or x.dtype != torch.float32:
+        raise ValueError(f"maxpool3x3s2 backward: dy {tuple(dy.shape)} does not belong to x {tuple(x.shape)}")
+    dx = torch.empty_like(x)
+    with _guard(dev):
+        _check(load().ww_maxpool3x3s2_bwd(ctx(dev), _p(x), _p(dy), B, H, W, Cn, _p(dx), _stream(dev)), "ww_maxpool3x3s2_bwd")
     return dx
 
 

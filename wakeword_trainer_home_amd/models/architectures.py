@@ -410,3 +410,5 @@ def create_model(architecture: str, num_classes: int = 2, pretrained: bool = Fal
 from .lstm import LSTMWakeword  # noqa: E402,F401
 # likewise the reference's TCNWakeword (causal dilated Conv1d on the matrix cores, models/tcn.py)
 from .tcn import NativeCausalConv1d, TemporalBlock, TemporalConvNet, TCNWakeword  # noqa: E402,F401
+# and the reference's ResNet18Wakeword (dense Conv2d as an implicit GEMM on the matrix cores, models/resnet.py)
+from .resnet import NativeConv2d, BasicBlock, ResNet18Wakeword  # noqa: E402,F401

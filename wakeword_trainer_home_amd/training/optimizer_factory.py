@@ -88,6 +88,9 @@ class FlatFusedOptimizer(optim.Optimizer):
         if not flat.is_cuda:
             raise nat.NativeError("FlatFusedOptimizer needs the model on an MI355X ('cuda') device")
         self._flat_ptr = flat.data_ptr()
+        # (held so that the storage behind that address outlives the check in step(): a bucket rebuilt after model.to(...) could
+        # otherwise be handed the freed block again by the caching allocator and pass for the old one)
+        self._flat_at_creation = flat
         self._m = torch.zeros_like(flat)
         self._v = torch.zeros_like(flat) if self._kind != nat.OPT_SGD else None
         self._step_state = torch.zeros(2, dtype=torch.int64, device=flat.device)
