@@ -117,6 +117,7 @@ template <> struct Act<ww_f16> {
 };
 
 // matrix-core forms of the two 16-bit types (8-element operands, fp32 accumulation; same cycles per instruction)
+typedef float floatx16 __attribute__((ext_vector_type(16)));
 template <typename H> struct H16;
 template <> struct H16<ww_bf16> {
     typedef __bf16 x8 __attribute__((ext_vector_type(8)));
@@ -132,6 +133,9 @@ template <> struct H16<ww_f16> {
     static __device__ __forceinline__ acc16 mfma32(x8 a, x8 b, acc16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ acc4 mfma16(x8 a, x8 b, acc4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 };
+// matrix mode of a kernel (its MODE template parameter): 0 = fp32 MFMA, 1 = bf16, 2 = fp16 operands (fp32 accumulation)
+template <int MODE> struct ModeH { typedef ww_bf16 type; };
+template <> struct ModeH<2> { typedef ww_f16 type; };
 template <typename H> __device__ __forceinline__ typename H16<H>::x8 ww_pack8(const float (&v)[8]) {
     typedef float f32x8 __attribute__((ext_vector_type(8)));
     f32x8 f = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};

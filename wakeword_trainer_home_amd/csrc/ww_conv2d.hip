@@ -3,230 +3,64 @@
 //   fwd : y[b,ho,wo,n]  = sum_{r,s,c} x[b, ho st + r - p, wo st + s - p, c] w[n,c,r,s]      (pixels outside the image read as 0)
 //   dX  : dx[b,hi,wi,c] = sum_{r,s,n} dy[b, (hi + p - r) / st, (wi + p - s) / st, n] w[n,c,r,s]   (exact quotients in range only)
 //   dW  : dw[n,c,r,s]   = sum_{b,ho,wo} dy[b,ho,wo,n] x[b, ho st + r - p, wo st + s - p, c]
-// fwd and dX are one implicit GEMM (k_conv2d_rows): M = the pixels of the tensor being written, k*k K-segments (the taps) whose A
-// rows are the displaced pixels of the tensor being read -- taken only while the displaced (h, w) stays inside the row's own image,
-// so an M tile that spans image rows or samples never reads a neighbour as "padding".  No patch matrix exists in memory.  The
-// weights are first re-laid per tap (k_conv2d_pack: nn.Conv2d's (Cout,Cin,k,k) has the tap as its fastest index).  dW
-// (k_conv2d_dw) contracts over the output pixels, split into ranges whose partial products are summed in a fixed order (or queued
-// with ww_defer).  Tile shape, LDS strides and fragments are those of ww_tconv.hip: 64 x 64 block tiles, 4 wavefronts x one 32x32
-// MFMA tile; WW_ACT_F32: v_mfma_f32_32x32x2_f32 (an exact fp32 fma chain per LDS stage, the parity mode); WW_ACT_BF16 / WW_ACT_F16:
-// operands rounded when they are staged into LDS, v_mfma_f32_32x32x16_{bf16,f16}, fp32 accumulation.  The stages' sums are added per
-// tap and the taps at the end (blocked summation).  All tensors are fp32 in HBM.
-#include "ww_internal.h"
-#include "ww_act.h"
-#include "ww_mfma_stage.h"
-#include <algorithm>
+// The three products are the tap GEMM of ww_tap_gemm.h with the geometry of an image: an implicit GEMM whose M is the pixels of the
+// tensor being written and whose k*k K-segments (the taps, r k + s) read the displaced pixels of the tensor being read -- taken only
+// while the displaced (h, w) stays inside the row's own image, so an M tile that spans image rows or samples never reads a
+// neighbour as "padding".  No patch matrix exists in memory.  The stages' sums are added per tap and the taps at the end
+// (SumBlocked); the rows kernel has no epilogue.  The partial products of the dW pixel ranges are summed in a fixed order (or
+// queued with ww_defer).
+#include "ww_tap_gemm.h"
 
 namespace {
 
-// ---- the implicit GEMM:  C[m][n] (+)= sum_{(r,s)} sum_c A[src(m, r, s)][c] W[r k + s][n][c]
-// m = (b, oh, ow) on the (OH, OW) grid of the tensor being written, A lies on the (SH, SW) grid of the tensor being read.
+// ---- the image.  m = (b, oh, ow) on the (OH, OW) grid of the tensor being written, A lies on the (SH, SW) grid of the tensor read.
 //   DX == false: src = (b, oh st + r - p, ow st + s - p)                    -- the forward product (A = x, C = y)
 //   DX == true : src = (b, (oh + p - r) / st, (ow + p - s) / st), exact only -- the input gradient (A = dy, C = dx)
-// A row without a source in its own image contributes 0; a dx pixel no output read is therefore WRITTEN as 0.  CA, N multiples of 4.
-struct RowArgs {
-    const float *A;      // (B, SH, SW, CA)
-    const float *W;      // (k*k, N, CA): k_conv2d_pack
-    float *C;            // (M, N)
-    int M, OH, OW, SH, SW, CA, N, k, stride, pad, accumulate;
-};
+// A row without a source in its own image contributes 0; a dx pixel no output read is therefore WRITTEN as 0.
 constexpr int NO_ROW = -(1 << 24);       // "oh" of a row past M: every bounds test below fails on it
-template <int MODE, bool DX>
-__global__ __launch_bounds__(256) void k_conv2d_rows(RowArgs a) {
-    typedef typename ModeH<MODE>::type H;
-    constexpr int KT = MODE ? 64 : 32;             // K per LDS stage: 16 fp32 MFMAs (2 k each) / 4 16-bit ones (16 k each)
-    constexpr int NV = 64 * KT / 1024;             // float4 per thread and operand tile
-    constexpr int F4 = KT / 4;                     // float4 per tile row
-    constexpr int LD = MODE ? KT + 8 : KT + 4;     // [row][k] LDS stride (elements)
-    constexpr int TILE_BYTES = 64 * LD * (MODE ? 2 : 4);
-    __shared__ __align__(16) unsigned char lds[2 * TILE_BYTES];
-    void *As = lds, *Bs = lds + TILE_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, rh = wv >> 1, nh = wv & 1;
-    const long m0 = (long)blockIdx.y * 64;
-    const int n0 = blockIdx.x * 64;
-    // the rows this thread stages are the same in every stage: their pixel is worked out once
-    int oh[NV], ow[NV], img[NV];                   // img = b SH SW: the first source pixel of the row's own image
-#pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const long m = m0 + (tid + 256 * j) / F4;
-        oh[j] = NO_ROW; ow[j] = 0; img[j] = 0;
-        if (m < a.M) {
-            const unsigned per = (unsigned)a.OH * a.OW, um = (unsigned)m, b = um / per, rem = um - b * per;
-            oh[j] = (int)(rem / (unsigned)a.OW);
-            ow[j] = (int)(rem - (unsigned)oh[j] * a.OW);
-            img[j] = (int)b * a.SH * a.SW;
-        }
-    }
-    const int nk = (a.CA + KT - 1) / KT, stages = a.k * a.k * nk, sh1 = a.stride - 1;      // stride 1 | 2: a shift by 0 | 1
-    float4 va[NV], vb[NV];
-    auto fetch = [&](int it) {
-        const int seg = it / nk, k0 = (it - seg * nk) * KT, tr = seg / a.k, ts = seg - tr * a.k;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int q = tid + 256 * j, kk = k0 + 4 * (q % F4), n = n0 + q / F4;
-            int sh, sw;
-            bool ok;
-            if constexpr (DX) {
-                const int th = oh[j] + a.pad - tr, tw = ow[j] + a.pad - ts;
-                sh = th >> sh1; sw = tw >> sh1;
-                ok = th >= 0 && tw >= 0 && ((th | tw) & sh1) == 0 && sh < a.SH && sw < a.SW;
-            } else {
-                sh = oh[j] * a.stride + tr - a.pad; sw = ow[j] * a.stride + ts - a.pad;
-                ok = sh >= 0 && sh < a.SH && sw >= 0 && sw < a.SW;
-            }
-            ok = ok && kk < a.CA;
-            va[j] = ok ? *reinterpret_cast<const float4 *>(a.A + ((long)img[j] + sh * a.SW + sw) * a.CA + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const bool okb = n < a.N && kk < a.CA;
-            vb[j] = okb ? *reinterpret_cast<const float4 *>(a.W + ((long)seg * a.N + n) * a.CA + kk) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    floatx16 acc = floatx16{0.f}, tap = floatx16{0.f};
-    int in_tap = 0;
-    fetch(0);
-    for (int it = 0; it < stages; ++it) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int q = tid + 256 * j, off = (q / F4) * LD + 4 * (q % F4);
-            put4<MODE>(As, off, va[j]);
-            put4<MODE>(Bs, off, vb[j]);
-        }
-        __syncthreads();
-        if (it + 1 < stages) fetch(it + 1);        // the next stage in flight under the MFMAs
-        // blocked summation: a stage's KT products are one chain, the stages of a tap are summed per tap, the taps at the end --
-        // chains of KT, Cin / KT and k k terms instead of one of k k Cin (4608 in the last ResNet stage)
-        floatx16 part = floatx16{0.f};
-        if constexpr (MODE != 0) {
-            typedef typename H16<H>::x8 x8;
-            const H *pa = reinterpret_cast<const H *>(As) + (32 * rh + r) * LD + 8 * h;
-            const H *pb = reinterpret_cast<const H *>(Bs) + (32 * nh + r) * LD + 8 * h;
-#pragma unroll
-            for (int t = 0; t < KT / 16; ++t)
-                part = H16<H>::mfma32(*reinterpret_cast<const x8 *>(pa + 16 * t), *reinterpret_cast<const x8 *>(pb + 16 * t), part);
-        } else {
-            const float *pa = reinterpret_cast<const float *>(As) + (32 * rh + r) * LD + h;
-            const float *pb = reinterpret_cast<const float *>(Bs) + (32 * nh + r) * LD + h;
-#pragma unroll
-            for (int t = 0; t < KT / 2; ++t) part = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * t], pb[2 * t], part, 0, 0, 0);
-        }
-        tap += part;
-        if (++in_tap == nk) { acc += tap; tap = floatx16{0.f}; in_tap = 0; }
-    }
-    const int col = n0 + 32 * nh + r;
-    if (col >= a.N) return;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const long row = m0 + 32 * rh + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        if (row >= a.M) continue;
-        float v = acc[reg];
-        if (a.accumulate) v += a.C[row * a.N + col];
-        a.C[row * a.N + col] = v;
-    }
-}
+struct ImageTap { int tr, ts; };           // (r, s) of segment r k + s
 template <bool DX>
-void launch_rows(int mode, const RowArgs &a, hipStream_t st) {
-    const dim3 grid((a.N + 63) / 64, (unsigned)((a.M + 63) / 64));
-    if (mode == WW_ACT_BF16) hipLaunchKernelGGL((k_conv2d_rows<1, DX>), grid, dim3(256), 0, st, a);
-    else if (mode == WW_ACT_F16) hipLaunchKernelGGL((k_conv2d_rows<2, DX>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_conv2d_rows<0, DX>), grid, dim3(256), 0, st, a);
-}
-
-// ---- the weight gradient:  out[z][n][c][r k + s] = sum_{m in range z} G[m][n] X[src(m, r, s)][c]   (src as the forward's)
-// grid: x = c tiles, y = n tiles, z = tap * nsplit + range.  Both operands are row-contiguous ([k][row] tiles in LDS).
-struct DwArgs {
-    const float *G;      // dy (M, N), M = B Ho Wo
-    const float *X;      // (B, H, W, C)
-    float *out;          // (nsplit, N, C, k, k)
-    int M, Ho, Wo, H, W, N, C, k, stride, pad, rps, nsplit;
-};
-template <int MODE>
-__global__ __launch_bounds__(256) void k_conv2d_dw(DwArgs a) {
-    typedef typename ModeH<MODE>::type H;
-    constexpr int KT = MODE ? 64 : 32;
-    constexpr int NV = 64 * KT / 1024;
-    constexpr int LD = MODE ? 64 + 8 : 64 + 4;     // [k][row] LDS stride (elements)
-    constexpr int TILE_BYTES = KT * LD * (MODE ? 2 : 4);
-    __shared__ __align__(16) unsigned char lds[2 * TILE_BYTES];
-    void *As = lds, *Bs = lds + TILE_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int r = lane & 31, h = lane >> 5, rh = wv >> 1, nh = wv & 1;
-    const int c0 = blockIdx.x * 64, n0 = blockIdx.y * 64;
-    const int seg = blockIdx.z / a.nsplit, z = blockIdx.z - seg * a.nsplit;
-    const int tr = seg / a.k, ts = seg - tr * a.k, sh1 = a.stride - 1;
-    const int mb = (int)min((long)a.M, (long)z * a.rps), me = (int)min((long)a.M, (long)mb + a.rps);
-    const unsigned per = (unsigned)a.Ho * a.Wo;
-    float4 va[NV], vb[NV];
-    auto fetch = [&](int mk0) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int q = tid + 256 * j, m = mk0 + q / 16, e = 4 * (q % 16);
-            const bool okm = m < me;
-            const bool oka = okm && n0 + e < a.N;
-            va[j] = oka ? *reinterpret_cast<const float4 *>(a.G + (long)m * a.N + n0 + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const unsigned um = okm ? (unsigned)m : 0u, b = um / per, rem = um - b * per, ho = rem / (unsigned)a.Wo, wo = rem - ho * a.Wo;
-            const int hi = ((int)ho << sh1) + tr - a.pad, wi = ((int)wo << sh1) + ts - a.pad;
-            const bool okb = okm && c0 + e < a.C && hi >= 0 && hi < a.H && wi >= 0 && wi < a.W;
-            vb[j] = okb ? *reinterpret_cast<const float4 *>(a.X + (((long)b * a.H + hi) * a.W + wi) * a.C + c0 + e) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    floatx16 acc = floatx16{0.f};
-    if (mb < me) fetch(mb);
-    for (int mk0 = mb; mk0 < me; mk0 += KT) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int q = tid + 256 * j, off = (q / 16) * LD + 4 * (q % 16);
-            put4<MODE>(As, off, va[j]);
-            put4<MODE>(Bs, off, vb[j]);
-        }
-        __syncthreads();
-        if (mk0 + KT < me) fetch(mk0 + KT);
-        floatx16 part = floatx16{0.f};             // blocked summation, as in k_conv2d_rows: a chain per stage, then the stages
-        if constexpr (MODE != 0) {
-            const H *pa = reinterpret_cast<const H *>(As), *pb = reinterpret_cast<const H *>(Bs);
-#pragma unroll
-            for (int t = 0; t < KT / 16; ++t)
-                part = H16<H>::mfma32(tr_frag(pa, LD, 16 * t, 32 * rh, lane), tr_frag(pb, LD, 16 * t, 32 * nh, lane), part);
+struct ImageRows {
+    typedef ImageTap Tap;
+    struct Row { int oh, ow, img; };     // img = b SH SW: the first source pixel of the row's own image
+    int OH, OW, SH, SW, k, stride, pad;
+    __device__ Row row(long m, int M) const {
+        if (m >= M) return Row{NO_ROW, 0, 0};
+        const unsigned per = (unsigned)OH * OW, um = (unsigned)m, b = um / per, rem = um - b * per;
+        const int oh = (int)(rem / (unsigned)OW);
+        return Row{oh, (int)(rem - (unsigned)oh * OW), (int)b * SH * SW};
+    }
+    __device__ Tap tap(int seg) const { const int tr = seg / k; return Tap{tr, seg - tr * k}; }
+    __device__ bool src(const Row &p, long, Tap t, long &at) const {
+        const int tr = t.tr, ts = t.ts, sh1 = stride - 1;                 // stride 1 | 2: a shift by 0 | 1
+        int sh, sw;
+        bool ok;
+        if constexpr (DX) {
+            const int th = p.oh + pad - tr, tw = p.ow + pad - ts;
+            sh = th >> sh1; sw = tw >> sh1;
+            ok = th >= 0 && tw >= 0 && ((th | tw) & sh1) == 0 && sh < SH && sw < SW;
         } else {
-            const float *pa = reinterpret_cast<const float *>(As) + h * LD + 32 * rh + r;
-            const float *pb = reinterpret_cast<const float *>(Bs) + h * LD + 32 * nh + r;
-#pragma unroll
-            for (int t = 0; t < KT / 2; ++t) part = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[2 * t * LD], pb[2 * t * LD], part, 0, 0, 0);
+            sh = p.oh * stride + tr - pad; sw = p.ow * stride + ts - pad;
+            ok = sh >= 0 && sh < SH && sw >= 0 && sw < SW;
         }
-        acc += part;
+        at = (long)p.img + sh * SW + sw;
+        return ok;
     }
-    const int c = c0 + 32 * nh + r;
-    if (c >= a.C) return;
-    const int kk = a.k * a.k;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int n = n0 + 32 * rh + (reg & 3) + 8 * (reg >> 2) + 4 * h;
-        if (n < a.N) a.out[(((long)z * a.N + n) * a.C + c) * kk + seg] = acc[reg];
+};
+// dW: the output pixel m = (b, ho, wo) of dy meets the source pixel of the forward product
+struct ImageDw {
+    int Ho, Wo, H, W, k, stride, pad;
+    typedef ImageTap Tap;
+    __device__ Tap tap(int seg) const { const int tr = seg / k; return Tap{tr, seg - tr * k}; }
+    __device__ bool src(int m, Tap t, long &at) const {
+        const int tr = t.tr, ts = t.ts, sh1 = stride - 1;
+        const unsigned per = (unsigned)Ho * Wo, um = (unsigned)m, b = um / per, rem = um - b * per, ho = rem / (unsigned)Wo, wo = rem - ho * Wo;
+        const int hi = ((int)ho << sh1) + tr - pad, wi = ((int)wo << sh1) + ts - pad;
+        at = ((long)b * H + hi) * W + wi;
+        return hi >= 0 && hi < H && wi >= 0 && wi < W;
     }
-}
-
-// out[t][n][c] = w[n][c][t] (transpose == 0: the forward's taps) or out[t][c][n] = w[n][c][t] (the dX product's); t = r k + s
-__global__ __launch_bounds__(256) void k_conv2d_pack(const float *__restrict__ w, int Cout, int Cin, int kk, int transpose,
-                                                     float *__restrict__ out) {
-    const long per = (long)Cout * Cin, n_all = per * kk;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_all; i += (long)gridDim.x * 256) {
-        const int t = (int)(i / per);
-        const long rem = i - (long)t * per;
-        int n, c;
-        if (transpose) { c = (int)(rem / Cout); n = (int)(rem - (long)c * Cout); }
-        else { n = (int)(rem / Cin); c = (int)(rem - (long)n * Cin); }
-        out[i] = w[((long)n * Cin + c) * kk + t];
-    }
-}
-// dst[i] = sum_z part[z*n + i], z in order (the immediate form of the deferred reduction)
-__global__ __launch_bounds__(256) void k_conv2d_sum(const float *__restrict__ part, long n, int splits, float *__restrict__ dst) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        double s = 0.0;
-        for (int z = 0; z < splits; ++z) s += (double)part[(long)z * n + i];
-        dst[i] = (float)s;
-    }
-}
+};
+template <bool DX> using RowArgs = RowsArgs<ImageRows<DX>, EpiNone>;      // {A, W, C, {}, M, CA, N, nseg, accumulate, {OH, OW, SH, SW, k, stride, pad}}
 
 // ---- the one-channel stem, a direct convolution: x (B,H,W), w (C,1,k,k) -> y (B,Ho,Wo,C).  Threads = (pixel lane, channel quad);
 // the weights sit in LDS as [tap][channel], so a pixel lane's quads read neighbouring float4s and the image sample is a broadcast.
@@ -375,16 +209,8 @@ __global__ __launch_bounds__(256) void k_maxpool_bwd(const float *__restrict__ x
     }
 }
 
-int ew_grid(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 4096)); }
 int out_size(int n, int k, int stride) { return (n + 2 * (k / 2) - k) / stride + 1; }
 
-// ranges of the weight-gradient contraction: enough of them for ~1024 workgroups, each at least 128 pixels deep, at most 256
-int dw_splits(long M, int Cin, int Cout, int kk) {
-    const long tiles = (long)((Cout + 63) / 64) * ((Cin + 63) / 64) * kk;
-    long s = (1024 + tiles - 1) / tiles;
-    s = std::min<long>(s, M / 128);
-    return (int)std::max<long>(1, std::min<long>(s, 256));
-}
 struct Layout { size_t wp, dwp, total; };      // float offsets of the scratch regions
 Layout layout(long M, int Cin, int Cout, int k) {
     Layout l;
@@ -428,7 +254,6 @@ int check_pool(const char *who, int B, int H, int W, int C, PoolArgs *g) {
     *g = PoolArgs{B, H, W, C, (H - 1) / 2 + 1, (W - 1) / 2 + 1};
     return WW_OK;
 }
-bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
@@ -449,10 +274,10 @@ extern "C" int ww_conv2d_fwd(ww_ctx *ctx, int mode, const float *x, const float 
     hipStream_t st = (hipStream_t)stream;
     ww_prof_scope ps_(ctx, WW_K_LINEAR, st);
     float *wp = (float *)scratch;
-    hipLaunchKernelGGL(k_conv2d_pack, dim3(ew_grid((long)k * k * Cin * Cout)), dim3(256), 0, st, w, Cout, Cin, k * k, 0, wp);
+    hipLaunchKernelGGL(k_tap_pack, dim3(ew_grid((long)k * k * Cin * Cout)), dim3(256), 0, st, w, Cout, Cin, k * k, 0, wp);
     WW_LAUNCH_CHECK();
-    const RowArgs a{x, wp, y, (int)M, Ho, Wo, H, W, Cin, Cout, k, stride, k / 2, 0};
-    launch_rows<false>(mode, a, st);
+    const RowArgs<false> a{x, wp, y, {}, (int)M, Cin, Cout, k * k, 0, {Ho, Wo, H, W, k, stride, k / 2}};
+    tap_launch_rows<SumBlocked>(mode, a, st);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
@@ -473,29 +298,13 @@ extern "C" int ww_conv2d_bwd(ww_ctx *ctx, int mode, const float *x, const float 
     float *base = (float *)scratch;
     if (dx) {
         float *wp = base + l.wp;
-        hipLaunchKernelGGL(k_conv2d_pack, dim3(ew_grid((long)kk * Cin * Cout)), dim3(256), 0, st, w, Cout, Cin, kk, 1, wp);
+        hipLaunchKernelGGL(k_tap_pack, dim3(ew_grid((long)kk * Cin * Cout)), dim3(256), 0, st, w, Cout, Cin, kk, 1, wp);
         WW_LAUNCH_CHECK();
-        const RowArgs a{dy, wp, dx, (int)((long)B * H * W), H, W, Ho, Wo, Cout, Cin, k, stride, k / 2, accumulate_dx != 0};
-        launch_rows<true>(mode, a, st);
-        WW_LAUNCH_CHECK();
-    }
-    const int kt = mode == WW_ACT_F32 ? 32 : 64;
-    const int want = dw_splits(M, Cin, Cout, kk);
-    const long rps = ((M + want - 1) / want + kt - 1) / kt * kt;      // whole K stages per range
-    const int nz = (int)((M + rps - 1) / rps);                         // <= want
-    const long n = (long)Cout * Cin * kk;
-    float *part = base + l.dwp;
-    const DwArgs a{dy, x, nz > 1 ? part : dw, (int)M, Ho, Wo, H, W, Cout, Cin, k, stride, k / 2, (int)rps, nz};
-    const dim3 grid((Cin + 63) / 64, (Cout + 63) / 64, kk * nz);
-    if (mode == WW_ACT_BF16) hipLaunchKernelGGL(k_conv2d_dw<1>, grid, dim3(256), 0, st, a);
-    else if (mode == WW_ACT_F16) hipLaunchKernelGGL(k_conv2d_dw<2>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_conv2d_dw<0>, grid, dim3(256), 0, st, a);
-    WW_LAUNCH_CHECK();
-    if (nz > 1 && !ww_defer(ctx, part, dw, n, nz, 0)) {
-        hipLaunchKernelGGL(k_conv2d_sum, dim3(ew_grid(n)), dim3(256), 0, st, part, n, nz, dw);
+        const RowArgs<true> a{dy, wp, dx, {}, (int)((long)B * H * W), Cout, Cin, kk, accumulate_dx != 0, {H, W, Ho, Wo, k, stride, k / 2}};
+        tap_launch_rows<SumBlocked>(mode, a, st);
         WW_LAUNCH_CHECK();
     }
-    return WW_OK;
+    return tap_dw<SumBlocked>(ctx, mode, dy, x, ImageDw{Ho, Wo, H, W, k, stride, k / 2}, M, Cin, Cout, kk, base + l.dwp, dw, st);
 }
 
 extern "C" size_t ww_conv2d_stem_scratch_bytes(int C, int k) {
@@ -533,7 +342,7 @@ extern "C" int ww_conv2d_stem_bwd_dw(ww_ctx *ctx, const float *x, const float *d
     hipLaunchKernelGGL(k_conv2d_stem_dw, dim3(blocks, k), dim3(256), 0, st, x, dy, g, blocks > 1 ? part : dw);
     WW_LAUNCH_CHECK();
     if (blocks > 1 && !ww_defer(ctx, part, dw, n, blocks, 0)) {
-        hipLaunchKernelGGL(k_conv2d_sum, dim3(ew_grid(n)), dim3(256), 0, st, part, n, blocks, dw);
+        hipLaunchKernelGGL(k_tap_sum, dim3(ew_grid(n)), dim3(256), 0, st, part, n, blocks, dw);
         WW_LAUNCH_CHECK();
     }
     return WW_OK;

@@ -19,8 +19,6 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 constexpr int PW_LD = 68;
 
 // ------------------------------------------------------------------------------------- head

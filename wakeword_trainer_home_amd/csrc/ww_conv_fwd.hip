@@ -23,8 +23,6 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
 // BatchNorm + ReLU on load.  ReLU propagates NaN like torch.relu (v_max would silently turn it into 0).
 __device__ __forceinline__ float bnrelu(float y, float s, float t) {
     const float z = fmaf(y, s, t);

@@ -17,11 +17,6 @@
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-// matrix mode of a kernel: 0 = fp32 MFMA, 1 = bf16, 2 = fp16 operands (fp32 accumulation)
-template <int MODE> struct ModeH { typedef ww_bf16 type; };
-template <> struct ModeH<2> { typedef ww_f16 type; };
-
 // block tiles are 64 or 128 rows/columns (template parameters TM, TN of k_gemm)
 constexpr int GK = 32;      // K per LDS stage, fp32 mode
 constexpr int GKH = 128;    // K per LDS stage, bf16 mode

@@ -17,9 +17,7 @@ constexpr int RH = 128;              // hidden size
 constexpr int RBT = 16;              // batch rows of the MFMA tile
 constexpr int RS_LD = RH + 4;        // fp32 LDS row stride: lane (row i, k) -> bank 4i + k, conflict-free fragment reads
 constexpr int RB_LD = RH + 8;        // 16-bit row strides (16-byte aligned 8-element fragments)
-// matrix mode of the recurrent kernels: 0 = fp32 MFMA, 1 = bf16, 2 = fp16 operands (state, gates, updates stay fp32)
-template <int MODE> struct ModeH { typedef ww_bf16 type; };
-template <> struct ModeH<2> { typedef ww_f16 type; };
+// (in the 16-bit matrix modes of the recurrent kernels, ModeH<MODE>, the state, the gates and the updates stay fp32)
 
 // 16-bit matrix modes: v_exp_f32 + v_rcp_f32 forms (1 ulp reciprocal, absolute error ~2e-7 -- far below what the 16-bit operands
 // of those modes cost); the IEEE division and libm tanhf of the parity mode are ~50 of the ~80 instructions of a GRU cell, and
