@@ -255,6 +255,19 @@ int ww_dwconv3x3_bwd(ww_ctx *ctx, int act_dtype, const void *g, const void *y_ou
                      float *dbeta_in, void *scratch, ww_stream_t stream);
 int ww_conv_stem_bwd(ww_ctx *ctx, int act_dtype, const void *g, const void *y_out, const float *coef, const float *x,
                      int B, int Hin, int Win, float *dw, void *scratch, ww_stream_t stream);
+/* The form the whole-model backward runs: the stem's output is not read but recomputed from x and the stem weights w
+ * (64,1,3,3) with the forward kernel's fma chain and rounding, i.e. bit-identical to the tensor ww_conv_stem_fwd stored. */
+int ww_conv_stem_bwd_recompute(ww_ctx *ctx, int act_dtype, const void *g, const float *w, const float *coef,
+                               const float *x, int B, int Hin, int Win, float *dw, void *scratch, ww_stream_t stream);
+
+/* A test and tuning parameter, not a performance setting.  Every kernel of the conv stack (the layer calls above, the
+ * whole-model calls below and the CRNN front end's frequency pooling) is persistent: a workgroup walks item, item + grid,
+ * ... and carries prefetched items, LDS double buffers and accumulators from one trip to the next.  n > 0 launches each of
+ * them with min(grid, n) workgroups, and hands that many partial rows to the finalize launch, so that a small tensor
+ * already takes many trips per workgroup; 0 (default) = no cap, the grids are exactly the uncapped ones.  Results do not
+ * depend on n beyond the order of fp32 partial sums.  The cap is read when a launch is issued: a captured graph keeps
+ * the grids it was captured with.  The log-mel kernel has its own knob (ww_ctx_set_logmel_workgroups).                  */
+int ww_ctx_set_grid_cap(ww_ctx *ctx, int n);
 
 /* ------------------------------------------------------------------ whole model
  * cnn_small (added to create_model, src/models/architectures.py:437):

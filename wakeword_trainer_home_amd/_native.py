@@ -126,6 +126,7 @@ _SIGS = {
     "ww_ctx_destroy": (C.c_int, [_vp]),
     "ww_ctx_bind_step_ctl": (C.c_int, [_vp, _vp]),
     "ww_ctx_set_logmel_workgroups": (C.c_int, [_vp, C.c_int]),
+    "ww_ctx_set_grid_cap": (C.c_int, [_vp, C.c_int]),
     "ww_step_ctl_advance": (C.c_int, [_vp, _vp]),
     "ww_feat_num_frames": (C.c_int, [_i, _i]),
     "ww_feat_mel_tables": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
@@ -202,6 +203,7 @@ _SIGS = {
     "ww_pwconv1x1_bwd": (C.c_int, [_vp, _i] + [_vp] * 10 + [_i, _i, _i] + [_vp] * 7),
     "ww_dwconv3x3_bwd": (C.c_int, [_vp, _i] + [_vp] * 8 + [_i, _i, _i] + [_vp] * 7),
     "ww_conv_stem_bwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "ww_conv_stem_bwd_recompute": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "ww_cnn_small_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ww_cnn_small_fwd": (C.c_int, [_vp, _i, C.POINTER(_vp), _vp, _i, _i, _i, _i, _f, _f, _f, _u64, _u64, _u64, _vp, _sz,
                                    _vp, _vp]),
@@ -1287,6 +1289,12 @@ def set_logmel_workgroups(dev, n: int):
     _check(load().ww_ctx_set_logmel_workgroups(ctx(dev), int(n)), "ww_ctx_set_logmel_workgroups")
 
 
+def set_grid_cap(dev, n: int):
+    """Test / tuning parameter: the persistent conv-stack launches that follow on ``dev`` use at most n workgroups (0 = no
+    cap), so a workgroup walks many items.  Read when a launch is issued: a captured graph keeps its grids."""
+    _check(load().ww_ctx_set_grid_cap(ctx(dev), int(n)), "ww_ctx_set_grid_cap")
+
+
 def bind_step_ctl(dev, ctl):
     """Bind (ctl = uint8[32] device tensor) or unbind (None) the device-resident step control of ``dev``'s context."""
     if ctl is not None and (not ctl.is_cuda or ctl.numel() < STEP_CTL_BYTES or ctl.dtype != torch.uint8):
@@ -1424,13 +1432,18 @@ def dwconv3x3_bwd(g, y_out, coef, y_in, ss_in, mr_in, gamma_in, w, scratch):
     return g_in, dw, coef_in, dgamma, dbeta
 
 
-def conv_stem_bwd(g, y_out, coef, x, scratch):
-    dev = _dev(g, y_out, coef, x, scratch)
+def conv_stem_bwd(g, y_out, coef, x, scratch, w=None):
+    """``w`` (the stem weights) selects the form the whole-model backward runs: y_out is recomputed from x, not read."""
+    dev = _dev(g, y_out, coef, x, scratch, w)
     B, Hin, Win = x.shape[0], x.shape[-2], x.shape[-1]
     dw = torch.empty((64, 1, 3, 3), dtype=torch.float32, device=dev)
     with _guard(dev):
-        _check(load().ww_conv_stem_bwd(ctx(dev), act_code(y_out.dtype), _p(g), _p(y_out), _p(coef), _p(x), B, Hin, Win, _p(dw), _p(scratch),
-                                       _stream(dev)), "ww_conv_stem_bwd")
+        if w is None:
+            _check(load().ww_conv_stem_bwd(ctx(dev), act_code(y_out.dtype), _p(g), _p(y_out), _p(coef), _p(x), B, Hin, Win, _p(dw),
+                                           _p(scratch), _stream(dev)), "ww_conv_stem_bwd")
+        else:
+            _check(load().ww_conv_stem_bwd_recompute(ctx(dev), act_code(g.dtype), _p(g), _p(w), _p(coef), _p(x), B, Hin, Win,
+                                                     _p(dw), _p(scratch), _stream(dev)), "ww_conv_stem_bwd_recompute")
     return dw
 
 

@@ -736,7 +736,7 @@ __global__ __launch_bounds__(256, Act<T>::is_f32 ? 2 : 3) void k_dw_bwd(const T 
 // RECOMP: the layer's own output is recomputed from the input rows that sit in LDS for the weight gradient anyway (the
 // forward kernel's nine fmaf in the same order, then its rounding: bit-identical to the stored tensor) instead of read
 // back -- the stem reads 2A -> 1A per launch.  Needs the stem weights, which the stand-alone C entry point does not get
-// (its signature predates this): the whole-model path passes them, ww_conv_stem_bwd reads y_out.
+// (its signature predates this): the whole-model path and ww_conv_stem_bwd_recompute pass them, ww_conv_stem_bwd reads y_out.
 template <typename T, bool RECOMP>
 __global__ __launch_bounds__(256) void k_stem_bwd(const T *__restrict__ g, const T *__restrict__ y_out,
                                                   const float *__restrict__ w, const float *__restrict__ coef,
@@ -888,7 +888,7 @@ int launch_pw_bwd_bf16(ww_ctx *ctx, const void *g, const float *dpool, const voi
     int grid;
     ww_prof_scope ps_(ctx, WW_K_PW_BWD, st);
     auto go = [&](auto kern) {
-        grid = ww_occupancy_grid((const void *)kern, 256, 0, ntiles, WW_DW_SLAB_ROWS);
+        grid = ww_conv_grid(ctx, (const void *)kern, 256, 0, ntiles, WW_DW_SLAB_ROWS);
         static const int rev = ww_env_int("WW_PW_BWD_REV", 1);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, (cp)g, dpool, ss_out, coef, (cp)y_in, ss_in, mr_in, w, M, HW,
                            (H *)g_in, stat, dwp, rev);
@@ -908,11 +908,11 @@ int launch_pw_bwd(ww_ctx *ctx, const void *g, const float *dpool, const void *y_
     int grid;
     ww_prof_scope ps_(ctx, WW_K_PW_BWD, st);
     if (g) {
-        grid = ww_occupancy_grid((const void *)k_pw_bwd<T, false>, 256, 0, ntiles, WW_DW_SLAB_ROWS);
+        grid = ww_conv_grid(ctx, (const void *)k_pw_bwd<T, false>, 256, 0, ntiles, WW_DW_SLAB_ROWS);
         hipLaunchKernelGGL((k_pw_bwd<T, false>), dim3(grid), dim3(256), 0, st, (const T *)g, dpool, (const T *)y_out,
                            ss_out, coef, (const T *)y_in, ss_in, mr_in, w, M, HW, (T *)g_in, stat, dwp);
     } else {
-        grid = ww_occupancy_grid((const void *)k_pw_bwd<T, true>, 256, 0, ntiles, WW_DW_SLAB_ROWS);
+        grid = ww_conv_grid(ctx, (const void *)k_pw_bwd<T, true>, 256, 0, ntiles, WW_DW_SLAB_ROWS);
         hipLaunchKernelGGL((k_pw_bwd<T, true>), dim3(grid), dim3(256), 0, st, (const T *)g, dpool, (const T *)y_out,
                            ss_out, coef, (const T *)y_in, ss_in, mr_in, w, M, HW, (T *)g_in, stat, dwp);
     }
@@ -925,7 +925,7 @@ int launch_dw_bwd(ww_ctx *ctx, const void *g, const void *y_out, const float *co
                   const float *ss_in, const float *mr_in, const float *w, const DwGeom &gm, void *g_in, float *stat,
                   float *dwp, int *grid_out, hipStream_t st) {
     const long nblk = (gm.items + 7) / 8;
-    const int grid = ww_occupancy_grid((const void *)k_dw_bwd<T>, 256, 0, nblk, WW_MAX_PARTIALS);
+    const int grid = ww_conv_grid(ctx, (const void *)k_dw_bwd<T>, 256, 0, nblk, WW_MAX_PARTIALS);
     ww_prof_scope ps_(ctx, WW_K_DW_BWD, st);
     hipLaunchKernelGGL(k_dw_bwd<T>, dim3(grid), dim3(256), 0, st, (const T *)g, (const T *)y_out, coef, (const T *)y_in,
                        ss_in, mr_in, w, gm, (T *)g_in, stat, dwp);
@@ -942,7 +942,7 @@ int launch_stem_bwd(ww_ctx *ctx, const void *g, const void *y_out, const float *
     ww_prof_scope ps_(ctx, WW_K_STEM_BWD, st);
     auto go = [&](auto kern) {
         // only the weight-gradient slab is used (576 columns): room for 2048 rows -> full occupancy
-        const int grid = ww_occupancy_grid((const void *)kern, 256, smem, nrows, 2048);
+        const int grid = ww_conv_grid(ctx, (const void *)kern, 256, smem, nrows, 2048);
         static const int rev = ww_env_int("WW_STEM_BWD_REV", 1);
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, (const T *)g, (const T *)y_out, w, coef, x, B, Hin, Win, Ho,
                            Wo, dwp, rev);
@@ -1041,4 +1041,11 @@ extern "C" int ww_conv_stem_bwd(ww_ctx *ctx, int act_dtype, const void *g, const
                                 const float *x, int B, int Hin, int Win, float *dw, void *scratch,
                                 ww_stream_t stream) {
     return ww_stem_bwd_impl(ctx, act_dtype, g, y_out, nullptr, coef, x, B, Hin, Win, dw, scratch, stream);
+}
+
+extern "C" int ww_conv_stem_bwd_recompute(ww_ctx *ctx, int act_dtype, const void *g, const float *w, const float *coef,
+                                          const float *x, int B, int Hin, int Win, float *dw, void *scratch,
+                                          ww_stream_t stream) {
+    WW_REQUIRE(w != nullptr, WW_E_INVALID, "ww_conv_stem_bwd_recompute: w is null");
+    return ww_stem_bwd_impl(ctx, act_dtype, g, /*y_out: not read*/ g, w, coef, x, B, Hin, Win, dw, scratch, stream);
 }

@@ -580,7 +580,7 @@ int launch_stem_fwd(ww_ctx *ctx, const float *x, const float *w, int B, int Hin,
     const int Ho = (Hin + 1) / 2, Wo = (Win + 1) / 2;
     const long nrows = (long)B * ((Ho + 1) / 2);          // work items: pairs of output rows
     const size_t smem = (size_t)5 * (Win + 2) * sizeof(float);
-    const int grid = ww_occupancy_grid((const void *)k_stem_fwd<T>, 256, smem, nrows, WW_MAX_PARTIALS);
+    const int grid = ww_conv_grid(ctx, (const void *)k_stem_fwd<T>, 256, smem, nrows, WW_MAX_PARTIALS);
     {
         ww_prof_scope ps_(ctx, WW_K_STEM_FWD, st);
         static const int rev = ww_env_int("WW_STEM_FWD_REV", 1);
@@ -595,7 +595,7 @@ template <typename T>
 int launch_dw_fwd(ww_ctx *ctx, const void *y_in, const float *ss_in, const float *w, const DwGeom &g, void *y,
                   float *partials, int *grid_out, hipStream_t st) {
     const long nblk = (g.items + 7) / 8;
-    const int grid = ww_occupancy_grid((const void *)k_dw_fwd<T>, 256, 0, nblk, WW_MAX_PARTIALS);
+    const int grid = ww_conv_grid(ctx, (const void *)k_dw_fwd<T>, 256, 0, nblk, WW_MAX_PARTIALS);
     {
         ww_prof_scope ps_(ctx, WW_K_DW_FWD, st);
         hipLaunchKernelGGL(k_dw_fwd<T>, dim3(grid), dim3(256), 0, st, (const T *)y_in, ss_in, w, g, (T *)y, partials);
@@ -610,7 +610,7 @@ int launch_pw_fwd_bf16(ww_ctx *ctx, const void *y_in, const float *ss_in, const 
                        float *partials, int *grid_out, hipStream_t st) {
     const long ntiles = (M + PW_TILE - 1) / PW_TILE;
     const size_t smem = (size_t)2 * PW_TILE * PWH_LD * 2;
-    const int grid = ww_occupancy_grid((const void *)k_pw_fwd_bf16<H>, 256, smem, ntiles, WW_MAX_PARTIALS);
+    const int grid = ww_conv_grid(ctx, (const void *)k_pw_fwd_bf16<H>, 256, smem, ntiles, WW_MAX_PARTIALS);
     {
         ww_prof_scope ps_(ctx, WW_K_PW_FWD, st);
         static const int rev = ww_env_int("WW_PW_FWD_REV", 1);
@@ -627,7 +627,7 @@ int launch_pw_fwd(ww_ctx *ctx, const void *y_in, const float *ss_in, const float
     const long ntiles = (M + PW_TILE - 1) / PW_TILE;
     const size_t smem = (size_t)(Act<T>::is_f32 ? 1 : 2) * PW_TILE * PW_LD * sizeof(float);
     WW_HIP(hipFuncSetAttribute((const void *)k_pw_fwd<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const int grid = ww_occupancy_grid((const void *)k_pw_fwd<T>, 256, smem, ntiles, WW_MAX_PARTIALS);
+    const int grid = ww_conv_grid(ctx, (const void *)k_pw_fwd<T>, 256, smem, ntiles, WW_MAX_PARTIALS);
     {
         ww_prof_scope ps_(ctx, WW_K_PW_FWD, st);
         hipLaunchKernelGGL(k_pw_fwd<T>, dim3(grid), dim3(256), smem, st, (const T *)y_in, ss_in, w, M, (T *)y, partials);

@@ -51,6 +51,7 @@ extern "C" int ww_ctx_create(int device, ww_ctx **out) {
     c->prof_mask = 0;
     c->step_ctl = nullptr;
     c->logmel_wgs = 0;
+    c->grid_cap = 0;
     c->tw16k = nullptr;
     c->norm_partials = nullptr;
     c->defer_on = 0;
@@ -78,6 +79,13 @@ extern "C" int ww_ctx_set_logmel_workgroups(ww_ctx *ctx, int n) {
     WW_REQUIRE(ctx != nullptr, WW_E_INVALID, "ww_ctx_set_logmel_workgroups: ctx is null");
     WW_REQUIRE(n >= 0, WW_E_INVALID, "ww_ctx_set_logmel_workgroups: n=%d must be >= 0", n);
     ctx->logmel_wgs = n;
+    return WW_OK;
+}
+
+extern "C" int ww_ctx_set_grid_cap(ww_ctx *ctx, int n) {
+    WW_REQUIRE(ctx != nullptr, WW_E_INVALID, "ww_ctx_set_grid_cap: ctx is null");
+    WW_REQUIRE(n >= 0, WW_E_INVALID, "ww_ctx_set_grid_cap: n=%d must be >= 0", n);
+    ctx->grid_cap = n;
     return WW_OK;
 }
 

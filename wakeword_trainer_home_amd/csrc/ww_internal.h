@@ -83,6 +83,7 @@ struct ww_ctx {
     double *norm_partials;                 // (WW_NORM_PARTS) block sums of squares of a large gradient bucket; lazy
     const ww_step_ctl *step_ctl;           // bound device control block (ww_ctx_bind_step_ctl) or NULL
     int logmel_wgs;                        // persistent workgroups of k_logmel (ww_ctx_set_logmel_workgroups); 0 = fill the device
+    int grid_cap;                          // most workgroups of a persistent conv-stack launch (ww_ctx_set_grid_cap); 0 = no cap
     uint32_t prof_mask;
     std::vector<ww_prof_rec> *prof_recs;   // recorded, not yet collected
     std::vector<ww_prof_rec> *prof_free;   // event pairs ready for reuse
@@ -144,12 +145,21 @@ int ww_colsum_rows(const float *a, long rows, int cols, float *out, float *part,
 int ww_colsum_pair(const float *a, int rows, int cols, float *out0, float *out1, hipStream_t st);
 int ww_colsum_rows_small(const float *a, int rows, int cols, float *out, hipStream_t st);
 int ww_occupancy_grid(const void *fn, int block, size_t smem, long want, int cap);
+// the conv stack's persistent launches: that grid under the context's test / tuning cap (ww_ctx_set_grid_cap), read when
+// the launch is issued; the same number goes to the finalize launch as its count of partial rows
+static inline int ww_capped_grid(const ww_ctx *ctx, int grid) {
+    return ctx->grid_cap > 0 && grid > ctx->grid_cap ? ctx->grid_cap : grid;
+}
+static inline int ww_conv_grid(const ww_ctx *ctx, const void *fn, int block, size_t smem, long want, int cap) {
+    return ww_capped_grid(ctx, ww_occupancy_grid(fn, block, smem, want, cap));
+}
 // integer environment knob (tuning / A-B experiments); call sites cache the result in a function-local static
 static inline int ww_env_int(const char *name, int dflt) {
     const char *e = getenv(name);
     return e ? atoi(e) : dflt;
 }
-// ww_conv_bwd.hip: ww_conv_stem_bwd with the stem weights (w != NULL: y_out is recomputed from x instead of read)
+// ww_conv_bwd.hip: ww_conv_stem_bwd with the stem weights (w != NULL: y_out is recomputed from x instead of read);
+// ww_conv_stem_bwd_recompute is its C entry point
 int ww_stem_bwd_impl(ww_ctx *ctx, int act_dtype, const void *g, const void *y_out, const float *w, const float *coef,
                      const float *x, int B, int Hin, int Win, float *dw, void *scratch, ww_stream_t stream);
 // ww_ctx.hip: block sums of squares of g[0..n) into ctx->norm_partials (fixed partition -> deterministic); returns the count

@@ -256,7 +256,7 @@ extern "C" int ww_cnn_front_fwd(ww_ctx *ctx, int act_dtype, void *const *params,
     rc = conv_stack_fwd(ctx, act_dtype, params, x, B, F, T, training, bn_momentum, bn_eps, L, w, stream);
     if (rc) return rc;
     const long items = (long)B * L.Wo;
-    const int grid = (int)std::min<long>((items + 7) / 8, 2048);
+    const int grid = ww_capped_grid(ctx, (int)std::min<long>((items + 7) / 8, 2048));
     hipStream_t st = (hipStream_t)stream;
     if (act_dtype == WW_ACT_BF16)
         hipLaunchKernelGGL(k_freqpool_fwd<ww_bf16>, dim3(grid), dim3(256), 0, st, (const ww_bf16 *)(w + L.y[8]),
@@ -284,7 +284,7 @@ extern "C" int ww_cnn_front_bwd(ww_ctx *ctx, int act_dtype, void *const *params,
     hipStream_t st = (hipStream_t)stream;
     float *stat = (float *)(w + L.scratch);
     const long items = (long)B * L.Wo;
-    const int grid = (int)std::min<long>((items + 7) / 8, (long)WW_MAX_PARTIALS);
+    const int grid = ww_capped_grid(ctx, (int)std::min<long>((items + 7) / 8, (long)WW_MAX_PARTIALS));
     if (act_dtype == WW_ACT_BF16)
         hipLaunchKernelGGL(k_freqpool_bwd<ww_bf16>, dim3(grid), dim3(256), 0, st, dseq, (const ww_bf16 *)(w + L.y[8]),
                            (const float *)(w + L.ss[8]), (const float *)(w + L.mr[8]), B, L.Ho, L.Wo, (ww_bf16 *)(w + L.g[0]), stat);
