@@ -529,6 +529,57 @@ int ww_conv2d_stem_bwd_dw(ww_ctx *ctx, const float *x, const float *dy, int B, i
 int ww_maxpool3x3s2_fwd(ww_ctx *ctx, const float *x, int B, int H, int W, int C, float *y, ww_stream_t stream);
 int ww_maxpool3x3s2_bwd(ww_ctx *ctx, const float *x, const float *dy, int B, int H, int W, int C, float *dx, ww_stream_t stream);
 
+/* ------------------------------------------------------------------ the same layers with 16-bit ACTIVATION STORAGE (`_st`)
+ * Every (B,H,W,C) activation tensor and every activation gradient (the void* arguments) is bf16 (storage = WW_ACT_BF16) or fp16
+ * (WW_ACT_F16) in HBM, contiguous and 16-byte aligned; features in, parameters, weight gradients, BatchNorm vectors and the pooled
+ * mean stay fp32.  Arithmetic is fp32; a value is rounded (round to nearest even; fp16 overflow -> inf, the loss scaler's signal)
+ * exactly where a tensor is stored.  storage = WW_ACT_F32, a channel count that is no multiple of 8 (a 16-byte access is 8
+ * elements) or a null pointer is WW_E_INVALID before any launch; shapes, k and stride otherwise as for the fp32 entry points.
+ *
+ * ww_conv2d_st_fwd / _bwd: ww_conv2d_fwd / _bwd whose matrix mode IS the storage type: the operands go from HBM into the LDS tiles as
+ * they are, the weights are rounded once when they are re-laid per tap, products accumulate in fp32 (blocked, as ww_conv2d_*).
+ *   y = S(conv(x, S(w)));  dx = S(dX(dy, S(w)) + (accumulate_dx ? float(dx) : 0));  dw (fp32) = dW(dy, x) in the fixed order of
+ * ww_conv2d_bwd (partials queued while ww_ctx_set_deferred_reduce is in force).  scratch: ww_conv2d_st_scratch_bytes(...).
+ * stat_part (forward, nullable): ceil(M / 64) rows of 2 Cout floats, M = B Ho Wo; the kernel leaves in row t the per-column sums of the
+ * STORED values of output rows [64 t, 64 t + 64) and of their squares ([sum (Cout) | sum of squares (Cout)], fp32, fixed order, no
+ * atomics) -- BatchNorm's statistics without another pass over y: hand them to ww_bn_act_st_fwd.                                 */
+size_t ww_conv2d_st_scratch_bytes(int B, int H, int W, int Cin, int Cout, int k, int stride);
+int ww_conv2d_st_fwd(ww_ctx *ctx, int storage, const void *x, const float *w, int B, int H, int W, int Cin, int Cout, int k, int stride,
+                     void *y, float *stat_part /* nullable */, void *scratch, size_t scratch_bytes, ww_stream_t stream);
+int ww_conv2d_st_bwd(ww_ctx *ctx, int storage, const void *x, const float *w, const void *dy, int B, int H, int W, int Cin, int Cout,
+                     int k, int stride, void *dx /* nullable */, int accumulate_dx, float *dw, void *scratch, size_t scratch_bytes,
+                     ww_stream_t stream);
+/* BatchNorm(+activation) of a 16-bit x (M, C), C a multiple of 8 in 8..1024.  Training: the statistics are those of the STORED x
+ * (column sums in fp64 per row chunk, fp32 partials, finished in fp64 in a fixed order); eval: the running statistics.  ss
+ * (scale|shift, 2C) and mr (mean|rstd, 2C) are written and the running statistics move exactly as in ww_bn_act_fwd.
+ *   y = S(act(fma(x, scale, shift) + idn)),  idn = 0 (res == NULL) | float(res) | fma(float(res), res_ss[0:C], res_ss[C:2C])
+ * -- with res / res_ss the tail of a BasicBlock, relu(bn2(c2) + (x | bn_d(cd))), is one pass with one rounding.  y == NULL: only the
+ * statistics (ss, mr, running statistics).  scratch: ww_nhwc_scratch_bytes(C).
+ * stat_part / stat_rows (nullable / ignored then; ignored in eval mode): a producer's statistics partials of x in the layout above;
+ * they are finished in fp64 in row order (more than 1024 rows: folded to 256 first, each the fp64 sum of consecutive rows), and
+ * the column-statistics pass over x is not run.
+ * bwd: the two passes of ww_bn_act_bwd; x, da in S, dx = S(...), dgamma / dbeta fp32 (C each).                                  */
+int ww_bn_act_st_fwd(ww_ctx *ctx, int storage, const void *x, long M, int C, const ww_bn_t *bn, int act, const void *res /* nullable */,
+                     const float *res_ss /* nullable */, const float *stat_part /* nullable */, long stat_rows, void *y /* nullable */,
+                     float *ss, float *mr, void *scratch, ww_stream_t stream);
+int ww_bn_act_st_bwd(ww_ctx *ctx, int storage, const void *x, const void *da, long M, int C, const float *ss, const float *mr, int act,
+                     int training, void *dx, float *dgamma, float *dbeta, void *scratch, ww_stream_t stream);
+/* The one-channel stem with an S output (x, w fp32: y = S(conv(x, w))) and its weight gradient from an S dy (dw fp32); C a multiple
+ * of 8 in 8..128.  MaxPool2d(3, 2, 1) in S: the forward selects and never rounds, the backward rounds the fp32 sum of the (at most
+ * four) window gradients of a pixel once.                                                                                      */
+int ww_conv2d_stem_st_fwd(ww_ctx *ctx, int storage, const float *x, const float *w, int B, int H, int W, int C, int k, int stride,
+                          void *y, ww_stream_t stream);
+int ww_conv2d_stem_st_bwd_dw(ww_ctx *ctx, int storage, const float *x, const void *dy, int B, int H, int W, int C, int k, int stride,
+                             float *dw, void *scratch, size_t scratch_bytes, ww_stream_t stream);
+int ww_maxpool3x3s2_st_fwd(ww_ctx *ctx, int storage, const void *x, int B, int H, int W, int C, void *y, ww_stream_t stream);
+int ww_maxpool3x3s2_st_bwd(ww_ctx *ctx, int storage, const void *x, const void *dy, int B, int H, int W, int C, void *dx,
+                           ww_stream_t stream);
+/* mean (B,C) fp32 = the mean over HW of x (B,HW,C) in S, summed in a fixed order;  dx (B,HW,C) = S(dmean[b][c] / HW).
+ * ww_relu_mask_st_bwd: dx = dy where the stored y != 0, else 0 (n elements, a multiple of 8; exact).                              */
+int ww_mean_hw_st_fwd(ww_ctx *ctx, int storage, const void *x, int B, int HW, int C, float *mean, ww_stream_t stream);
+int ww_mean_hw_st_bwd(ww_ctx *ctx, int storage, const float *dmean, int B, int HW, int C, void *dx, ww_stream_t stream);
+int ww_relu_mask_st_bwd(ww_ctx *ctx, int storage, const void *dy, const void *y, size_t n, void *dx, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ GRU layer, one direction
  * torch.nn.GRU's cell and parameter layout (gate order r|z|n; w_ih (3H,I), w_hh (3H,H), b_ih, b_hh (3H)) -- what the
  * reference's GRUWakeword wraps (src/models/architectures.py:228-235).  batch_first: x (B,T,I) with row stride ldx

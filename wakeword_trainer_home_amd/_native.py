@@ -159,6 +159,18 @@ _SIGS = {
     "ww_conv2d_stem_bwd_dw": (C.c_int, [_vp, _vp, _vp] + [_i] * 6 + [_vp, _vp, _sz, _vp]),
     "ww_maxpool3x3s2_fwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ww_maxpool3x3s2_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ww_conv2d_st_scratch_bytes": (_sz, [_i] * 7),
+    "ww_conv2d_st_fwd": (C.c_int, [_vp, _i, _vp, _vp] + [_i] * 7 + [_vp, _vp, _vp, _sz, _vp]),
+    "ww_conv2d_st_bwd": (C.c_int, [_vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_vp, _i, _vp, _vp, _sz, _vp]),
+    "ww_bn_act_st_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _i, C.POINTER(BN), _i, _vp, _vp, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp]),
+    "ww_bn_act_st_bwd": (C.c_int, [_vp, _i, _vp, _vp, C.c_long, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ww_conv2d_stem_st_fwd": (C.c_int, [_vp, _i, _vp, _vp] + [_i] * 6 + [_vp, _vp]),
+    "ww_conv2d_stem_st_bwd_dw": (C.c_int, [_vp, _i, _vp, _vp] + [_i] * 6 + [_vp, _vp, _sz, _vp]),
+    "ww_maxpool3x3s2_st_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ww_maxpool3x3s2_st_bwd": (C.c_int, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ww_mean_hw_st_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "ww_mean_hw_st_bwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "ww_relu_mask_st_bwd": (C.c_int, [_vp, _i, _vp, _vp, _sz, _vp, _vp]),
     "ww_dropout_bt": (C.c_int, [_vp, _vp, C.c_long, _i, _i, _i, _f, _u64, _u64, _u64, _i, _vp, C.c_long, _vp]),
     "ww_nhwc_scratch_bytes": (_sz, [_i]),
     "ww_bn_act_fwd": (C.c_int, [_vp, _vp, C.c_long, _i, C.POINTER(BN), _i, _vp, _vp, _vp, _vp, _vp]),
@@ -845,6 +857,187 @@ def maxpool3x3s2_bwd(x, dy):
     dx = torch.empty_like(x)
     with _guard(dev):
         _check(load().ww_maxpool3x3s2_bwd(ctx(dev), _p(x), _p(dy), B, H, W, Cn, _p(dx), _stream(dev)), "ww_maxpool3x3s2_bwd")
+    return dx
+
+
+# ---- the same layers with 16-bit activation storage (ResNet18Wakeword(storage=...)): activations and their gradients are contiguous
+# bf16 / fp16 tensors, the storage code is their dtype's; parameters, weight gradients, BatchNorm vectors and the pooled mean are fp32
+def _st_code(*tensors):
+    """The storage code of 16-bit activation tensors that must all have one dtype."""
+    dt = tensors[0].dtype
+    if dt not in (torch.bfloat16, torch.float16) or any(t is not None and t.dtype != dt for t in tensors):
+        raise ValueError(f"16-bit activation storage: need bfloat16 or float16 tensors of one dtype, got {[t.dtype for t in tensors if t is not None]}")
+    return _ACT[dt]
+
+
+def _conv2d_st_check(x, w):
+    if x.dim() != 4 or w.dim() != 4 or x.shape[3] != w.shape[1] or w.shape[2] != w.shape[3] or w.dtype != torch.float32:
+        raise ValueError(f"conv2d: need 16-bit x (B,H,W,Cin) and float32 weight (Cout,Cin,k,k), got {tuple(x.shape)} and {tuple(w.shape)}")
+
+
+def _conv2d_st_scratch(B, H, W, Cin, Cout, k, stride, dev):
+    return torch.empty(max(load().ww_conv2d_st_scratch_bytes(B, H, W, Cin, Cout, k, stride) // 4, 4), dtype=torch.float32, device=dev)
+
+
+def conv2d_st_fwd(x, w, stride=1, stats=False):
+    """y = S(conv2d(x, S(w), stride, padding=k//2)); x (B,H,W,Cin) in S = bf16 | fp16, w (Cout,Cin,k,k) fp32 -> y (B,Ho,Wo,Cout) in S.
+    stats: -> (y, part), part (ceil(M / 64), 2 Cout) fp32 = per 64-row tile the column sums of the stored y and of its squares, for
+    bn_act_st_fwd(part=...)."""
+    dev = _dev(x, w)
+    _conv2d_st_check(x, w)
+    code = _st_code(x)
+    B, H, W, Cin = x.shape
+    Cout, _, k, _ = w.shape
+    y = torch.empty((B, *_dw_out_hw(H, W, k, max(stride, 1)), Cout), dtype=x.dtype, device=dev)
+    scratch = _conv2d_st_scratch(B, H, W, Cin, Cout, k, stride, dev)
+    part = torch.empty(((y.numel() // max(Cout, 1) + 63) // 64, 2 * Cout), dtype=torch.float32, device=dev) if stats else None
+    with _guard(dev):
+        _check(load().ww_conv2d_st_fwd(ctx(dev), code, _p(x), _p(w), B, H, W, Cin, Cout, k, stride, _p(y), _p(part), _p(scratch),
+                                       scratch.numel() * 4, _stream(dev)), "ww_conv2d_st_fwd")
+    return (y, part) if stats else y
+
+
+def conv2d_st_bwd(x, w, dy, stride=1, need_dx=True, dx=None, dw_out=None, defer=False, accumulate=True):
+    """conv2d_bwd on 16-bit x, dy, dx: -> (dx | None, dw fp32).  dx given: dx = S(dX + float(dx)) (accumulate=False: written over)."""
+    dev = _dev(x, w, dy, dx)
+    _conv2d_st_check(x, w)
+    code = _st_code(x, dy, dx)
+    B, H, W, Cin = x.shape
+    Cout, _, k, _ = w.shape
+    oshape = (B, *_dw_out_hw(H, W, k, max(stride, 1)), Cout)
+    if tuple(dy.shape) != oshape:
+        raise ValueError(f"conv2d backward: dy must be {oshape}, got {tuple(dy.shape)}")
+    if dx is not None and tuple(dx.shape) != tuple(x.shape):
+        raise ValueError(f"conv2d backward: dx must be {tuple(x.shape)}, got {tuple(dx.shape)}")
+    accumulate = bool(accumulate) and dx is not None
+    if dx is None and need_dx:
+        dx = torch.empty((B, H, W, Cin), dtype=x.dtype, device=dev)
+    dw = _out(dw_out, (Cout, Cin, k, k), dev)
+    scratch = _conv2d_st_scratch(B, H, W, Cin, Cout, k, stride, dev)
+    with _guard(dev), (_deferring(dev, scratch) if defer else contextlib.nullcontext()):
+        _check(load().ww_conv2d_st_bwd(ctx(dev), code, _p(x), _p(w), _p(dy), B, H, W, Cin, Cout, k, stride, _p(dx), int(accumulate),
+                                       _p(dw), _p(scratch), scratch.numel() * 4, _stream(dev)), "ww_conv2d_st_bwd")
+    return dx, dw
+
+
+def bn_act_st_fwd(x, bn: BN, act, Cn, res=None, res_ss=None, want_y=True, part=None):
+    """x (..., C) in S -> (y | None, ss (2C), mr (2C)): y = S(act(bn(x) + idn)), idn = 0 | res | res * res_ss[:C] + res_ss[C:];
+    want_y=False: the statistics only.  part: the statistics partials conv2d_st_fwd(stats=True) left for x."""
+    dev = _dev(x, res, res_ss, part)
+    if part is not None and (part.dtype != torch.float32 or part.dim() != 2 or part.shape[1] != 2 * Cn):
+        raise ValueError("bn_act_st_fwd: part must be float32 (rows, 2C)")
+    code = _st_code(x, res)
+    if res is not None and res.shape != x.shape:
+        raise ValueError(f"bn_act_st_fwd: the residual {tuple(res.shape)} does not have x's shape {tuple(x.shape)}")
+    if res_ss is not None and (res_ss.dtype != torch.float32 or res_ss.numel() != 2 * Cn):
+        raise ValueError("bn_act_st_fwd: res_ss must be float32 (2C)")
+    M = x.numel() // Cn
+    y = torch.empty_like(x) if want_y else None
+    ss = torch.empty(2 * Cn, dtype=torch.float32, device=dev)
+    mr = torch.empty(2 * Cn, dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_bn_act_st_fwd(ctx(dev), code, _p(x), M, Cn, C.byref(bn), act, _p(res), _p(res_ss), _p(part),
+                                       0 if part is None else part.shape[0], _p(y), _p(ss), _p(mr),
+                                       _p(nhwc_scratch(Cn, dev)), _stream(dev)), "ww_bn_act_st_fwd")
+    return y, ss, mr
+
+
+def bn_act_st_bwd(x, da, ss, mr, act, training, Cn, dgamma_out=None, dbeta_out=None):
+    dev = _dev(x, da, ss, mr)
+    code = _st_code(x, da)
+    if da.shape != x.shape:
+        raise ValueError(f"bn_act_st_bwd: da {tuple(da.shape)} does not have x's shape {tuple(x.shape)}")
+    M = x.numel() // Cn
+    dx = torch.empty_like(x)
+    dgamma = _out(dgamma_out, (Cn,), dev)
+    dbeta = _out(dbeta_out, (Cn,), dev)
+    with _guard(dev):
+        _check(load().ww_bn_act_st_bwd(ctx(dev), code, _p(x), _p(da), M, Cn, _p(ss), _p(mr), act, int(training), _p(dx), _p(dgamma),
+                                       _p(dbeta), _p(nhwc_scratch(Cn, dev)), _stream(dev)), "ww_bn_act_st_bwd")
+    return dx, dgamma, dbeta
+
+
+def conv2d_stem_st_fwd(x, w, stride=2, storage=torch.bfloat16):
+    """conv2d_stem_fwd with the output stored in `storage`: fp32 x (B,H,W), w (C,1,k,k) -> y (B,Ho,Wo,C) = S(conv(x, w))."""
+    dev = _dev(x, w)
+    _stem_check(x, w)
+    B, H, W = x.shape
+    Cn, k = w.shape[0], w.shape[2]
+    y = torch.empty((B, *_dw_out_hw(H, W, k, max(stride, 1)), Cn), dtype=storage, device=dev)
+    with _guard(dev):
+        _check(load().ww_conv2d_stem_st_fwd(ctx(dev), _st_code(y), _p(x), _p(w), B, H, W, Cn, k, stride, _p(y), _stream(dev)),
+               "ww_conv2d_stem_st_fwd")
+    return y
+
+
+def conv2d_stem_st_bwd_dw(x, dy, w_shape, stride=2, dw_out=None, defer=False):
+    """dw (C,1,k,k) fp32 of conv2d_stem_st_fwd from a 16-bit dy."""
+    dev = _dev(x, dy)
+    B, H, W = x.shape
+    Cn, _, k, _ = w_shape
+    oshape = (B, *_dw_out_hw(H, W, k, max(stride, 1)), Cn)
+    if x.dtype != torch.float32 or tuple(dy.shape) != oshape:
+        raise ValueError(f"conv2d stem backward: dy must be {oshape}, got {tuple(dy.shape)}")
+    dw = _out(dw_out, tuple(w_shape), dev)
+    scratch = torch.empty(max(load().ww_conv2d_stem_scratch_bytes(Cn, k) // 4, 4), dtype=torch.float32, device=dev)
+    with _guard(dev), (_deferring(dev, scratch) if defer else contextlib.nullcontext()):
+        _check(load().ww_conv2d_stem_st_bwd_dw(ctx(dev), _st_code(dy), _p(x), _p(dy), B, H, W, Cn, k, stride, _p(dw), _p(scratch),
+                                               scratch.numel() * 4, _stream(dev)), "ww_conv2d_stem_st_bwd_dw")
+    return dw
+
+
+def maxpool3x3s2_st_fwd(x):
+    dev = _dev(x)
+    if x.dim() != 4:
+        raise ValueError(f"maxpool3x3s2: need x (B,H,W,C), got {tuple(x.shape)}")
+    B, H, W, Cn = x.shape
+    y = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cn), dtype=x.dtype, device=dev)
+    with _guard(dev):
+        _check(load().ww_maxpool3x3s2_st_fwd(ctx(dev), _st_code(x), _p(x), B, H, W, Cn, _p(y), _stream(dev)), "ww_maxpool3x3s2_st_fwd")
+    return y
+
+
+def maxpool3x3s2_st_bwd(x, dy):
+    dev = _dev(x, dy)
+    B, H, W, Cn = x.shape
+    if tuple(dy.shape) != (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cn):
+        raise ValueError(f"maxpool3x3s2 backward: dy {tuple(dy.shape)} does not belong to x {tuple(x.shape)}")
+    dx = torch.empty_like(x)
+    with _guard(dev):
+        _check(load().ww_maxpool3x3s2_st_bwd(ctx(dev), _st_code(x, dy), _p(x), _p(dy), B, H, W, Cn, _p(dx), _stream(dev)),
+               "ww_maxpool3x3s2_st_bwd")
+    return dx
+
+
+def mean_hw_st_fwd(x):
+    """x (B,HW,C) in S -> the mean over HW, (B,C) fp32."""
+    dev = _dev(x)
+    B, HW, Cn = x.shape
+    s = torch.empty((B, Cn), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_mean_hw_st_fwd(ctx(dev), _st_code(x), _p(x), B, HW, Cn, _p(s), _stream(dev)), "ww_mean_hw_st_fwd")
+    return s
+
+
+def mean_hw_st_bwd(dmean, HW, storage):
+    """dmean (B,C) fp32 -> dx (B,HW,C) = S(dmean / HW)."""
+    dev = _dev(dmean)
+    if dmean.dim() != 2 or dmean.dtype != torch.float32:
+        raise ValueError("mean_hw_st_bwd: need a float32 (B,C) gradient")
+    B, Cn = dmean.shape
+    dx = torch.empty((B, HW, Cn), dtype=storage, device=dev)
+    with _guard(dev):
+        _check(load().ww_mean_hw_st_bwd(ctx(dev), _st_code(dx), _p(dmean), B, HW, Cn, _p(dx), _stream(dev)), "ww_mean_hw_st_bwd")
+    return dx
+
+
+def relu_mask_st_bwd(dy, y):
+    dev = _dev(dy, y)
+    if dy.shape != y.shape:
+        raise ValueError("relu_mask_st_bwd: dy and y differ in shape")
+    dx = torch.empty_like(dy)
+    with _guard(dev):
+        _check(load().ww_relu_mask_st_bwd(ctx(dev), _st_code(dy, y), _p(dy), _p(y), dy.numel(), _p(dx), _stream(dev)), "ww_relu_mask_st_bwd")
     return dx
 
 

@@ -146,13 +146,6 @@ __global__ __launch_bounds__(256) void k_bn_act_apply(Idx<V> nv, const float *__
         stv<V>(y + (size_t)i * V, o);
     }
 }
-__device__ __forceinline__ float bnact_bwd_one(float xv, float dav, float sc, float sf, float mu, float rs, float s1, float s2,
-                                               float invM, int act, int training) {
-    const float dz = dav * lin_act_grad(act, fmaf(xv, sc, sf));
-    if (!training) return sc * dz;
-    const float xh = (xv - mu) * rs;
-    return sc * (dz - s1 * invM - xh * s2 * invM);
-}
 // backward pass 2: dx = gamma*rstd*(dz - mean(dz) - xhat*mean(dz*xhat))   (training);  eval: dx = scale*dz
 template <int V>
 __global__ __launch_bounds__(256) void k_bnact_bwd_apply(Idx<V> nv, const float *__restrict__ x, const float *__restrict__ da,
@@ -218,38 +211,6 @@ __global__ __launch_bounds__(1024) void k_bnact_bwd_finish(const float *__restri
 // float4 loads in batches of eight, the same fixed order in every workgroup, so all of them hold bit-identical totals.  Used
 // when that re-read is <= 24 KB per workgroup (the caller picks CG4); with the layer library's own statistics pass (up to 256
 // chunks x 64 channels) it was slower than the three-launch form (profiles/r02_mnv3_experiments).
-struct BnTile { int CG4, G_c, R; long rows_per_block; };
-// totals of the group's 2*CG partial columns -> tot[2*CG] (LDS, double).  part rows are [2C] floats.  256 threads.
-__device__ __forceinline__ void bn_group_totals(const float *__restrict__ part, int chunks, int C, int c0, int CG4, double *tot,
-                                                double *redd /* [256][4] */) {
-    const int nq = 2 * CG4;                         // float4 columns of the group (both statistics)
-    const int LA = 256 / nq;                        // chunk lanes (>= 8)
-    const int k4 = threadIdx.x % nq, la = threadIdx.x / nq;
-    const int comp = k4 / CG4, cq = k4 - comp * CG4, col = comp * C + min(c0 + 4 * cq, C - 4);
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    if (la < LA)
-        for (int q0 = la; q0 < chunks; q0 += 8 * LA) {
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4 *>(part + (size_t)min(q0 + u * LA, chunks - 1) * 2 * C + col);
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (q0 + u * LA < chunks) { a0 += v[u].x; a1 += v[u].y; a2 += v[u].z; a3 += v[u].w; }
-        }
-    double *r = redd + (size_t)threadIdx.x * 4;
-    r[0] = a0; r[1] = a1; r[2] = a2; r[3] = a3;
-    __syncthreads();
-    if (threadIdx.x < nq) {
-        double t0 = 0.0, t1 = 0.0, t2 = 0.0, t3 = 0.0;
-        for (int q = 0; q < LA; ++q) {
-            const double *u = redd + (size_t)(q * nq + k4) * 4;
-            t0 += u[0]; t1 += u[1]; t2 += u[2]; t3 += u[3];
-        }
-        double *o = tot + comp * 4 * CG4 + 4 * cq;
-        o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
-    }
-    __syncthreads();
-}
 // grid G_r * G_c, block 256: thread = (float4 of the group's channels, row lane)
 __global__ __launch_bounds__(256) void k_bn_act_apply_fin(const float *__restrict__ x, const float *__restrict__ part, int chunks,
                                                           long M, int C, BnTile t, ww_bn_t bn, int act, float *__restrict__ y,
@@ -924,6 +885,18 @@ static int bn_finish_apply(const float *part, int chunks, const float *x, long M
     return WW_OK;
 }
 
+// the finish launches alone, for the 16-bit-storage passes of ww_conv2d16.hip that bring partials of their own
+int ww_bn_finish_launch(const float *part, int chunks, long M, int C, const ww_bn_t *bn, float *ss, float *mr, hipStream_t st) {
+    hipLaunchKernelGGL(k_bn_finish, dim3((C + 63) / 64), dim3(1024), 0, st, part, chunks, M, C, *bn, ss, mr);
+    WW_LAUNCH_CHECK();
+    return WW_OK;
+}
+int ww_bnact_bwd_finish_launch(const float *part, int chunks, int C, float *sums, float *dgamma, float *dbeta, hipStream_t st) {
+    hipLaunchKernelGGL(k_bnact_bwd_finish, dim3((C + 63) / 64), dim3(1024), 0, st, part, chunks, C, sums, dgamma, dbeta);
+    WW_LAUNCH_CHECK();
+    return WW_OK;
+}
+
 extern "C" int ww_bn_act_fwd(ww_ctx *ctx, const float *x, long M, int C, const ww_bn_t *bn, int act, float *y, float *ss,
                              float *mr, void *scratch, ww_stream_t stream) {
     WW_REQUIRE(ctx && x && bn && bn->gamma && bn->beta && y && ss && mr && scratch, WW_E_INVALID, "ww_bn_act_fwd: null argument");
@@ -944,21 +917,6 @@ extern "C" int ww_bn_act_fwd(ww_ctx *ctx, const float *x, long M, int C, const w
     return bn_finish_apply(part, chunks, x, M, C, bn, act, y, ss, mr, st);
 }
 
-// (row chunk, channel group) tiling of k_bn_act_apply_fin: the widest group (16, 8 or 4 channel float4s) whose re-read of the
-// partials stays <= 32 KB per workgroup; CG4 == 0: too many partial rows, take the finish launch instead
-static BnTile bn_tile(long M, int C, int chunks) {
-    BnTile t = {0, 0, 0, 0};
-    const int C4 = C / 4;
-    for (int cg4 = 16; cg4 >= 4; cg4 >>= 1) {
-        const int G_c = (C4 + cg4 - 1) / cg4, CG4 = (C4 + G_c - 1) / G_c;
-        if ((size_t)chunks * 2 * 4 * CG4 * sizeof(float) > 32 * 1024) continue;
-        t.G_c = G_c; t.CG4 = CG4; t.R = 256 / CG4;
-        const long G_r = std::max<long>(1, std::min<long>(std::max(1, 1024 / G_c), M / (4L * t.R)));
-        t.rows_per_block = (M + G_r - 1) / G_r;
-        break;
-    }
-    return t;
-}
 // training-mode BatchNorm(+activation) of x (M, C) whose statistics partials -- `chunks` rows of [sum (C) | sum of squares (C)]
 // -- a producer has already written to `part`
 int ww_bn_act_from_partials(ww_ctx *ctx, const float *x, long M, int C, const ww_bn_t *bn, int act, float *y, float *ss, float *mr,

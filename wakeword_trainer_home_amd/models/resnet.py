@@ -10,7 +10,14 @@ published definition (``tests/resnet_cases.py`` carries the same restatement in 
 The stem (conv1 -> bn1 -> ReLU -> maxpool) is ONE autograd node and so is a ``BasicBlock`` (conv1 -> BN+ReLU -> conv2 -> BN ->
 [downsample conv1x1 -> BN] -> add+ReLU); a block keeps its input, the two (three) pre-BatchNorm convolution outputs, conv2's input
 and its own output for the backward.  Weight and BatchNorm gradients are born in their slots of the model's flat bucket, the sums
-of the weight-gradient partials wait for the one flush at the end of the backward pass."""
+of the weight-gradient partials wait for the one flush at the end of the backward pass.
+
+``storage="bf16" | "fp16"`` (opt-in; it must equal the matrix ``mode``) keeps every (B,H,W,C) activation tensor between the stem
+convolution and the global mean, every gradient of one and everything autograd saves of them in that type (the ``*_st_*`` kernels):
+values are rounded exactly where a tensor is stored, arithmetic, BatchNorm vectors, parameters and their gradients stay fp32, and a
+block's tail relu(bn2(c2) + identity) is one pass that never stores bn2(c2) or bn_d(cd); the block BatchNorms' batch statistics come
+from the convolutions' own epilogue (only the stem's takes a pass over its input).  The default, ``storage="fp32"``, is the
+path described above, unchanged; state-dict keys, parameter layouts and initialisation do not depend on it."""
 import torch
 import torch.nn as nn
 
@@ -37,10 +44,29 @@ def _bn(c):
     return bn
 
 
-def _bn_fwd(bn, y, act):
-    """BatchNorm (+ activation) of a convolution output -> (a, ss, mr); counts the training forward on the host."""
+def _storage(mode, storage):
+    """(matrix mode, storage) as torch dtypes.  A 16-bit storage must be the matrix mode: an operand in HBM then already has the
+    matrix cores' type."""
+    m, s = _MODES.get(mode, mode), _MODES.get(storage, storage)
+    nat.act_code(m)
+    if s is torch.float32:
+        return m, s
+    if s not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"storage must be 'fp32', 'bf16' or 'fp16', got {storage!r}")
+    if s is not m:
+        raise ValueError(f"16-bit activation storage must equal the matrix mode: storage={storage!r} with mode={mode!r}")
+    return m, s
+
+
+def _bn_fwd(bn, y, act, **st):
+    """BatchNorm (+ activation) of a convolution output -> (a, ss, mr); counts the training forward on the host.  A 16-bit y goes
+    through ww_bn_act_st_fwd, which also takes the residual of a block's tail and the statistics partials the convolution's
+    epilogue left (``st``: res, res_ss, want_y, part)."""
     bnp = nat.make_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum=bn.momentum, eps=bn.eps, training=bn.training)
-    a, ss, mr = nat.bn_act_fwd(y, bnp, act, y.shape[-1])
+    if y.dtype is torch.float32:
+        a, ss, mr = nat.bn_act_fwd(y, bnp, act, y.shape[-1])
+    else:
+        a, ss, mr = nat.bn_act_st_fwd(y, bnp, act, y.shape[-1], **st)
     if bn.training:
         bn._pending_tracked += 1
     return a, ss, mr
@@ -61,6 +87,8 @@ class _ConvFn(torch.autograd.Function):
     def forward(ctx, x, weight, mod):
         ctx.save_for_backward(x, weight)
         ctx.mod = mod
+        if x.dtype is not torch.float32:
+            return nat.conv2d_st_fwd(x, weight, mod.stride)
         return nat.conv2d_fwd(x, weight, mod.stride, mode=mod.mode)
 
     @staticmethod
@@ -68,32 +96,37 @@ class _ConvFn(torch.autograd.Function):
         x, weight = ctx.saved_tensors
         mod = ctx.mod
         (slot,), defer = _defer_slots([mod.weight], x.device)
-        dx, dw = nat.conv2d_bwd(x, weight, dy.contiguous(), mod.stride, mode=mod.mode, need_dx=ctx.needs_input_grad[0], dw_out=slot,
-                                defer=defer)
+        if x.dtype is not torch.float32:
+            dx, dw = nat.conv2d_st_bwd(x, weight, dy.contiguous(), mod.stride, need_dx=ctx.needs_input_grad[0], dw_out=slot, defer=defer)
+        else:
+            dx, dw = nat.conv2d_bwd(x, weight, dy.contiguous(), mod.stride, mode=mod.mode, need_dx=ctx.needs_input_grad[0], dw_out=slot,
+                                    defer=defer)
         return dx, dw, None
 
 
 class NativeConv2d(nn.Module):
     """``nn.Conv2d(cin, cout, k, stride, padding=k // 2, bias=False)`` on (B, H, W, C) channels-last activations.  ``weight``
-    (Cout, Cin, k, k) is nn.Conv2d's, with its initialisation."""
+    (Cout, Cin, k, k) is nn.Conv2d's, with its initialisation.  ``storage``: the type of x, y and their gradients (see the module text)."""
 
-    def __init__(self, cin, cout, k, stride=1, mode="fp32"):
+    def __init__(self, cin, cout, k, stride=1, mode="fp32", storage="fp32"):
         super().__init__()
+        mode, storage = _storage(mode, storage)
         if cin < 4 or cout < 4 or cin % 4 or cout % 4:
             raise nat.NativeError(f"the HIP Conv2d kernels take channel counts that are positive multiples of 4, got {cin} -> {cout}")
+        if storage is not torch.float32 and (cin % 8 or cout % 8):
+            raise nat.NativeError(f"16-bit activation storage takes channel counts that are multiples of 8, got {cin} -> {cout}")
         if k not in (1, 3, 5, 7) or stride not in (1, 2):
             raise nat.NativeError(f"the HIP Conv2d kernels take an odd kernel_size in 1..7 and stride 1 or 2, got {k}, {stride}")
         ref = nn.Conv2d(cin, cout, k, stride, k // 2, bias=False)           # torch's own initialisation
         self.weight = nn.Parameter(ref.weight.detach().clone())
         self.in_channels, self.out_channels, self.kernel_size, self.stride = cin, cout, k, stride
-        self.mode = _MODES.get(mode, mode)
-        nat.act_code(self.mode)
+        self.mode, self.storage = mode, storage
 
     def forward(self, x):
         _no_cpu("NativeConv2d", x)
         if x.dim() != 4 or x.shape[3] != self.in_channels:
             raise ValueError(f"expected input (B,H,W,{self.in_channels}), got {tuple(x.shape)}")
-        return _ConvFn.apply(x.float().contiguous(), self.weight, self)
+        return _ConvFn.apply(x.to(self.storage).contiguous(), self.weight, self)
 
 
 class _StemFn(torch.autograd.Function):
@@ -101,21 +134,25 @@ class _StemFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, gamma, beta, net):
-        y = nat.conv2d_stem_fwd(x, w, net.conv1.stride)
+        st = net.storage is not torch.float32
+        y = nat.conv2d_stem_st_fwd(x, w, net.conv1.stride, net.storage) if st else nat.conv2d_stem_fwd(x, w, net.conv1.stride)
         a, ss, mr = _bn_fwd(net.bn1, y, nat.LIN_RELU)
         ctx.save_for_backward(x, y, a, ss, mr)
         ctx.net, ctx.training = net, net.bn1.training
-        return nat.maxpool3x3s2_fwd(a)
+        return nat.maxpool3x3s2_st_fwd(a) if st else nat.maxpool3x3s2_fwd(a)
 
     @staticmethod
     def backward(ctx, dout):
         x, y, a, ss, mr = ctx.saved_tensors
         net = ctx.net
-        da = nat.maxpool3x3s2_bwd(a, dout.contiguous())
-        dy, dgamma, dbeta = nat.bn_act_bwd(y, da, ss, mr, nat.LIN_RELU, ctx.training, y.shape[-1], dgamma_out=grad_slot(net.bn1.weight),
-                                           dbeta_out=grad_slot(net.bn1.bias))
+        st = y.dtype is not torch.float32
+        pool_bwd, bn_bwd, stem_dw = ((nat.maxpool3x3s2_st_bwd, nat.bn_act_st_bwd, nat.conv2d_stem_st_bwd_dw) if st else
+                                     (nat.maxpool3x3s2_bwd, nat.bn_act_bwd, nat.conv2d_stem_bwd_dw))
+        da = pool_bwd(a, dout.contiguous())
+        dy, dgamma, dbeta = bn_bwd(y, da, ss, mr, nat.LIN_RELU, ctx.training, y.shape[-1], dgamma_out=grad_slot(net.bn1.weight),
+                                   dbeta_out=grad_slot(net.bn1.bias))
         (slot,), defer = _defer_slots([net.conv1.weight], x.device)
-        dw = nat.conv2d_stem_bwd_dw(x, dy, net.conv1.weight.shape, net.conv1.stride, dw_out=slot, defer=defer)
+        dw = stem_dw(x, dy, net.conv1.weight.shape, net.conv1.stride, dw_out=slot, defer=defer)
         return None, dw, dgamma, dbeta, None
 
 
@@ -126,6 +163,8 @@ class _BlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, blk, *params):
         mode, s = blk.mode, blk.stride
+        if x.dtype is not torch.float32:
+            return _BlockFn._forward_st(ctx, x, blk, params)
         c1 = nat.conv2d_fwd(x, params[0], s, mode=mode)
         a1, ss1, mr1 = _bn_fwd(blk.bn1, c1, nat.LIN_RELU)
         c2 = nat.conv2d_fwd(a1, params[3], 1, mode=mode)
@@ -143,12 +182,39 @@ class _BlockFn(torch.autograd.Function):
         return out
 
     @staticmethod
+    def _forward_st(ctx, x, blk, params):
+        """The 16-bit-storage forward: the same saved list, but bn2(c2) and bn_d(cd) are never stored -- the tail is one pass."""
+        s = blk.stride
+
+        def conv(inp, w, stride, bn):
+            """-> (the convolution's output, its statistics partials from the conv epilogue when bn will take batch statistics)"""
+            return nat.conv2d_st_fwd(inp, w, stride, stats=True) if bn.training else (nat.conv2d_st_fwd(inp, w, stride), None)
+        c1, p1 = conv(x, params[0], s, blk.bn1)
+        a1, ss1, mr1 = _bn_fwd(blk.bn1, c1, nat.LIN_RELU, part=p1)
+        c2, p2 = conv(a1, params[3], 1, blk.bn2)
+        if blk.downsample is not None:
+            cd, pd = conv(x, params[6], s, blk.downsample[1])
+            _, ssd, mrd = _bn_fwd(blk.downsample[1], cd, nat.LIN_NONE, want_y=False, part=pd)
+            out, ss2, mr2 = _bn_fwd(blk.bn2, c2, nat.LIN_RELU, res=cd, res_ss=ssd, part=p2)
+            saved = [x, c1, a1, c2, ss1, mr1, ss2, mr2, cd, ssd, mrd]
+        else:
+            out, ss2, mr2 = _bn_fwd(blk.bn2, c2, nat.LIN_RELU, res=x, part=p2)
+            saved = [x, c1, a1, c2, ss1, mr1, ss2, mr2]
+        ctx.save_for_backward(out, *saved, *params)
+        ctx.blk, ctx.training, ctx.n_saved = blk, blk.bn1.training, len(saved)
+        return out
+
+    @staticmethod
     def backward(ctx, dout):
         out, *rest = ctx.saved_tensors
         saved, params = rest[:ctx.n_saved], rest[ctx.n_saved:]
         x, c1, a1, c2, ss1, mr1, ss2, mr2 = saved[:8]
         blk, tr = ctx.blk, ctx.training
-        mode, s = blk.mode, blk.stride
+        s = blk.stride
+        if x.dtype is torch.float32:
+            relu_mask, bn_bwd, conv_bwd, cm = nat.relu_mask_bwd, nat.bn_act_bwd, nat.conv2d_bwd, dict(mode=blk.mode)
+        else:                                       # 16-bit storage: the storage type is the matrix mode
+            relu_mask, bn_bwd, conv_bwd, cm = nat.relu_mask_st_bwd, nat.bn_act_st_bwd, nat.conv2d_st_bwd, {}
         need_dx = ctx.needs_input_grad[0]
         mods = [blk.conv1, blk.bn1, blk.conv2, blk.bn2] + (list(blk.downsample) if blk.downsample is not None else [])
         # gradients born in their slots of the model's flat bucket, so the sums of the weight-gradient partials can wait for the
@@ -157,30 +223,31 @@ class _BlockFn(torch.autograd.Function):
         bns = mods[1::2]
         gslots = [(grad_slot(b.weight), grad_slot(b.bias)) for b in bns]
         grads = [None] * len(params)
-        dsum = nat.relu_mask_bwd(dout.contiguous(), out)            # feeds bn2 and the skip path alike
-        dc2, grads[4], grads[5] = nat.bn_act_bwd(c2, dsum, ss2, mr2, nat.LIN_NONE, tr, c2.shape[-1], dgamma_out=gslots[1][0],
-                                                 dbeta_out=gslots[1][1])
-        da1, grads[3] = nat.conv2d_bwd(a1, params[3], dc2, 1, mode=mode, dw_out=wslots[1], defer=defer)
-        dc1, grads[1], grads[2] = nat.bn_act_bwd(c1, da1, ss1, mr1, nat.LIN_RELU, tr, c1.shape[-1], dgamma_out=gslots[0][0],
-                                                 dbeta_out=gslots[0][1])
+        dsum = relu_mask(dout.contiguous(), out)                    # feeds bn2 and the skip path alike
+        dc2, grads[4], grads[5] = bn_bwd(c2, dsum, ss2, mr2, nat.LIN_NONE, tr, c2.shape[-1], dgamma_out=gslots[1][0], dbeta_out=gslots[1][1])
+        da1, grads[3] = conv_bwd(a1, params[3], dc2, 1, dw_out=wslots[1], defer=defer, **cm)
+        dc1, grads[1], grads[2] = bn_bwd(c1, da1, ss1, mr1, nat.LIN_RELU, tr, c1.shape[-1], dgamma_out=gslots[0][0], dbeta_out=gslots[0][1])
         if blk.downsample is not None:
             cd, ssd, mrd = saved[8:11]
-            dcd, grads[7], grads[8] = nat.bn_act_bwd(cd, dsum, ssd, mrd, nat.LIN_NONE, tr, cd.shape[-1], dgamma_out=gslots[2][0],
-                                                     dbeta_out=gslots[2][1])
-            dx, grads[6] = nat.conv2d_bwd(x, params[6], dcd, s, mode=mode, need_dx=need_dx, dw_out=wslots[2], defer=defer)
+            dcd, grads[7], grads[8] = bn_bwd(cd, dsum, ssd, mrd, nat.LIN_NONE, tr, cd.shape[-1], dgamma_out=gslots[2][0],
+                                             dbeta_out=gslots[2][1])
+            dx, grads[6] = conv_bwd(x, params[6], dcd, s, need_dx=need_dx, dw_out=wslots[2], defer=defer, **cm)
         else:
             dx = dsum if need_dx else None
         # conv1's input gradient is added onto the skip path's
-        dx, grads[0] = nat.conv2d_bwd(x, params[0], dc1, s, mode=mode, need_dx=need_dx, dx=dx, dw_out=wslots[0], defer=defer)
+        dx, grads[0] = conv_bwd(x, params[0], dc1, s, need_dx=need_dx, dx=dx, dw_out=wslots[0], defer=defer, **cm)
         return (dx, None) + tuple(grads)
 
 
 class BasicBlock(nn.Module):
     """torchvision's BasicBlock (expansion 1): children conv1, bn1, conv2, bn2 and, where the shape changes, ``downsample`` =
-    Sequential(conv1x1 stride s, BatchNorm)."""
+    Sequential(conv1x1 stride s, BatchNorm).  ``storage``: the type of its input, its output and everything between."""
 
-    def __init__(self, inplanes, planes, stride=1, mode="fp32"):
+    def __init__(self, inplanes, planes, stride=1, mode="fp32", storage="fp32"):
         super().__init__()
+        mode, storage = _storage(mode, storage)
+        if storage is not torch.float32 and (inplanes % 8 or planes % 8):
+            raise nat.NativeError(f"BasicBlock: 16-bit activation storage takes channel multiples of 8, got {inplanes} -> {planes}")
         if stride not in (1, 2) or inplanes % 4 or planes % 4 or inplanes < 4 or planes < 4:
             raise nat.NativeError(f"BasicBlock: the HIP Conv2d kernels take channel multiples of 4 and stride 1 or 2, got "
                                   f"{inplanes} -> {planes}, stride {stride}")
@@ -190,8 +257,7 @@ class BasicBlock(nn.Module):
         for conv in [self.conv1, self.conv2] + ([self.downsample[0]] if self.downsample is not None else []):
             nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")       # torchvision's ResNet initialisation
         self.stride, self.inplanes = stride, inplanes
-        self.mode = _MODES.get(mode, mode)
-        nat.act_code(self.mode)
+        self.mode, self.storage = mode, storage
 
     def forward(self, x):
         _no_cpu("BasicBlock", x)
@@ -200,7 +266,7 @@ class BasicBlock(nn.Module):
         params = [self.conv1.weight, self.bn1.weight, self.bn1.bias, self.conv2.weight, self.bn2.weight, self.bn2.bias]
         if self.downsample is not None:
             params += [self.downsample[0].weight, self.downsample[1].weight, self.downsample[1].bias]
-        return _BlockFn.apply(x.float().contiguous(), self, *params)
+        return _BlockFn.apply(x.to(self.storage).contiguous(), self, *params)
 
 
 class _StemConv(nn.Module):
@@ -212,17 +278,33 @@ class _StemConv(nn.Module):
         self.k, self.stride = k, stride
 
 
+class _MeanFn(torch.autograd.Function):
+    """(B,H,W,C) in 16-bit storage -> the (B,C) fp32 mean; its gradient is stored as S(dpooled / HW)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        B, H, W, Cn = x.shape
+        ctx.full, ctx.dtype = x.shape, x.dtype
+        return nat.mean_hw_st_fwd(x.reshape(B, H * W, Cn))
+
+    @staticmethod
+    def backward(ctx, ds):
+        return nat.mean_hw_st_bwd(ds.contiguous(), ctx.full[1] * ctx.full[2], ctx.dtype).reshape(ctx.full)
+
+
 class _ResNet(nn.Module):
     """torchvision's resnet18 module tree (conv1, bn1, layer1..4, fc): the children that hold no state are not registered."""
 
-    def __init__(self, num_classes, dropout, mode, dropout_seed):
+    def __init__(self, num_classes, dropout, mode, dropout_seed, storage=torch.float32):
         super().__init__()
+        self.storage = storage
         self.dropout, self.dropout_seed = float(dropout), dropout_seed
         self.dropout_step, self.sample_offset, self.fc_step = 0, 0, 0
         self.conv1, self.bn1 = _StemConv(), _bn(64)
         inplanes = 64
         for i, (planes, stride) in enumerate(LAYERS):
-            setattr(self, f"layer{i + 1}", nn.Sequential(BasicBlock(inplanes, planes, stride, mode), BasicBlock(planes, planes, 1, mode)))
+            setattr(self, f"layer{i + 1}", nn.Sequential(BasicBlock(inplanes, planes, stride, mode, storage),
+                                                         BasicBlock(planes, planes, 1, mode, storage)))
             inplanes = planes
         # indices as the reference replaces fc: Dropout(dropout), Linear(512, num_classes)
         self.fc = nn.Sequential(_HiddenDropout(dropout, self), MFMALinear(inplanes, num_classes, mode=mode))
@@ -231,7 +313,7 @@ class _ResNet(nn.Module):
         h = _StemFn.apply(x, self.conv1.weight, self.bn1.weight, self.bn1.bias, self)
         for i in range(len(LAYERS)):
             h = getattr(self, f"layer{i + 1}")(h)
-        return self.fc(_PoolFn.apply(h))
+        return self.fc((_PoolFn if self.storage is torch.float32 else _MeanFn).apply(h))
 
 
 class ResNet18Wakeword(FlatBuckets, nn.Module):
@@ -240,7 +322,7 @@ class ResNet18Wakeword(FlatBuckets, nn.Module):
     hip_backed = True      # every op is a HIP kernel of this build: the Trainer may run its sync-free step (no host reads)
 
     def __init__(self, num_classes: int = 2, pretrained: bool = False, dropout: float = 0.3, input_channels: int = 1,
-                 dropout_seed: int = 0, mode: str = "fp32"):
+                 dropout_seed: int = 0, mode: str = "fp32", storage: str = "fp32"):
         super().__init__()
         if pretrained:
             raise ValueError("pretrained ImageNet weights cannot be downloaded in this build (pass pretrained=False)")
@@ -248,9 +330,8 @@ class ResNet18Wakeword(FlatBuckets, nn.Module):
             raise ValueError(f"resnet18: the native stem takes one-channel spectrograms, got input_channels={input_channels}")
         if not 0.0 <= dropout < 1.0:
             raise ValueError(f"dropout must be in [0, 1), got {dropout}")
-        m = _MODES.get(mode, mode)
-        nat.act_code(m)
-        self.resnet = _ResNet(num_classes, dropout, m, dropout_seed)
+        m, st = _storage(mode, storage)
+        self.resnet = _ResNet(num_classes, dropout, m, dropout_seed, st)
 
     @property
     def sample_offset(self):

@@ -683,7 +683,8 @@ class Trainer:
 
     def _graph_mode_key(self):
         """What a captured graph bakes besides shapes: the storage / matrix modes of the model's HIP modules."""
-        return tuple((m.act if isinstance(m, CNNSmallWakeword) else None, str(getattr(m, "mode", None)))
+        return tuple((m.act if isinstance(m, CNNSmallWakeword) else None, str(getattr(m, "mode", None))) +
+                     ((str(m.storage),) if hasattr(m, "storage") else ())
                      for m in self.model.modules() if isinstance(m, CNNSmallWakeword) or hasattr(m, "mode"))
 
     def _graph_key(self, shape):
