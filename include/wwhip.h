@@ -460,6 +460,28 @@ int ww_stem3x3s2_bwd_dw(ww_ctx *ctx, const float *x, const float *dy, int B, int
 /* 3x3 stride-2 pad-1 patches of a one-channel image (B,H,W) -> (B*ceil(H/2)*ceil(W/2), 9): the stem conv becomes a GEMM */
 int ww_im2col3x3s2(ww_ctx *ctx, const float *x, int B, int H, int W, float *cols, ww_stream_t stream);
 int ww_add_f32(ww_ctx *ctx, const float *a, const float *b, size_t n, float *y, ww_stream_t stream);
+/* Host-only plan queries: the kernel form and grid the entry points above launch for a shape, computed by the code they launch
+ * from.  Nothing is allocated or launched and no device is needed.  aligned: every base pointer of the call is 16-byte aligned;
+ * 0 reports the call with ALL of them off that grid (a call with only some off it, such as a misaligned residual beside aligned
+ * x and y, takes the same launches but may keep V = 4 in those that do not touch the misaligned tensor).
+ * ww_nhwc_plan_dw: which = 0 ww_dwconv_nhwc_fwd (in training mode ww_dwconv_bn_act_fwd takes its statistics in the conv kernel
+ *   exactly when this is the LDS plan, one partial row per image group), 1 / 2 the dx / dw launch of ww_dwconv_nhwc_bwd;
+ *   out[8] = {LDS kernel 1 / gather 0, V, workgroups, images per workgroup, channel groups G_c, channel float4s per group CC4,
+ *   image groups (dw gather: pixel chunks), row lanes R (dw gather)}; the LDS-only fields are 0 for a gather plan.
+ * ww_nhwc_plan_bn: which = 0 ww_bn_act_fwd, 1 ww_bn_act_bwd, 2 the BatchNorm half of a conv + BatchNorm call whose producer left
+ *   `chunks` rows of partials (ww_conv1x1_bn_act_fwd: ceil(M / ww_conv1x1_row_tile), ww_dwconv_bn_act_fwd: image groups,
+ *   ww_stem3x3s2_bn_act_fwd: workgroups); out[10] = {chunks, rows per chunk, row lanes of the statistics launch, 1 if the apply
+ *   pass finishes the partials itself / 0 for finish launch + elementwise apply, then CG4, G_c, R, rows per workgroup of the
+ *   finishing pass (0 if not taken), workgroups and V of the apply launch}.
+ * ww_nhwc_plan_stem: out[2] = {workgroups of the persistent grid, pixel lanes per workgroup}.
+ * ww_nhwc_plan_ew: an elementwise pass over n floats of a (..., C) tensor (ww_add_f32: C = 4; ww_im2col3x3s2: aligned = 0);
+ *   out[2] = {workgroups of 256 threads, V}.                                                                            */
+int ww_nhwc_plan_dw(int which, int B, int H, int W, int C, int k, int stride, int aligned, int *out);
+int ww_nhwc_plan_bn(int which, long M, int C, int chunks, int training, int aligned, int *out);
+int ww_nhwc_plan_stem(int B, int H, int W, int C, int *out);
+int ww_nhwc_plan_ew(long n, int C, int aligned, int *out);
+int ww_se_plan(int B, int HW, int C, int Cs, int *out);      /* ww_se_fwd / _bwd: out[2] = {images per workgroup, workgroups} */
+int ww_conv1x1_row_tile(int mode, int M, int K, int N);      /* rows per statistics partial of ww_conv1x1_bn_act_fwd; 0: bad argument */
 
 /* ------------------------------------------------------------------ conv front-end of the CRNN
  * cnn_small's conv stack (stem + 4 depthwise-separable blocks) without GAP / classifier, followed by the mean over the

@@ -190,6 +190,12 @@ _SIGS = {
     "ww_stem3x3s2_bwd_dw": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ww_im2col3x3s2": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "ww_add_f32": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "ww_nhwc_plan_dw": (C.c_int, [_i] * 8 + [C.POINTER(C.c_int)]),
+    "ww_nhwc_plan_bn": (C.c_int, [_i, C.c_long, _i, _i, _i, _i, C.POINTER(C.c_int)]),
+    "ww_nhwc_plan_stem": (C.c_int, [_i] * 4 + [C.POINTER(C.c_int)]),
+    "ww_nhwc_plan_ew": (C.c_int, [C.c_long, _i, _i, C.POINTER(C.c_int)]),
+    "ww_conv1x1_row_tile": (C.c_int, [_i] * 4),
+    "ww_se_plan": (C.c_int, [_i] * 4 + [C.POINTER(C.c_int)]),
     "ww_gru_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ww_gru_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_long, _vp, _vp, _sz, _vp]),
     "ww_gru_bidir_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _i, _i, _i, _i, _vp, C.c_long, _sz, _vp]),
@@ -1269,6 +1275,42 @@ def add_f32(a, b):
     with _guard(dev):
         _check(load().ww_add_f32(ctx(dev), _p(a), _p(b), a.numel(), _p(y), _stream(dev)), "ww_add_f32")
     return y
+
+
+# ---- host-only plan queries (include/wwhip.h ww_nhwc_plan_*): what the layer library launches for a shape; no device needed
+def _plan(fn, names, *args):
+    out = (C.c_int * len(names))()
+    _check(getattr(load(), fn)(*args, out), fn)
+    return dict(zip(names, out))
+
+
+def plan_dw(which, B, H, W, Cn, k, stride, aligned=True):
+    """which: 'fwd' | 'dx' | 'dw' -> the depthwise launch's plan (LDS kernel or gather, images per workgroup, grid ...)."""
+    return _plan("ww_nhwc_plan_dw", ("lds", "V", "grid", "nimg", "G_c", "CC4", "groups", "R"),
+                 ("fwd", "dx", "dw").index(which), B, H, W, Cn, k, stride, int(aligned))
+
+
+def plan_bn(which, M, Cn, chunks=0, training=True, aligned=True):
+    """which: 'fwd' | 'bwd' | 'partials' (the BatchNorm half of a conv + BatchNorm call that left `chunks` rows of partials)."""
+    return _plan("ww_nhwc_plan_bn", ("chunks", "rows_per_chunk", "R", "fused", "CG4", "G_c", "tile_R", "rows_per_block", "grid", "V"),
+                 ("fwd", "bwd", "partials").index(which), M, Cn, chunks, int(training), int(aligned))
+
+
+def plan_stem(B, H, W, Cn):
+    return _plan("ww_nhwc_plan_stem", ("blocks", "L"), B, H, W, Cn)
+
+
+def plan_ew(n, Cn, aligned=True):
+    return _plan("ww_nhwc_plan_ew", ("grid", "V"), n, Cn, int(aligned))
+
+
+def plan_se(B, HW, Cn, Cs):
+    return _plan("ww_se_plan", ("img", "grid"), B, HW, Cn, Cs)
+
+
+def conv1x1_row_tile(M, K, N, mode=torch.float32):
+    """Rows per BatchNorm statistics partial of conv1x1_bn_act_fwd (the GEMM's row tile)."""
+    return load().ww_conv1x1_row_tile(act_code(mode), M, K, N)
 
 
 # ---- recurrent layers (include/wwhip.h ww_gru_* / ww_lstm_*): one implementation, parameterised by the cell's gate count,

@@ -38,6 +38,8 @@ __device__ __forceinline__ void bn_group_totals(const float *__restrict__ part, 
     const int nq = 2 * CG4;                         // float4 columns of the group (both statistics)
     const int LA = 256 / nq;                        // chunk lanes (>= 8)
     const int k4 = threadIdx.x % nq, la = threadIdx.x / nq;
+    // (the clamp is a bounds guard only: where the last group is short, the lanes past C re-read the last quad, and their totals
+    //  land in tot entries of channels >= C that no caller reads -- no output depends on it, so no test can see it)
     const int comp = k4 / CG4, cq = k4 - comp * CG4, col = comp * C + min(c0 + 4 * cq, C - 4);
     double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
     if (la < LA)

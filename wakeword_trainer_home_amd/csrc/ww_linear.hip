@@ -470,6 +470,12 @@ int make_epilogue(const ww_ctx *ctx, const ww_linear_epi *epi, const float *bias
     return WW_OK;
 }
 
+// block tile of launch_gemm (rowsA x rowsB outputs in nz K splits, epilogue kind epi): 0 = 64 x 64, 1 = 128 x 64, 2 = 128 x 128;
+// the one copy of the rule, for launch_gemm, gemm_plan and ww_conv1x1_row_tile (the reasons stand in launch_gemm)
+static inline int gemm_tile_cfg(int epi, int mode, long rowsA, long rowsB, int nz) {
+    const long tiles128 = ((rowsA + 127) / 128) * ((rowsB + 127) / 128) * nz;
+    return (epi != 1 && mode != WW_ACT_F32 && rowsA >= 128 && rowsB >= 128 && tiles128 >= 256) ? 2 : (rowsA >= 8192 ? 1 : 0);
+}
 // splits > 1: partial products into `part` (splits x rows x cols), then summed in fixed order into C
 template <bool KCA, bool KCB, int EPI, bool A16 = false, bool SEG = false>
 int launch_gemm(int mode, const GemmOperand &A, const GemmOperand &B, int K, float *C, long ldc, const Epilogue &e,
@@ -485,11 +491,10 @@ int launch_gemm(int mode, const GemmOperand &A, const GemmOperand &B, int K, flo
     const int nz = (K + kps - 1) / kps;
     // Block tile: 64 x 64 by default; 128 x 128 (each staged byte feeds twice the MFMA work: these GEMMs are bound by operand
     // traffic, not by the matrix cores) when both extents allow it and enough workgroups remain; 128 x 64 for very tall ones
-    const long tiles128 = (long)((A.rows + 127) / 128) * ((B.rows + 127) / 128) * nz;
     // (the 128 x 128 form pays in bf16 mode only: in fp32 mode its 64 accumulator + 32 prefetch registers cost occupancy, 72 vs 82 TF)
     // (the dense head's full epilogue -- EPI = 1 -- stays off the 128 x 128 form: with 64 accumulators beside the Philox dropout
     // the kernel spilled scalar registers and carried a scratch segment; the head's GEMMs are far too small to miss that tile)
-    const int cfg = (EPI != 1 && mode != WW_ACT_F32 && A.rows >= 128 && B.rows >= 128 && tiles128 >= 256) ? 2 : (A.rows >= 8192 ? 1 : 0);
+    const int cfg = gemm_tile_cfg(EPI, mode, A.rows, B.rows, nz);
     const int RA = cfg ? 128 : 64, RBt = cfg == 2 ? 128 : 64;
     if (row_tile_out) *row_tile_out = RA;
     dim3 grid((B.rows + RBt - 1) / RBt, (A.rows + RA - 1) / RA, nz);
@@ -530,8 +535,7 @@ GemmPlan gemm_plan(int mode, const GemmOperand &A, const GemmOperand &B, int K, 
     const int kt = mode != WW_ACT_F32 ? GKH : GK;
     if (splits > 1) p.kps = ((K + splits - 1) / splits + kt - 1) / kt * kt;
     p.nz = (K + p.kps - 1) / p.kps;
-    const long tiles128 = (long)((A.rows + 127) / 128) * ((B.rows + 127) / 128) * p.nz;
-    p.cfg = (mode != WW_ACT_F32 && A.rows >= 128 && B.rows >= 128 && tiles128 >= 256) ? 2 : (A.rows >= 8192 ? 1 : 0);
+    p.cfg = gemm_tile_cfg(0, mode, A.rows, B.rows, p.nz);
     p.shallow = K <= 32 && p.nz == 1 && p.cfg != 2 && mode != WW_ACT_F32;
     return p;
 }
@@ -704,6 +708,13 @@ extern "C" int ww_conv1x1_bn_act_fwd(ww_ctx *ctx, int mode, const float *x, cons
     }
     ww_prof_scope ps_(ctx, WW_K_NHWC, st);
     return ww_bn_act_from_partials(ctx, y, M, N, bn, act, a, ss, mr, (const float *)scratch, (M + row_tile - 1) / row_tile, residual, st);
+}
+
+// host-only: rows per statistics partial (= the GEMM's row tile) of ww_conv1x1_bn_act_fwd, by the rule launch_gemm applies;
+// ceil(M / it) rows of partials reach ww_bn_act_from_partials (ww_nhwc_plan_bn, which = 2)
+extern "C" int ww_conv1x1_row_tile(int mode, int M, int K, int N) {
+    if (check_dims("ww_conv1x1_row_tile", mode, M, K, N)) return 0;
+    return gemm_tile_cfg(2, mode, M, N, 1) ? 128 : 64;        // its GEMM: EPI = 2, one K split
 }
 
 // K splits of the weight-gradient product dW (N x K) = dpre^T x: its contraction runs over the M rows (batch x pixels), which

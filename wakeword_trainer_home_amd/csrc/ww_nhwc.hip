@@ -856,18 +856,33 @@ inline bool aligned16(std::initializer_list<const void *> ptrs) {            // 
     return (bits & 15) == 0;
 }
 // float4 form usable: channel count a multiple of 4, every base pointer 16-byte aligned, index fits 32 bits
-inline bool vec4_ok(long n, int C, std::initializer_list<const void *> ptrs) {
-    return !(C & 3) && !(n & 3) && n / 4 < (1L << 31) && aligned16(ptrs);
-}
+inline bool vec4_ok(long n, int C, bool aligned) { return !(C & 3) && !(n & 3) && n / 4 < (1L << 31) && aligned; }
+inline bool vec4_ok(long n, int C, std::initializer_list<const void *> ptrs) { return vec4_ok(n, C, aligned16(ptrs)); }
 inline int rows_r(int C) { return std::max(1, 1024 / C); }                       // row lanes R of a C*R-thread block
 inline int chunks_for(long M, int C) { return (int)std::max<long>(1, std::min<long>(NCHUNK, M / (4L * rows_r(C)))); }
+
+// ---- launch plans: every decision an entry point takes from the shape and the pointers' alignment alone, in one place each, so
+// that ww_nhwc_plan_* (below) reports exactly what the entry points launch
+struct EwPlan { int V, grid; };            // an elementwise / gather pass over n floats: vector width, workgroups of 256
+inline EwPlan ew_plan(long n, bool v4) { return {v4 ? 4 : 1, egrid(v4 ? n / 4 : n)}; }
+struct StatsPlan { int chunks, R; long rows_per_chunk; };      // k_colstats / k_bnact_bwd_stats
+inline StatsPlan stats_plan(long M, int C) {
+    const int chunks = chunks_for(M, C);
+    return {chunks, rows_r(C), (M + chunks - 1) / chunks};
+}
+// tile of the apply pass that finishes `chunks` rows of partials itself; CG4 == 0: finish launch + elementwise apply instead
+inline BnTile fin_tile(long M, int C, int chunks, bool aligned) {
+    return vec4_ok(M * C, C, aligned) ? bn_tile(M, C, chunks) : BnTile{0, 0, 0, 0};
+}
+inline int fin_blocks(long M, const BnTile &t) { return (int)((M + t.rows_per_block - 1) / t.rows_per_block) * t.G_c; }
 }  // namespace
 
-// an elementwise kernel template over n floats: kern<4> over n / 4 float4s when v4 (vec4_ok), else kern<1> over n floats
-#define WW_LAUNCH_EW(kern, v4, n, st, ...)                                                                                   \
+// an elementwise kernel template over n floats by its EwPlan: kern<4> over n / 4 float4s (vec4_ok), else kern<1> over n floats
+#define WW_LAUNCH_EW(kern, plan, n, st, ...)                                                                                 \
     do {                                                                                                                     \
-        if (v4) hipLaunchKernelGGL(kern<4>, dim3(egrid((n) / 4)), dim3(256), 0, st, (uint32_t)((n) / 4), __VA_ARGS__);       \
-        else hipLaunchKernelGGL(kern<1>, dim3(egrid(n)), dim3(256), 0, st, (long)(n), __VA_ARGS__);                         \
+        const EwPlan ep_ = (plan);                                                                                           \
+        if (ep_.V == 4) hipLaunchKernelGGL(kern<4>, dim3(ep_.grid), dim3(256), 0, st, (uint32_t)((n) / 4), __VA_ARGS__);     \
+        else hipLaunchKernelGGL(kern<1>, dim3(ep_.grid), dim3(256), 0, st, (long)(n), __VA_ARGS__);                         \
     } while (0)
 // the instance of a depthwise kernel template for the layer's k (3 or 5: make_dwg); the other template arguments follow
 #define WW_DW_K(k, kern, ...) ((k) == 3 ? kern<3, __VA_ARGS__> : kern<5, __VA_ARGS__>)
@@ -880,7 +895,7 @@ static int bn_finish_apply(const float *part, int chunks, const float *x, long M
                            float *ss, float *mr, hipStream_t st) {
     hipLaunchKernelGGL(k_bn_finish, dim3((C + 63) / 64), dim3(1024), 0, st, part, chunks, M, C, *bn, ss, mr);
     WW_LAUNCH_CHECK();
-    WW_LAUNCH_EW(k_bn_act_apply, vec4_ok(M * C, C, {x, y, ss}), M * C, st, x, (const float *)ss, C, act, y);
+    WW_LAUNCH_EW(k_bn_act_apply, ew_plan(M * C, vec4_ok(M * C, C, {x, y, ss})), M * C, st, x, (const float *)ss, C, act, y);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
@@ -907,14 +922,13 @@ extern "C" int ww_bn_act_fwd(ww_ctx *ctx, const float *x, long M, int C, const w
     ww_prof_scope ps_(ctx, WW_K_NHWC, st);
     float *part = (float *)scratch;
     WW_REQUIRE(C <= 1024, WW_E_UNSUPPORTED, "ww_bn_act_fwd: C=%d > 1024", C);
-    const int R = rows_r(C);
-    const int chunks = chunks_for(M, C);
+    const StatsPlan sp = stats_plan(M, C);
     if (bn->training) {
-        hipLaunchKernelGGL(k_colstats, dim3(chunks), dim3(C * R), (size_t)2 * R * C * sizeof(double), st, x, M, C, R,
-                           (M + chunks - 1) / chunks, part);
+        hipLaunchKernelGGL(k_colstats, dim3(sp.chunks), dim3(C * sp.R), (size_t)2 * sp.R * C * sizeof(double), st, x, M, C, sp.R,
+                           sp.rows_per_chunk, part);
         WW_LAUNCH_CHECK();
     }
-    return bn_finish_apply(part, chunks, x, M, C, bn, act, y, ss, mr, st);
+    return bn_finish_apply(part, sp.chunks, x, M, C, bn, act, y, ss, mr, st);
 }
 
 // training-mode BatchNorm(+activation) of x (M, C) whose statistics partials -- `chunks` rows of [sum (C) | sum of squares (C)]
@@ -922,10 +936,9 @@ extern "C" int ww_bn_act_fwd(ww_ctx *ctx, const float *x, long M, int C, const w
 int ww_bn_act_from_partials(ww_ctx *ctx, const float *x, long M, int C, const ww_bn_t *bn, int act, float *y, float *ss, float *mr,
                             const float *part, int chunks, const float *res, hipStream_t st) {
     WW_REQUIRE(C <= 1024 && chunks >= 1, WW_E_UNSUPPORTED, "ww_bn_act_from_partials: C=%d > 1024", C);
-    const BnTile t = vec4_ok(M * C, C, {x, y, part, res}) ? bn_tile(M, C, chunks) : BnTile{0, 0, 0, 0};
+    const BnTile t = fin_tile(M, C, chunks, aligned16({x, y, part, res}));
     if (t.CG4) {
-        const int blocks = (int)((M + t.rows_per_block - 1) / t.rows_per_block) * t.G_c;
-        hipLaunchKernelGGL(k_bn_act_apply_fin, dim3(blocks), dim3(256), 0, st, x, part, chunks, M, C, t, *bn, act, y, ss, mr, res);
+        hipLaunchKernelGGL(k_bn_act_apply_fin, dim3(fin_blocks(M, t)), dim3(256), 0, st, x, part, chunks, M, C, t, *bn, act, y, ss, mr, res);
         WW_LAUNCH_CHECK();
         return WW_OK;
     }
@@ -934,6 +947,14 @@ int ww_bn_act_from_partials(ww_ctx *ctx, const float *x, long M, int C, const ww
     return ww_add_f32(ctx, y, res, (size_t)(M * C), y, (ww_stream_t)st);      // tall layers: the add stays its own pass (in place)
 }
 
+// the backward apply pass finishes the partials itself (2 launches instead of 3) up to WW_BN_BWD_FUSED_MAX_KB of activation tensor:
+// MobileNetV3 B=256 step 2.414 / 2.398 / 2.393 / 2.385 / 2.388 ms at 0 / 1 / 4 / 16 / 64 MB (profiles/r03_p_*).  CG4 == 0: finish
+// launch + elementwise apply (eval mode, larger tensors, C % 4 != 0 or a pointer off the 16-byte grid)
+static BnTile bwd_fin_tile(long M, int C, int chunks, int training, bool aligned) {
+    static const long fused_max = (long)ww_env_int("WW_BN_BWD_FUSED_MAX_KB", 16384) * 1024;
+    if (training && M * C * (long)sizeof(float) <= fused_max) return fin_tile(M, C, chunks, aligned);
+    return BnTile{0, 0, 0, 0};
+}
 extern "C" int ww_bn_act_bwd(ww_ctx *ctx, const float *x, const float *da, long M, int C, const float *ss, const float *mr, int act,
                              int training, float *dx, float *dgamma, float *dbeta, void *scratch, ww_stream_t stream) {
     WW_REQUIRE(ctx && x && da && ss && mr && dx && dgamma && dbeta && scratch, WW_E_INVALID, "ww_bn_act_bwd: null argument");
@@ -942,28 +963,22 @@ extern "C" int ww_bn_act_bwd(ww_ctx *ctx, const float *x, const float *da, long 
     ww_prof_scope ps_(ctx, WW_K_NHWC, st);
     float *part = (float *)scratch, *sums = part + (size_t)NCHUNK * 2 * C;
     WW_REQUIRE(C <= 1024, WW_E_UNSUPPORTED, "ww_bn_act_bwd: C=%d > 1024", C);
-    const int R = rows_r(C);
-    const int chunks = chunks_for(M, C);
-    hipLaunchKernelGGL(k_bnact_bwd_stats, dim3(chunks), dim3(C * R), (size_t)2 * R * C * sizeof(double), st, x, da, ss, mr, M, C, R,
-                       act, (M + chunks - 1) / chunks, part);
+    const StatsPlan sp = stats_plan(M, C);
+    const int chunks = sp.chunks;
+    hipLaunchKernelGGL(k_bnact_bwd_stats, dim3(chunks), dim3(C * sp.R), (size_t)2 * sp.R * C * sizeof(double), st, x, da, ss, mr, M, C,
+                       sp.R, act, sp.rows_per_chunk, part);
     WW_LAUNCH_CHECK();
-    // the apply pass finishes the partials itself (2 launches instead of 3) up to WW_BN_BWD_FUSED_MAX_KB of activation tensor:
-    // MobileNetV3 B=256 step 2.414 / 2.398 / 2.393 / 2.385 / 2.388 ms at 0 / 1 / 4 / 16 / 64 MB (profiles/r03_p_*)
-    static const long fused_max = (long)ww_env_int("WW_BN_BWD_FUSED_MAX_KB", 16384) * 1024;
-    if (training && M * C * (long)sizeof(float) <= fused_max && vec4_ok(M * C, C, {x, da, dx, ss, mr, part})) {
-        const BnTile t = bn_tile(M, C, chunks);
-        if (t.CG4) {
-            const int blocks = (int)((M + t.rows_per_block - 1) / t.rows_per_block) * t.G_c;
-            hipLaunchKernelGGL(k_bnact_bwd_apply_fin, dim3(blocks), dim3(256), 0, st, x, da, part, chunks, M, C, t, ss, mr, act, dx,
-                               dgamma, dbeta);
-            WW_LAUNCH_CHECK();
-            return WW_OK;
-        }
+    const BnTile t = bwd_fin_tile(M, C, chunks, training, aligned16({x, da, dx, ss, mr, part}));
+    if (t.CG4) {
+        hipLaunchKernelGGL(k_bnact_bwd_apply_fin, dim3(fin_blocks(M, t)), dim3(256), 0, st, x, da, part, chunks, M, C, t, ss, mr, act, dx,
+                           dgamma, dbeta);
+        WW_LAUNCH_CHECK();
+        return WW_OK;
     }
     hipLaunchKernelGGL(k_bnact_bwd_finish, dim3((C + 63) / 64), dim3(1024), 0, st, part, chunks, C, sums, dgamma, dbeta);
     WW_LAUNCH_CHECK();
-    WW_LAUNCH_EW(k_bnact_bwd_apply, vec4_ok(M * C, C, {x, da, dx, ss, mr, sums}), M * C, st, x, da, ss, mr, (const float *)sums, M, C, act,
-                 training, dx);
+    WW_LAUNCH_EW(k_bnact_bwd_apply, ew_plan(M * C, vec4_ok(M * C, C, {x, da, dx, ss, mr, sums})), M * C, st, x, da, ss, mr,
+                 (const float *)sums, M, C, act, training, dx);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
@@ -982,6 +997,41 @@ static bool dwl_plan(const DwG &g, size_t bytes_per_img_cc4, size_t budget, DwL 
     l->nimg = nimg;
     return true;
 }
+// one depthwise launch: the LDS kernel (l, `groups` image groups, grid = groups * G_c) or the gather kernel (V, grid; the weight
+// gradient also R row lanes, `groups` pixel chunks and T taps per LDS round)
+struct DwPlan { int lds, V, grid, groups, R, T; DwL l; };
+// y = conv(x) (bwd = false) or dx = conv^T(dy) (bwd = true): the staged tensor is the kernel's input, x or dy
+static DwPlan dw_conv_plan(const DwG &g, bool bwd, bool aligned) {
+    DwPlan p = {};
+    const bool v4 = (g.C & 3) == 0 && aligned;
+    if (v4 && dwl_plan(g, (size_t)(bwd ? g.Ho * g.Wo : g.H * g.W) * 16, 40 * 1024, &p.l)) {
+        p.lds = 1; p.V = 4;
+        p.groups = (g.B + p.l.nimg - 1) / p.l.nimg;
+        p.grid = p.groups * p.l.G_c;
+    } else {
+        p.V = v4 ? 4 : 1;
+        p.grid = egrid((long)g.B * (bwd ? g.H * g.W : g.Ho * g.Wo) * (g.C / p.V));
+    }
+    return p;
+}
+static DwPlan dw_dw_plan(const DwG &g, int k, bool aligned) {
+    DwPlan p = {};
+    const bool v4 = (g.C & 3) == 0 && aligned;
+    const long P = (long)g.B * g.Ho * g.Wo;
+    if (v4 && dwl_plan(g, (size_t)(g.H * g.W + g.Ho * g.Wo) * 16, 56 * 1024, &p.l) && (g.B + p.l.nimg - 1) / p.l.nimg <= NCHUNK_DW) {
+        p.lds = 1; p.V = 4;
+        p.groups = (g.B + p.l.nimg - 1) / p.l.nimg;
+        p.grid = p.groups * p.l.G_c;
+    } else {
+        // row lanes and pixel chunks: (C/4)*R <= 512 threads and up to NCHUNK_DW chunks at V = 4; the column-reduction layout at V = 1
+        p.V = v4 ? 4 : 1;
+        p.R = v4 ? std::max(1, std::min(32, 512 / (g.C / 4))) : rows_r(g.C);
+        p.groups = v4 ? (int)std::max<long>(1, std::min<long>(NCHUNK_DW, P / (4L * p.R))) : chunks_for(P, g.C);
+        p.T = std::max(1, std::min(k * k, 12288 / (p.R * g.C)));   // taps per LDS round: <= 48 KB
+        p.grid = p.groups;
+    }
+    return p;
+}
 static int make_dwg(const char *who, int B, int H, int W, int C, int k, int s, DwG *g) {
     WW_REQUIRE(B >= 1 && H >= 1 && W >= 1 && C >= 1, WW_E_INVALID, "%s: bad shape", who);
     WW_REQUIRE((k == 3 || k == 5) && (s == 1 || s == 2), WW_E_UNSUPPORTED, "%s: kernel %d stride %d not implemented", who, k, s);
@@ -998,17 +1048,16 @@ extern "C" int ww_dwconv_nhwc_fwd(ww_ctx *ctx, const float *x, const float *w, i
     if (rc) return rc;
     ww_prof_scope ps_(ctx, WW_K_NHWC, (hipStream_t)stream);
     const size_t wbytes = (size_t)C * k * k * sizeof(float);
-    WW_REQUIRE(wbytes <= 64 * 1024, WW_E_UNSUPPORTED, "ww_dwconv_nhwc_fwd: C*k*k = %d weights do not fit the LDS cache", C * k * k);
     WW_REQUIRE((long)B * H * W * C < (1L << 31), WW_E_UNSUPPORTED, "ww_dwconv_nhwc_fwd: tensor too large for 32-bit indices");
-    const bool v4 = (C & 3) == 0 && aligned16({x, y});
-    DwL l;
-    if (v4 && dwl_plan(g, (size_t)H * W * 16, 40 * 1024, &l)) {
-        const dim3 lg((unsigned)((B + l.nimg - 1) / l.nimg) * l.G_c);
+    const DwPlan p = dw_conv_plan(g, false, aligned16({x, y}));
+    if (p.lds) {
+        const DwL &l = p.l;
         const size_t lds = ((size_t)k * k * l.CC4 + (size_t)l.nimg * H * W * l.CC4) * 16;
-        hipLaunchKernelGGL(WW_DW_K(k, k_dwl_conv, false, false), lg, dim3(256), lds, (hipStream_t)stream, x, w, g, l, y, (float *)nullptr);
+        hipLaunchKernelGGL(WW_DW_K(k, k_dwl_conv, false, false), dim3(p.grid), dim3(256), lds, (hipStream_t)stream, x, w, g, l, y, (float *)nullptr);
     } else {
-        const dim3 grid(egrid((long)B * g.Ho * g.Wo * (C / (v4 ? 4 : 1))));
-        hipLaunchKernelGGL(v4 ? WW_DW_K(k, k_dwg_fwd, 4) : WW_DW_K(k, k_dwg_fwd, 1), grid, dim3(256), wbytes, (hipStream_t)stream, x, w, g, y);
+        // (the gather kernel keeps the whole layer's weights in LDS; the LDS kernel above stages its own channel chunk's only)
+        WW_REQUIRE(wbytes <= 64 * 1024, WW_E_UNSUPPORTED, "ww_dwconv_nhwc_fwd: C*k*k = %d weights do not fit the LDS cache", C * k * k);
+        hipLaunchKernelGGL(p.V == 4 ? WW_DW_K(k, k_dwg_fwd, 4) : WW_DW_K(k, k_dwg_fwd, 1), dim3(p.grid), dim3(256), wbytes, (hipStream_t)stream, x, w, g, y);
     }
     WW_LAUNCH_CHECK();
     return WW_OK;
@@ -1022,17 +1071,16 @@ extern "C" int ww_dwconv_bn_act_fwd(ww_ctx *ctx, const float *x, const float *w,
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const long M = (long)B * g.Ho * g.Wo;
-    DwL l;
-    if (bn->training && aligned16({x, y, scratch}) && dwl_plan(g, (size_t)H * W * 16, 40 * 1024, &l)) {
+    const DwPlan p = dw_conv_plan(g, false, aligned16({x, y, scratch}));
+    if (bn->training && p.lds) {
         // the LDS kernel leaves one row of statistics partials per image group: conv + (finishing) apply = 2 launches
         ww_prof_scope ps_(ctx, WW_K_NHWC, st);
-        const int groups = (B + l.nimg - 1) / l.nimg;
-        const dim3 lg((unsigned)groups * l.G_c);
+        const DwL &l = p.l;
         const size_t lds = ((size_t)k * k * l.CC4 + (size_t)l.nimg * H * W * l.CC4 + 512) * 16;
         float *part = (float *)scratch;
-        hipLaunchKernelGGL(WW_DW_K(k, k_dwl_conv, false, true), lg, dim3(256), lds, st, x, w, g, l, y, part);
+        hipLaunchKernelGGL(WW_DW_K(k, k_dwl_conv, false, true), dim3(p.grid), dim3(256), lds, st, x, w, g, l, y, part);
         WW_LAUNCH_CHECK();
-        return ww_bn_act_from_partials(ctx, y, M, C, bn, act, a, ss, mr, part, groups, nullptr, st);
+        return ww_bn_act_from_partials(ctx, y, M, C, bn, act, a, ss, mr, part, p.groups, nullptr, st);
     }
     if ((rc = ww_dwconv_nhwc_fwd(ctx, x, w, B, H, W, C, k, stride, y, stream))) return rc;
     return ww_bn_act_fwd(ctx, y, M, C, bn, act, a, ss, mr, scratch, stream);
@@ -1047,39 +1095,32 @@ extern "C" int ww_dwconv_nhwc_bwd(ww_ctx *ctx, const float *x, const float *w, c
     ww_prof_scope ps_(ctx, WW_K_NHWC, st);
     if (dx) {
         const size_t wbytes = (size_t)C * k * k * sizeof(float);
-        WW_REQUIRE(wbytes <= 64 * 1024, WW_E_UNSUPPORTED, "ww_dwconv_nhwc_bwd: C*k*k = %d weights do not fit the LDS cache", C * k * k);
         WW_REQUIRE((long)B * H * W * C < (1L << 31), WW_E_UNSUPPORTED, "ww_dwconv_nhwc_bwd: tensor too large for 32-bit indices");
-        const bool v4 = (C & 3) == 0 && aligned16({dy, dx});
-        DwL l;
-        if (v4 && dwl_plan(g, (size_t)g.Ho * g.Wo * 16, 40 * 1024, &l)) {
-            const dim3 lg((unsigned)((B + l.nimg - 1) / l.nimg) * l.G_c);
+        const DwPlan p = dw_conv_plan(g, true, aligned16({dy, dx}));
+        if (p.lds) {
+            const DwL &l = p.l;
             const size_t lds = ((size_t)k * k * l.CC4 + (size_t)l.nimg * g.Ho * g.Wo * l.CC4) * 16;
-            hipLaunchKernelGGL(WW_DW_K(k, k_dwl_conv, true, false), lg, dim3(256), lds, st, dy, w, g, l, dx, (float *)nullptr);
+            hipLaunchKernelGGL(WW_DW_K(k, k_dwl_conv, true, false), dim3(p.grid), dim3(256), lds, st, dy, w, g, l, dx, (float *)nullptr);
         } else {
-            const dim3 grid(egrid((long)B * H * W * (C / (v4 ? 4 : 1))));
-            hipLaunchKernelGGL(v4 ? WW_DW_K(k, k_dwg_bwd_dx, 4) : WW_DW_K(k, k_dwg_bwd_dx, 1), grid, dim3(256), wbytes, st, dy, w, g, dx);
+            WW_REQUIRE(wbytes <= 64 * 1024, WW_E_UNSUPPORTED, "ww_dwconv_nhwc_bwd: C*k*k = %d weights do not fit the LDS cache", C * k * k);
+            hipLaunchKernelGGL(p.V == 4 ? WW_DW_K(k, k_dwg_bwd_dx, 4) : WW_DW_K(k, k_dwg_bwd_dx, 1), dim3(p.grid), dim3(256), wbytes, st, dy, w, g, dx);
         }
         WW_LAUNCH_CHECK();
     }
     WW_REQUIRE(C <= 1024, WW_E_UNSUPPORTED, "ww_dwconv_nhwc_bwd: C=%d > 1024", C);
     const long P = (long)B * g.Ho * g.Wo;
     float *part = (float *)scratch;
-    int chunks;
-    DwL l;
-    const bool v4 = (C & 3) == 0 && aligned16({x, dy});
-    if (v4 && dwl_plan(g, (size_t)(H * W + g.Ho * g.Wo) * 16, 56 * 1024, &l) && (B + l.nimg - 1) / l.nimg <= NCHUNK_DW) {
-        chunks = (B + l.nimg - 1) / l.nimg;
+    const DwPlan p = dw_dw_plan(g, k, aligned16({x, dy}));
+    const int chunks = p.groups;
+    if (p.lds) {
+        const DwL &l = p.l;
         const size_t lds = (size_t)l.nimg * (H * W + g.Ho * g.Wo) * l.CC4 * 16;
-        if (k == 3) hipLaunchKernelGGL(k_dwl_dw<3>, dim3((unsigned)chunks * l.G_c), dim3(256), lds, st, x, dy, g, l, part);
-        else hipLaunchKernelGGL(k_dwl_dw<5>, dim3((unsigned)chunks * l.G_c), dim3(256), lds, st, x, dy, g, l, part);
+        if (k == 3) hipLaunchKernelGGL(k_dwl_dw<3>, dim3(p.grid), dim3(256), lds, st, x, dy, g, l, part);
+        else hipLaunchKernelGGL(k_dwl_dw<5>, dim3(p.grid), dim3(256), lds, st, x, dy, g, l, part);
     } else {
-        // row lanes and pixel chunks: (C/4)*R <= 512 threads and up to NCHUNK_DW chunks at V = 4; the column-reduction layout at V = 1
-        const int V = v4 ? 4 : 1, R = v4 ? std::max(1, std::min(32, 512 / (C / 4))) : rows_r(C);
         WW_REQUIRE(P < (1L << 31) && (long)H * W * C < (1L << 31), WW_E_UNSUPPORTED, "ww_dwconv_nhwc_bwd: tensor too large for 32-bit pixel indices");
-        chunks = v4 ? (int)std::max<long>(1, std::min<long>(NCHUNK_DW, P / (4L * R))) : chunks_for(P, C);
-        const int T = std::max(1, std::min(k * k, 12288 / (R * C)));   // taps per LDS round: <= 48 KB
-        hipLaunchKernelGGL(v4 ? WW_DW_K(k, k_dwg_bwd_dw, 4) : WW_DW_K(k, k_dwg_bwd_dw, 1), dim3(chunks), dim3((C / V) * R),
-                           (size_t)T * R * C * sizeof(float), st, x, dy, g, R, (uint32_t)((P + chunks - 1) / chunks), T, part);
+        hipLaunchKernelGGL(p.V == 4 ? WW_DW_K(k, k_dwg_bwd_dw, 4) : WW_DW_K(k, k_dwg_bwd_dw, 1), dim3(chunks), dim3((C / p.V) * p.R),
+                           (size_t)p.T * p.R * C * sizeof(float), st, x, dy, g, p.R, (uint32_t)((P + chunks - 1) / chunks), p.T, part);
     }
     WW_LAUNCH_CHECK();
     if (ww_defer(ctx, part, dw, (long)C * k * k, chunks, 0)) return WW_OK;      // (the caller keeps `scratch` until the flush)
@@ -1095,11 +1136,12 @@ extern "C" int ww_pool_hw_fwd(ww_ctx *ctx, const float *x, int B, int HW, int C,
 extern "C" int ww_scale_bc_fwd(ww_ctx *ctx, const float *x, const float *gate, int B, int HW, int C, float *y, ww_stream_t stream) {
     WW_REQUIRE(ctx && x && gate && y && B >= 1 && HW >= 1 && C >= 1, WW_E_INVALID, "ww_scale_bc_fwd: bad argument");
     const long n = (long)B * HW * C;
-    if (vec4_ok(n, C, {x, gate, y}))
-        hipLaunchKernelGGL(k_scale_fwd<4>, dim3(egrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (uint32_t)(n / 4), x, gate,
+    const EwPlan p = ew_plan(n, vec4_ok(n, C, {x, gate, y}));
+    if (p.V == 4)
+        hipLaunchKernelGGL(k_scale_fwd<4>, dim3(p.grid), dim3(256), 0, (hipStream_t)stream, (uint32_t)(n / 4), x, gate,
                            (uint32_t)((long)HW * C / 4), C, y);
     else
-        hipLaunchKernelGGL(k_scale_fwd<1>, dim3(egrid(n)), dim3(256), 0, (hipStream_t)stream, n, x, gate, (long)HW * C, C, y);
+        hipLaunchKernelGGL(k_scale_fwd<1>, dim3(p.grid), dim3(256), 0, (hipStream_t)stream, n, x, gate, (long)HW * C, C, y);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
@@ -1114,11 +1156,12 @@ extern "C" int ww_scale_pool_bwd(ww_ctx *ctx, const float *dy, const float *gate
                                  float *dx, ww_stream_t stream) {
     WW_REQUIRE(ctx && dx && (dy || dpool) && (!dy || gate) && B >= 1 && HW >= 1 && C >= 1, WW_E_INVALID, "ww_scale_pool_bwd: bad argument");
     const long n = (long)B * HW * C;
-    if (vec4_ok(n, C, {dy, gate, dpool, dx}))
-        hipLaunchKernelGGL(k_scale_pool_bwd<4>, dim3(egrid(n / 4)), dim3(256), 0, (hipStream_t)stream, (uint32_t)(n / 4), dy, gate, dpool,
+    const EwPlan p = ew_plan(n, vec4_ok(n, C, {dy, gate, dpool, dx}));
+    if (p.V == 4)
+        hipLaunchKernelGGL(k_scale_pool_bwd<4>, dim3(p.grid), dim3(256), 0, (hipStream_t)stream, (uint32_t)(n / 4), dy, gate, dpool,
                            (uint32_t)((long)HW * C / 4), HW, C, dx);
     else
-        hipLaunchKernelGGL(k_scale_pool_bwd<1>, dim3(egrid(n)), dim3(256), 0, (hipStream_t)stream, n, dy, gate, dpool, (long)HW * C, HW, C, dx);
+        hipLaunchKernelGGL(k_scale_pool_bwd<1>, dim3(p.grid), dim3(256), 0, (hipStream_t)stream, n, dy, gate, dpool, (long)HW * C, HW, C, dx);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
@@ -1130,6 +1173,12 @@ static int make_stem(const char *who, int B, int H, int W, int C, StemG *g) {
     return WW_OK;
 }
 constexpr int STEM_BLOCKS = 512;        // persistent grid = rows of BatchNorm / weight-gradient partials
+struct StemPlan { int blocks, L; };     // workgroups of the persistent grid, pixel lanes per workgroup
+static StemPlan stem_plan(const StemG &g) {
+    const long P = (long)g.B * g.Ho * g.Wo;
+    const int L = 256 / (g.C / 4);
+    return {(int)std::max<long>(1, std::min<long>(STEM_BLOCKS, (P + L - 1) / L)), L};
+}
 // Conv2d(1, C, 3, stride 2, padding 1, bias=False) on (B,H,W) one-channel images + training-mode BatchNorm + activation: the direct
 // convolution leaves the statistics partials, ww_bn_act_from_partials finishes and applies them.  scratch: ww_nhwc_scratch_bytes(C).
 extern "C" int ww_stem3x3s2_bn_act_fwd(ww_ctx *ctx, const float *x, const float *w, int B, int H, int W, int C, const ww_bn_t *bn,
@@ -1143,7 +1192,7 @@ extern "C" int ww_stem3x3s2_bn_act_fwd(ww_ctx *ctx, const float *x, const float 
     hipStream_t st = (hipStream_t)stream;
     ww_prof_scope ps_(ctx, WW_K_NHWC, st);
     const long P = (long)B * g.Ho * g.Wo;
-    const int L = 256 / (C / 4), blocks = (int)std::max<long>(1, std::min<long>(STEM_BLOCKS, (P + L - 1) / L));
+    const int blocks = stem_plan(g).blocks;
     hipLaunchKernelGGL(k_stem3x3s2_fwd, dim3(blocks), dim3(256), 0, st, x, w, g, y, (float *)scratch);
     WW_LAUNCH_CHECK();
     return ww_bn_act_from_partials(ctx, y, P, C, bn, act, a, ss, mr, (const float *)scratch, blocks, nullptr, st);
@@ -1158,8 +1207,7 @@ extern "C" int ww_stem3x3s2_bwd_dw(ww_ctx *ctx, const float *x, const float *dy,
     WW_REQUIRE(aligned16({dy}), WW_E_INVALID, "ww_stem3x3s2_bwd_dw: dy must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     ww_prof_scope ps_(ctx, WW_K_NHWC, st);
-    const long P = (long)B * g.Ho * g.Wo;
-    const int L = 256 / (C / 4), blocks = (int)std::max<long>(1, std::min<long>(STEM_BLOCKS, (P + L - 1) / L));
+    const int blocks = stem_plan(g).blocks;
     hipLaunchKernelGGL(k_stem3x3s2_dw, dim3(blocks), dim3(256), 0, st, x, dy, g, (float *)scratch);
     WW_LAUNCH_CHECK();
     if (ww_defer(ctx, (const float *)scratch, dw, (long)C * 9, blocks, 0)) return WW_OK;
@@ -1168,14 +1216,67 @@ extern "C" int ww_stem3x3s2_bwd_dw(ww_ctx *ctx, const float *x, const float *dy,
 extern "C" int ww_im2col3x3s2(ww_ctx *ctx, const float *x, int B, int H, int W, float *cols, ww_stream_t stream) {
     WW_REQUIRE(ctx && x && cols && B >= 1 && H >= 1 && W >= 1, WW_E_INVALID, "ww_im2col3x3s2: bad argument");
     const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
-    hipLaunchKernelGGL(k_im2col3x3s2, dim3(egrid((long)B * Ho * Wo * 9)), dim3(256), 0, (hipStream_t)stream, x, B, H, W, Ho, Wo, cols);
+    hipLaunchKernelGGL(k_im2col3x3s2, dim3(ew_plan((long)B * Ho * Wo * 9, false).grid), dim3(256), 0, (hipStream_t)stream, x, B, H, W, Ho, Wo, cols);
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
 extern "C" int ww_add_f32(ww_ctx *ctx, const float *a, const float *b, size_t n, float *y, ww_stream_t stream) {
     WW_REQUIRE(ctx && a && b && y, WW_E_INVALID, "ww_add_f32: null argument");
     if (n == 0) return WW_OK;
-    WW_LAUNCH_EW(k_add, vec4_ok((long)n, 4, {a, b, y}), (long)n, (hipStream_t)stream, a, b, y);
+    WW_LAUNCH_EW(k_add, ew_plan((long)n, vec4_ok((long)n, 4, {a, b, y})), (long)n, (hipStream_t)stream, a, b, y);
     WW_LAUNCH_CHECK();
+    return WW_OK;
+}
+
+// ---- host-only plan queries: which kernel form and grid an entry point would launch for a shape, from the same helpers the
+// entry points call.  Nothing is allocated or launched (no device is needed).  `aligned`: every base pointer of the call sits on
+// the 16-byte grid.
+// depthwise: which = 0 ww_dwconv_nhwc_fwd (and, in training mode, ww_dwconv_bn_act_fwd: it takes the statistics in the conv
+// kernel exactly when this plan is the LDS one, with out[6] rows of partials), 1 the dx launch of ww_dwconv_nhwc_bwd, 2 its dw launch.
+// out[8] = {LDS kernel (1) / gather (0), V, workgroups, nimg, G_c, CC4, image groups (dw gather: pixel chunks), R (dw gather)}
+extern "C" int ww_nhwc_plan_dw(int which, int B, int H, int W, int C, int k, int stride, int aligned, int *out) {
+    WW_REQUIRE(out && which >= 0 && which <= 2, WW_E_INVALID, "ww_nhwc_plan_dw: bad argument");
+    DwG g;
+    int rc = make_dwg("ww_nhwc_plan_dw", B, H, W, C, k, stride, &g);
+    if (rc) return rc;
+    const DwPlan p = which == 2 ? dw_dw_plan(g, k, aligned != 0) : dw_conv_plan(g, which == 1, aligned != 0);
+    const int o[8] = {p.lds, p.V, p.grid, p.lds ? p.l.nimg : 0, p.lds ? p.l.G_c : 0, p.lds ? p.l.CC4 : 0, p.groups, p.R};
+    std::copy(o, o + 8, out);
+    return WW_OK;
+}
+// BatchNorm: which = 0 ww_bn_act_fwd, 1 ww_bn_act_bwd, 2 ww_bn_act_from_partials over `chunks` rows of producer partials (the
+// second half of ww_conv1x1_bn_act_fwd, ww_dwconv_bn_act_fwd and ww_stem3x3s2_bn_act_fwd; `aligned` covers the residual too).
+// out[10] = {chunks, rows per chunk, R of the statistics launch (0 for which = 2), apply pass finishes the partials itself (1) /
+// finish launch + elementwise apply (0), CG4, G_c, R, rows per workgroup of the finishing pass (0 when not taken), workgroups and
+// V of the apply launch}
+extern "C" int ww_nhwc_plan_bn(int which, long M, int C, int chunks, int training, int aligned, int *out) {
+    WW_REQUIRE(out && which >= 0 && which <= 2 && M >= 1 && C >= 1 && C <= 1024, WW_E_INVALID, "ww_nhwc_plan_bn: bad argument");
+    WW_REQUIRE(which != 2 || chunks >= 1, WW_E_INVALID, "ww_nhwc_plan_bn: chunks");
+    StatsPlan sp = {chunks, 0, 0};
+    if (which != 2) sp = stats_plan(M, C);
+    BnTile t = {0, 0, 0, 0};
+    if (which == 1) t = bwd_fin_tile(M, C, sp.chunks, training, aligned != 0);
+    if (which == 2) t = fin_tile(M, C, sp.chunks, aligned != 0);
+    const EwPlan e = ew_plan(M * C, vec4_ok(M * C, C, aligned != 0));
+    const int o[10] = {sp.chunks, (int)sp.rows_per_chunk, sp.R, t.CG4 != 0, t.CG4, t.G_c, t.R, (int)t.rows_per_block,
+                       t.CG4 ? fin_blocks(M, t) : e.grid, t.CG4 ? 4 : e.V};
+    std::copy(o, o + 10, out);
+    return WW_OK;
+}
+// the stem's persistent grid: out[2] = {workgroups, pixel lanes L per workgroup}
+extern "C" int ww_nhwc_plan_stem(int B, int H, int W, int C, int *out) {
+    WW_REQUIRE(out, WW_E_INVALID, "ww_nhwc_plan_stem: null argument");
+    StemG g;
+    int rc = make_stem("ww_nhwc_plan_stem", B, H, W, C, &g);
+    if (rc) return rc;
+    const StemPlan p = stem_plan(g);
+    out[0] = p.blocks; out[1] = p.L;
+    return WW_OK;
+}
+// an elementwise pass over n floats of a (..., C) tensor (ww_add_f32: C = 4): out[2] = {workgroups of 256 threads, V}
+extern "C" int ww_nhwc_plan_ew(long n, int C, int aligned, int *out) {
+    WW_REQUIRE(out && n >= 1 && C >= 1, WW_E_INVALID, "ww_nhwc_plan_ew: bad argument");
+    const EwPlan p = ew_plan(n, vec4_ok(n, C, aligned != 0));
+    out[0] = p.grid; out[1] = p.V;
     return WW_OK;
 }

@@ -446,3 +446,14 @@ extern "C" int ww_se_bwd(ww_ctx *ctx, const float *x, const float *dy, const flo
     WW_LAUNCH_CHECK();
     return WW_OK;
 }
+
+// host-only: what ww_se_fwd / ww_se_bwd launch for a shape (by se_img, as they do): out[2] = {images per workgroup, workgroups};
+// nothing is allocated or launched
+extern "C" int ww_se_plan(int B, int HW, int C, int Cs, int *out) {
+    WW_REQUIRE(out, WW_E_INVALID, "ww_se_plan: null argument");
+    int rc = se_check("ww_se_plan", B, HW, C, Cs);
+    if (rc) return rc;
+    const int img = se_img(B, C, Cs);
+    out[0] = img; out[1] = (B + img - 1) / img;
+    return WW_OK;
+}
