@@ -31,11 +31,9 @@
 extern "C" {
 #endif
 
-/* 16 still: ww_loader_indices / ww_loader_batch (the loader section below) are purely additive -- no existing signature,
- * struct or constant changed, so a binding built against 16 keeps working.
- * 16 still: the weighted loss entry and its WW_REDUCE_* / WW_DIV_* constants (the loss section below) are purely additive
- * too; the unweighted loss entry keeps its signature and its results. */
-#define WW_ABI_VERSION 16
+/* 17: ww_pass_plan / ww_loader_plan (host-only pass plans of the capped-grid support launches) were added; no existing
+ * signature, struct, constant or result changed. */
+#define WW_ABI_VERSION 17
 
 #define WW_OK 0
 #define WW_E_INVALID (-1)     /* bad argument (shape, null pointer, unsupported size) */
@@ -482,6 +480,25 @@ int ww_nhwc_plan_stem(int B, int H, int W, int C, int *out);
 int ww_nhwc_plan_ew(long n, int C, int aligned, int *out);
 int ww_se_plan(int B, int HW, int C, int Cs, int *out);      /* ww_se_fwd / _bwd: out[2] = {images per workgroup, workgroups} */
 int ww_conv1x1_row_tile(int mode, int M, int K, int N);      /* rows per statistics partial of ww_conv1x1_bn_act_fwd; 0: bad argument */
+/* Host-only pass plans of the support launches whose grid is capped on the host and whose kernel walks its n items in passes of
+ * that grid (`for (i = ...; i < n; i += one pass)`), computed by the function the launch site takes its grid from; no context,
+ * no device.  ww_pass_plan: out[2] = {workgroups of 256 threads, items one pass holds}; the launch makes ceil(n / out[1]) passes.
+ *   WW_PASS_EW           the element-wise launches of the Conv1d / Conv2d families: ww_add_relu_fwd and ww_relu_mask_bwd (n
+ *                        floats), the masked gradient of ww_tconv1d_bwd (n = B T Cout / 4 float4s), ww_maxpool3x3s2_fwd / _bwd
+ *                        (n = B Ho Wo C / 4 resp. B H W C / 4 channel quads), the weight packing and the sum of dW partials
+ *   WW_PASS_DROPOUT_BT   ww_dropout_bt: n = B T ceil(C / 4) channel quads
+ *   WW_PASS_WAVE_WINDOWS ww_wave_windows: n = W windows, one workgroup each
+ *   WW_PASS_TO16_PAIR    the 16-bit copies of x and W_ih in front of ww_gru_fwd's input projection (16-bit modes, I % 64 == 0):
+ *                        n = (B T I + 384 I) / 4 float4s, four per thread and pass
+ * ww_loader_plan: ww_loader_batch launches out[0] = S workgroups per row of out[1] = `passes` x 256 chunks of 8 samples; workgroup
+ * s of a row takes passes s, s + S, ...: ceil(passes / S) trips, one fewer for the workgroups from passes % S on when S does not
+ * divide passes.                                                                                                              */
+#define WW_PASS_EW 0
+#define WW_PASS_DROPOUT_BT 1
+#define WW_PASS_WAVE_WINDOWS 2
+#define WW_PASS_TO16_PAIR 3
+int ww_pass_plan(int launch, long n, long *out);
+int ww_loader_plan(int B, int n_out, int *out);
 
 /* ------------------------------------------------------------------ conv front-end of the CRNN
  * cnn_small's conv stack (stem + 4 depthwise-separable blocks) without GAP / classifier, followed by the mean over the

@@ -147,10 +147,10 @@ def test_values_per_thread_follow_the_kernel_geometry():
     assert K.values_per_thread("pw", (2, 20, 76), 1) == 48 * 16 + 2 and K.values_per_thread("pw", (2, 20, 76), 0) == 18
 
 
-def test_header_declares_the_grid_cap_under_abi_16():
+def test_header_declares_the_grid_cap_and_the_abi_version():
     from wakeword_trainer_home_amd import _native as nat
     header = (REPO / "include" / "wwhip.h").read_text()
-    assert nat.ABI_VERSION == 16 and re.search(r"#define WW_ABI_VERSION 16\b", header)
+    assert nat.ABI_VERSION == 17 and re.search(r"#define WW_ABI_VERSION 17\b", header)
     assert re.search(r"\bint ww_ctx_set_grid_cap\(ww_ctx \*ctx, int n\);", header)
     assert re.search(r"\bint ww_conv_stem_bwd_recompute\(", header)
     for name in ("ww_ctx_set_grid_cap", "ww_conv_stem_bwd_recompute"):

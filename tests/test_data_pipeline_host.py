@@ -169,7 +169,7 @@ def test_error_messages_and_conventions():
     from wakeword_trainer_home_amd import _native as nat
     from wakeword_trainer_home_amd.data import DeviceClipBank, ShardedEpochSampler, sampler_weights
     from wakeword_trainer_home_amd.data.loader import cumulative_table
-    assert nat.ABI_VERSION == 16
+    assert nat.ABI_VERSION == 17
     assert "ww_loader_batch" in nat.EXPORTS and "ww_loader_indices" in nat.EXPORTS
     for call in (lambda: sampler_weights([0, 1], None, "uniform"), lambda: ShardedEpochSampler(4, strategy="uniform")):
         with pytest.raises(ValueError) as e:

@@ -130,7 +130,7 @@ def test_evaluation_result_and_native_layout():
     assert [f.name for f in dataclasses.fields(EvaluationResult)] == ["filename", "prediction", "confidence", "latency_ms",
                                                                       "logits"]
     assert _native.EVAL_COUNTERS[:7] == ("tp", "tn", "fp", "fn", "count", "bad_target", "nan_score")
-    assert len(_native.EVAL_COUNTERS) == 8 and _native.ABI_VERSION == 16
+    assert len(_native.EVAL_COUNTERS) == 8 and _native.ABI_VERSION == 17
     assert (_native.SCORE_LOGITS, _native.SCORE_CONF, _native.EVAL_MAX_THRESHOLDS) == (0, 1, 1024)
     lib = ctypes.CDLL(str(_native.lib_path()))
     assert all(hasattr(lib, n) for n in ("ww_eval_accumulate", "ww_wave_windows", "ww_wave_num_windows"))

@@ -57,7 +57,7 @@ def test_header_library_and_binding_carry_the_storage_entry_points():
     lib = nat.load()
     for name in ST_NAMES:
         assert name in declared and name in nat.EXPORTS and hasattr(lib, name), name
-    assert nat.ABI_VERSION == 16 and re.search(r"#define WW_ABI_VERSION 16\b", header) and lib.ww_abi_version() == 16
+    assert nat.ABI_VERSION == 17 and re.search(r"#define WW_ABI_VERSION 17\b", header) and lib.ww_abi_version() == 17
     # the scratch size is host arithmetic: packed 16-bit weights + fp32 partials; 0 for the shapes the kernels refuse
     assert lib.ww_conv2d_st_scratch_bytes(2, 5, 7, 8, 16, 3, 2) >= 9 * 8 * 16 * (2 + 4)
     for bad in ((2, 5, 7, 4, 16, 3, 1), (2, 5, 7, 8, 12, 3, 1), (2, 5, 7, 8, 16, 2, 1), (2, 5, 7, 8, 16, 3, 3), (0, 5, 7, 8, 16, 3, 1)):

@@ -224,7 +224,7 @@ def test_library_exports_the_tsm_entry_points():
     lib = ctypes.CDLL(str(nat.lib_path()))
     assert all(n in nat.EXPORTS and hasattr(lib, n) for n in names)
     lib = nat.load()
-    assert lib.ww_abi_version() == 16 == nat.ABI_VERSION
+    assert lib.ww_abi_version() == 17 == nat.ABI_VERSION
     assert ctypes.sizeof(nat.AudioTsmCfg) == 24
     for N in (1, 300, 700, 2048, 5000, 24000, 40000):         # host-only sizes follow the restatement
         for smax in (-12, -3, 0, 2, 7, 12):

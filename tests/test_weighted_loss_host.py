@@ -134,8 +134,8 @@ def test_weighted_entry_is_declared_bound_and_exported():
     assert name in set(re.findall(r"\b(ww_[a-z0-9_]+)\s*\(", header))
     assert name in nat.EXPORTS and "ww_ce2_loss_fwd_bwd" in nat.EXPORTS
     assert hasattr(ctypes.CDLL(str(nat.lib_path())), name)
-    assert nat.ABI_VERSION == 16 and nat.load().ww_abi_version() == 16
-    assert re.search(r"#define WW_ABI_VERSION 16\b", header)
+    assert nat.ABI_VERSION == 17 and nat.load().ww_abi_version() == 17
+    assert re.search(r"#define WW_ABI_VERSION 17\b", header)
     for macro, value in (("WW_REDUCE_MEAN", 0), ("WW_REDUCE_SUM", 1), ("WW_REDUCE_NONE", 2), ("WW_DIV_BATCH", 0), ("WW_DIV_WEIGHT_SUM", 1)):
         assert re.search(rf"#define {macro} {value}\b", header), macro
     assert len(nat._SIGS[name][1]) == len(nat._SIGS["ww_ce2_loss_fwd_bwd"][1]) + 4

@@ -15,7 +15,7 @@ _LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libwwhip.so"
 _lib = None
 _ctx = {}
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 BWD_ALL, BWD_LATE, BWD_EARLY = 0, 1, 2
 ACT_F32, ACT_BF16, ACT_F16 = 0, 1, 2
 LOSS_CE, LOSS_FOCAL = 0, 1
@@ -196,6 +196,8 @@ _SIGS = {
     "ww_nhwc_plan_ew": (C.c_int, [C.c_long, _i, _i, C.POINTER(C.c_int)]),
     "ww_conv1x1_row_tile": (C.c_int, [_i] * 4),
     "ww_se_plan": (C.c_int, [_i] * 4 + [C.POINTER(C.c_int)]),
+    "ww_pass_plan": (C.c_int, [_i, C.c_long, C.POINTER(C.c_long)]),
+    "ww_loader_plan": (C.c_int, [_i, _i, C.POINTER(C.c_int)]),
     "ww_gru_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ww_gru_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_long, _vp, _vp, _sz, _vp]),
     "ww_gru_bidir_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _i, _i, _i, _i, _vp, C.c_long, _sz, _vp]),
@@ -1306,6 +1308,25 @@ def plan_ew(n, Cn, aligned=True):
 
 def plan_se(B, HW, Cn, Cs):
     return _plan("ww_se_plan", ("img", "grid"), B, HW, Cn, Cs)
+
+
+PASS_LAUNCHES = ("ew", "dropout_bt", "wave_windows", "to16_pair")      # WW_PASS_* of include/wwhip.h, in order
+
+
+def plan_passes(launch, n):
+    """The pass plan of a capped-grid support launch over n items (ww_pass_plan; `launch` one of PASS_LAUNCHES) ->
+    {grid, per_pass, passes}: workgroups, items one pass of the grid holds, passes the kernel's loop makes."""
+    out = (C.c_long * 2)()
+    _check(load().ww_pass_plan(PASS_LAUNCHES.index(launch), int(n), out), "ww_pass_plan")
+    return {"grid": out[0], "per_pass": out[1], "passes": -(-int(n) // out[1])}
+
+
+def plan_loader(B, n_out):
+    """ww_loader_batch's split of a row (ww_loader_plan) -> {S, passes, trips}: workgroups per row, passes of 256 chunks in
+    a row, and the trips of workgroup s = 0 .. S-1 of a row."""
+    p = _plan("ww_loader_plan", ("S", "passes"), int(B), int(n_out))
+    p["trips"] = tuple(len(range(s, p["passes"], p["S"])) for s in range(p["S"]))
+    return p
 
 
 def conv1x1_row_tile(M, K, N, mode=torch.float32):

@@ -31,6 +31,29 @@ extern "C" void ww_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], u
     ww_philox(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1], out);
 }
 
+// host-only: the pass plan a capped-grid support launch takes for n items, from the function its launch site calls
+extern "C" int ww_pass_plan(int launch, long n, long *out) {
+    WW_REQUIRE(out && n >= 1, WW_E_INVALID, "ww_pass_plan: bad argument");
+    ww_pass p;
+    switch (launch) {
+    case WW_PASS_EW: p = ww_pass_ew(n); break;
+    case WW_PASS_DROPOUT_BT: p = ww_pass_dropout_bt(n); break;
+    case WW_PASS_WAVE_WINDOWS: p = ww_pass_wave_windows(n); break;
+    case WW_PASS_TO16_PAIR: p = ww_pass_to16_pair(n); break;
+    default: WW_REQUIRE(false, WW_E_INVALID, "ww_pass_plan: unknown launch %d", launch);
+    }
+    out[0] = p.grid;
+    out[1] = p.per_pass;
+    return WW_OK;
+}
+extern "C" int ww_loader_plan(int B, int n_out, int *out) {
+    WW_REQUIRE(out && B >= 1 && n_out >= 1, WW_E_INVALID, "ww_loader_plan: bad argument");
+    const ww_loader_split s = ww_loader_plan_rows(B, n_out);
+    out[0] = s.S;
+    out[1] = s.passes;
+    return WW_OK;
+}
+
 extern "C" int ww_feat_num_frames(int n_samples, int hop) {
     if (hop <= 0 || n_samples < 0) return WW_E_INVALID;
     return 1 + n_samples / hop;

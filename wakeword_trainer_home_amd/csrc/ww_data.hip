@@ -208,11 +208,8 @@ extern "C" int ww_loader_batch(ww_ctx *ctx, const int16_t *bank, const int32_t *
     ww_draw d;
     const int rc = fill_draw("ww_loader_batch", d, n_clips, strategy, shuffle, cdf, n_cdf, seed, epoch, rank, world, k0, B);
     if (rc != WW_OK) return rc;
-    // enough workgroups to fill the device at small B, never more than the row has passes of 256 chunks
-    const int passes = (n_out / 8 + LD_BLOCK - 1) / LD_BLOCK;
-    int S = (2048 + B - 1) / B;
-    S = S < passes ? S : passes;
-    S = S < 1 ? 1 : S;
+    static_assert(LD_BLOCK == 256, "ww_loader_plan_rows counts passes of 256 chunks");
+    const int S = ww_loader_plan_rows(B, n_out).S;
     WW_REQUIRE((long long)B * S < (1ll << 31), WW_E_INVALID, "ww_loader_batch: B=%d is too large", B);
     hipLaunchKernelGGL(k_loader_batch, dim3((unsigned)(B * S)), dim3(LD_BLOCK), 0, (hipStream_t)stream, bank, length, label,
                        (long long)L, (long long)n_clips * L, d, training != 0, n_out, S, out, targets, clip_index);

@@ -161,7 +161,7 @@ extern "C" int ww_wave_windows(ww_ctx *ctx, const float *wave, long S, int chunk
                "ww_wave_windows: W=%d but %ld samples hold %ld windows of %d", W, S, ww_wave_num_windows(S, chunk), chunk);
     if (W == 0) return WW_OK;
     WW_REQUIRE(wave && out && peaks, WW_E_INVALID, "ww_wave_windows: null argument");
-    const int grid = W < 4096 ? W : 4096;
+    const int grid = ww_pass_wave_windows(W).grid;
     hipLaunchKernelGGL(k_wave_windows, dim3(grid), dim3(WIN_BLOCK), 0, (hipStream_t)stream, wave, chunk, chunk / 2, W, out,
                        peaks);
     WW_LAUNCH_CHECK();

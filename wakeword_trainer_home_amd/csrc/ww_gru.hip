@@ -426,8 +426,7 @@ extern "C" int ww_dropout_bt(ww_ctx *ctx, const float *x, long ldx, int B, int T
     WW_REQUIRE(T <= 4096 && C <= 1024 && stream_id >= 0 && stream_id < 16, WW_E_UNSUPPORTED,
                "ww_dropout_bt: T <= 4096, C <= 1024, stream_id < 16");
     WW_REQUIRE(p >= 0.f && p < 1.f, WW_E_INVALID, "ww_dropout_bt: p=%f not in [0,1)", (double)p);
-    const long n = (long)B * T * ((C + 3) / 4);
-    const int grid = (int)std::min<long>((n + 255) / 256, 256 * 16);
+    const int grid = ww_pass_dropout_bt((long)B * T * ((C + 3) / 4)).grid;
     hipLaunchKernelGGL(k_dropout_bt, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, ldx, B, T, C,
                        (float)(1.0 / (1.0 - (double)p)), ww_prob_threshold((double)p), (uint32_t)seed, (uint32_t)(seed >> 32),
                        (uint32_t)step, (uint32_t)(step >> 32), sample_offset, (uint32_t)stream_id, out, ldo, ctx->step_ctl);

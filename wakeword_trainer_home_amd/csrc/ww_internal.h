@@ -153,6 +153,35 @@ static inline int ww_capped_grid(const ww_ctx *ctx, int grid) {
 static inline int ww_conv_grid(const ww_ctx *ctx, const void *fn, int block, size_t smem, long want, int cap) {
     return ww_capped_grid(ctx, ww_occupancy_grid(fn, block, smem, want, cap));
 }
+// ---- pass plans of the support kernels whose grid is capped on the host and whose body is `for (i = ...; i < n; i += one
+// pass)`: the workgroups of a launch over n items and the items one pass of that grid holds.  The launch sites take their grid
+// from these and ww_pass_plan / ww_loader_plan (wwhip.h) report them, so a test that claims a second pass asks the code that
+// launches.
+struct ww_pass { int grid; long per_pass; };
+static inline ww_pass ww_pass_capped(long n, int per_wg, int cap) {
+    long g = (n + per_wg - 1) / per_wg;
+    g = g > cap ? cap : g;
+    g = g < 1 ? 1 : g;
+    return ww_pass{(int)g, g * per_wg};
+}
+// the 256-thread element-wise launches (ew_grid of ww_tap_gemm.h): n items as the kernel counts them (floats, float4s, quads)
+static inline ww_pass ww_pass_ew(long n) { return ww_pass_capped(n, 256, 4096); }
+// k_dropout_bt: n = B * T * ceil(C / 4) channel quads
+static inline ww_pass ww_pass_dropout_bt(long quads) { return ww_pass_capped(quads, 256, 256 * 16); }
+// k_wave_windows: one workgroup per window
+static inline ww_pass ww_pass_wave_windows(long W) { return ww_pass_capped(W, 1, 4096); }
+// k_to16_pair: n4 float4s of x and W_ih together, four per thread and trip
+static inline ww_pass ww_pass_to16_pair(long n4) { return ww_pass_capped(n4, 4 * 256, 4096); }
+// k_loader_batch: S workgroups per row of `passes` x 256 chunks of 8 samples -- enough workgroups to fill the device at small
+// B, never more than the row has passes; a thread makes ceil(passes / S) trips (the last ones of a row may be short)
+struct ww_loader_split { int S, passes; };
+static inline ww_loader_split ww_loader_plan_rows(int B, int n_out) {
+    const int passes = (n_out / 8 + 255) / 256;
+    int S = (2048 + B - 1) / B;
+    S = S < passes ? S : passes;
+    S = S < 1 ? 1 : S;
+    return ww_loader_split{S, passes};
+}
 // integer environment knob (tuning / A-B experiments); call sites cache the result in a function-local static
 static inline int ww_env_int(const char *name, int dflt) {
     const char *e = getenv(name);

@@ -141,7 +141,7 @@ int rnn_project(ww_ctx *ctx, int mode, const float *x, long ldx, const RnnFwdHos
             const bool have_x = xh_shared && *xh_shared;
             const long rows = have_x ? 0 : Mrows;                          // rows of x this launch still has to convert
             const long n4 = rows * (I / 4) + (long)G * I / 4;
-            const int grid = (int)std::min<long>((n4 + 4 * 256 - 1) / (4 * 256), 4096);
+            const int grid = ww_pass_to16_pair(n4).grid;
             if (mode == WW_ACT_BF16)
                 hipLaunchKernelGGL(k_to16_pair<ww_bf16>, dim3(grid), dim3(256), 0, st, x, ldx, rows, I, d.w_ih, (long)G * I, (ww_bf16 *)xh, (ww_bf16 *)wh);
             else

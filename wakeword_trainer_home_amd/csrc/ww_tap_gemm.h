@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void k_tap_sum(const float *__restrict__ part,
 }
 
 // ---- host side
-int ew_grid(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 4096)); }
+int ew_grid(long n) { return ww_pass_ew(n).grid; }      // (ww_internal.h: what ww_pass_plan reports)
 bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 // f(std::integral_constant<int, MODE>) for the MODE template parameter of a matrix mode
 template <class F>
