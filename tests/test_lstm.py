@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.lstm_cases import _BOUND, _inputs, lstm_restated
+
 gpu = pytest.mark.gpu
 DEV = "cuda:0"
 H = 128
@@ -121,52 +123,6 @@ def test_factory_still_refuses_lstm():
 
 
 # ------------------------------------------------------------------------------------------ restatements
-def lstm_restated(x, w_ih, w_hh, b_ih, b_hh, h0=None, c0=None, dy=None, dh_n=None, dc_n=None, mtype=None, reverse=False):
-    """One direction of the device's LSTM in float64, rounding exactly what the kernels round to the matrix type (mtype None:
-    the exact LSTM): forward -- x and W_ih (projection operands), each step's h_{t-1} and W_hh; backward -- dG (it leaves
-    k_lstm_bwd in the matrix type and feeds the per-step dG W_hh), W_hh, and the other operand of the dW / dX products
-    (h_{t-1}, x, W_ih).  Bias gradients are sums of the unrounded dG; c, dc and the gates stay wide."""
-    from oracle.rounding import mround
-    f64 = lambda t: None if t is None else torch.as_tensor(t).detach().double().cpu()
-    x, w_ih, w_hh, b_ih, b_hh, h0, c0, dy, dh_n, dc_n = map(f64, (x, w_ih, w_hh, b_ih, b_hh, h0, c0, dy, dh_n, dc_n))
-    B, T, I = x.shape
-    rw_ih, rw_hh = mround(w_ih, mtype), mround(w_hh, mtype)
-    gi = mround(x, mtype) @ rw_ih.t() + b_ih
-    h = torch.zeros(B, H, dtype=torch.float64) if h0 is None else h0
-    c = torch.zeros(B, H, dtype=torch.float64) if c0 is None else c0
-    order = list(range(T - 1, -1, -1) if reverse else range(T))
-    y = torch.empty(B, T, H, dtype=torch.float64)
-    sv = {}
-    for t in order:
-        G = gi[:, t] + mround(h, mtype) @ rw_hh.t() + b_hh
-        i, f, g, o = torch.sigmoid(G[:, :H]), torch.sigmoid(G[:, H:2 * H]), torch.tanh(G[:, 2 * H:3 * H]), torch.sigmoid(G[:, 3 * H:])
-        cn = f * c + i * g
-        sv[t] = (i, f, g, o, torch.tanh(cn), c, h)
-        c, h = cn, o * torch.tanh(cn)
-        y[:, t] = h
-    out = {"y": y, "h_n": h, "c_n": c}
-    if dy is None and dh_n is None and dc_n is None:
-        return out
-    dh = torch.zeros(B, H, dtype=torch.float64) if dh_n is None else dh_n.clone()
-    dc = torch.zeros(B, H, dtype=torch.float64) if dc_n is None else dc_n.clone()
-    dG = torch.empty(B, T, 4 * H, dtype=torch.float64)
-    hp_all = torch.empty(B, T, H, dtype=torch.float64)
-    for t in reversed(order):
-        i, f, g, o, tc, cp, hp = sv[t]
-        if dy is not None:
-            dh = dh + dy[:, t]
-        dc = dc + dh * o * (1.0 - tc * tc)
-        dG[:, t] = torch.cat([dc * g * i * (1 - i), dc * cp * f * (1 - f), dc * i * (1 - g * g), dh * tc * o * (1 - o)], 1)
-        hp_all[:, t] = hp
-        dc = dc * f
-        dh = mround(dG[:, t], mtype) @ rw_hh
-    rg = mround(dG.reshape(B * T, 4 * H), mtype)
-    db = dG.sum((0, 1))
-    out.update(dh0=dh, dc0=dc, db_ih=db, db_hh=db, dw_hh=rg.t() @ mround(hp_all.reshape(B * T, H), mtype),
-               dw_ih=rg.t() @ mround(x.reshape(B * T, I), mtype), dx=(rg @ rw_ih).reshape(B, T, I))
-    return out
-
-
 class LSTMOracle(torch.nn.Module):
     """The reference model in float64 with single-layer nn.LSTM modules and the build's Philox masks between layers (stream
     1 + k) and in front of fc (stream 15)."""
@@ -222,18 +178,6 @@ def lstm_rows(request, monkeypatch):
     """Both workgroup shapes of the recurrent kernels (8 or 16 batch rows per workgroup; the library picks by batch size)."""
     monkeypatch.setenv("WW_LSTM_ROWS", str(request.param))
     return request.param
-
-
-def _inputs(B, T, I, seed, nd):
-    """fp32-representable float64 inputs: nn.LSTM's initialisation, x ~ N(0,1), h0 / c0 ~ 0.3 N(0,1), dy / dh_n / dc_n ~ N(0,1)."""
-    g = torch.Generator().manual_seed(seed)
-    k = H ** -0.5
-    q = lambda t: t.float().double()
-    r = lambda *s: q(torch.randn(*s, generator=g, dtype=torch.float64))
-    P = [[q((torch.rand(*s, generator=g, dtype=torch.float64) * 2 - 1) * k) for s in ((4 * H, I), (4 * H, H), (4 * H,), (4 * H,))]
-         for _ in range(nd)]
-    return dict(P=P, x=r(B, T, I), h0=[0.3 * r(B, H) for _ in range(nd)], c0=[0.3 * r(B, H) for _ in range(nd)],
-                dy=r(B, T, nd * H), dhn=[r(B, H) for _ in range(nd)], dcn=[r(B, H) for _ in range(nd)])
 
 
 # (B, T, I, reverse, with h0 / c0, with dc_n): every B in {1, 7, 16, 40, 512}, T in {1, 31, 76}, I in {40, 64, 256}
@@ -344,10 +288,6 @@ def test_bidirectional_layer_in_one_launch_equals_two_launches(B, T, I, mode, ls
     assert ddx <= 2e-6
 
 
-# Bounds of the restated comparisons: (y | h_n | c_n absolute, dh0 | dc0 absolute, gradients relative to their largest entry),
-# 10x the largest error measured on the MI355X over both workgroup shapes and every case of a mode (printed with -rP):
-# fp32 4.7e-7, 6.8e-7, 2.1e-6; bf16 1.2e-4, 3.5e-4, 8.0e-4; fp16 2.1e-5, 6.0e-5, 1.6e-4 (profiles/r04_lstm_parity_measured.txt)
-_BOUND = {"fp32": (5e-6, 7e-6, 2.2e-5), "bf16": (1.3e-3, 3.5e-3, 8e-3), "fp16": (2.2e-4, 6.1e-4, 1.6e-3)}
 _REF = {}
 
 
