@@ -32,7 +32,8 @@ extern "C" {
 #endif
 
 /* 17: ww_pass_plan / ww_loader_plan (host-only pass plans of the capped-grid support launches) were added; no existing
- * signature, struct, constant or result changed. */
+ * signature, struct, constant or result changed.  ww_dw_plan / ww_ctx_set_dw_wide_addr came later under the same number: pure
+ * additions again. */
 #define WW_ABI_VERSION 17
 
 #define WW_OK 0
@@ -267,6 +268,12 @@ int ww_conv_stem_bwd_recompute(ww_ctx *ctx, int act_dtype, const void *g, const 
  * the grids it was captured with.  The log-mel kernel has its own knob (ww_ctx_set_logmel_workgroups).                  */
 int ww_ctx_set_grid_cap(ww_ctx *ctx, int n);
 
+/* A test switch, not a performance setting.  The depthwise kernels address a tensor as a scalar base plus one 32-bit byte
+ * offset per lane when its byte size fits 32 bits, and with 64-bit lane addresses otherwise (ww_dw_plan reports which).  on = 1
+ * makes ww_dwconv3x3_fwd / _bwd and the whole-model calls take the 64-bit form at any size, so that a small tensor tests it; 0
+ * (default) = by size.  Results do not depend on it.  Read when a launch is issued.                                        */
+int ww_ctx_set_dw_wide_addr(ww_ctx *ctx, int on);
+
 /* ------------------------------------------------------------------ whole model
  * cnn_small (added to create_model, src/models/architectures.py:437):
  * stem + 4 x (dw,pw) + GAP + dropout + Linear(64,2).  params/grads: arrays of
@@ -499,6 +506,12 @@ int ww_conv1x1_row_tile(int mode, int M, int K, int N);      /* rows per statist
 #define WW_PASS_TO16_PAIR 3
 int ww_pass_plan(int launch, long n, long *out);
 int ww_loader_plan(int B, int n_out, int *out);
+/* Host-only: the dispatch of ww_dwconv3x3_fwd / _bwd for a (B, H, W, 64) tensor of act_dtype, from the code the launchers run; no
+ * context, no device (wide = what ww_ctx_set_dw_wide_addr would hold).  An item is one 4-column strip of one row segment of one
+ * image and a wave holds items 2k, 2k + 1 at any grid.  out[7] = {ncs strips per row, nseg row segments per image, hs_len rows per
+ * segment, items, waves (item pairs) of the launch, how many of them take the interior body (both strips have all six window
+ * columns inside the image; no column clamps, selects or guards), address form: 32 or 64}.                                      */
+int ww_dw_plan(int B, int H, int W, int act_dtype, int wide, long *out);
 
 /* ------------------------------------------------------------------ conv front-end of the CRNN
  * cnn_small's conv stack (stem + 4 depthwise-separable blocks) without GAP / classifier, followed by the mean over the

@@ -127,6 +127,7 @@ _SIGS = {
     "ww_ctx_bind_step_ctl": (C.c_int, [_vp, _vp]),
     "ww_ctx_set_logmel_workgroups": (C.c_int, [_vp, C.c_int]),
     "ww_ctx_set_grid_cap": (C.c_int, [_vp, C.c_int]),
+    "ww_ctx_set_dw_wide_addr": (C.c_int, [_vp, C.c_int]),
     "ww_step_ctl_advance": (C.c_int, [_vp, _vp]),
     "ww_feat_num_frames": (C.c_int, [_i, _i]),
     "ww_feat_mel_tables": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
@@ -197,6 +198,7 @@ _SIGS = {
     "ww_conv1x1_row_tile": (C.c_int, [_i] * 4),
     "ww_se_plan": (C.c_int, [_i] * 4 + [C.POINTER(C.c_int)]),
     "ww_pass_plan": (C.c_int, [_i, C.c_long, C.POINTER(C.c_long)]),
+    "ww_dw_plan": (C.c_int, [_i, _i, _i, _i, _i, C.POINTER(C.c_long)]),
     "ww_loader_plan": (C.c_int, [_i, _i, C.POINTER(C.c_int)]),
     "ww_gru_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ww_gru_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_long, _vp, _vp, _sz, _vp]),
@@ -1321,6 +1323,14 @@ def plan_passes(launch, n):
     return {"grid": out[0], "per_pass": out[1], "passes": -(-int(n) // out[1])}
 
 
+def plan_dw_strips(B, H, W, dtype=torch.float32, wide=False):
+    """The dispatch of dwconv3x3_fwd / _bwd for a (B, H, W, 64) tensor (ww_dw_plan) -> {ncs, nseg, hs_len, items, waves,
+    interior_waves, addr_bits}; ``wide`` = what set_dw_wide_addr would hold."""
+    out = (C.c_long * 7)()
+    _check(load().ww_dw_plan(int(B), int(H), int(W), act_code(dtype), int(bool(wide)), out), "ww_dw_plan")
+    return dict(zip(("ncs", "nseg", "hs_len", "items", "waves", "interior_waves", "addr_bits"), out))
+
+
 def plan_loader(B, n_out):
     """ww_loader_batch's split of a row (ww_loader_plan) -> {S, passes, trips}: workgroups per row, passes of 256 chunks in
     a row, and the trips of workgroup s = 0 .. S-1 of a row."""
@@ -1549,6 +1559,12 @@ def set_grid_cap(dev, n: int):
     """Test / tuning parameter: the persistent conv-stack launches that follow on ``dev`` use at most n workgroups (0 = no
     cap), so a workgroup walks many items.  Read when a launch is issued: a captured graph keeps its grids."""
     _check(load().ww_ctx_set_grid_cap(ctx(dev), int(n)), "ww_ctx_set_grid_cap")
+
+
+def set_dw_wide_addr(dev, on: bool):
+    """Test switch: the depthwise conv launches that follow on ``dev`` take their 64-bit address form whatever the tensor's
+    size (False = by size, the default).  Results do not depend on it."""
+    _check(load().ww_ctx_set_dw_wide_addr(ctx(dev), int(bool(on))), "ww_ctx_set_dw_wide_addr")
 
 
 def bind_step_ctl(dev, ctl):

@@ -552,12 +552,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 }
 
 // -------------------------------------------------------------------------------- depthwise
-struct DwGeom {
-    int B, H, W, ncs, nseg, hs_len;
-    long items;
-};
+typedef ww_dw_geom DwGeom;       // ww_internal.h: the geometry and the dispatch rules, shared with ww_conv_fwd.hip and ww_dw_plan
 
-constexpr int DW_HS = 20;   // max rows per strip segment (matches ww_conv_fwd.hip)
+constexpr int DW_HS = WW_DW_HS;  // max rows per strip segment
 
 template <typename T>
 __device__ __forceinline__ void dwb_issue(const T *__restrict__ gimg, const T *__restrict__ yimg, int h, int w0, int H,
@@ -634,6 +631,43 @@ __device__ __forceinline__ void dwb_row(const typename Act<T>::raw2 (&yc)[4], T 
     }
 }
 
+// the end of k_dw_bwd and k_dw_bwd_sb: the slots' statistics and weight-gradient sums -> this workgroup's partial rows
+__device__ __forceinline__ void dwb_epilogue(const float *__restrict__ mr_in, float *sh /*8*576*/, int slot, int cl, int tid,
+                                             float s1a, float s1b, float s2a, float s2b, const float (&dwa)[9],
+                                             const float (&dwb)[9], float *__restrict__ stat_partials,
+                                             float *__restrict__ dw_partials) {
+    // statistics partial: sum g*yhat = rstd * (sum g*y - mean * sum g)
+    {
+        const float2 mu = *reinterpret_cast<const float2 *>(mr_in + 2 * cl);
+        const float2 rsd = *reinterpret_cast<const float2 *>(mr_in + 64 + 2 * cl);
+        s2a = rsd.x * (s2a - mu.x * s1a);
+        s2b = rsd.y * (s2b - mu.y * s1b);
+    }
+    sh[slot * 128 + 2 * cl] = s1a;       sh[slot * 128 + 2 * cl + 1] = s1b;
+    sh[slot * 128 + 64 + 2 * cl] = s2a;  sh[slot * 128 + 64 + 2 * cl + 1] = s2b;
+    __syncthreads();
+    if (tid < 128) {
+        float t = 0.f;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) t += sh[s * 128 + tid];
+        stat_partials[(size_t)blockIdx.x * 128 + tid] = t;
+    }
+    __syncthreads();
+    // weight-gradient partial, layout [c][tap] like Conv2d.weight (64,1,3,3)
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        sh[slot * 576 + (2 * cl) * 9 + t] = dwa[t];
+        sh[slot * 576 + (2 * cl + 1) * 9 + t] = dwb[t];
+    }
+    __syncthreads();
+    for (int i = tid; i < 576; i += 256) {
+        float t = 0.f;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) t += sh[s * 576 + i];
+        dw_partials[(size_t)blockIdx.x * 576 + i] = t;
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256, Act<T>::is_f32 ? 2 : 3) void k_dw_bwd(const T *__restrict__ g, const T *__restrict__ y_out,
                                                 const float *__restrict__ coef, const T *__restrict__ y_in,
@@ -700,36 +734,218 @@ __global__ __launch_bounds__(256, Act<T>::is_f32 ? 2 : 3) void k_dw_bwd(const T 
           }
         }
     }
-    // statistics partial: sum g*yhat = rstd * (sum g*y - mean * sum g)
-    {
-        const float2 mu = *reinterpret_cast<const float2 *>(mr_in + 2 * cl);
-        const float2 rsd = *reinterpret_cast<const float2 *>(mr_in + 64 + 2 * cl);
-        s2a = rsd.x * (s2a - mu.x * s1a);
-        s2b = rsd.y * (s2b - mu.y * s1b);
-    }
-    sh[slot * 128 + 2 * cl] = s1a;       sh[slot * 128 + 2 * cl + 1] = s1b;
-    sh[slot * 128 + 64 + 2 * cl] = s2a;  sh[slot * 128 + 64 + 2 * cl + 1] = s2b;
-    __syncthreads();
-    if (tid < 128) {
-        float t = 0.f;
+    dwb_epilogue(mr_in, sh, slot, cl, tid, s1a, s1b, s2a, s2b, dwa, dwb, stat_partials, dw_partials);
+}
+
+// ---- scalar-base form of the same kernel (the tensors' byte size fits 32 bits: ww_dw_addr32); see k_dw_fwd_sb in
+// ww_conv_fwd.hip for the two bodies.  Same lane map, item walk, operations and operation order as k_dw_bwd: g_in and the
+// partial rows are bit-identical to it.  The arrived dy row is finished into rows[] and the arrived centre row is converted
+// BEFORE their registers are loaded again, so nothing in flight is copied; the next row's 16 loads are still issued ahead of
+// the step's FMAs.
+typedef __attribute__((address_space(1))) char *dw_gptr;       // a global-memory pointer keeps its address space through the pin
+// pins a wave-uniform pointer in scalar registers: without it the compiler folds the lane offset into the row base once per item
+// and pays a 64-bit vector multiply-add per row for the address
+__device__ __forceinline__ dw_gptr dw_sbase(const void *p) {
+    dw_gptr q = (dw_gptr)const_cast<void *>(p);
+    asm("" : "+s"(q));
+    return q;
+}
+template <typename T>
+__device__ __forceinline__ const T *dw_at(const void *base, uint32_t byte_off) {
+    return reinterpret_cast<const T *>(static_cast<const char *>(base) + byte_off);
+}
+
+// centre row h with the centre values already converted: dwb_row's arithmetic; GUARD = its `w0 + i < W` test
+template <typename T, bool GUARD, typename ST>
+__device__ __forceinline__ void dwb_row_cv(const float2 (&ycv)[4], ST store, int w0, int W,
+                                           const float2 (&rs0)[6], const float2 (&rs1)[6], const float2 (&rs2)[6],
+                                           const float (&wa)[9], const float (&wb)[9], float2 sc, float2 sf,
+                                           float (&dwa)[9], float (&dwb)[9], float &s1a, float &s1b, float &s2a,
+                                           float &s2b) {
 #pragma unroll
-        for (int s = 0; s < 8; ++s) t += sh[s * 128 + tid];
-        stat_partials[(size_t)blockIdx.x * 128 + tid] = t;
+    for (int i = 0; i < 4; ++i) {
+        if (!GUARD || w0 + i < W) {
+            const float2 yv = ycv[i];
+            const float z0 = fmaf(yv.x, sc.x, sf.x), z1 = fmaf(yv.y, sc.y, sf.y);
+            const float a0 = z0 < 0.f ? 0.f : z0, a1 = z1 < 0.f ? 0.f : z1;
+            float d0 = 0.f, d1 = 0.f;
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                const float2 t0 = rs0[i + 2 - kw], t1 = rs1[i + 2 - kw], t2 = rs2[i + 2 - kw];
+                d0 = fmaf(t0.x, wa[kw], d0);     d1 = fmaf(t0.y, wb[kw], d1);
+                d0 = fmaf(t1.x, wa[3 + kw], d0); d1 = fmaf(t1.y, wb[3 + kw], d1);
+                d0 = fmaf(t2.x, wa[6 + kw], d0); d1 = fmaf(t2.y, wb[6 + kw], d1);
+                dwa[kw] = fmaf(a0, t0.x, dwa[kw]);         dwb[kw] = fmaf(a1, t0.y, dwb[kw]);
+                dwa[3 + kw] = fmaf(a0, t1.x, dwa[3 + kw]); dwb[3 + kw] = fmaf(a1, t1.y, dwb[3 + kw]);
+                dwa[6 + kw] = fmaf(a0, t2.x, dwa[6 + kw]); dwb[6 + kw] = fmaf(a1, t2.y, dwb[6 + kw]);
+            }
+            const float2 go = Act<T>::round2(make_float2(z0 > 0.f ? d0 : 0.f, z1 > 0.f ? d1 : 0.f));
+            const float g0 = go.x, g1 = go.y;
+            store(i, go);
+            s1a += g0; s1b += g1;
+            s2a = fmaf(g0, yv.x, s2a);      // sum g*y, as in dwb_row
+            s2b = fmaf(g1, yv.y, s2b);
+        }
     }
-    __syncthreads();
-    // weight-gradient partial, layout [c][tap] like Conv2d.weight (64,1,3,3)
+}
+
+template <typename T, bool INTERIOR>
+__device__ __forceinline__ void dw_bwd_item(const T *__restrict__ g, const T *__restrict__ y_out, const T *__restrict__ y_in,
+                                            T *__restrict__ g_in, const DwGeom &gm, long item, int cl, float2 cA, float2 cB,
+                                            float2 cC, float2 sc, float2 sf, const float (&wa)[9], const float (&wb)[9],
+                                            float (&dwa)[9], float (&dwb)[9], float &s1a, float &s1b, float &s2a,
+                                            float &s2b) {
+    typedef typename Act<T>::raw2 raw2;
+    constexpr uint32_t PX = 64 * sizeof(T);          // bytes of one pixel
+    const int cs = (int)(item % gm.ncs);
+    const long t = item / gm.ncs;
+    int seg = (int)(t % gm.nseg), b = (int)(t / gm.nseg);
+    if (INTERIOR) {                                  // equal in both strips of the wave: keep them in scalar registers
+        seg = __builtin_amdgcn_readfirstlane(seg);
+        b = __builtin_amdgcn_readfirstlane(b);
+    }
+    const int w0 = cs * 4, hs = seg * gm.hs_len;
+    const int he = min(gm.H, hs + gm.hs_len);
+    const uint32_t rowb = (uint32_t)gm.W * PX;
+    float2 rows[3][6], ycv[4];
+    raw2 ag[6], ay[6], ayc[4];
+    auto convert_centre = [&]() {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ycv[i] = Act<T>::cvt2(ayc[i]);
+    };
+    if (INTERIOR) {
+        const size_t ib = (size_t)b * gm.H * rowb;
+        const char *gp = reinterpret_cast<const char *>(g) + ib, *yop = reinterpret_cast<const char *>(y_out) + ib;
+        const char *yip = reinterpret_cast<const char *>(y_in) + ib;
+        char *gip = reinterpret_cast<char *>(g_in) + ib;
+        const uint32_t vo = (uint32_t)(w0 - 1) * PX + (uint32_t)cl * (2 * sizeof(T));   // window column 0, this lane's channels
+        auto issue = [&](int r) {
+            const dw_gptr rg = dw_sbase(gp + (size_t)r * rowb), ry = dw_sbase(yop + (size_t)r * rowb);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                ag[i] = Act<T>::ldraw2(dw_at<T>((const char *)(rg + i * PX), vo));
+                ay[i] = Act<T>::ldraw2(dw_at<T>((const char *)(ry + i * PX), vo));
+            }
+        };
+        auto issue_centre = [&](int r) {
+            const dw_gptr rc = dw_sbase(yip + (size_t)r * rowb);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ayc[i] = Act<T>::ldraw2_nt(dw_at<T>((const char *)(rc + (i + 1) * PX), vo));
+        };
+        auto finish = [&](float2 (&r)[6]) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                const float2 gv = Act<T>::cvt2(ag[i]), yv = Act<T>::cvt2(ay[i]);
+                r[i].x = fmaf(cA.x, gv.x, fmaf(cB.x, yv.x, cC.x));
+                r[i].y = fmaf(cA.y, gv.y, fmaf(cB.y, yv.y, cC.y));
+            }
+        };
+        auto zero = [&](float2 (&r)[6]) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) r[i] = make_float2(0.f, 0.f);
+        };
+        if (hs == 0) zero(rows[0]);
+        else { issue(hs - 1); finish(rows[0]); }
+        issue(hs); finish(rows[1]);
+        if (hs + 1 < gm.H) issue(hs + 1);
+        issue_centre(hs);
+#pragma unroll 1
+        for (int i0 = 0; i0 < DW_HS; i0 += 3) {
+#pragma unroll
+          for (int ii = 0; ii < 3; ++ii) {
+            const int h = hs + i0 + ii;              // (i0 + ii) % 3 == ii: the row rotation stays compile-time
+            if (h < he) {
+                convert_centre();
+                finish(rows[(ii + 2) % 3]);          // unconditional: the wait for the loads in flight stays exact
+                if (h + 1 >= gm.H) zero(rows[(ii + 2) % 3]);
+                if (h + 1 < he) {
+                    if (h + 2 < gm.H) issue(h + 2);
+                    issue_centre(h + 1);
+                }
+                const dw_gptr orow = dw_sbase(gip + (size_t)h * rowb);
+                dwb_row_cv<T, false>(ycv, [&](int i, float2 go) { Act<T>::st2((T *)(orow + (i + 1) * PX + vo), go); }, w0, gm.W,
+                                     rows[(ii + 2) % 3], rows[(ii + 1) % 3], rows[ii % 3], wa, wb, sc, sf, dwa, dwb, s1a, s1b,
+                                     s2a, s2b);
+            }
+          }
+        }
+    } else {
+        const uint32_t ib = (uint32_t)b * (uint32_t)gm.H * rowb + (uint32_t)cl * (2 * sizeof(T));
+        uint32_t co[6];                              // image + clamped window column + channel pair
+#pragma unroll
+        for (int i = 0; i < 6; ++i) co[i] = ib + (uint32_t)min(max(w0 - 1 + i, 0), gm.W - 1) * PX;
+        auto issue = [&](int r) {
+            const uint32_t ro = (uint32_t)min(max(r, 0), gm.H - 1) * rowb;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                ag[i] = Act<T>::ldraw2(dw_at<T>(g, co[i] + ro));
+                ay[i] = Act<T>::ldraw2(dw_at<T>(y_out, co[i] + ro));
+            }
+        };
+        auto issue_centre = [&](int r) {
+            const uint32_t ro = (uint32_t)min(max(r, 0), gm.H - 1) * rowb;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ayc[i] = Act<T>::ldraw2_nt(dw_at<T>(y_in, co[i + 1] + ro));
+        };
+        auto finish = [&](int r, float2 (&rw)[6]) { dwb_finish<T>(ag, ay, r, w0, gm.H, gm.W, cA, cB, cC, rw); };
+        issue(hs - 1); finish(hs - 1, rows[0]);
+        issue(hs); finish(hs, rows[1]);
+        issue(hs + 1);
+        issue_centre(hs);
+#pragma unroll 1
+        for (int i0 = 0; i0 < DW_HS; i0 += 3) {
+#pragma unroll
+          for (int ii = 0; ii < 3; ++ii) {
+            const int h = hs + i0 + ii;
+            if (h < he) {
+                convert_centre();
+                finish(h + 1, rows[(ii + 2) % 3]);
+                if (h + 1 < he) {
+                    issue(h + 2);
+                    issue_centre(h + 1);
+                }
+                const uint32_t ro = ib + (uint32_t)h * rowb + (uint32_t)w0 * PX;
+                dwb_row_cv<T, true>(ycv, [&](int i, float2 go) {
+                                        Act<T>::st2(reinterpret_cast<T *>(reinterpret_cast<char *>(g_in) + (ro + i * PX)), go);
+                                    }, w0, gm.W, rows[(ii + 2) % 3], rows[(ii + 1) % 3], rows[ii % 3], wa, wb, sc, sf, dwa, dwb,
+                                    s1a, s1b, s2a, s2b);
+            }
+          }
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, Act<T>::is_f32 ? 2 : 3) void k_dw_bwd_sb(const T *__restrict__ g, const T *__restrict__ y_out,
+                                                const float *__restrict__ coef, const T *__restrict__ y_in,
+                                                const float *__restrict__ ss_in, const float *__restrict__ mr_in,
+                                                const float *__restrict__ w, DwGeom gm, T *__restrict__ g_in,
+                                                float *__restrict__ stat_partials, float *__restrict__ dw_partials) {
+    __shared__ float sh[8 * 576];
+    const int tid = threadIdx.x, slot = tid >> 5, cl = tid & 31;
+    float wa[9], wb[9], dwa[9], dwb[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-        sh[slot * 576 + (2 * cl) * 9 + t] = dwa[t];
-        sh[slot * 576 + (2 * cl + 1) * 9 + t] = dwb[t];
+        wa[t] = w[(2 * cl) * 9 + t];
+        wb[t] = w[(2 * cl + 1) * 9 + t];
+        dwa[t] = 0.f;
+        dwb[t] = 0.f;
     }
-    __syncthreads();
-    for (int i = tid; i < 576; i += 256) {
-        float t = 0.f;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) t += sh[s * 576 + i];
-        dw_partials[(size_t)blockIdx.x * 576 + i] = t;
+    const float2 cA = *reinterpret_cast<const float2 *>(coef + 2 * cl);
+    const float2 cB = *reinterpret_cast<const float2 *>(coef + 64 + 2 * cl);
+    const float2 cC = *reinterpret_cast<const float2 *>(coef + 128 + 2 * cl);
+    const float2 sc = *reinterpret_cast<const float2 *>(ss_in + 2 * cl);
+    const float2 sf = *reinterpret_cast<const float2 *>(ss_in + 64 + 2 * cl);
+    float s1a = 0.f, s1b = 0.f, s2a = 0.f, s2b = 0.f;
+    for (long item = (long)blockIdx.x * 8 + slot; item < gm.items; item += (long)gridDim.x * 8) {
+        // all 64 lanes here and interior <=> the wave's two strips are interior (an idle slot's lanes are not in the ballot)
+        const bool in = ww_dw_strip_interior((int)(item % gm.ncs), gm.W);
+        if (__builtin_amdgcn_ballot_w64(in) == ~0ull)
+            dw_bwd_item<T, true>(g, y_out, y_in, g_in, gm, item, cl, cA, cB, cC, sc, sf, wa, wb, dwa, dwb, s1a, s1b, s2a, s2b);
+        else
+            dw_bwd_item<T, false>(g, y_out, y_in, g_in, gm, item, cl, cA, cB, cC, sc, sf, wa, wb, dwa, dwb, s1a, s1b, s2a, s2b);
     }
+    dwb_epilogue(mr_in, sh, slot, cl, tid, s1a, s1b, s2a, s2b, dwa, dwb, stat_partials, dw_partials);
 }
 
 // ------------------------------------------------------------------------------------- stem
@@ -925,9 +1141,10 @@ int launch_dw_bwd(ww_ctx *ctx, const void *g, const void *y_out, const float *co
                   const float *ss_in, const float *mr_in, const float *w, const DwGeom &gm, void *g_in, float *stat,
                   float *dwp, int *grid_out, hipStream_t st) {
     const long nblk = (gm.items + 7) / 8;
-    const int grid = ww_conv_grid(ctx, (const void *)k_dw_bwd<T>, 256, 0, nblk, WW_MAX_PARTIALS);
+    auto kern = ww_dw_addr32(gm, sizeof(T), ctx->dw_wide) ? k_dw_bwd_sb<T> : k_dw_bwd<T>;
+    const int grid = ww_conv_grid(ctx, (const void *)kern, 256, 0, nblk, WW_MAX_PARTIALS);
     ww_prof_scope ps_(ctx, WW_K_DW_BWD, st);
-    hipLaunchKernelGGL(k_dw_bwd<T>, dim3(grid), dim3(256), 0, st, (const T *)g, (const T *)y_out, coef, (const T *)y_in,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, (const T *)g, (const T *)y_out, coef, (const T *)y_in,
                        ss_in, mr_in, w, gm, (T *)g_in, stat, dwp);
     *grid_out = grid;
     return WW_OK;
@@ -997,12 +1214,7 @@ extern "C" int ww_dwconv3x3_bwd(ww_ctx *ctx, int act_dtype, const void *g, const
     WW_REQUIRE((long)H * W * 64 < (1L << 31), WW_E_UNSUPPORTED, "ww_dwconv3x3_bwd: one image of %d x %d x 64 exceeds 2^31 elements", H, W);
     int rc = check_act_b("ww_dwconv3x3_bwd", act_dtype);
     if (rc) return rc;
-    DwGeom gm;
-    gm.B = B; gm.H = H; gm.W = W;
-    gm.ncs = (W + 3) / 4;
-    gm.nseg = (H + DW_HS - 1) / DW_HS;
-    gm.hs_len = (H + gm.nseg - 1) / gm.nseg;   // <= DW_HS
-    gm.items = (long)B * gm.nseg * gm.ncs;
+    const DwGeom gm = ww_dw_geometry(B, H, W);
     hipStream_t st = (hipStream_t)stream;
     float *stat = (float *)scratch, *dwp = stat + WW_STAT_SLAB_FLOATS;
     int grid = 0;

@@ -148,12 +148,9 @@ __global__ __launch_bounds__(256) void k_stem_fwd(const float *__restrict__ x, c
 }
 
 // -------------------------------------------------------------------------------- depthwise
-struct DwGeom {
-    int B, H, W, ncs, nseg, hs_len;  // column strips per row, row segments per image, rows per segment
-    long items;
-};
+typedef ww_dw_geom DwGeom;       // ww_internal.h: the geometry and the dispatch rules, shared with ww_conv_bwd.hip and ww_dw_plan
 
-constexpr int DW_HS = 20;   // max rows per strip segment (compile-time so the row loop fully unrolls)
+constexpr int DW_HS = WW_DW_HS;  // max rows per strip segment (compile-time so the row loop fully unrolls)
 
 // raw (pre-BatchNorm) row of 6 pixels around the strip; addresses are clamped so the loads are branch-free
 template <typename T>
@@ -256,6 +253,179 @@ __global__ __launch_bounds__(256) void k_dw_fwd(const T *__restrict__ yin, const
             }
           }
         }
+    }
+    if (partials) reduce_stats_slots(s0, s1, q0, q1, sh, partials + (size_t)blockIdx.x * 128);
+}
+
+// ---- scalar-base form of the same kernel (the tensor's byte size fits 32 bits: ww_dw_addr32).  Every load and store is a
+// wave-uniform base plus one unsigned 32-bit byte offset per lane.  Same lane map, item walk, operations and operation order
+// as k_dw_fwd, so y and the partial rows are bit-identical to it.  Two bodies per item, picked by a wave-uniform branch:
+//   interior : both strips of the wave have all six window columns inside the image (ww_dw_strip_interior).  They then lie in
+//              one image and one segment, so b, hs, he and the row index are wave-uniform: the row base is a scalar pointer that
+//              advances with scalar adds, the lane offset is computed once per item, and there are no column clamps, no
+//              padding selects and no `w0 + i < W` guards.  A row outside the image (above row 0, below row H - 1) is zeros
+//              without a load.
+//   edge     : k_dw_fwd's row step (clamped columns, padding selects, guarded stores); the clamped column offsets are
+//              computed once per item, not once per row.
+// In both, the arrived row is finished into rows[] BEFORE its registers are loaded again, so the row in flight is never
+// copied; the next row's loads are still issued ahead of the step's FMAs.
+// pins a wave-uniform pointer in scalar registers: without it the compiler folds the lane offset into the row base once per item
+// and pays a 64-bit vector multiply-add per row for the address
+typedef __attribute__((address_space(1))) char *dw_gptr;       // a global-memory pointer keeps its address space through the pin
+__device__ __forceinline__ dw_gptr dw_sbase(const void *p) {
+    dw_gptr q = (dw_gptr)const_cast<void *>(p);
+    asm("" : "+s"(q));
+    return q;
+}
+template <typename T>
+__device__ __forceinline__ typename Act<T>::raw2 dw_ld(const void *base, uint32_t byte_off) {
+    return Act<T>::ldraw2(reinterpret_cast<const T *>(static_cast<const char *>(base) + byte_off));
+}
+
+template <typename T, bool INTERIOR>
+__device__ __forceinline__ void dw_fwd_item(const T *__restrict__ yin, T *__restrict__ y, const DwGeom &g, long item, int cl,
+                                            float2 sc, float2 sf, const float (&wa)[9], const float (&wb)[9], float &s0,
+                                            float &s1, float &q0, float &q1) {
+    typedef typename Act<T>::raw2 raw2;
+    constexpr uint32_t PX = 64 * sizeof(T);          // bytes of one pixel
+    const int cs = (int)(item % g.ncs);
+    const long t = item / g.ncs;
+    int seg = (int)(t % g.nseg), b = (int)(t / g.nseg);
+    if (INTERIOR) {                                  // equal in both strips of the wave: keep them in scalar registers
+        seg = __builtin_amdgcn_readfirstlane(seg);
+        b = __builtin_amdgcn_readfirstlane(b);
+    }
+    const int w0 = cs * 4, hs = seg * g.hs_len;
+    const int he = min(g.H, hs + g.hs_len);
+    const uint32_t rowb = (uint32_t)g.W * PX;
+    float2 rows[3][6];
+    raw2 ahead[6];
+    if (INTERIOR) {
+        const size_t ib = (size_t)b * g.H * rowb;
+        const char *ip = reinterpret_cast<const char *>(yin) + ib;
+        char *op = reinterpret_cast<char *>(y) + ib;
+        const uint32_t vo = (uint32_t)(w0 - 1) * PX + (uint32_t)cl * (2 * sizeof(T));   // window column 0, this lane's channels
+        auto issue = [&](int r) {
+            const dw_gptr rp = dw_sbase(ip + (size_t)r * rowb);
+#pragma unroll
+            for (int i = 0; i < 6; ++i) ahead[i] = dw_ld<T>((const char *)(rp + i * PX), vo);
+        };
+        auto finish = [&](float2 (&r)[6]) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                const float2 v = Act<T>::cvt2(ahead[i]);
+                r[i].x = bnrelu(v.x, sc.x, sf.x);
+                r[i].y = bnrelu(v.y, sc.y, sf.y);
+            }
+        };
+        auto zero = [&](float2 (&r)[6]) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) r[i] = make_float2(0.f, 0.f);
+        };
+        if (hs == 0) zero(rows[0]);
+        else { issue(hs - 1); finish(rows[0]); }
+        issue(hs); finish(rows[1]);
+        if (hs + 1 < g.H) issue(hs + 1);
+#pragma unroll 1
+        for (int i0 = 0; i0 < DW_HS; i0 += 3) {
+#pragma unroll
+          for (int ii = 0; ii < 3; ++ii) {
+            const int h = hs + i0 + ii;              // (i0 + ii) % 3 == ii: the row rotation stays compile-time
+            if (h < he) {
+                finish(rows[(ii + 2) % 3]);          // unconditional: the wait for the loads in flight stays exact
+                if (h + 1 >= g.H) zero(rows[(ii + 2) % 3]);
+                if (h + 1 < he && h + 2 < g.H) issue(h + 2);                             // one row ahead of its use
+                const float2 (&top)[6] = rows[ii % 3], (&mid)[6] = rows[(ii + 1) % 3], (&bot)[6] = rows[(ii + 2) % 3];
+                const dw_gptr orow = dw_sbase(op + (size_t)h * rowb);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+                    for (int kw = 0; kw < 3; ++kw) {
+                        a0 = fmaf(top[i + kw].x, wa[kw], a0);
+                        a1 = fmaf(top[i + kw].y, wb[kw], a1);
+                        a0 = fmaf(mid[i + kw].x, wa[3 + kw], a0);
+                        a1 = fmaf(mid[i + kw].y, wb[3 + kw], a1);
+                        a0 = fmaf(bot[i + kw].x, wa[6 + kw], a0);
+                        a1 = fmaf(bot[i + kw].y, wb[6 + kw], a1);
+                    }
+                    const float2 o = Act<T>::round2(make_float2(a0, a1));
+                    Act<T>::st2((T *)(orow + (i + 1) * PX + vo), o);
+                    s0 += o.x; s1 += o.y;
+                    q0 = fmaf(o.x, o.x, q0); q1 = fmaf(o.y, o.y, q1);
+                }
+            }
+          }
+        }
+    } else {
+        const uint32_t ib = (uint32_t)b * (uint32_t)g.H * rowb + (uint32_t)cl * (2 * sizeof(T));
+        uint32_t co[6];                              // image + clamped window column + channel pair
+#pragma unroll
+        for (int i = 0; i < 6; ++i) co[i] = ib + (uint32_t)min(max(w0 - 1 + i, 0), g.W - 1) * PX;
+        auto issue = [&](int r) {
+            const uint32_t ro = (uint32_t)min(max(r, 0), g.H - 1) * rowb;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) ahead[i] = dw_ld<T>(yin, co[i] + ro);
+        };
+        auto finish = [&](int r, float2 (&rw)[6]) { dw_finish_row<T>(ahead, r, w0, g.H, g.W, sc, sf, rw); };
+        issue(hs - 1); finish(hs - 1, rows[0]);
+        issue(hs); finish(hs, rows[1]);
+        issue(hs + 1);
+#pragma unroll 1
+        for (int i0 = 0; i0 < DW_HS; i0 += 3) {
+#pragma unroll
+          for (int ii = 0; ii < 3; ++ii) {
+            const int h = hs + i0 + ii;
+            if (h < he) {
+                finish(h + 1, rows[(ii + 2) % 3]);
+                if (h + 1 < he) issue(h + 2);
+                const float2 (&top)[6] = rows[ii % 3], (&mid)[6] = rows[(ii + 1) % 3], (&bot)[6] = rows[(ii + 2) % 3];
+                const uint32_t ro = ib + (uint32_t)h * rowb + (uint32_t)w0 * PX;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+                    for (int kw = 0; kw < 3; ++kw) {
+                        a0 = fmaf(top[i + kw].x, wa[kw], a0);
+                        a1 = fmaf(top[i + kw].y, wb[kw], a1);
+                        a0 = fmaf(mid[i + kw].x, wa[3 + kw], a0);
+                        a1 = fmaf(mid[i + kw].y, wb[3 + kw], a1);
+                        a0 = fmaf(bot[i + kw].x, wa[6 + kw], a0);
+                        a1 = fmaf(bot[i + kw].y, wb[6 + kw], a1);
+                    }
+                    if (w0 + i < g.W) {
+                        const float2 o = Act<T>::round2(make_float2(a0, a1));
+                        Act<T>::st2(reinterpret_cast<T *>(reinterpret_cast<char *>(y) + (ro + i * PX)), o);
+                        s0 += o.x; s1 += o.y;
+                        q0 = fmaf(o.x, o.x, q0); q1 = fmaf(o.y, o.y, q1);
+                    }
+                }
+            }
+          }
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256, 4) void k_dw_fwd_sb(const T *__restrict__ yin, const float *__restrict__ ss,
+                                                   const float *__restrict__ w, DwGeom g, T *__restrict__ y,
+                                                   float *__restrict__ partials) {
+    __shared__ float sh[8 * 128];
+    const int tid = threadIdx.x, slot = tid >> 5, cl = tid & 31;
+    float wa[9], wb[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        wa[t] = w[(2 * cl) * 9 + t];
+        wb[t] = w[(2 * cl + 1) * 9 + t];
+    }
+    const float2 sc = *reinterpret_cast<const float2 *>(ss + 2 * cl);
+    const float2 sf = *reinterpret_cast<const float2 *>(ss + 64 + 2 * cl);
+    float s0 = 0.f, s1 = 0.f, q0 = 0.f, q1 = 0.f;
+    for (long item = (long)blockIdx.x * 8 + slot; item < g.items; item += (long)gridDim.x * 8) {
+        // all 64 lanes here and interior <=> the wave's two strips are interior (an idle slot's lanes are not in the ballot)
+        const bool in = ww_dw_strip_interior((int)(item % g.ncs), g.W);
+        if (__builtin_amdgcn_ballot_w64(in) == ~0ull) dw_fwd_item<T, true>(yin, y, g, item, cl, sc, sf, wa, wb, s0, s1, q0, q1);
+        else dw_fwd_item<T, false>(yin, y, g, item, cl, sc, sf, wa, wb, s0, s1, q0, q1);
     }
     if (partials) reduce_stats_slots(s0, s1, q0, q1, sh, partials + (size_t)blockIdx.x * 128);
 }
@@ -595,10 +765,11 @@ template <typename T>
 int launch_dw_fwd(ww_ctx *ctx, const void *y_in, const float *ss_in, const float *w, const DwGeom &g, void *y,
                   float *partials, int *grid_out, hipStream_t st) {
     const long nblk = (g.items + 7) / 8;
-    const int grid = ww_conv_grid(ctx, (const void *)k_dw_fwd<T>, 256, 0, nblk, WW_MAX_PARTIALS);
+    auto kern = ww_dw_addr32(g, sizeof(T), ctx->dw_wide) ? k_dw_fwd_sb<T> : k_dw_fwd<T>;
+    const int grid = ww_conv_grid(ctx, (const void *)kern, 256, 0, nblk, WW_MAX_PARTIALS);
     {
         ww_prof_scope ps_(ctx, WW_K_DW_FWD, st);
-        hipLaunchKernelGGL(k_dw_fwd<T>, dim3(grid), dim3(256), 0, st, (const T *)y_in, ss_in, w, g, (T *)y, partials);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, (const T *)y_in, ss_in, w, g, (T *)y, partials);
     }
     WW_LAUNCH_CHECK();
     *grid_out = grid;
@@ -664,12 +835,7 @@ extern "C" int ww_dwconv3x3_fwd(ww_ctx *ctx, int act_dtype, const void *y_in, co
     WW_REQUIRE((long)H * W * 64 < (1L << 31), WW_E_UNSUPPORTED, "ww_dwconv3x3_fwd: one image of %d x %d x 64 exceeds 2^31 elements", H, W);
     int rc = check_bn("ww_dwconv3x3_fwd", bn, ss_out, mr_out, scratch);
     if (rc || (rc = check_act("ww_dwconv3x3_fwd", act_dtype))) return rc;
-    DwGeom g;
-    g.B = B; g.H = H; g.W = W;
-    g.ncs = (W + 3) / 4;
-    g.nseg = (H + DW_HS - 1) / DW_HS;
-    g.hs_len = (H + g.nseg - 1) / g.nseg;      // <= DW_HS
-    g.items = (long)B * g.nseg * g.ncs;
+    const DwGeom g = ww_dw_geometry(B, H, W);
     hipStream_t st = (hipStream_t)stream;
     float *partials = bn->training ? (float *)scratch : nullptr;
     int grid = 0;

@@ -46,6 +46,19 @@ extern "C" int ww_pass_plan(int launch, long n, long *out) {
     out[1] = p.per_pass;
     return WW_OK;
 }
+// host-only: what ww_dwconv3x3_fwd / _bwd launch for (B, H, W), from the functions their launchers call
+extern "C" int ww_dw_plan(int B, int H, int W, int act_dtype, int wide, long *out) {
+    WW_REQUIRE(out && B >= 1 && H >= 1 && W >= 1 && (wide == 0 || wide == 1), WW_E_INVALID, "ww_dw_plan: bad argument");
+    WW_REQUIRE(act_dtype == WW_ACT_F32 || act_dtype == WW_ACT_BF16 || act_dtype == WW_ACT_F16, WW_E_INVALID,
+               "ww_dw_plan: unknown act_dtype %d", act_dtype);
+    const ww_dw_geom g = ww_dw_geometry(B, H, W);
+    const bool a32 = ww_dw_addr32(g, act_dtype == WW_ACT_F32 ? 4 : 2, wide);
+    long waves = 0, interior = 0;
+    ww_dw_wave_counts(g, a32, &waves, &interior);
+    out[0] = g.ncs; out[1] = g.nseg; out[2] = g.hs_len; out[3] = g.items;
+    out[4] = waves; out[5] = interior; out[6] = a32 ? 32 : 64;
+    return WW_OK;
+}
 extern "C" int ww_loader_plan(int B, int n_out, int *out) {
     WW_REQUIRE(out && B >= 1 && n_out >= 1, WW_E_INVALID, "ww_loader_plan: bad argument");
     const ww_loader_split s = ww_loader_plan_rows(B, n_out);
@@ -75,6 +88,7 @@ extern "C" int ww_ctx_create(int device, ww_ctx **out) {
     c->step_ctl = nullptr;
     c->logmel_wgs = 0;
     c->grid_cap = 0;
+    c->dw_wide = 0;
     c->tw16k = nullptr;
     c->norm_partials = nullptr;
     c->defer_on = 0;
@@ -109,6 +123,13 @@ extern "C" int ww_ctx_set_grid_cap(ww_ctx *ctx, int n) {
     WW_REQUIRE(ctx != nullptr, WW_E_INVALID, "ww_ctx_set_grid_cap: ctx is null");
     WW_REQUIRE(n >= 0, WW_E_INVALID, "ww_ctx_set_grid_cap: n=%d must be >= 0", n);
     ctx->grid_cap = n;
+    return WW_OK;
+}
+
+extern "C" int ww_ctx_set_dw_wide_addr(ww_ctx *ctx, int on) {
+    WW_REQUIRE(ctx != nullptr, WW_E_INVALID, "ww_ctx_set_dw_wide_addr: ctx is null");
+    WW_REQUIRE(on == 0 || on == 1, WW_E_INVALID, "ww_ctx_set_dw_wide_addr: on=%d must be 0 or 1", on);
+    ctx->dw_wide = on;
     return WW_OK;
 }
 

@@ -89,6 +89,7 @@ struct ww_ctx {
     std::vector<ww_prof_rec> *prof_free;   // event pairs ready for reuse
     int defer_on;                          // ww_ctx_set_deferred_reduce: partial-sum steps are queued instead of launched
     std::vector<ww_reduce_item> *deferred; // queued partial sums (ww_deferred_reduce_flush runs them as ONE launch)
+    int dw_wide;                           // test switch: the depthwise kernels take their 64-bit address form (ww_ctx_set_dw_wide_addr)
 };
 // queue dst[i] (+)= sum_z part[z*n + i] when the context is deferring (returns true), else leave it to the caller
 static inline bool ww_defer(ww_ctx *ctx, const float *part, float *dst, long n, int splits, int accumulate) {
@@ -153,6 +154,40 @@ static inline int ww_capped_grid(const ww_ctx *ctx, int grid) {
 static inline int ww_conv_grid(const ww_ctx *ctx, const void *fn, int block, size_t smem, long want, int cap) {
     return ww_capped_grid(ctx, ww_occupancy_grid(fn, block, smem, want, cap));
 }
+// ---- dispatch of the depthwise kernels (k_dw_fwd / k_dw_bwd and their scalar-base forms): the launchers, the kernels and
+// ww_dw_plan (wwhip.h) all take it from here.  An item is one 4-column strip of one row segment of one image; item =
+// (b * nseg + seg) * ncs + cs.  A wave holds items 2k and 2k + 1 whatever the grid (the walk steps by a multiple of 8).
+struct ww_dw_geom {
+    int B, H, W, ncs, nseg, hs_len;  // column strips per row, row segments per image, rows per segment
+    long items;
+};
+#define WW_DW_HS 20                  // most rows per strip segment (compile-time so the row loop fully unrolls)
+static inline ww_dw_geom ww_dw_geometry(int B, int H, int W) {
+    ww_dw_geom g;
+    g.B = B; g.H = H; g.W = W;
+    g.ncs = (W + 3) / 4;
+    g.nseg = (H + WW_DW_HS - 1) / WW_DW_HS;
+    g.hs_len = (H + g.nseg - 1) / g.nseg;      // <= WW_DW_HS
+    g.items = (long)B * g.nseg * g.ncs;
+    return g;
+}
+// a strip is interior when its six window columns and four output columns all lie inside the image
+__host__ __device__ static inline bool ww_dw_strip_interior(int cs, int W) { return cs >= 1 && 4 * cs + 5 <= W; }
+// scalar base + 32-bit byte offset per lane needs every byte of a tensor within 2^32 of its base; `wide` (the context's
+// test switch, ww_ctx_set_dw_wide_addr) forces the 64-bit form
+static inline bool ww_dw_addr32(const ww_dw_geom &g, size_t elt_bytes, int wide) {
+    return !wide && (size_t)g.B * g.H * g.W * 64 * elt_bytes <= 0xffffffffull;
+}
+// waves (item pairs) of a launch, and how many of them take the interior body: both strips interior, which puts both in
+// the same image and segment; the 64-bit form has no interior body
+static inline void ww_dw_wave_counts(const ww_dw_geom &g, bool addr32, long *waves, long *interior) {
+    *waves = (g.items + 1) / 2;
+    *interior = 0;
+    if (!addr32) return;
+    for (long e = 0; e + 1 < g.items; e += 2)
+        *interior += ww_dw_strip_interior((int)(e % g.ncs), g.W) && ww_dw_strip_interior((int)((e + 1) % g.ncs), g.W);
+}
+
 // ---- pass plans of the support kernels whose grid is capped on the host and whose body is `for (i = ...; i < n; i += one
 // pass)`: the workgroups of a launch over n items and the items one pass of that grid holds.  The launch sites take their grid
 // from these and ww_pass_plan / ww_loader_plan (wwhip.h) report them, so a test that claims a second pass asks the code that
