@@ -632,6 +632,32 @@ int ww_mean_hw_st_fwd(ww_ctx *ctx, int storage, const void *x, int B, int HW, in
 int ww_mean_hw_st_bwd(ww_ctx *ctx, int storage, const float *dmean, int B, int HW, int C, void *dx, ww_stream_t stream);
 int ww_relu_mask_st_bwd(ww_ctx *ctx, int storage, const void *dy, const void *y, size_t n, void *dx, ww_stream_t stream);
 
+/* ------------------------------------------------------------------ the causal Conv1d layer with 16-bit ACTIVATION STORAGE
+ * ww_tconv1d_fwd / _bwd with every (B,T,C) activation tensor and its gradient in S = bf16 | fp16 (`storage`: WW_ACT_BF16 |
+ * WW_ACT_F16 -- also the matrix mode).  Arithmetic is fp32; a value is rounded (RNE) exactly where a tensor is stored and nowhere
+ * else.  w, bias, dw, db stay fp32.  Channel counts are multiples of 8, tensors contiguous and 16-byte aligned, 1 <= k <= 8,
+ * dilation >= 1; anything else (a null argument, an unknown storage code) is WW_E_INVALID before any launch, a scratch below
+ * ww_tconv1d_st_scratch_bytes(...) bytes WW_E_WORKSPACE.
+ *   fwd : y = S([relu](acc + bias [+ float(residual)])), acc the fp32 chain over the stored x and S(w) (rounded once, when packed)
+ *   bwd : dpre = S(dy * mask_scale * [y != 0] * [y2 != 0]) -- the masks are read off the STORED outputs (dpre is dy itself without
+ *         masks and with mask_scale == 1);  dx = S(acc) or S(acc + float(dx));  dw: fp32 partials over the stored dpre and x, summed
+ *         in range order here or by the deferred flush (ww_defer);  db = the fp32 sum, in a fixed order, of the stored dpre.
+ * ww_dropout_bt_st: ww_dropout_bt's Philox law on contiguous rows, out = S(keep ? float(x) * (1 / (1 - p)) : 0); out may be x.
+ * ww_add_relu_st_fwd: y = S(relu(float(a) + float(b))), n elements (a multiple of 8).
+ * ww_seq_round_st: out (B,T,F) = S(x); x fp32 is (B,F,T) (transposed != 0: the Trainer's (B,1,F,T) batches) or (B,T,F).          */
+size_t ww_tconv1d_st_scratch_bytes(int storage, int B, int T, int Cin, int Cout, int k);
+int ww_tconv1d_st_fwd(ww_ctx *ctx, int storage, const void *x, const float *w, const float *bias, int B, int T, int Cin, int Cout,
+                      int k, int dilation, int relu, const void *residual /* nullable */, void *y, void *scratch, size_t scratch_bytes,
+                      ww_stream_t stream);
+int ww_tconv1d_st_bwd(ww_ctx *ctx, int storage, const void *x, const float *w, const void *y /* nullable */,
+                      const void *y2 /* nullable */, float mask_scale, const void *dy, int B, int T, int Cin, int Cout, int k,
+                      int dilation, void *dx /* nullable */, int accumulate_dx, float *dw, float *db, void *scratch,
+                      size_t scratch_bytes, ww_stream_t stream);
+int ww_dropout_bt_st(ww_ctx *ctx, int storage, const void *x, int B, int T, int C, float p, uint64_t seed, uint64_t step,
+                     uint64_t sample_offset, int stream_id, void *out, ww_stream_t stream);
+int ww_add_relu_st_fwd(ww_ctx *ctx, int storage, const void *a, const void *b, size_t n, void *y, ww_stream_t stream);
+int ww_seq_round_st(ww_ctx *ctx, int storage, const float *x, int B, int T, int F, int transposed, void *out, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ GRU layer, one direction
  * torch.nn.GRU's cell and parameter layout (gate order r|z|n; w_ih (3H,I), w_hh (3H,H), b_ih, b_hh (3H)) -- what the
  * reference's GRUWakeword wraps (src/models/architectures.py:228-235).  batch_first: x (B,T,I) with row stride ldx

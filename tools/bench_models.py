@@ -21,17 +21,20 @@ dev = "cuda:0"
 CONFIGS = (("crnn", 512, "bf16"), ("crnn", 4096, "bf16"), ("gru", 4096, "fp32"), ("mobilenetv3", 256, "bf16"),
            ("mobilenetv3", 2048, "bf16"))
 GRAPH = "--graph" in sys.argv                 # replay the step as a captured HIP graph (Trainer hip_graph mode)
-# --storage (resnet18): also run the step with 16-bit activation storage (storage = the matrix mode) -- the fp32-storage arm first, the
-# storage arm second, the torch yardstick once, between them (after the first arm), all in this process
-STORAGE = "--storage" in sys.argv
-argv = [a for a in sys.argv[1:] if a not in ("--graph", "--storage")]
+# --storage (resnet18 | tcn): also run the step with 16-bit activation storage (storage = the matrix mode) -- the fp32-storage arm first,
+# the storage arm second, resnet18's torch yardstick once, between them (after the first arm), all in this process
+# --storage-only: the storage arm alone (a profiler run of that arm)
+STORAGE_ONLY = "--storage-only" in sys.argv
+STORAGE = "--storage" in sys.argv or STORAGE_ONLY
+argv = [a for a in sys.argv[1:] if a not in ("--graph", "--storage", "--storage-only")]
 if argv:                                      # e.g.  bench_models.py crnn 4096 fp16 [--graph]  |  lstm 512 fp32  |  tcn 512 bf16
     CONFIGS = ((argv[0], int(argv[1]), argv[2]),)          # | resnet18 128 bf16 [N_MELS N_SAMPLES: 128 40000 = the preset's features]
 N_MELS, N_SAMPLES = (int(argv[3]), int(argv[4])) if len(argv) > 4 else (40, 24000)
-if STORAGE and (len(CONFIGS) != 1 or CONFIGS[0][0] != "resnet18" or CONFIGS[0][2] == "fp32"):
-    sys.exit("--storage: resnet18 in a 16-bit matrix mode only, e.g.  bench_models.py resnet18 128 bf16 128 40000 --storage")
+if STORAGE and (len(CONFIGS) != 1 or CONFIGS[0][0] not in ("resnet18", "tcn") or CONFIGS[0][2] == "fp32"):
+    sys.exit("--storage: resnet18 or tcn in a 16-bit matrix mode only, e.g.  bench_models.py resnet18 128 bf16 128 40000 --storage  |  "
+             "bench_models.py tcn 512 bf16 --storage")
 TORCH_MS = None
-RUNS = [c + (None,) for c in CONFIGS] + ([CONFIGS[0] + (CONFIGS[0][2],)] if STORAGE else [])
+RUNS = ([] if STORAGE_ONLY else [c + (None,) for c in CONFIGS]) + ([CONFIGS[0] + (CONFIGS[0][2],)] if STORAGE else [])
 for arch, B, act, storage in RUNS:
     cfg = get_preset("cnn_small_logmel40")
     cfg.training.batch_size = B
@@ -86,7 +89,7 @@ for arch, B, act, storage in RUNS:
         t_ms = TORCH_MS
         extra = {"features": [1, F_, T_], "conv_tflops": round(3 * B * conv_flop(F_, T_) / dt / 1e12, 2),
                  "torch_ms_per_step_no_front_end": round(t_ms, 3), "native_over_torch": round(dt * 1e3 / t_ms, 3)}
-    print(json.dumps({"model": arch, "batch": B, "conv_storage": act if arch == "crnn" else (storage or "fp32" if arch == "resnet18" else None), "matrix_mode": act,
+    print(json.dumps({"model": arch, "batch": B, "conv_storage": act if arch == "crnn" else (storage or "fp32" if arch in ("resnet18", "tcn") else None), "matrix_mode": act,
                       "hip_graph": tr._graph is not None, "loss_scale": tr.scaler.get_scale() if tr.loss_scale is not None else None,
                       "ms_per_step": round(dt * 1e3, 3),
                       "samples_per_s": round(B / dt, 1),

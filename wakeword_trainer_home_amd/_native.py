@@ -172,6 +172,12 @@ _SIGS = {
     "ww_mean_hw_st_fwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "ww_mean_hw_st_bwd": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "ww_relu_mask_st_bwd": (C.c_int, [_vp, _i, _vp, _vp, _sz, _vp, _vp]),
+    "ww_tconv1d_st_scratch_bytes": (_sz, [_i] * 6),
+    "ww_tconv1d_st_fwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ww_tconv1d_st_bwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ww_dropout_bt_st": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _f, _u64, _u64, _u64, _i, _vp, _vp]),
+    "ww_add_relu_st_fwd": (C.c_int, [_vp, _i, _vp, _vp, _sz, _vp, _vp]),
+    "ww_seq_round_st": (C.c_int, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ww_dropout_bt": (C.c_int, [_vp, _vp, C.c_long, _i, _i, _i, _f, _u64, _u64, _u64, _i, _vp, C.c_long, _vp]),
     "ww_nhwc_scratch_bytes": (_sz, [_i]),
     "ww_bn_act_fwd": (C.c_int, [_vp, _vp, C.c_long, _i, C.POINTER(BN), _i, _vp, _vp, _vp, _vp, _vp]),
@@ -1049,6 +1055,102 @@ def relu_mask_st_bwd(dy, y):
     with _guard(dev):
         _check(load().ww_relu_mask_st_bwd(ctx(dev), _st_code(dy, y), _p(dy), _p(y), dy.numel(), _p(dx), _stream(dev)), "ww_relu_mask_st_bwd")
     return dx
+
+
+# ---- the causal Conv1d layer with 16-bit activation storage (TCNWakeword(storage=...)): contiguous bf16 / fp16 (B, T, C) tensors
+def _tconv_st_check(x, w, *more):
+    if x.dim() != 3 or w.dim() != 3 or x.shape[2] != w.shape[1] or w.dtype != torch.float32:
+        raise ValueError(f"tconv1d: need 16-bit x (B,T,Cin) and float32 weight (Cout,Cin,k), got {tuple(x.shape)} and {tuple(w.shape)}")
+    for t in (x,) + more:
+        if t is not None and not t.is_contiguous():
+            raise ValueError("tconv1d: 16-bit activation tensors must be contiguous")
+
+
+def _tconv_st_scratch(code, B, T, Cin, Cout, k, dev):
+    return torch.empty(max(load().ww_tconv1d_st_scratch_bytes(code, B, T, Cin, Cout, k) // 4, 4), dtype=torch.float32, device=dev)
+
+
+def tconv1d_st_fwd(x, w, bias, dilation=1, relu=False, residual=None):
+    """y = S([relu](causal_conv1d(x, S(w), dilation) + bias [+ residual])); x (B,T,Cin) and residual in S = bf16 | fp16 -> y in S."""
+    dev = _dev(x, w, bias, residual)
+    _tconv_st_check(x, w, residual)
+    code = _st_code(x, residual)
+    B, T, Cin = x.shape
+    Cout, _, k = w.shape
+    if residual is not None and tuple(residual.shape) != (B, T, Cout):
+        raise ValueError(f"tconv1d: residual must be {(B, T, Cout)}, got {tuple(residual.shape)}")
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (Cout,):
+        raise ValueError(f"tconv1d: bias must be float32 ({Cout},), got {bias.dtype} {tuple(bias.shape)}")
+    y = torch.empty((B, T, Cout), dtype=x.dtype, device=dev)
+    scratch = _tconv_st_scratch(code, B, T, Cin, Cout, k, dev)
+    with _guard(dev):
+        _check(load().ww_tconv1d_st_fwd(ctx(dev), code, _p(x), _p(w), _p(bias), B, T, Cin, Cout, k, dilation, int(relu), _p(residual),
+                                        _p(y), _p(scratch), scratch.numel() * 4, _stream(dev)), "ww_tconv1d_st_fwd")
+    return y
+
+
+def tconv1d_st_bwd(x, w, dy, dilation=1, y=None, y2=None, mask_scale=1.0, need_dx=True, dx=None, dw_out=None, db_out=None,
+                   defer=False):
+    """tconv1d_bwd on 16-bit x, dy, y, y2, dx: -> (dx | None, dw fp32, db fp32).  dx given: dx = S(dX + float(dx))."""
+    dev = _dev(x, w, dy, y, y2, dx)
+    _tconv_st_check(x, w, dy, y, y2, dx)
+    code = _st_code(x, dy, y, y2, dx)
+    B, T, Cin = x.shape
+    Cout, _, k = w.shape
+    for t in (dy, y, y2):
+        if t is not None and tuple(t.shape) != (B, T, Cout):
+            raise ValueError(f"tconv1d backward: dy / y / y2 must be {(B, T, Cout)}, got {tuple(t.shape)}")
+    if dx is not None and tuple(dx.shape) != (B, T, Cin):
+        raise ValueError(f"tconv1d backward: dx must be {(B, T, Cin)}, got {tuple(dx.shape)}")
+    accumulate = dx is not None
+    if dx is None and need_dx:
+        dx = torch.empty((B, T, Cin), dtype=x.dtype, device=dev)
+    dw = _out(dw_out, (Cout, Cin, k), dev)
+    db = _out(db_out, (Cout,), dev)
+    scratch = _tconv_st_scratch(code, B, T, Cin, Cout, k, dev)
+    with _guard(dev), (_deferring(dev, scratch) if defer else contextlib.nullcontext()):
+        _check(load().ww_tconv1d_st_bwd(ctx(dev), code, _p(x), _p(w), _p(y), _p(y2), mask_scale, _p(dy), B, T, Cin, Cout, k, dilation,
+                                        _p(dx), int(accumulate), _p(dw), _p(db), _p(scratch), scratch.numel() * 4, _stream(dev)),
+               "ww_tconv1d_st_bwd")
+    return dx, dw, db
+
+
+def dropout_bt_st(x, p, seed=0, step=0, sample_offset=0, stream_id=0, out=None):
+    """dropout_bt on a contiguous 16-bit (B,T,C) tensor: out = S(keep ? x / (1 - p) : 0); out may be x (in place)."""
+    dev = _dev(x, out)
+    if x.dim() != 3 or not x.is_contiguous() or (out is not None and (out.shape != x.shape or not out.is_contiguous())):
+        raise ValueError("dropout_bt_st: need contiguous (B,T,C) tensors of one shape")
+    if out is None:
+        out = torch.empty_like(x)
+    B, T, Cc = x.shape
+    with _guard(dev):
+        _check(load().ww_dropout_bt_st(ctx(dev), _st_code(x, out), _p(x), B, T, Cc, p, seed, step, sample_offset, stream_id, _p(out),
+                                       _stream(dev)), "ww_dropout_bt_st")
+    return out
+
+
+def add_relu_st_fwd(a, b):
+    dev = _dev(a, b)
+    if a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous():
+        raise ValueError("add_relu_st_fwd: need two contiguous tensors of one shape")
+    y = torch.empty_like(a)
+    with _guard(dev):
+        _check(load().ww_add_relu_st_fwd(ctx(dev), _st_code(a, b), _p(a), _p(b), a.numel(), _p(y), _stream(dev)), "ww_add_relu_st_fwd")
+    return y
+
+
+def seq_round_st(x, storage, transposed=True):
+    """The network input in S: x float32 (B,F,T) (transposed: also a contiguous (B,1,F,T) batch) or (B,T,F) -> (B,T,F) in S."""
+    dev = _dev(x)
+    if x.dim() == 4 and x.shape[1] == 1:
+        x = x[:, 0]
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError(f"seq_round_st: need a contiguous float32 (B,F,T) or (B,T,F) tensor, got {x.dtype} {tuple(x.shape)}")
+    B, T, F = (x.shape[0], x.shape[2], x.shape[1]) if transposed else x.shape
+    out = torch.empty((B, T, F), dtype=storage, device=dev)
+    with _guard(dev):
+        _check(load().ww_seq_round_st(ctx(dev), _st_code(out), _p(x), B, T, F, int(transposed), _p(out), _stream(dev)), "ww_seq_round_st")
+    return out
 
 
 # ---- generic channels-last layers (MobileNetV3 body); activations are contiguous fp32 (M, C) / (B, H, W, C) tensors

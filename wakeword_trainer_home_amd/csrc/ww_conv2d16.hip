@@ -2,11 +2,11 @@
 // mean, and every gradient of one, is S = bf16 | fp16 in HBM (the `_st` entry points of wwhip.h; ww_conv2d.hip is the fp32-storage
 // path).  The contract: arithmetic is fp32, a value is rounded (RNE, Act<S>::pack2) exactly where a tensor is stored and nowhere
 // else, and BatchNorm statistics are taken from the STORED values (ww_act.h), finished in fp64 from fp32 partials.
-//   * Conv2d: the tap GEMM of ww_tap_gemm.h with the image geometry of ww_image.h, in the forms whose A operand already has the
-//     matrix cores' type in HBM: a stage is two 16-byte loads per thread and operand whose halves go into the LDS tile as they
-//     are -- no conversion in the staging loop.  The weights are rounded once, by the per-tap packing pass.  The rows kernel stores
-//     S(acc) (S(acc + float(C)) when it accumulates); the dW kernel leaves fp32 partials for the existing sum / ww_defer path.
-//     With a partials pointer the forward rows kernel also leaves the per-column sums of its tile's STORED values and their squares.
+//   * Conv2d: the 16-bit tap GEMM of ww_tap_gemm16.h (operands already of the matrix cores' type in HBM) with the image geometry of
+//     ww_image.h, blocked summation, no epilogue and the statistics tail.  The weights are rounded once, by the per-tap packing pass.
+//     The rows kernel stores S(acc) (S(acc + float(C)) when it accumulates); the dW kernel leaves fp32 partials for the existing sum
+//     / ww_defer path.  With a partials pointer the forward rows kernel also leaves the per-column sums of its tile's STORED values
+//     and their squares.
 //   * BatchNorm(+activation): those partials (folded once when there are more than 1024 tiles), or a column-statistics pass over the
 //     16-bit tensor where no producer left any (the stem) -> k_bn_finish (ww_nhwc.hip) -> one apply pass that can
 //     add a residual, plain or with a scale|shift of its own: the block tail relu(bn2(c2) + (x | bn_d(cd))) is ONE pass with one
@@ -15,195 +15,9 @@
 // Channel counts are multiples of 8: a 16-byte access is 8 elements.
 #include "ww_image.h"
 #include "ww_layers.h"
+#include "ww_tap_gemm16.h"
 
 namespace {
-
-// ---- 8 consecutive elements of a 16-bit tensor
-template <typename T> __device__ __forceinline__ void ld8(const T *p, float (&v)[8]) {
-    const uint4 r = *reinterpret_cast<const uint4 *>(p);
-    const float2 a = Act<T>::cvt2(r.x), b = Act<T>::cvt2(r.y), c = Act<T>::cvt2(r.z), d = Act<T>::cvt2(r.w);
-    v[0] = a.x; v[1] = a.y; v[2] = b.x; v[3] = b.y; v[4] = c.x; v[5] = c.y; v[6] = d.x; v[7] = d.y;
-}
-__device__ __forceinline__ void ld8(const float *p, float (&v)[8]) {
-    const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-template <typename T> __device__ __forceinline__ void st8(T *p, const float (&v)[8]) {
-    Act<T>::st8(p, make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]));
-}
-
-// ---- the tap GEMM with 16-bit operands in HBM.  Tiles, lane map, MFMA stage and summation are ww_tap_gemm.h's; KT = 64, so an
-// operand tile is 64 rows x 8 uint4 = two uint4 per thread.
-constexpr int KT16 = 64;
-template <class Fetch, class Mfma>
-__device__ __forceinline__ void stages16(void *As, void *Bs, int ld, int stages, Fetch &&fetch, Mfma &&mfma) {
-    const int tid = threadIdx.x;
-    uint4 va[2], vb[2];
-    fetch(0, va, vb);
-    for (int it = 0; it < stages; ++it) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = tid + 256 * j, off = ((q >> 3) * ld + 8 * (q & 7)) * 2;      // bytes
-            *reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(As) + off) = va[j];
-            *reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(Bs) + off) = vb[j];
-        }
-        __syncthreads();
-        if (it + 1 < stages) fetch(it + 1, va, vb);
-        mfma();
-    }
-}
-
-// rows: C[m][n] = S( sum_seg sum_c A[src(m, seg)][c] W[seg][n][c] (+ float(C[m][n])) ).  grid: x = N tiles, y = M tiles.
-template <typename H, bool DX>
-struct Rows16 {
-    const H *A;      // the tensor being read, rows of CA elements
-    const H *W;      // (nseg, N, CA): k_tap_pack16
-    H *C;            // (M, N)
-    float *part;     // nullable: [M tile][sum (N) | sum of squares (N)] of the ROUNDED values of the tile's rows (BatchNorm's statistics)
-    int M, CA, N, nseg, accumulate;
-    ImageRows<DX> g;
-};
-template <int MODE, bool DX>
-__global__ __launch_bounds__(256) void k_tap_rows16(Rows16<typename ModeH<MODE>::type, DX> a) {
-    typedef TapTile<MODE> TT;
-    typedef typename ModeH<MODE>::type H;
-    __shared__ __align__(16) unsigned char lds[2 * TT::ROWS_BYTES];
-    void *As = lds, *Bs = lds + TT::ROWS_BYTES;
-    const int tid = threadIdx.x;
-    const TapLane t;
-    const long m0 = (long)blockIdx.y * 64;
-    const int n0 = blockIdx.x * 64;
-    typename ImageRows<DX>::Row row[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) row[j] = a.g.row(m0 + ((tid + 256 * j) >> 3), a.M);
-    const int nk = (a.CA + KT16 - 1) / KT16;
-    auto fetch = [&](int it, uint4(&va)[2], uint4(&vb)[2]) {
-        const int seg = it / nk, k0 = (it - seg * nk) * KT16;
-        const auto tap = a.g.tap(seg);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = tid + 256 * j, kk = k0 + 8 * (q & 7), n = n0 + (q >> 3);
-            va[j] = vb[j] = make_uint4(0u, 0u, 0u, 0u);
-            long at = 0;
-            if (a.g.src(row[j], m0 + (q >> 3), tap, at) & (kk < a.CA)) va[j] = *reinterpret_cast<const uint4 *>(a.A + at * a.CA + kk);
-            if (n < a.N && kk < a.CA) vb[j] = *reinterpret_cast<const uint4 *>(a.W + ((long)seg * a.N + n) * a.CA + kk);
-        }
-    };
-    SumBlocked sum;
-    int in_tap = 0;
-    stages16(As, Bs, TT::LD_ROWS, a.nseg * nk, fetch, [&] {
-        sum.out(tap_mfma_rows<MODE>(As, Bs, t, sum.in()));
-        if (++in_tap == nk) { sum.end_tap(); in_tap = 0; }
-    });
-    // a lane holds ONE column of 16 rows; neighbouring lanes hold neighbouring columns.  Lanes (2i, 2i + 1) trade every other register,
-    // after which the even lane holds both columns of the even registers' rows and the odd lane those of the odd registers' rows: eight
-    // 4-byte stores per lane instead of sixteen 2-byte ones
-    const floatx16 acc = sum.total();
-    // forward statistics from the epilogue: per column the fp32 sums of the 64 rows' STORED values and of their squares, in a fixed
-    // order -- the lane's 16 registers, then the two lane halves (rows 4h .. of each group of 8), then the two row wavefronts through
-    // LDS.  Rows past M and columns past N hold zeros.  (a.part is uniform: every thread of the grid takes the same branch.)
-    if (a.part) {
-        __shared__ float sh[2][2][64];
-        float s = 0.f, q = 0.f;
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const float v = Act<H>::round1(acc[reg]);
-            if (m0 + tap_d_row(t, reg) < a.M) { s += v; q = fmaf(v, v, q); }
-        }
-        const float s1 = __shfl_xor(s, 32), q1 = __shfl_xor(q, 32);
-        if (t.h == 0) { sh[0][t.rh][t.d_col()] = s + s1; sh[1][t.rh][t.d_col()] = q + q1; }
-        __syncthreads();
-        if (tid < 64 && n0 + tid < a.N) {
-            float *p = a.part + (long)blockIdx.y * 2 * a.N + n0 + tid;
-            p[0] = sh[0][0][tid] + sh[0][1][tid];
-            p[a.N] = sh[1][0][tid] + sh[1][1][tid];
-        }
-    }
-    const int odd = t.lane & 1;
-    float lo[8], hi[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const float got = __shfl_xor(odd ? acc[2 * i] : acc[2 * i + 1], 1);
-        lo[i] = odd ? got : acc[2 * i];
-        hi[i] = odd ? acc[2 * i + 1] : got;
-    }
-    const int col = n0 + (t.d_col() & ~1);
-    if (col >= a.N) return;                        // (N is even: both columns of a pair are in range or neither is)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const long r = m0 + tap_d_row(t, 2 * i + odd);
-        if (r >= a.M) continue;
-        H *p = a.C + r * a.N + col;
-        float2 v = make_float2(lo[i], hi[i]);
-        if (a.accumulate) {
-            const float2 o = Act<H>::cvt2(Act<H>::ldraw2(p));
-            v.x += o.x; v.y += o.y;
-        }
-        Act<H>::st2(p, v);
-    }
-}
-
-// dW: out[z][n][c][seg] = sum_{m in range z} G[m][n] X[src(m, seg)][c], fp32.  grid: x = c tiles, y = n tiles, z = seg * nsplit + range
-template <typename H>
-struct Dw16 {
-    const H *G;      // the output gradient (M, N)
-    const H *X;      // the layer input, rows of C elements
-    float *out;      // (nsplit, N, C, nseg)
-    int M, N, C, nseg, rps, nsplit;
-    ImageDw g;
-};
-template <int MODE>
-__global__ __launch_bounds__(256) void k_tap_dw16(Dw16<typename ModeH<MODE>::type> a) {
-    typedef TapTile<MODE> TT;
-    __shared__ __align__(16) unsigned char lds[2 * TT::DW_BYTES];
-    void *As = lds, *Bs = lds + TT::DW_BYTES;
-    const int tid = threadIdx.x;
-    const TapLane t;
-    const int c0 = blockIdx.x * 64, n0 = blockIdx.y * 64;
-    const int seg = blockIdx.z / a.nsplit, z = blockIdx.z - seg * a.nsplit;
-    const int mb = (int)min((long)a.M, (long)z * a.rps), me = (int)min((long)a.M, (long)mb + a.rps);
-    const auto tap = a.g.tap(seg);
-    auto fetch = [&](int it, uint4(&va)[2], uint4(&vb)[2]) {
-        const int mk0 = mb + it * KT16;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int q = tid + 256 * j, m = mk0 + (q >> 3), e = 8 * (q & 7);
-            const bool okm = m < me;
-            va[j] = vb[j] = make_uint4(0u, 0u, 0u, 0u);
-            if (okm && n0 + e < a.N) va[j] = *reinterpret_cast<const uint4 *>(a.G + (long)m * a.N + n0 + e);
-            long at = 0;
-            const bool hit = a.g.src(okm ? m : 0, tap, at);
-            if (okm && c0 + e < a.C && hit) vb[j] = *reinterpret_cast<const uint4 *>(a.X + at * a.C + c0 + e);
-        }
-    };
-    SumBlocked sum;
-    stages16(As, Bs, TT::LD_DW, (me - mb + KT16 - 1) / KT16, fetch, [&] { sum.out(tap_mfma_dw<MODE>(As, Bs, t, sum.in())); });
-    sum.end_tap();
-    const int c = c0 + t.d_col();
-    if (c >= a.C) return;
-    const floatx16 acc = sum.total();
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int n = n0 + tap_d_row(t, reg);
-        if (n < a.N) a.out[(((long)z * a.N + n) * a.C + c) * a.nseg + seg] = acc[reg];
-    }
-}
-
-// k_tap_pack with the weights rounded to the matrix type on the way: out[s][n][c] | out[s][c][n] = S(w[n][c][s])
-template <typename H>
-__global__ __launch_bounds__(256) void k_tap_pack16(const float *__restrict__ w, int Cout, int Cin, int nseg, int transpose,
-                                                    H *__restrict__ out) {
-    const long per = (long)Cout * Cin, n_all = per * nseg;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_all; i += (long)gridDim.x * 256) {
-        const int s = (int)(i / per);
-        const long rem = i - (long)s * per;
-        int n, c;
-        if (transpose) { c = (int)(rem / Cout); n = (int)(rem - (long)c * Cout); }
-        else { n = (int)(rem / Cin); c = (int)(rem - (long)n * Cin); }
-        reinterpret_cast<uint16_t *>(out)[i] = (uint16_t)Act<H>::pack2(w[((long)n * Cin + c) * nseg + s], 0.f);
-    }
-}
 
 // ---- column statistics of a tall 16-bit (M, C) matrix: thread = (8 columns, row lane), one workgroup per row chunk, fp64
 // accumulators that meet in LDS in a fixed order.  part[chunk][0:C | C:2C] (fp32) =
@@ -417,20 +231,12 @@ __global__ __launch_bounds__(256) void k_mean_bwd16(uint32_t n8, const float *__
 // ---- host side
 // f(T *) with T = the storage type of code st (WW_ACT_BF16 | WW_ACT_F16; the callers have refused everything else)
 template <class F>
-void with_mode16(int st, F &&f) {      // f(std::integral_constant<int, MODE>), MODE = 1 | 2
-    if (st == WW_ACT_BF16) f(std::integral_constant<int, 1>{});
-    else f(std::integral_constant<int, 2>{});
-}
-template <class F>
 void with_storage(int st, F &&f) {
     if (st == WW_ACT_BF16) f((ww_bf16 *)nullptr);
     else f((ww_f16 *)nullptr);
 }
-bool storage_ok(int st) { return st == WW_ACT_BF16 || st == WW_ACT_F16; }
-#define ST_REQUIRE_STORAGE(who, st) \
-    WW_REQUIRE(storage_ok(st), WW_E_INVALID, "%s: storage must be WW_ACT_BF16 or WW_ACT_F16, got %d", who, st)
-// elementwise launches: n elements, 8 per thread, at most 4096 workgroups
-bool ew8_ok(long n) { return n >= 8 && n % 8 == 0 && n / 8 < (1L << 31); }
+// the image layer's instantiations of the 16-bit tap GEMM
+template <typename H, bool DX> using ImageRows16 = Rows16<H, ImageRows<DX>, Epi16None, Tail16Stats>;
 
 struct Layout16 { size_t wp_bytes, total_bytes; };      // [packed 16-bit weights | fp32 dW partials]
 Layout16 layout16(long M, int Cin, int Cout, int k) {
@@ -491,9 +297,9 @@ extern "C" int ww_conv2d_st_fwd(ww_ctx *ctx, int storage, const void *x, const f
         constexpr int MODE = decltype(m)::value;
         typedef typename ModeH<MODE>::type Hh;
         hipLaunchKernelGGL(k_tap_pack16<Hh>, dim3(ew_grid((long)k * k * Cin * Cout)), dim3(256), 0, st, w, Cout, Cin, k * k, 0, (Hh *)scratch);
-        const Rows16<Hh, false> a{(const Hh *)x, (const Hh *)scratch, (Hh *)y, stat_part, (int)M, Cin, Cout, k * k, 0,
-                                  {Ho, Wo, H, W, k, stride, k / 2}};
-        hipLaunchKernelGGL((k_tap_rows16<MODE, false>), grid, dim3(256), 0, st, a);
+        const ImageRows16<Hh, false> a{(const Hh *)x, (const Hh *)scratch, (Hh *)y, {stat_part}, (int)M, Cin, Cout, k * k, 0,
+                                       {Ho, Wo, H, W, k, stride, k / 2}, {}};
+        hipLaunchKernelGGL((k_tap_rows16<MODE, ImageRows<false>, SumBlocked, Epi16None, Tail16Stats>), grid, dim3(256), 0, st, a);
     });
     WW_LAUNCH_CHECK();
     return WW_OK;
@@ -513,10 +319,9 @@ extern "C" int ww_conv2d_st_bwd(ww_ctx *ctx, int storage, const void *x, const f
     hipStream_t st = (hipStream_t)stream;
     ww_prof_scope ps_(ctx, WW_K_LINEAR, st);
     float *part = (float *)((unsigned char *)scratch + l.wp_bytes);
-    // the dW row ranges of tap_dw (ww_tap_gemm.h): whole K stages per range
-    const int want = dw_splits(M, Cin, Cout, kk);
-    const long rps = ((M + want - 1) / want + KT16 - 1) / KT16 * KT16;
-    const int nz = (int)((M + rps - 1) / rps);
+    const DwRanges rg = dw_ranges16(M, Cin, Cout, kk);
+    const long rps = rg.rps;
+    const int nz = rg.nz;
     const long n = (long)Cout * Cin * kk;
     with_mode16(storage, [&](auto m) {
         constexpr int MODE = decltype(m)::value;
@@ -524,12 +329,14 @@ extern "C" int ww_conv2d_st_bwd(ww_ctx *ctx, int storage, const void *x, const f
         if (dx) {
             hipLaunchKernelGGL(k_tap_pack16<Hh>, dim3(ew_grid((long)kk * Cin * Cout)), dim3(256), 0, st, w, Cout, Cin, kk, 1, (Hh *)scratch);
             const long Mx = (long)B * H * W;
-            const Rows16<Hh, true> a{(const Hh *)dy, (const Hh *)scratch, (Hh *)dx, nullptr, (int)Mx, Cout, Cin, kk, accumulate_dx != 0,
-                                     {H, W, Ho, Wo, k, stride, k / 2}};
-            hipLaunchKernelGGL((k_tap_rows16<MODE, true>), dim3((Cin + 63) / 64, (unsigned)((Mx + 63) / 64)), dim3(256), 0, st, a);
+            const ImageRows16<Hh, true> a{(const Hh *)dy, (const Hh *)scratch, (Hh *)dx, {nullptr}, (int)Mx, Cout, Cin, kk,
+                                          accumulate_dx != 0, {H, W, Ho, Wo, k, stride, k / 2}, {}};
+            hipLaunchKernelGGL((k_tap_rows16<MODE, ImageRows<true>, SumBlocked, Epi16None, Tail16Stats>),
+                               dim3((Cin + 63) / 64, (unsigned)((Mx + 63) / 64)), dim3(256), 0, st, a);
         }
-        const Dw16<Hh> d{(const Hh *)dy, (const Hh *)x, nz > 1 ? part : dw, (int)M, Cout, Cin, kk, (int)rps, nz, {Ho, Wo, H, W, k, stride, k / 2}};
-        hipLaunchKernelGGL(k_tap_dw16<MODE>, dim3((Cin + 63) / 64, (Cout + 63) / 64, kk * nz), dim3(256), 0, st, d);
+        const Dw16<Hh, ImageDw> d{(const Hh *)dy, (const Hh *)x, nz > 1 ? part : dw, (int)M, Cout, Cin, kk, (int)rps, nz,
+                                  {Ho, Wo, H, W, k, stride, k / 2}};
+        hipLaunchKernelGGL((k_tap_dw16<MODE, ImageDw, SumBlocked>), dim3((Cin + 63) / 64, (Cout + 63) / 64, kk * nz), dim3(256), 0, st, d);
     });
     WW_LAUNCH_CHECK();
     if (nz > 1 && !ww_defer(ctx, part, dw, n, nz, 0)) {

@@ -8,7 +8,7 @@
 // is here, once: 64 x 64 block tiles, 4 wavefronts x one 32x32 MFMA tile; mode WW_ACT_F32: v_mfma_f32_32x32x2_f32 (an exact fp32
 // fma chain, the parity mode); WW_ACT_BF16 / WW_ACT_F16: operands rounded when they are staged into LDS,
 // v_mfma_f32_32x32x16_{bf16,f16}, fp32 accumulation.  All tensors are fp32 in HBM; channel counts are multiples of 4 and buffers
-// 16-byte aligned (al16), so every global access is a float4 and a K tail is whole float4s of zeros.  (ww_conv2d16.hip has the rows / dW
+// 16-byte aligned (al16), so every global access is a float4 and a K tail is whole float4s of zeros.  (ww_tap_gemm16.h has the rows / dW
 // forms whose operands are ALREADY 16-bit in HBM: the same tiles, lane map, MFMA stage and summation, a staging loop of their own.)
 // (A 128 x 128 form of the rows kernel -- each staged byte feeding twice the MFMA work, 224 VGPRs -- was measured on the Conv1d
 // layer and dropped: the B = 512 step read 2.27 ms against 2.16 in the 16-bit modes and 3.17 against 3.08 in fp32.)

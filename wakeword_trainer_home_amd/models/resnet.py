@@ -26,8 +26,8 @@ from .flat_buckets import FlatBuckets, grad_slot
 from .heads import MFMALinear
 from .mobilenet import _BN, _Conv, _PoolFn
 from .recurrent import _HiddenDropout
+from .storage import _storage
 
-_MODES = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
 LAYERS = ((64, 1), (128, 2), (256, 2), (512, 2))          # (planes, stride of the stage's first block); two blocks per stage
 
 
@@ -42,20 +42,6 @@ def _bn(c):
     bn = _BN(c)
     bn.eps, bn.momentum = 1e-5, 0.1
     return bn
-
-
-def _storage(mode, storage):
-    """(matrix mode, storage) as torch dtypes.  A 16-bit storage must be the matrix mode: an operand in HBM then already has the
-    matrix cores' type."""
-    m, s = _MODES.get(mode, mode), _MODES.get(storage, storage)
-    nat.act_code(m)
-    if s is torch.float32:
-        return m, s
-    if s not in (torch.bfloat16, torch.float16):
-        raise ValueError(f"storage must be 'fp32', 'bf16' or 'fp16', got {storage!r}")
-    if s is not m:
-        raise ValueError(f"16-bit activation storage must equal the matrix mode: storage={storage!r} with mode={mode!r}")
-    return m, s
 
 
 def _bn_fwd(bn, y, act, **st):
