@@ -371,6 +371,38 @@ int ww_ce2_loss_weighted_fwd_bwd(ww_ctx *ctx, const float *logits, const int64_t
                                  int reduction, int mean_divisor, float *loss_out, float *loss_vec, float *dlogits,
                                  ww_step_stats *stats, float *found_inf_out, const ww_loss_scale *loss_scale,
                                  int loss_scale_slot, ww_stream_t stream);
+/* The same losses for C = num_classes columns, 2 <= C <= WW_LOSS_MAX_CLASSES (anything else is WW_E_INVALID): what the
+ * reference's three losses compute for any width (src/models/losses.py:66-102, :163-212, :256).  logits and dlogits are (B,C),
+ * class_weight is C floats in DEVICE memory read at run time (NULL = ones), w_b = class_weight[y_b].  Per sample, with
+ * p = softmax(z), lp = log_softmax(z) and onehot of the target y:
+ *   CE, smoothing eps   s = onehot (1-eps) + (1-onehot) eps/(C-1);  l = -sum_j s_j lp_j;  g = p - s
+ *   focal               pt = clamp(p[y], 1e-7, 1-1e-7), fw = (1-pt)^gamma, a_t = alpha if y == 1 else 1-alpha (class 1 is the
+ *                       wakeword for every C), ce = -lp[y];  l = a_t fw ce;
+ *                       g_j = a_t (fw (p_j - onehot_j) + dfw ce p[y] (onehot_j - p_j)), dfw = -gamma (1-pt)^(gamma-1) strictly
+ *                       inside the clamp and for gamma != 0, else 0
+ * and the table of the entry above holds unchanged, s = the loss scale:
+ *
+ *   reduction, mean_divisor        loss                      dlogits[b][j]
+ *   MEAN, WW_DIV_BATCH             sum w_b l_b / B           s w_b g_bj / B
+ *   MEAN, WW_DIV_WEIGHT_SUM        sum w_b l_b / sum w_b     s w_b g_bj / sum w_b
+ *   SUM                            sum w_b l_b               s w_b g_bj
+ *   NONE                           loss_vec[b] = w_b l_b     s w_b g_bj
+ *
+ * loss_out, stats->loss, loss_vec, found_inf_out, loss_scale / loss_scale_slot and the ww_step_ctl parity are those of the entry
+ * above; sums run in double in one fixed order.  A target outside [0,C) is clamped to 0 or C-1, takes that class's weight and
+ * sets bad_target and found_inf.  The counters keep the reference's meaning (src/training/metrics.py:105-116): pred = the first
+ * index of the row maximum under > (a NaN never wins), correct = #(pred == y), tp = #(pred==1 & y==1), tn = #(pred==0 & y==0),
+ * fp = #(pred==1 & y==0), fn = #(pred==0 & y==1), count = B -- so tp+tn+fp+fn < count once classes 2.. occur.
+ * confusion (nullable): C x C uint64 in DEVICE memory indexed [target][pred], added to and never reset here; the batch is
+ * counted in LDS and added only when this launch leaves found_inf at 0 (finite loss, no bad target) -- the batches the
+ * reference's tracker sees (src/training/trainer.py:177-200).  Integer adds only: independent of any order.
+ * One block, one thread per sample; rows are walked from global memory, never held in a per-thread array. */
+#define WW_LOSS_MAX_CLASSES 64
+int ww_cen_loss_fwd_bwd(ww_ctx *ctx, const float *logits, const int64_t *targets, int B, int num_classes, int loss_kind,
+                        float label_smoothing, float focal_alpha, float focal_gamma, const float *class_weight,
+                        int reduction, int mean_divisor, float *loss_out, float *loss_vec, float *dlogits,
+                        ww_step_stats *stats, float *found_inf_out, uint64_t *confusion /* nullable */,
+                        const ww_loss_scale *loss_scale, int loss_scale_slot, ww_stream_t stream);
 /* Replaces clip_gradients -> torch.nn.utils.clip_grad_norm_
  * (src/training/optimizer_factory.py:446-452) on one flat gradient bucket.  max_norm <= 0:
  * only the norm is computed.  norm_out (nullable) receives the pre-clip L2 norm.          */
@@ -795,6 +827,14 @@ typedef struct {
 int ww_eval_accumulate(ww_ctx *ctx, const float *scores, int score_kind, const int64_t *targets, int B,
                        const double *thresholds, int K, double decision, float *conf, uint8_t *pred, int32_t *bin,
                        size_t offset, uint64_t *hist, ww_eval_counters *counters, ww_stream_t stream);
+/* The WW_SCORE_LOGITS form for logits (B,C), 2 <= C = num_classes <= WW_LOSS_MAX_CLASSES: conf = softmax(row)[1] with the
+ * maximum over all C columns subtracted (src/evaluation/evaluator.py:379-380); pred, bin, hist and the counters as above, with
+ * tp/tn/fp/fn from torch.argmax over the C columns (first maximum wins, a NaN wins, the first NaN wins) on targets 0 and 1.
+ * Targets 2..C-1 are valid: they count in `count` only and stay out of hist, as the reference's ROC loop leaves them out
+ * (evaluator.py:393-399); bad_target counts targets outside [0,C).  Already-computed confidences need no such form. */
+int ww_eval_accumulate_classes(ww_ctx *ctx, const float *logits, int num_classes, const int64_t *targets, int B,
+                               const double *thresholds, int K, double decision, float *conf, uint8_t *pred, int32_t *bin,
+                               size_t offset, uint64_t *hist, ww_eval_counters *counters, ww_stream_t stream);
 /* The chunking of MicrophoneInference's buffer loop (src/evaluation/inference.py:150-153) applied to a whole recording
  * wave (S) fp32 on the device: window w = wave[w*(chunk/2) .. +chunk), W = 0 if S < chunk else (S - chunk)/(chunk/2) + 1 (host
  * only: the first function below); out (W,chunk), peaks (W).  Each window is divided by its own peak max|x| when that is > 0

@@ -242,8 +242,11 @@ _SIGS = {
     "ww_ce2_loss_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "ww_ce2_loss_weighted_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,
                                                _vp]),
+    "ww_cen_loss_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                      _vp]),
     "ww_grad_norm_clip": (C.c_int, [_vp, _vp, _sz, _f, _vp, _vp, _vp]),
     "ww_eval_accumulate": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ww_eval_accumulate_classes": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ww_wave_num_windows": (C.c_long, [C.c_long, _i]),
     "ww_wave_windows": (C.c_int, [_vp, _vp, C.c_long, _i, _i, _vp, _vp, _vp]),
     "ww_loader_indices": (C.c_int, [_vp, _i, _i, _i, _vp, _i, _u64, _u64, _i, _i, C.c_int64, _i, _vp, _vp]),
@@ -1919,6 +1922,48 @@ def ce2_loss_weighted_fwd_bwd(logits, targets, kind=LOSS_CE, label_smoothing=0.0
     return loss, loss_vec, dl, stats
 
 
+LOSS_MAX_CLASSES = 64                 # WW_LOSS_MAX_CLASSES
+
+
+def _num_classes_of(logits, what):
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"{what} needs float32 logits of shape (B,C), got {logits.dtype} {tuple(logits.shape)}")
+    C_ = int(logits.shape[1])
+    if not 2 <= C_ <= LOSS_MAX_CLASSES:
+        raise ValueError(f"{what}: num_classes = {C_} outside [2, {LOSS_MAX_CLASSES}]")
+    return C_
+
+
+def cen_loss_fwd_bwd(logits, targets, kind=LOSS_CE, label_smoothing=0.0, focal_alpha=0.25, focal_gamma=2.0,
+                     class_weight=None, reduction=REDUCE_MEAN, mean_divisor=DIV_BATCH, stats=None, found_inf_out=None,
+                     loss_scale=None, loss_scale_slot=0, confusion=None):
+    """The C-class entry (ww_cen_loss_fwd_bwd; include/wwhip.h has the formulas and the table), C = logits.shape[1] in
+    [2, LOSS_MAX_CLASSES] -> (loss (1,) f32, loss_vec (B,) f32 or None, dlogits (B,C) f32, stats uint8[STEP_STATS_BYTES]).
+    ``class_weight``: float32 device tensor (C,), read through its pointer; None = ones.  ``confusion``: int64 device tensor
+    (C,C) indexed [target, pred] that the launch adds this batch to unless it sets found_inf; None = nothing is counted."""
+    C_ = _num_classes_of(logits, "native loss")
+    if targets.dim() != 1 or targets.shape[0] != logits.shape[0] or targets.dtype != torch.int64:
+        raise ValueError("targets must be int64 of shape (B,)")
+    if class_weight is not None and (class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (C_,)):
+        raise ValueError(f"class_weight must be float32 of shape ({C_},), got {class_weight.dtype} {tuple(class_weight.shape)}")
+    if confusion is not None and (confusion.dtype != torch.int64 or tuple(confusion.shape) != (C_, C_)):
+        raise ValueError(f"confusion must be int64 of shape ({C_}, {C_}), got {confusion.dtype} {tuple(confusion.shape)}")
+    dev = _dev(logits, targets, class_weight, stats, found_inf_out, loss_scale, confusion)
+    B = logits.shape[0]
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    loss_vec = torch.empty(B, dtype=torch.float32, device=dev) if reduction == REDUCE_NONE else None
+    dl = torch.empty_like(logits)
+    if stats is None:
+        stats = torch.zeros(STEP_STATS_BYTES, dtype=torch.uint8, device=dev)
+    with _guard(dev):
+        _check(load().ww_cen_loss_fwd_bwd(ctx(dev), _p(logits), _p(targets), B, C_, kind, label_smoothing, focal_alpha,
+                                          focal_gamma, _p(class_weight), int(reduction), int(mean_divisor), _p(loss),
+                                          _p(loss_vec), _p(dl), _p(stats), _p(found_inf_out), _p(confusion), _p(loss_scale),
+                                          int(loss_scale_slot), _stream(dev)),
+               "ww_cen_loss_fwd_bwd")
+    return loss, loss_vec, dl, stats
+
+
 def grad_norm_clip_(flat, max_norm, norm_out=None, stats=None):
     """clip_grad_norm_ on a flat bucket.  `stats` (uint8[STEP_STATS_BYTES], optional): its grad_norm / found_inf
     fields are updated on the device."""
@@ -1963,6 +2008,29 @@ def eval_accumulate(scores, targets, thresholds, decision, conf, pred, bins, off
         _check(load().ww_eval_accumulate(ctx(dev), _p(scores), kind, _p(targets), B, _p(thresholds), K, float(decision),
                                          _p(conf), _p(pred), _p(bins), offset, _p(hist), _p(counters), _stream(dev)),
                "ww_eval_accumulate")
+
+
+def eval_accumulate_classes(logits, targets, thresholds, decision, conf, pred, bins, offset, hist, counters):
+    """eval_accumulate for logits (B,C), C in [2, LOSS_MAX_CLASSES] (ww_eval_accumulate_classes): the confidence is
+    softmax(row)[1], the counters compare targets 0 and 1 with the argmax over C columns, targets 2..C-1 stay out of hist."""
+    C_ = _num_classes_of(logits, "eval_accumulate_classes")
+    B, K = logits.shape[0], thresholds.numel()
+    if targets is not None and (targets.dtype != torch.int64 or targets.shape != (B,)):
+        raise ValueError("targets must be int64 of shape (B,)")
+    if thresholds.dtype != torch.float64 or thresholds.dim() != 1:
+        raise ValueError("thresholds must be a 1-D float64 tensor")
+    if conf.dtype != torch.float32 or pred.dtype != torch.uint8 or (bins is not None and bins.dtype != torch.int32):
+        raise ValueError("conf / pred / bins must be float32 / uint8 / int32")
+    offset = int(offset)
+    if offset < 0 or any(t is not None and (t.dim() != 1 or t.numel() < offset + B) for t in (conf, pred, bins)):
+        raise ValueError(f"per-sample outputs must be 1-D and hold offset + B = {offset + B} elements")
+    if hist.dtype != torch.int64 or hist.numel() != 2 * (K + 1) or counters.dtype != torch.int64 or counters.numel() != 8:
+        raise ValueError(f"hist must be int64 with 2*(K+1) = {2 * (K + 1)} elements and counters int64 with 8")
+    dev = _dev(logits, targets, thresholds, conf, pred, bins, hist, counters)
+    with _guard(dev):
+        _check(load().ww_eval_accumulate_classes(ctx(dev), _p(logits), C_, _p(targets), B, _p(thresholds), K, float(decision),
+                                                 _p(conf), _p(pred), _p(bins), offset, _p(hist), _p(counters), _stream(dev)),
+               "ww_eval_accumulate_classes")
 
 
 def wave_num_windows(n_samples, chunk):

@@ -86,6 +86,76 @@ __global__ __launch_bounds__(EVAL_BLOCK) void k_eval_accumulate(const float *__r
     }
 }
 
+// The logits form of the kernel above for rows of C columns: conf = softmax(row)[1] with the maximum over all C columns
+// subtracted, the predicted class is torch.argmax over C columns.  Targets 2..C-1 are valid and are counted nowhere but in
+// `count`: the reference's ROC loop and its four counters look at targets 0 and 1 only.  The row is walked twice from global
+// memory (no per-thread array); the exponent sum runs in double over the fp32 terms.
+__global__ __launch_bounds__(EVAL_BLOCK) void k_eval_accumulate_classes(const float *__restrict__ logits, int C,
+                                                                        const int64_t *__restrict__ targets, int B,
+                                                                        const double *__restrict__ thr, int K, double decision,
+                                                                        float *__restrict__ conf_out,
+                                                                        uint8_t *__restrict__ pred_out,
+                                                                        int32_t *__restrict__ bin_out,
+                                                                        unsigned long long *__restrict__ hist,
+                                                                        unsigned long long *__restrict__ counters) {
+    __shared__ double s_thr[WW_EVAL_MAX_THRESHOLDS];
+    __shared__ unsigned s_hist[2 * (WW_EVAL_MAX_THRESHOLDS + 1)];
+    __shared__ unsigned s_cnt[8];
+    const int tid = threadIdx.x, nb = K + 1;
+    for (int i = tid; i < K; i += EVAL_BLOCK) s_thr[i] = thr[i];
+    for (int i = tid; i < 2 * nb; i += EVAL_BLOCK) s_hist[i] = 0u;
+    if (tid < 8) s_cnt[tid] = 0u;
+    __syncthreads();
+    const int i = blockIdx.x * EVAL_BLOCK + tid;
+    if (i < B) {
+        const float *__restrict__ z = logits + (size_t)i * C;
+        // torch.argmax: the first maximum wins a tie, a NaN is a maximum, the first NaN wins
+        float m = z[0], top = z[0];
+        int amax = 0;
+        for (int j = 1; j < C; ++j) {
+            const float v = z[j];
+            m = fmaxf(m, v);
+            if ((top == top) && ((v != v) || v > top)) {
+                top = v;
+                amax = j;
+            }
+        }
+        double se = 0.0;
+        for (int j = 0; j < C; ++j) se += (double)exp_diff(z[j], m);
+        const float c = exp_diff(z[1], m) / (float)se;
+        const double cd = (double)c;
+        int lo = 0, hi = K;             // number of table entries t with cd >= t (ascending table); NaN -> 0
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (cd >= s_thr[mid]) lo = mid + 1; else hi = mid;
+        }
+        conf_out[i] = c;
+        pred_out[i] = cd >= decision ? 1 : 0;
+        if (bin_out) bin_out[i] = lo;
+        atomicAdd(&s_cnt[4], 1u);
+        if (c != c) atomicAdd(&s_cnt[6], 1u);
+        if (targets) {
+            const long long t = targets[i];
+            if (t == 0 || t == 1) {
+                atomicAdd(&s_hist[(int)t * nb + lo], 1u);
+                if (amax == 1) atomicAdd(&s_cnt[t == 1 ? 0 : 2], 1u);                 // tp | fp
+                else if (amax == 0) atomicAdd(&s_cnt[t == 1 ? 3 : 1], 1u);            // fn | tn
+            } else if (t < 0 || t >= C) {
+                atomicAdd(&s_cnt[5], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < 2 * nb; j += EVAL_BLOCK) {
+        const unsigned v = s_hist[j];
+        if (v) atomicAdd(&hist[j], (unsigned long long)v);
+    }
+    if (tid < 7) {
+        const unsigned v = s_cnt[tid];
+        if (v) atomicAdd(&counters[tid], (unsigned long long)v);
+    }
+}
+
 constexpr int WIN_BLOCK = 256;
 
 __global__ __launch_bounds__(WIN_BLOCK) void k_wave_windows(const float *__restrict__ wave, int chunk, int half, int W,
@@ -143,6 +213,26 @@ extern "C" int ww_eval_accumulate(ww_ctx *ctx, const float *scores, int score_ki
     const int grid = (B + EVAL_BLOCK - 1) / EVAL_BLOCK;
     hipLaunchKernelGGL(k_eval_accumulate, dim3(grid), dim3(EVAL_BLOCK), 0, (hipStream_t)stream, scores, score_kind, targets, B,
                        thresholds, K, decision, conf + offset, pred + offset, bin ? bin + offset : nullptr,
+                       (unsigned long long *)hist, (unsigned long long *)counters);
+    WW_LAUNCH_CHECK();
+    return WW_OK;
+}
+
+extern "C" int ww_eval_accumulate_classes(ww_ctx *ctx, const float *logits, int num_classes, const int64_t *targets, int B,
+                                          const double *thresholds, int K, double decision, float *conf, uint8_t *pred,
+                                          int32_t *bin, size_t offset, uint64_t *hist, ww_eval_counters *counters,
+                                          ww_stream_t stream) {
+    WW_REQUIRE(ctx && logits && thresholds && conf && pred && hist && counters, WW_E_INVALID,
+               "ww_eval_accumulate_classes: null argument");
+    WW_REQUIRE(num_classes >= 2 && num_classes <= WW_LOSS_MAX_CLASSES, WW_E_INVALID,
+               "ww_eval_accumulate_classes: num_classes=%d outside [2, %d]", num_classes, WW_LOSS_MAX_CLASSES);
+    WW_REQUIRE(B >= 1, WW_E_INVALID, "ww_eval_accumulate_classes: B=%d", B);
+    WW_REQUIRE(K >= 1 && K <= WW_EVAL_MAX_THRESHOLDS, WW_E_INVALID, "ww_eval_accumulate_classes: K=%d outside [1, %d]", K,
+               WW_EVAL_MAX_THRESHOLDS);
+    WW_REQUIRE(decision == decision, WW_E_INVALID, "ww_eval_accumulate_classes: the decision threshold is NaN");
+    const int grid = (B + EVAL_BLOCK - 1) / EVAL_BLOCK;
+    hipLaunchKernelGGL(k_eval_accumulate_classes, dim3(grid), dim3(EVAL_BLOCK), 0, (hipStream_t)stream, logits, num_classes,
+                       targets, B, thresholds, K, decision, conf + offset, pred + offset, bin ? bin + offset : nullptr,
                        (unsigned long long *)hist, (unsigned long long *)counters);
     WW_LAUNCH_CHECK();
     return WW_OK;

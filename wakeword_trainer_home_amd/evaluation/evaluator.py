@@ -87,9 +87,11 @@ def _collate(items):
 
 class ModelEvaluator:
     def __init__(self, model: nn.Module, sample_rate: int = 16000, audio_duration: float = 1.5, device: str = "cuda",
-                 feature_type: str = "mel", n_mels: int = 128, n_mfcc: int = 40, n_fft: int = 1024, hop_length: int = 160):
+                 feature_type: str = "mel", n_mels: int = 128, n_mfcc: int = 40, n_fft: int = 1024, hop_length: int = 160,
+                 num_classes: Optional[int] = None):
         enforce_cuda()
         self.model, self.sample_rate, self.audio_duration, self.device = model, sample_rate, audio_duration, device
+        self.num_classes = num_classes         # None: the width of the first batch of logits of each pass
         self.n_samples = int(sample_rate * audio_duration)
         self.model.to(device)
         self.model.eval()
@@ -111,11 +113,19 @@ class ModelEvaluator:
             return self.feature_extractor(x)
         return x.float()
 
+    def _add(self, run: Optional[ScoreRun], n: int, thresholds, decision: float, logits: torch.Tensor, targets=None) -> ScoreRun:
+        """Queue one batch; the first batch of a pass creates the run, as wide as ``num_classes`` or as these logits."""
+        if run is None:
+            C = self.num_classes if self.num_classes is not None else int(logits.shape[1])
+            run = ScoreRun(n, thresholds, decision, self.device, num_classes=C)
+        run.add(logits, targets)
+        return run
+
     def _finish(self, run: ScoreRun, t0: float):
         host = run.finish()
         self.last_counters = {k: host[k] for k in ("tp", "tn", "fp", "fn", "count", "bad_target", "nan_score")}
         if host["bad_target"]:
-            logger.warning("%d target(s) outside {0, 1}: counted in total_samples only", host["bad_target"])
+            logger.warning("%d target(s) outside [0, %d]: counted in total_samples only", host["bad_target"], run.num_classes - 1)
         if host["nan_score"]:
             logger.warning("%d sample(s) with a NaN confidence: predicted Negative", host["nan_score"])
         return host, (time.time() - t0) * 1000.0 / max(run.filled, 1)
@@ -142,9 +152,9 @@ class ModelEvaluator:
         if n == 0:
             return []
         t0 = time.time()
-        run = ScoreRun(n, [decision], decision, self.device)
+        run = None
         for i in range(0, n, batch_size):
-            run.add(self._logits(self._features(waves[i:i + batch_size])))
+            run = self._add(run, n, [decision], decision, self._logits(self._features(waves[i:i + batch_size])))
         host, latency = self._finish(run, t0)
         return self._results(names, host, latency)
 
@@ -168,12 +178,12 @@ class ModelEvaluator:
         slots = []
         t0 = time.time()
         decision = file_threshold(threshold)
-        run = ScoreRun(len(paths), [decision], decision, self.device) if paths else None
+        run = None
         for i in range(0, len(paths), batch_size):
             waves, ok = load_batch(paths[i:i + batch_size], self.sample_rate, self.n_samples)
             slots += [i + k for k in ok]
             if ok:
-                run.add(self._logits(self._features(torch.from_numpy(waves))))
+                run = self._add(run, len(paths), [decision], decision, self._logits(self._features(torch.from_numpy(waves))))
         for i in set(range(len(paths))) - set(slots):
             results[i] = error_result(paths[i])
         if slots:
@@ -188,23 +198,28 @@ class ModelEvaluator:
             raise ValueError("empty dataset")
         logger.info("Evaluating dataset with %d samples...", n)
         t0 = time.time()
-        run, names = ScoreRun(n, thresholds, decision, self.device), []
+        run, names = None, []
         for batch_idx, i in enumerate(range(0, n, batch_size)):
             inputs, targets, metadata = _collate([dataset[j] for j in range(i, min(i + batch_size, n))])
             names += [_filename(m, batch_idx, k) for k, m in enumerate(metadata)]
-            run.add(self._logits(self._features(inputs)), targets.to(self.device, non_blocking=True).long())
+            run = self._add(run, n, thresholds, decision, self._logits(self._features(inputs)),
+                            targets.to(self.device, non_blocking=True).long())
         host, latency = self._finish(run, t0)
         return host, names, latency
 
     def evaluate_dataset(self, dataset, threshold: float = 0.5, batch_size: int = 32) -> Tuple[MetricResults, List[EvaluationResult]]:
         """Items are ``(features_or_waveform, label, metadata)``; a 1-D first element is a waveform.  ``MetricResults``
-        come from the argmax counters, as ``MetricsCalculator.calculate`` on the collected (n,2) logits does
-        (``evaluator.py:321-324``); ``prediction`` is the threshold decision (``:307``)."""
+        come from the argmax counters, as ``MetricsCalculator.calculate`` on the collected (n,C) logits does
+        (``evaluator.py:321-324``); ``prediction`` is the threshold decision (``:307``).  With more than two classes the
+        positive and negative sample counts are the rows of the histogram -- the targets equal to 1 and to 0 -- because a
+        sample of either class that is predicted as class 2.. is in none of the four counters."""
         decision = file_threshold(threshold)
         host, names, latency = self._run_dataset(dataset, [decision], decision, batch_size)
         metrics = MetricResults.from_counts(host["tp"], host["tn"], host["fp"], host["fn"])
         metrics.total_samples = host["count"]                 # len(targets): labels outside {0,1} count here only
         metrics.accuracy = (host["tp"] + host["tn"]) / host["count"] if host["count"] > 0 else 0.0
+        if host["logits"].shape[1] > 2:
+            metrics.positive_samples, metrics.negative_samples = int(host["hist"][1].sum()), int(host["hist"][0].sum())
         logger.info("Evaluation complete: %s", metrics)
         return metrics, self._results(names, host, latency)
 

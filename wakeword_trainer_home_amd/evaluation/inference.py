@@ -37,8 +37,10 @@ def window_starts(n_samples: int, chunk: int) -> List[int]:
 class RecordingScanner:
     def __init__(self, model: nn.Module, sample_rate: int = 16000, audio_duration: float = 1.5, threshold: float = 0.5,
                  device: str = "cuda", callback: Optional[Callable] = None, feature_type: str = "mel", n_mels: int = 128,
-                 n_mfcc: int = 40, n_fft: int = 1024, hop_length: int = 160, batch_size: int = 32):
+                 n_mfcc: int = 40, n_fft: int = 1024, hop_length: int = 160, batch_size: int = 32,
+                 num_classes: Optional[int] = None):
         enforce_cuda()
+        self.num_classes = num_classes         # None: the width of the first batch of logits of each scan
         self.model, self.sample_rate, self.audio_duration = model, sample_rate, audio_duration
         self.chunk_samples = int(sample_rate * audio_duration)
         self.threshold, self.device, self.callback, self.batch_size = threshold, device, callback, batch_size
@@ -71,10 +73,14 @@ class RecordingScanner:
         self.last_peaks = peaks
         if W == 0:
             return []
-        run = ScoreRun(W, [self.threshold], self.threshold, self.device)
+        run = None
         with torch.no_grad():
             for i in range(0, W, self.batch_size):
-                run.add(self.model(self.feature_extractor(windows[i:i + self.batch_size])))
+                logits = self.model(self.feature_extractor(windows[i:i + self.batch_size]))
+                if run is None:
+                    C = self.num_classes if self.num_classes is not None else int(logits.shape[1])
+                    run = ScoreRun(W, [self.threshold], self.threshold, self.device, num_classes=C)
+                run.add(logits)
         host = run.finish()
         results = [(float(c), bool(p)) for c, p in zip(host["conf"], host["pred"])]
         for confidence, is_positive in results:

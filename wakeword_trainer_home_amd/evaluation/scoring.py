@@ -60,15 +60,19 @@ def roc_from_hist(hist):
 
 class ScoreRun:
     """Device accumulators of one pass over ``n`` samples, carved from ONE byte buffer so that ``finish`` is one D2H copy:
-    hist i64 (2,K+1) | counters i64 (8) | logits f32 (n,2) | conf f32 (n) | bin i32 (n) | pred u8 (n)."""
+    hist i64 (2,K+1) | counters i64 (8) | logits f32 (n,C) | conf f32 (n) | bin i32 (n) | pred u8 (n).  ``num_classes`` = C is
+    the width of the logits: 2 scores through ``ww_eval_accumulate`` as always, more through ``ww_eval_accumulate_classes``."""
 
-    def __init__(self, n: int, thresholds, decision: float, device):
+    def __init__(self, n: int, thresholds, decision: float, device, num_classes: int = 2):
+        if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= nat.LOSS_MAX_CLASSES:
+            raise ValueError(f"num_classes must be an int in [2, {nat.LOSS_MAX_CLASSES}], got {num_classes!r}")
+        self.num_classes = num_classes
         thr = np.ascontiguousarray(thresholds, np.float64)
         if thr.ndim != 1 or not 1 <= thr.size <= nat.EVAL_MAX_THRESHOLDS or np.any(np.diff(thr) < 0) or np.isnan(thr).any():
             raise ValueError(f"thresholds must be 1 to {nat.EVAL_MAX_THRESHOLDS} ascending float64 values")
         self.n, self.K, self.decision, self.filled = int(n), thr.size, float(decision), 0
         self.thresholds = torch.from_numpy(thr).to(device)
-        fields = (("hist", torch.int64, 2 * (self.K + 1)), ("counters", torch.int64, 8), ("logits", torch.float32, 2 * self.n),
+        fields = (("hist", torch.int64, 2 * (self.K + 1)), ("counters", torch.int64, 8), ("logits", torch.float32, num_classes * self.n),
                   ("conf", torch.float32, self.n), ("bin", torch.int32, self.n), ("pred", torch.uint8, self.n))
         self._layout, off = [], 0
         for name, dt, count in fields:                       # descending element size: every view stays aligned
@@ -78,18 +82,21 @@ class ScoreRun:
         self._buf = torch.zeros(off, dtype=torch.uint8, device=device)
         for name, dt, start, nbytes in self._layout:
             setattr(self, name, self._buf[start:start + nbytes].view(dt))
-        self.logits = self.logits.view(self.n, 2)
+        self.logits = self.logits.view(self.n, num_classes)
 
     def add(self, scores: torch.Tensor, targets=None):
-        """Queue one batch: (B,2) logits, or (B,) confidences (their logits slots stay zero).  No host synchronisation."""
+        """Queue one batch: (B,C) logits, or (B,) confidences (their logits slots stay zero).  No host synchronisation."""
         B = scores.shape[0]
         if self.filled + B > self.n:
             raise ValueError(f"ScoreRun holds {self.n} samples; batch of {B} at {self.filled} does not fit")
         scores = scores.detach().float().contiguous()
         if scores.dim() == 2:
+            if scores.shape[1] != self.num_classes:
+                raise ValueError(f"ScoreRun was built for num_classes = {self.num_classes}, got logits with {scores.shape[1]} columns")
             self.logits[self.filled:self.filled + B].copy_(scores)
-        nat.eval_accumulate(scores, targets, self.thresholds, self.decision, self.conf, self.pred, self.bin, self.filled,
-                            self.hist, self.counters)
+        accumulate = nat.eval_accumulate_classes if scores.dim() == 2 and self.num_classes > 2 else nat.eval_accumulate
+        accumulate(scores, targets, self.thresholds, self.decision, self.conf, self.pred, self.bin, self.filled, self.hist,
+                   self.counters)
         self.filled += B
 
     def finish(self) -> dict:
@@ -98,7 +105,7 @@ class ScoreRun:
         np_dt = {torch.int64: np.int64, torch.float32: np.float32, torch.int32: np.int32, torch.uint8: np.uint8}
         out = {name: host[start:start + nbytes].view(np_dt[dt]) for name, dt, start, nbytes in self._layout}
         m = self.filled
-        res = {"hist": out["hist"].reshape(2, self.K + 1), "logits": out["logits"].reshape(self.n, 2)[:m],
+        res = {"hist": out["hist"].reshape(2, self.K + 1), "logits": out["logits"].reshape(self.n, self.num_classes)[:m],
                "conf": out["conf"][:m], "bin": out["bin"][:m], "pred": out["pred"][:m]}
         res.update({k: int(v) for k, v in zip(nat.EVAL_COUNTERS, out["counters"])})
         return res

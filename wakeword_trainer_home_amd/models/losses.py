@@ -1,11 +1,13 @@
 """Loss factory of the hot path: same names, constructor arguments and input validation as
 the reference (``src/models/losses.py:14-270``); the arithmetic (loss, gradient, batch
-counters) is one HIP kernel.  Scope: 2 classes; optional per-class ``weight`` (``:89-92``, ``:199-202``, ``:256``) and
-``reduction`` in mean / sum / none (``:95-102``).
+counters) is one HIP kernel.  Scope: ``num_classes`` from 2 to ``LOSS_MAX_CLASSES`` (2 by default); optional per-class
+``weight`` (``:89-92``, ``:199-202``, ``:256``) and ``reduction`` in mean / sum / none (``:95-102``).
 
-Two C-ABI entries.  ``weight=None`` with ``reduction="mean"`` -- what ``Trainer`` builds unless it is handed class weights
-(``src/training/trainer.py:78-86`` passes ``class_weights=None``) -- calls ``ww_ce2_loss_fwd_bwd``; every other combination
-calls ``ww_ce2_loss_weighted_fwd_bwd``.  The weighted mean follows the reference class by class: ``CrossEntropyLoss`` divides
+Three C-ABI entries.  With two classes, ``weight=None`` with ``reduction="mean"`` -- what ``Trainer`` builds unless it is handed
+class weights (``src/training/trainer.py:78-86`` passes ``class_weights=None``) -- calls ``ww_ce2_loss_fwd_bwd`` and every other
+combination calls ``ww_ce2_loss_weighted_fwd_bwd``; with more than two classes every combination calls ``ww_cen_loss_fwd_bwd``,
+which can also count the batch into a (C,C) confusion matrix on the device (``track_confusion``).
+The weighted mean follows the reference class by class: ``CrossEntropyLoss`` divides
 by the sum of the batch's weights as ``nn.CrossEntropyLoss(weight=...)`` does, ``LabelSmoothingCrossEntropy`` and
 ``FocalLoss`` divide by the batch size (``(loss * weight).mean()``).
 
@@ -42,11 +44,16 @@ class _NativeLoss(nn.Module):
     _eps, _alpha, _gamma = 0.0, 0.25, 2.0
     _divisor = nat.DIV_BATCH              # what a weighted 'mean' divides by: (loss * weight).mean() of the reference classes
 
-    def __init__(self, weight: Optional[torch.Tensor], reduction: str):
+    def __init__(self, weight: Optional[torch.Tensor], reduction: str, num_classes: int = 2):
         super().__init__()
-        if weight is not None and not (torch.is_tensor(weight) and weight.dtype == torch.float32 and tuple(weight.shape) == (2,)):
+        if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 2 <= num_classes <= nat.LOSS_MAX_CLASSES:
+            raise ValueError(f"num_classes must be an int in [2, {nat.LOSS_MAX_CLASSES}] for the HIP loss kernels, got {num_classes!r}")
+        C = num_classes
+        if weight is not None and not (torch.is_tensor(weight) and weight.dtype == torch.float32 and tuple(weight.shape) == (C,)):
             what = f"{weight.dtype} {tuple(weight.shape)}" if torch.is_tensor(weight) else type(weight).__name__
-            raise ValueError(f"weight must be a float32 tensor of shape (2,) [w_neg, w_pos] for the 2-class HIP loss kernel, got {what}")
+            layout = "[w_neg, w_pos] for the 2-class" if C == 2 else f"(one weight per class) for the {C}-class"
+            raise ValueError(f"weight must be a float32 tensor of shape ({C},) {layout} HIP loss kernel, got {what}")
+        self.num_classes = C
         if reduction not in _REDUCTIONS:
             raise ValueError(f"Invalid reduction: {reduction}")
         # a buffer, so that criterion.to(device) takes it along; the kernel reads it through its pointer at run time, so an
@@ -58,7 +65,22 @@ class _NativeLoss(nn.Module):
         self.found_inf_out = None         # float32[1] device tensor that also receives found_inf (data-parallel bucket slot)
         self.loss_scale = None            # device ww_loss_scale (fp16 storage): dL/dlogits leaves the kernel times scale[slot]
         self.loss_scale_slot = 0
+        self.confusion = None             # int64 (C,C) device tensor [target, pred] once track_confusion() was called (C > 2)
         self._stats = {}
+
+    def track_confusion(self, device=None):
+        """Allocate, once, a zeroed (C,C) int64 device matrix indexed [target, pred]; every launch from then on adds its batch
+        to it unless the launch sets found_inf (non-finite loss or a bad target).  The tensor is never replaced, so a captured
+        graph keeps counting into it; the caller zeroes it in place (``criterion.confusion.zero_()``) and reads it when it wants.
+        Only the C-class entry counts, so this needs num_classes > 2."""
+        if self.num_classes == 2:
+            raise ValueError("track_confusion needs num_classes > 2: with two classes ww_step_stats' tp/tn/fp/fn are the matrix")
+        if self.confusion is None:
+            dev = device if device is not None else (self.weight.device if self.weight is not None else "cuda")
+            if torch.device(dev).type != "cuda":
+                raise nat.NativeError("the confusion matrix lives on an MI355X ('cuda') device -- there is no CPU fallback")
+            self.confusion = torch.zeros(self.num_classes, self.num_classes, dtype=torch.int64, device=dev)
+        return self.confusion
 
     def _stats_for(self, dev):
         if dev not in self._stats:
@@ -66,10 +88,10 @@ class _NativeLoss(nn.Module):
         return self._stats[dev]
 
     def _launch(self, logits, targets, found_inf_out):
-        """One kernel launch -> (loss (1,), loss_vec (B,) or None, dlogits, stats): the unweighted mean through the entry it
-        always had, everything else through the weighted one."""
+        """One kernel launch -> (loss (1,), loss_vec (B,) or None, dlogits, stats).  Two classes: the unweighted mean through
+        the entry it always had, everything else through the weighted one.  More than two: the C-class entry."""
         stats = self._stats_for(logits.device)
-        if self.reduction == "mean" and self.weight is None:
+        if self.num_classes == 2 and self.reduction == "mean" and self.weight is None:
             loss, dl, stats = nat.ce2_loss_fwd_bwd(logits, targets, self._kind, self._eps, self._alpha, self._gamma, stats=stats,
                                                    found_inf_out=found_inf_out, loss_scale=self.loss_scale,
                                                    loss_scale_slot=self.loss_scale_slot)
@@ -79,6 +101,13 @@ class _NativeLoss(nn.Module):
             # no copy here: a host-to-device copy per step would sync, and could not be captured into a graph
             raise ValueError(f"the loss weight is {w.dtype} on {w.device} but the logits are on {logits.device}: move the "
                              "criterion with .to(device) (it must stay float32)")
+        if self.num_classes > 2:
+            if self.confusion is not None and self.confusion.device != logits.device:
+                raise ValueError(f"the confusion matrix is on {self.confusion.device} but the logits are on {logits.device}")
+            return nat.cen_loss_fwd_bwd(logits, targets, self._kind, self._eps, self._alpha, self._gamma, class_weight=w,
+                                        reduction=_REDUCTIONS[self.reduction], mean_divisor=self._divisor, stats=stats,
+                                        found_inf_out=found_inf_out, loss_scale=self.loss_scale,
+                                        loss_scale_slot=self.loss_scale_slot, confusion=self.confusion)
         return nat.ce2_loss_weighted_fwd_bwd(logits, targets, self._kind, self._eps, self._alpha, self._gamma, class_weight=w,
                                              reduction=_REDUCTIONS[self.reduction], mean_divisor=self._divisor, stats=stats,
                                              found_inf_out=found_inf_out, loss_scale=self.loss_scale,
@@ -88,8 +117,10 @@ class _NativeLoss(nn.Module):
         """Loss kernel without autograd: -> (device ww_step_stats, dL/dlogits).  Target range errors are reported through
         ``stats.bad_target`` (the caller reads the stats once per step).  With ``reduction='none'`` the gradient is that of
         the per-sample losses' sum and ``stats.loss`` their mean."""
-        if logits.dim() != 2 or logits.size(1) != 2 or target.dim() != 1 or logits.size(0) != target.size(0):
-            raise ValueError(f"expected logits (B,2) and targets (B,), got {tuple(logits.shape)} and {tuple(target.shape)}")
+        C = self.num_classes
+        if logits.dim() != 2 or logits.size(1) != C or target.dim() != 1 or logits.size(0) != target.size(0):
+            raise ValueError(f"expected logits (B,{C}) for num_classes = {C} and targets (B,), got {tuple(logits.shape)} and "
+                             f"{tuple(target.shape)}")
         _, _, dl, stats = self._launch(logits.contiguous(), target.long().contiguous(), found_inf_out)
         self.last_stats = stats
         return stats, dl
@@ -101,8 +132,8 @@ class _NativeLoss(nn.Module):
             raise ValueError(f"Targets must be 1D (batch,), got shape {target.shape}")
         if pred.size(0) != target.size(0):
             raise ValueError(f"Batch size mismatch: pred={pred.size(0)}, target={target.size(0)}")
-        if pred.size(1) != 2:
-            raise ValueError(f"the HIP loss kernel implements num_classes == 2, got {pred.size(1)}")
+        if pred.size(1) != self.num_classes:
+            raise ValueError(f"this criterion was built for num_classes = {self.num_classes}, got logits with {pred.size(1)} columns")
         if not pred.is_cuda:
             raise nat.NativeError("the loss runs on a hand-written HIP kernel only; tensors must be on an MI355X "
                                   "('cuda') device -- there is no CPU fallback")
@@ -110,15 +141,16 @@ class _NativeLoss(nn.Module):
         if self.validate_targets:
             st = nat.decode_stats(self.last_stats.cpu())
             if st["bad_target"]:
-                raise ValueError("Target values must be in [0, 1]")
+                raise ValueError(f"Target values must be in [0, {self.num_classes - 1}]")
         return loss
 
 
 class LabelSmoothingCrossEntropy(_NativeLoss):
-    def __init__(self, smoothing: float = 0.1, weight: Optional[torch.Tensor] = None, reduction: str = "mean"):
+    def __init__(self, smoothing: float = 0.1, weight: Optional[torch.Tensor] = None, reduction: str = "mean", *,
+                 num_classes: int = 2):
         if not 0.0 <= smoothing <= 1.0:
             raise ValueError(f"Label smoothing must be in [0, 1], got {smoothing}")
-        super().__init__(weight, reduction)
+        super().__init__(weight, reduction, num_classes)
         self.smoothing, self.confidence = smoothing, 1.0 - smoothing
         self._eps = float(smoothing)
 
@@ -128,8 +160,8 @@ class CrossEntropyLoss(LabelSmoothingCrossEntropy):
     by the sum of the batch's weights, not by the batch size."""
     _divisor = nat.DIV_WEIGHT_SUM
 
-    def __init__(self, weight: Optional[torch.Tensor] = None, reduction: str = "mean"):
-        super().__init__(0.0, weight, reduction)
+    def __init__(self, weight: Optional[torch.Tensor] = None, reduction: str = "mean", *, num_classes: int = 2):
+        super().__init__(0.0, weight, reduction, num_classes=num_classes)
 
 
 class FocalLoss(_NativeLoss):
@@ -137,12 +169,12 @@ class FocalLoss(_NativeLoss):
     EPS = 1e-7
 
     def __init__(self, alpha: float = 0.25, gamma: float = 2.0, weight: Optional[torch.Tensor] = None,
-                 reduction: str = "mean"):
+                 reduction: str = "mean", *, num_classes: int = 2):
         if not 0.0 <= alpha <= 1.0:
             raise ValueError(f"Alpha must be in [0, 1], got {alpha}")
         if gamma < 0:
             raise ValueError(f"Gamma must be non-negative, got {gamma}")
-        super().__init__(weight, reduction)
+        super().__init__(weight, reduction, num_classes)
         self.alpha, self.gamma = alpha, gamma
         self._alpha, self._gamma = float(alpha), float(gamma)
 
@@ -153,12 +185,11 @@ def create_loss_function(loss_name: str, num_classes: int = 2, label_smoothing: 
     name = loss_name.lower()
     if class_weights is not None:
         class_weights = class_weights.to(device)
-    if num_classes != 2 and name in ("cross_entropy", "focal_loss"):
-        raise ValueError(f"the HIP loss kernels implement num_classes == 2, got {num_classes}")
     if name == "cross_entropy":
         if label_smoothing > 0:
-            return LabelSmoothingCrossEntropy(smoothing=label_smoothing, weight=class_weights, reduction="mean")
-        return CrossEntropyLoss(weight=class_weights, reduction="mean")
+            return LabelSmoothingCrossEntropy(smoothing=label_smoothing, weight=class_weights, reduction="mean",
+                                              num_classes=num_classes)
+        return CrossEntropyLoss(weight=class_weights, reduction="mean", num_classes=num_classes)
     if name == "focal_loss":
-        return FocalLoss(alpha=focal_alpha, gamma=focal_gamma, weight=class_weights, reduction="mean")
+        return FocalLoss(alpha=focal_alpha, gamma=focal_gamma, weight=class_weights, reduction="mean", num_classes=num_classes)
     raise ValueError(f"Unknown loss function: {name}. Supported: cross_entropy, focal_loss")

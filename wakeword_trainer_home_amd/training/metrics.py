@@ -6,7 +6,9 @@ same zero-denominator conventions (:112-153), epoch tracker API (:187-290), slid
 Difference by design: the reference appends every batch's logits/targets to CPU lists (a D2H copy +
 sync per step, :219-220) and recounts at epoch end.  Here the tracker accumulates the five confusion
 counters the loss kernel already produced (``ww_step_stats``); because ``calculate`` is argmax-based for
-2-D predictions (:105-107) the epoch ``MetricResults`` are identical.
+2-D predictions (:105-107) the epoch ``MetricResults`` are identical.  With more than two classes the four counters no longer
+add up to the number of samples, so the tracker takes the loss kernel's (C,C) confusion matrix instead (``update_confusion``,
+``MetricResults.from_confusion``): class 1 stays "positive", as in the reference.
 """
 import logging
 from dataclasses import dataclass
@@ -54,6 +56,20 @@ class MetricResults:
                    negative_samples=tn + fp)
 
     @classmethod
+    def from_confusion(cls, matrix) -> "MetricResults":
+        """From a (C,C) count matrix indexed [target, pred], C >= 2: what the reference's ``MetricsCalculator.calculate``
+        returns for the same samples (``:105-153``).  Class 1 stays "positive" and class 0 "negative"; samples of the other
+        classes, and predictions of them, count in ``total_samples`` (hence in the accuracy's denominator) and nowhere else."""
+        m = np.asarray(matrix.detach().cpu() if torch.is_tensor(matrix) else matrix)
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 2 or not np.issubdtype(m.dtype, np.integer):
+            raise ValueError(f"expected a square integer matrix [target, pred] with at least 2 classes, got {m.dtype} {m.shape}")
+        res = cls.from_counts(int(m[1, 1]), int(m[0, 0]), int(m[0, 1]), int(m[1, 0]))
+        res.total_samples = int(m.sum())
+        res.positive_samples, res.negative_samples = int(m[1].sum()), int(m[0].sum())
+        res.accuracy = (res.true_positives + res.true_negatives) / res.total_samples if res.total_samples > 0 else 0.0
+        return res
+
+    @classmethod
     def empty(cls) -> "MetricResults":
         return cls.from_counts(0, 0, 0, 0)
 
@@ -76,6 +92,10 @@ class MetricsCalculator:
         res = MetricResults.from_counts(tp, tn, fp, fn)
         res.total_samples = len(targets)                      # reference: len(targets), labels outside {0,1} count here
         res.accuracy = (tp + tn) / res.total_samples if res.total_samples > 0 else 0.0
+        if predictions.dim() == 2 and predictions.shape[1] > 2:
+            # a class-0 or class-1 sample predicted as class 2.. is in none of the four counters: count the targets (:120-121)
+            pos, neg = torch.stack([(targets == 1).sum(), (targets == 0).sum()]).tolist()
+            res.positive_samples, res.negative_samples = int(pos), int(neg)
         return res
 
     def confusion_matrix(self, predictions: torch.Tensor, targets: torch.Tensor, num_classes: int = 2) -> torch.Tensor:
@@ -94,6 +114,16 @@ class MetricsTracker:
     def reset(self):
         self._c = [0, 0, 0, 0]
         self._seen = False
+        self._m = None                     # (C,C) int64 [target, pred] once update_confusion was given one
+
+    def update_confusion(self, matrix):
+        """More than two classes: a (C,C) count matrix [target, pred] (the loss kernel's, read once per epoch) is added to the
+        tracker's; from then on ``compute`` reports ``MetricResults.from_confusion`` of the sum instead of the four counters."""
+        m = np.asarray(matrix.detach().cpu() if torch.is_tensor(matrix) else matrix).astype(np.int64)
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or (self._m is not None and self._m.shape != m.shape):
+            raise ValueError(f"expected a square matrix [target, pred] of one size per epoch, got {m.shape}")
+        self._m = m.copy() if self._m is None else self._m + m
+        self._seen = True
 
     def update_counts(self, tp: int, tn: int, fp: int, fn: int):
         """Fast path: counters already produced on the device (ww_step_stats)."""
@@ -109,6 +139,8 @@ class MetricsTracker:
         if not self._seen:
             logger.warning("No predictions accumulated, returning zero metrics")
             return MetricResults.empty()
+        if self._m is not None:
+            return MetricResults.from_confusion(self._m)
         return MetricResults.from_counts(*self._c)
 
     def save_epoch_metrics(self, metrics: MetricResults):

@@ -107,6 +107,10 @@ class Trainer:
                 raise ValueError("a training step needs a scalar loss: reduction='none' is for per-clip loss ranking, "
                                  "use 'mean' or 'sum' for the Trainer's criterion")
             self.criterion.validate_targets = False      # checked from the per-step stats read instead
+        # more than two classes: the loss kernel counts every batch into one (C,C) matrix on the device, zeroed when an epoch
+        # begins and read once when it ends -- the epoch's MetricResults come from it (MetricResults.from_confusion)
+        self._num_classes = int(getattr(self.criterion, "num_classes", 2)) if self._native_loss else 2
+        self._confusion = self.criterion.track_confusion(device) if self._num_classes > 2 else None
 
         self.optimizer, self.scheduler = create_optimizer_and_scheduler(self.model, config)
         self.use_mixed_precision = config.optimizer.mixed_precision
@@ -425,7 +429,7 @@ class Trainer:
         event.synchronize()
         s = nat.decode_stats(buf)
         if s["bad_target"]:
-            logger.error("Unexpected error at batch %d: Target values must be in [0, 1]", batch_idx)
+            logger.error("Unexpected error at batch %d: Target values must be in [0, %d]", batch_idx, self._num_classes - 1)
             return None
         if s["found_inf"] != 0.0:
             if s["nonfinite"] or self.loss_scale is None:
@@ -702,7 +706,9 @@ class Trainer:
         flat = getattr(self.model, "flat_param", None)
         weight = getattr(self.criterion, "weight", None)
         crit += (("reduction", getattr(self.criterion, "reduction", None)), ("weight", weight is not None),
-                 ("weight_ptr", weight.data_ptr() if torch.is_tensor(weight) else None))
+                 ("weight_ptr", weight.data_ptr() if torch.is_tensor(weight) else None),
+                 ("num_classes", getattr(self.criterion, "num_classes", None)),
+                 ("confusion_ptr", None if self._confusion is None else self._confusion.data_ptr()))
         return (tuple(shape), self._graph_mode_key(), float(self.gradient_clip), groups, type(self.criterion).__name__, crit,
                 None if flat is None else flat.data_ptr())
 
@@ -850,7 +856,7 @@ class Trainer:
             self.criterion(self.model(inputs), targets)
             s = self._read_stats(self.criterion.last_stats)
             if s["bad_target"]:
-                raise ValueError("Target values must be in [0, 1]")
+                raise ValueError(f"Target values must be in [0, {self._num_classes - 1}]")
             if s["nonfinite"]:
                 return None
             self.val_metrics_tracker.update_counts(s["tp"], s["tn"], s["fp"], s["fn"])
@@ -876,12 +882,21 @@ class Trainer:
         self._dist.all_reduce(ls)
         tracker._c = [int(v) for v in t[:4].tolist()]
         tracker._seen = tracker._seen or sum(tracker._c) > 0
+        if self._confusion is not None:            # the (C,C) matrix is summed like the four counters (every rank has one)
+            C = self._num_classes
+            m = torch.zeros(C, C, dtype=torch.float64, device=dev) if tracker._m is None else \
+                torch.as_tensor(tracker._m, dtype=torch.float64, device=dev)
+            self._dist.all_reduce(m)
+            tracker._m = m.cpu().numpy().astype("int64")
+            tracker._seen = tracker._seen or int(tracker._m.sum()) > 0
         return float(ls.item()), int(t[4].item())
 
     # ------------------------------------------------------------------------------- epochs
     def train_epoch(self, epoch: int) -> Tuple[float, float]:
         self.model.train()
         self.train_metrics_tracker.reset()
+        if self._confusion is not None:
+            self._confusion.zero_()
         num_batches = len(self.train_loader)
         if num_batches == 0:
             logger.warning("Training loader is empty, skipping epoch")
@@ -970,6 +985,8 @@ class Trainer:
                 if not failed(e, batch_idx):
                     raise
         account(self._flush_pending())            # the last step's deferred results
+        if self._confusion is not None:
+            self.train_metrics_tracker.update_confusion(self._confusion)       # the epoch's one read of the matrix
         epoch_loss, num_batches = self._epoch_reduce(self.train_metrics_tracker, epoch_loss, num_batches)
         avg_loss = epoch_loss / max(num_batches, 1)
         train_metrics = self.train_metrics_tracker.compute()
@@ -979,6 +996,8 @@ class Trainer:
     def validate_epoch(self, epoch: int) -> Tuple[float, MetricResults]:
         self.model.eval()
         self.val_metrics_tracker.reset()
+        if self._confusion is not None:
+            self._confusion.zero_()
         num_batches = len(self.val_loader)
         if num_batches == 0:
             logger.warning("Validation loader is empty")
@@ -1006,6 +1025,8 @@ class Trainer:
                 except Exception as e:
                     logger.exception("Unexpected error during validation at batch %d: %s", batch_idx, e)
                     continue
+        if self._confusion is not None:
+            self.val_metrics_tracker.update_confusion(self._confusion)
         epoch_loss, num_batches = self._epoch_reduce(self.val_metrics_tracker, epoch_loss, num_batches)
         avg_loss = epoch_loss / max(num_batches, 1)
         val_metrics = self.val_metrics_tracker.compute()
