@@ -871,6 +871,51 @@ int ww_loader_batch(ww_ctx *ctx, const int16_t *bank, const int32_t *length, con
                     uint64_t epoch, int rank, int world, int64_t k0, int B, int n_out, int16_t *out, int64_t *targets,
                     int32_t *clip_index, ww_stream_t stream);
 
+/* ------------------------------------------------------------------ int8 inference of an exported cnn_small bundle
+ * The reference exports through ONNX and leaves the quantised network to onnxruntime (src/export/onnx_exporter.py:225-254); here
+ * the export package writes an int8 bundle and these entry points run it with integer arithmetic only -- the law is DESIGN.md
+ * "Export".  Activations are int8 NHWC (B,H,W,64); every tensor is 16-byte aligned.  Per conv:
+ *   w      int8: stem and depthwise (9,64) [tap kh*3+kw][channel], pointwise (64,64) [out][in]
+ *   bias   int32 (64): the EFFECTIVE bias q_b - z_in * sum(q_w over the channel's weights), wrapped to 32 bits -- with the
+ *          border filled with z_in, sum q_w q_in + bias is the law's sum q_w (q_in - z_in) + q_b in two's complement
+ *   mult   int32 (64) in [2^30, 2^31), shift int32 (64) in [1, 62]
+ *   q_out = clamp(-128 + ((int64(acc) * mult + 2^(shift-1)) >> shift), -128, 127)          (z_out = -128: the ReLU)
+ * ww_q8_quantize: q = clamp(rne(x / scale) + zero, -128, 127), one correctly rounded fp32 division; NaN -> zero, +-inf saturate.
+ * ww_q8_stem_fwd: xq int8 (B,F,T) -> (B,(F+1)/2,(T+1)/2,64), 3x3 stride 2 pad 1.  ww_q8_dwconv3x3_fwd: 3x3 pad 1 per channel.
+ * ww_q8_pwconv1x1_fwd: (N,64) -> (N,64) on v_mfma_i32_16x16x64_i8.  ww_q8_dwpw_fwd: the last two as one kernel, bit-equal.
+ * ww_q8_gap_fc_fwd: S[c] = sum_hw (q + 128); pool_out int8 (B,64) = the requantised S (pool_mult, pool_shift);
+ *   logits[k] = float32(sum_c fc_w[k][c] (pool[c] + 128) + fc_bias[k]) * fc_scale[k] -- fc_bias is the law's q_b, not an
+ *   effective bias; fc_w int8 (2,64), fc_bias int32 (2), fc_scale fp32 (2).
+ * The whole model: tab = WW_Q8_NPTR device pointers [stem w, bias, mult, shift] + 4 x [dw w, bias, mult, shift, pw w, bias, mult,
+ * shift] + [fc_w, fc_bias, fc_scale]; io on the host.  The workspace holds, each rounded up to 256 bytes: xq (B*F*T), then
+ * WW_Q8_NACT activation tensors of B*H*W*64 (stem, dw0, pw0, .. dw3, pw3), then pool (B*64).  form WW_Q8_FUSED leaves the dw
+ * slots unwritten.  Nothing synchronises with the host. */
+#define WW_Q8_NPTR 39
+#define WW_Q8_NACT 9
+#define WW_Q8_PAIR 0
+#define WW_Q8_FUSED 1
+typedef struct {
+    float in_scale;      /* s_x */
+    int32_t in_zero;     /* z_x */
+    int32_t pool_mult;   /* m_p */
+    int32_t pool_shift;  /* sh_p */
+} ww_q8_io;
+int ww_q8_quantize(ww_ctx *ctx, const float *x, long n, float scale, int zero, int8_t *out, ww_stream_t stream);
+int ww_q8_stem_fwd(ww_ctx *ctx, const int8_t *xq, const int8_t *w, const int32_t *bias, const int32_t *mult, const int32_t *shift,
+                   int B, int F, int T, int zero, int8_t *out, ww_stream_t stream);
+int ww_q8_dwconv3x3_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, const int32_t *bias, const int32_t *mult,
+                        const int32_t *shift, int B, int H, int W, int zero, int8_t *out, ww_stream_t stream);
+int ww_q8_pwconv1x1_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, const int32_t *bias, const int32_t *mult,
+                        const int32_t *shift, long N, int8_t *out, ww_stream_t stream);
+int ww_q8_dwpw_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w_dw, const int32_t *bias_dw, const int32_t *mult_dw,
+                   const int32_t *shift_dw, const int8_t *w_pw, const int32_t *bias_pw, const int32_t *mult_pw,
+                   const int32_t *shift_pw, int B, int H, int W, int zero, int8_t *out, ww_stream_t stream);
+int ww_q8_gap_fc_fwd(ww_ctx *ctx, const int8_t *in, int B, int HW, int pool_mult, int pool_shift, const int8_t *fc_w,
+                     const int32_t *fc_bias, const float *fc_scale, int8_t *pool_out, float *logits, ww_stream_t stream);
+size_t ww_q8_cnn_small_workspace_bytes(int B, int F, int T);
+int ww_q8_cnn_small_fwd(ww_ctx *ctx, const void *const *tab, const ww_q8_io *io, const float *x, int B, int F, int T, int form,
+                        void *ws, size_t ws_bytes, float *logits, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ collectives: deliberately NOT in this ABI
  * SURVEY.md §8b sketched two more entry points, `ww_comm_init` (ctx, nccl_unique_id, rank, world) and `ww_allreduce_f32`
  * (ctx, buf, n, avg, comm_stream).

@@ -118,6 +118,13 @@ class StepStats(C.Structure):
 
 STEP_STATS_BYTES = C.sizeof(StepStats)
 
+class Q8Io(C.Structure):
+    """ww_q8_io: the scalars of an int8 bundle (include/wwhip.h)."""
+    _fields_ = [("in_scale", C.c_float), ("in_zero", C.c_int32), ("pool_mult", C.c_int32), ("pool_shift", C.c_int32)]
+
+
+Q8_NPTR, Q8_NACT, Q8_PAIR, Q8_FUSED = 39, 9, 0, 1
+
 _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 _SIGS = {
     "ww_abi_version": (C.c_int, []),
@@ -252,6 +259,14 @@ _SIGS = {
     "ww_loader_indices": (C.c_int, [_vp, _i, _i, _i, _vp, _i, _u64, _u64, _i, _i, C.c_int64, _i, _vp, _vp]),
     "ww_loader_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _u64, _u64, _i, _i, C.c_int64, _i, _i, _vp, _vp,
                                   _vp, _vp]),
+    "ww_q8_quantize": (C.c_int, [_vp, _vp, C.c_long, _f, _i, _vp, _vp]),
+    "ww_q8_stem_fwd": (C.c_int, [_vp] * 6 + [_i] * 4 + [_vp, _vp]),
+    "ww_q8_dwconv3x3_fwd": (C.c_int, [_vp] * 6 + [_i] * 4 + [_vp, _vp]),
+    "ww_q8_pwconv1x1_fwd": (C.c_int, [_vp] * 6 + [C.c_long, _vp, _vp]),
+    "ww_q8_dwpw_fwd": (C.c_int, [_vp] * 10 + [_i] * 4 + [_vp, _vp]),
+    "ww_q8_gap_fc_fwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ww_q8_cnn_small_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ww_q8_cnn_small_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Q8Io), _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "ww_prof_num_classes": (C.c_int, []),
     "ww_prof_class_name": (C.c_char_p, [_i]),
     "ww_ctx_set_deferred_reduce": (C.c_int, [_vp, _i]),
@@ -2108,6 +2123,119 @@ def loader_batch(bank, length, label, strategy, shuffle, training, cdf, seed, ep
                                       int(bool(training)), _p(cdf), n_cdf, int(seed) & _U64, int(epoch) & _U64, int(rank),
                                       int(world), int(k0), B, n_out, _p(out), _p(targets), _p(clip_index), _stream(dev)),
                "ww_loader_batch")
+
+
+# ---- int8 inference of an exported cnn_small bundle (ww_q8.hip).  Tensors are int8 / int32 / float32 device tensors,
+# activations int8 NHWC; conv arguments are (w, bias_eff, mult, shift) as include/wwhip.h lays them out.
+def _q8_conv_check(w, bias, mult, shift, taps):
+    if w.dtype != torch.int8 or tuple(w.shape) != (taps, 64) or any(t.dtype != torch.int32 or t.numel() != 64
+                                                                     for t in (bias, mult, shift)):
+        raise ValueError(f"int8 conv parameters: w int8 ({taps},64), bias / mult / shift int32 (64)")
+
+
+def q8_quantize(x, scale, zero):
+    dev = _dev(x)
+    if x.dtype != torch.float32:
+        raise ValueError("q8_quantize: float32 features")
+    out = torch.empty(x.shape, dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_q8_quantize(ctx(dev), _p(x), x.numel(), float(scale), int(zero), _p(out), _stream(dev)), "ww_q8_quantize")
+    return out
+
+
+def q8_stem_fwd(xq, w, bias, mult, shift, zero):
+    dev = _dev(xq, w, bias, mult, shift)
+    _q8_conv_check(w, bias, mult, shift, 9)
+    if xq.dtype != torch.int8 or xq.dim() != 3:
+        raise ValueError("q8_stem_fwd: int8 (B,F,T) features")
+    B, F, T = xq.shape
+    out = torch.empty((B, (F + 1) // 2, (T + 1) // 2, 64), dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_q8_stem_fwd(ctx(dev), _p(xq), _p(w), _p(bias), _p(mult), _p(shift), B, F, T, int(zero), _p(out),
+                                     _stream(dev)), "ww_q8_stem_fwd")
+    return out
+
+
+def _q8_act_check(a):
+    if a.dtype != torch.int8 or a.dim() != 4 or a.shape[3] != 64:
+        raise ValueError("int8 activations are (B,H,W,64)")
+
+
+def q8_dwconv3x3_fwd(a, w, bias, mult, shift, zero=-128):
+    dev = _dev(a, w, bias, mult, shift)
+    _q8_conv_check(w, bias, mult, shift, 9)
+    _q8_act_check(a)
+    out = torch.empty_like(a)
+    with _guard(dev):
+        _check(load().ww_q8_dwconv3x3_fwd(ctx(dev), _p(a), _p(w), _p(bias), _p(mult), _p(shift), a.shape[0], a.shape[1], a.shape[2],
+                                          int(zero), _p(out), _stream(dev)), "ww_q8_dwconv3x3_fwd")
+    return out
+
+
+def q8_pwconv1x1_fwd(a, w, bias, mult, shift):
+    dev = _dev(a, w, bias, mult, shift)
+    _q8_conv_check(w, bias, mult, shift, 64)
+    _q8_act_check(a)
+    out = torch.empty_like(a)
+    with _guard(dev):
+        _check(load().ww_q8_pwconv1x1_fwd(ctx(dev), _p(a), _p(w), _p(bias), _p(mult), _p(shift), a.numel() // 64, _p(out),
+                                          _stream(dev)), "ww_q8_pwconv1x1_fwd")
+    return out
+
+
+def q8_dwpw_fwd(a, dw, pw, zero=-128):
+    """``dw`` / ``pw``: (w, bias, mult, shift) of the depthwise and the pointwise conv; one kernel, bit-equal to the pair."""
+    dev = _dev(a, *dw, *pw)
+    _q8_conv_check(*dw, 9)
+    _q8_conv_check(*pw, 64)
+    _q8_act_check(a)
+    out = torch.empty_like(a)
+    with _guard(dev):
+        _check(load().ww_q8_dwpw_fwd(ctx(dev), _p(a), *[_p(t) for t in dw], *[_p(t) for t in pw], a.shape[0], a.shape[1], a.shape[2],
+                                     int(zero), _p(out), _stream(dev)), "ww_q8_dwpw_fwd")
+    return out
+
+
+def q8_gap_fc_fwd(a, pool_mult, pool_shift, fc_w, fc_bias, fc_scale):
+    dev = _dev(a, fc_w, fc_bias, fc_scale)
+    _q8_act_check(a)
+    if (fc_w.dtype, fc_bias.dtype, fc_scale.dtype) != (torch.int8, torch.int32, torch.float32) or tuple(fc_w.shape) != (2, 64) \
+            or fc_bias.numel() != 2 or fc_scale.numel() != 2:
+        raise ValueError("q8_gap_fc_fwd: fc_w int8 (2,64), fc_bias int32 (2), fc_scale float32 (2)")
+    B = a.shape[0]
+    pool = torch.empty((B, 64), dtype=torch.int8, device=dev)
+    logits = torch.empty((B, 2), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_q8_gap_fc_fwd(ctx(dev), _p(a), B, a.shape[1] * a.shape[2], int(pool_mult), int(pool_shift), _p(fc_w),
+                                       _p(fc_bias), _p(fc_scale), _p(pool), _p(logits), _stream(dev)), "ww_q8_gap_fc_fwd")
+    return pool, logits
+
+
+def q8_cnn_small_workspace_bytes(B, F, T):
+    return load().ww_q8_cnn_small_workspace_bytes(B, F, T)
+
+
+def q8_cnn_small_fwd(tab, io: Q8Io, x, ws, logits, form=Q8_PAIR):
+    """``tab``: ``ptr_array`` of the Q8_NPTR bundle tensors; x float32 (B,F,T) or (B,1,F,T); ws uint8; logits float32 (B,2)."""
+    dev = _dev(x, ws, logits)
+    B, F, T = x.shape[0], x.shape[-2], x.shape[-1]
+    with _guard(dev):
+        _check(load().ww_q8_cnn_small_fwd(ctx(dev), tab, C.byref(io), _p(x), B, F, T, int(form), _p(ws),
+                                          ws.numel() * ws.element_size(), _p(logits), _stream(dev)), "ww_q8_cnn_small_fwd")
+
+
+def q8_workspace_views(ws, B, F, T):
+    """The tensors ww_q8_cnn_small_fwd left in ``ws`` (uint8), by stage name: xq (B,F,T), the nine activations (B,H,W,64)
+    in execution order, pool (B,64) -- the layout include/wwhip.h states."""
+    H, W = (F + 1) // 2, (T + 1) // 2
+    r256 = lambda n: (n + 255) // 256 * 256       # noqa: E731
+    i8 = ws.view(torch.int8)
+    out, off, act = {"xq": i8[:B * F * T].view(B, F, T)}, r256(B * F * T), B * H * W * 64
+    for name in ["stem"] + [f"{k}{j}" for j in range(4) for k in ("dw", "pw")]:
+        out[name] = i8[off:off + act].view(B, H, W, 64)
+        off += r256(act)
+    out["pool"] = i8[off:off + B * 64].view(B, 64)
+    return out
 
 
 def prof_classes():

@@ -1,0 +1,113 @@
+"""The bundle file: one ``.npz`` whose ``header`` entry is UTF-8 JSON (stored as bytes, so nothing in the file is pickled)
+and whose other entries are plain arrays.  ``numpy.load`` and ``json`` read it; ``check_bundle`` says whether it is whole."""
+import json
+from pathlib import Path
+
+import numpy as np
+
+from .reference import CONVS, FORMAT_NAME, FORMAT_VERSION, load_bundle  # noqa: F401  (load_bundle is re-exported)
+
+STATE_PREFIX = "state/"
+FP16_MAX = 65504.0
+
+
+class BundleError(ValueError):
+    """A bundle that is not what its header says: a missing array, a wrong shape or dtype, an unknown version, a value out
+    of its range."""
+
+
+def write_bundle(path, header: dict, arrays: dict) -> Path:
+    path = Path(path)
+    blob = np.frombuffer(json.dumps(header, sort_keys=True).encode("utf-8"), dtype=np.uint8)
+    with open(path, "wb") as f:                       # an open file: numpy appends no ".npz" to the name it was given
+        np.savez(f, header=blob, **arrays)
+    return path
+
+
+def make_header(kind: str, architecture: str, num_classes: int, input_shape, layers, config=None, **more) -> dict:
+    h = {"format": FORMAT_NAME, "version": FORMAT_VERSION, "kind": kind, "architecture": architecture,
+         "num_classes": int(num_classes), "input_shape": [int(v) for v in input_shape], "layers": list(layers)}
+    if config is not None:
+        h.update(opset_version=int(config.opset_version), dynamic_batch=bool(config.dynamic_batch), optimize=bool(config.optimize))
+    h.update(more)
+    return h
+
+
+def to_fp16(a: np.ndarray) -> np.ndarray:
+    """Round to nearest even, saturating at +-65504 (a NaN stays a NaN)."""
+    return np.clip(np.asarray(a, np.float32), -FP16_MAX, FP16_MAX).astype(np.float16)
+
+
+def float_arrays(state: dict, fp16: bool) -> dict:
+    """state_dict (NumPy) -> bundle arrays; with ``fp16`` every floating tensor is narrowed, the others stay as they are."""
+    out = {}
+    for k, v in state.items():
+        v = np.asarray(v)
+        out[STATE_PREFIX + k] = to_fp16(v) if fp16 and np.issubdtype(v.dtype, np.floating) else v
+    return out
+
+
+def _need(arrays, name, dtype, shape):
+    if name not in arrays:
+        raise BundleError(f"array {name!r} is missing")
+    a = arrays[name]
+    if a.dtype != np.dtype(dtype):
+        raise BundleError(f"array {name!r} is {a.dtype}, expected {np.dtype(dtype)}")
+    if tuple(a.shape) != tuple(shape):
+        raise BundleError(f"array {name!r} has shape {tuple(a.shape)}, expected {tuple(shape)}")
+    return a
+
+
+def _check_mult(arrays, prefix, n):
+    m, sh = _need(arrays, prefix + ".m", np.int32, (n,)), _need(arrays, prefix + ".sh", np.int32, (n,))
+    if (m < 2 ** 30).any():
+        raise BundleError(f"{prefix}.m: a multiplier outside [2^30, 2^31)")
+    if (sh < 1).any() or (sh > 62).any():
+        raise BundleError(f"{prefix}.sh: a shift outside [1, 62]")
+
+
+def check_bundle(header: dict, arrays: dict) -> None:
+    """Raises ``BundleError`` unless the bundle is complete and every value is in the range its law gives it."""
+    if not isinstance(header, dict) or header.get("format") != FORMAT_NAME:
+        raise BundleError("not a wakeword bundle (no such format name in the header)")
+    if header.get("version") != FORMAT_VERSION:
+        raise BundleError(f"format version {header.get('version')!r} is unknown (this reader knows {FORMAT_VERSION})")
+    kind = header.get("kind")
+    for key in ("architecture", "num_classes", "input_shape", "layers"):
+        if key not in header:
+            raise BundleError(f"header entry {key!r} is missing")
+    if len(header["input_shape"]) != 4:
+        raise BundleError(f"input_shape {header['input_shape']!r} is not (1,1,F,T)")
+    if kind in ("fp32", "fp16"):
+        want = np.float32 if kind == "fp32" else np.float16
+        names = [k for k in arrays if k.startswith(STATE_PREFIX)]
+        if not names:
+            raise BundleError("the bundle holds no state")
+        for k in names:
+            if np.issubdtype(arrays[k].dtype, np.floating) and arrays[k].dtype != want:
+                raise BundleError(f"array {k!r} is {arrays[k].dtype} in a bundle of kind {kind}")
+        return
+    if kind != "int8":
+        raise BundleError(f"unknown bundle kind {kind!r}")
+    if header["architecture"] != "cnn_small":
+        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small has an int8 form")
+    fs = header.get("feature_shape")
+    if not (isinstance(fs, list) and len(fs) == 2 and all(isinstance(v, int) and v >= 1 for v in fs)):
+        raise BundleError(f"feature_shape {fs!r} is not [F, T]")
+    s = _need(arrays, "input_scale", np.float32, (1,))
+    if not (np.isfinite(s[0]) and s[0] > 0):
+        raise BundleError("input_scale is not positive and finite")
+    z = _need(arrays, "input_zero", np.int32, (1,))
+    if not -128 <= int(z[0]) <= 127:
+        raise BundleError("input_zero is outside int8")
+    for name in CONVS:
+        w = _need(arrays, name + ".w", np.int8, (64, 64 if name.startswith("pw") else 9))
+        if (w == -128).any():
+            raise BundleError(f"{name}.w holds -128: weights are symmetric, in [-127, 127]")
+        _need(arrays, name + ".b", np.int32, (64,))
+        _check_mult(arrays, name, 64)
+    _check_mult(arrays, "pool", 1)
+    _need(arrays, "fc.w", np.int8, (2, 64))
+    _need(arrays, "fc.b", np.int32, (2,))
+    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (2,))).all():
+        raise BundleError("fc.scale is not finite")

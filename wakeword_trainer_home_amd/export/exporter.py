@@ -1,0 +1,304 @@
+"""The reference's export panel (``src/export/onnx_exporter.py``) without ONNX: neither an ONNX writer nor a runtime exists
+on the build machine, so ``export`` writes self-describing bundles (``bundle.py``) instead -- fp32, fp16 (weights only, as
+the reference's ``QFloat16`` call) and int8 (``cnn_small`` only; the law is DESIGN.md "Export") -- and the int8 bundle runs on
+the device with integer arithmetic (``runtime.QuantizedCNNSmall``).  Names, signatures, result keys and failure behaviour are
+the reference's; ``ONNXExporter``, ``export_model_to_onnx``, ``validate_onnx_model`` and ``benchmark_onnx_model`` stay as
+aliases.  Parity with onnxruntime's ``quantize_dynamic`` is not claimed."""
+import logging
+from dataclasses import dataclass
+from pathlib import Path
+from typing import Any, Dict, Iterable, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _native as nat
+from .bundle import STATE_PREFIX, BundleError, check_bundle, float_arrays, load_bundle, make_header, write_bundle
+from .quantize import QuantizationError, quantize_cnn_small
+from .reference import CONVS
+from .runtime import QuantizedCNNSmall
+
+logger = logging.getLogger(__name__)
+
+
+@dataclass
+class ExportConfig:
+    """The reference's fields and defaults (``onnx_exporter.py:25-34``).  ``opset_version``, ``dynamic_batch`` and ``optimize``
+    are recorded in the bundle's header and otherwise inert: a bundle has no opset, takes any batch size, and there is no
+    graph to optimise.  ``verbose`` logs the calibrated ranges."""
+    output_path: Path
+    opset_version: int = 14
+    dynamic_batch: bool = True
+    quantize_fp16: bool = False
+    quantize_int8: bool = False
+    optimize: bool = True
+    verbose: bool = False
+
+
+_FACTORY_NAMES = {"CNNSmallWakeword": "cnn_small", "MobileNetV3Wakeword": "mobilenetv3", "CRNNWakeword": "crnn",
+                  "GRUWakeword": "gru"}
+
+
+def _architecture(model: nn.Module) -> str:
+    """The factory's name of the model's class (what ``load_exported_model`` builds it from), else the class name."""
+    if getattr(model, "features_only", False):
+        return type(model).__name__
+    return _FACTORY_NAMES.get(type(model).__name__, type(model).__name__)
+
+
+def _state_numpy(model: nn.Module) -> Dict[str, np.ndarray]:
+    return {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
+
+
+def calibrate_cnn_small(model, batches: Iterable[torch.Tensor], feature_shape, device, feature_extractor=None) -> dict:
+    """Ranges of the fp32 model in eval mode over the calibration batches: the input's minimum and maximum, the maximum of
+    every conv's post-ReLU output and of the pooled vector.  Runs the model's own per-layer entry points with
+    ``training = 0``; the maxima are torch reductions on the device and come to the host once, at the end."""
+    F, T = feature_shape
+    dev = torch.device(device)
+    convs = [(model.stem.conv, model.stem.bn)]
+    for blk in model.blocks:
+        convs += [(blk.dw, blk.dw_bn), (blk.pw, blk.pw_bn)]
+    bns = [nat.make_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, 0.1, bn.eps, training=False) for _, bn in convs]
+    scratch = nat.layer_scratch(dev)
+    lo = torch.full((), float("inf"), device=dev)
+    hi = torch.full((), float("-inf"), device=dev)
+    a_max = torch.full((len(convs),), float("-inf"), device=dev)
+    p_max = torch.full((), float("-inf"), device=dev)
+    seen = 0
+    with torch.no_grad():
+        for x in batches:
+            x = torch.as_tensor(x).to(dev)
+            if x.dim() == 2:
+                if feature_extractor is None:
+                    raise QuantizationError("calibration waveforms need a feature_extractor")
+                x = feature_extractor(x)
+            if x.dim() == 3:
+                x = x[:, None]
+            if x.dim() != 4 or tuple(x.shape[1:]) != (1, F, T):
+                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{T})")
+            x = x.float().contiguous()
+            lo, hi = torch.minimum(lo, x.min()), torch.maximum(hi, x.max())
+            y = ss = mr = None
+            for i, ((conv, _), bn) in enumerate(zip(convs, bns)):
+                if i == 0:
+                    y, ss, mr = nat.conv_stem_fwd(x, conv.weight, bn, scratch)
+                elif i % 2:
+                    y, ss, mr = nat.dwconv3x3_fwd(y, ss, conv.weight, bn, scratch)
+                else:
+                    y, ss, mr = nat.pwconv1x1_fwd(y, ss, conv.weight, bn, scratch)
+                a_max[i] = torch.maximum(a_max[i], torch.relu(y * ss[:64] + ss[64:]).max())
+            pool = nat.gap_fwd(y, ss, mr)
+            p_max = torch.maximum(p_max, (pool[:, 0, :] / float(y.shape[1] * y.shape[2])).max())
+            seen += x.shape[0]
+    if seen == 0:
+        raise QuantizationError("the calibration data is empty")
+    return {"x_min": float(lo), "x_max": float(hi), "a_max": [float(v) for v in a_max.cpu()], "p_max": float(p_max),
+            "samples": seen}
+
+
+class ModelExporter:
+    """The reference's ``ONNXExporter`` (``onnx_exporter.py:37-193``).  ``calibration``: an iterable of feature batches
+    ``(B,1,F,T)`` -- or of waveforms ``(B,N)``, which go through ``feature_extractor`` (default: a mel ``FeatureExtractor``
+    with ``n_mels = F``) -- that the int8 export takes its ranges from.  It is never replaced by random data."""
+
+    def __init__(self, model: nn.Module, sample_input_shape: Tuple[int, ...], device: str = "cuda", calibration=None,
+                 feature_extractor=None, architecture: Optional[str] = None):
+        self.architecture = architecture         # the factory name to record; default: looked up from the model's class
+        self.model, self.sample_input_shape, self.device = model, tuple(int(v) for v in sample_input_shape), device
+        self.calibration, self.feature_extractor = calibration, feature_extractor
+        self.model.to(device)
+        self.model.eval()
+        logger.info("ModelExporter initialized with input shape: %s", self.sample_input_shape)
+
+    def export(self, config: ExportConfig) -> Dict[str, Any]:
+        output_path = Path(config.output_path)
+        logger.info("Exporting model to: %s", output_path)
+        try:
+            output_path.parent.mkdir(parents=True, exist_ok=True)
+        except Exception as e:                                    # noqa: BLE001 -- as the reference: any failure is reported
+            logger.error("Failed to create output directory: %s", e)
+            return {"success": False, "error": f"Directory creation failed: {e}"}
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            try:
+                dummy = torch.randn(*self.sample_input_shape).to(self.device)
+            except Exception as e:                                # noqa: BLE001
+                return {"success": False, "error": f"Input tensor creation failed: {e}"}
+            try:
+                with torch.no_grad():
+                    test_output = self.model(dummy)
+                    if not torch.isfinite(test_output).all():
+                        logger.error("Model produces non-finite outputs")
+                        return {"success": False, "error": "Model outputs contain NaN or Inf"}
+                arch = self.architecture or _architecture(self.model)
+                state = _state_numpy(self.model)
+                header = make_header("fp32", arch, int(test_output.shape[1]), self.sample_input_shape,
+                                     [k for k in state if k.endswith("weight")], config)
+                write_bundle(output_path, header, float_arrays(state, fp16=False))
+                if not output_path.exists():
+                    return {"success": False, "error": "Export completed but file not found"}
+                size_mb = output_path.stat().st_size / (1024 * 1024)
+                results = {"success": True, "path": str(output_path), "opset_version": config.opset_version,
+                           "dynamic_batch": config.dynamic_batch, "file_size_mb": size_mb}
+                for kind, wanted, write in (("fp16", config.quantize_fp16, self._write_fp16),
+                                            ("int8", config.quantize_int8, self._write_int8)):
+                    if not wanted:
+                        continue
+                    try:
+                        path = write(output_path, header, state, config)
+                        mb = path.stat().st_size / (1024 * 1024)
+                        results[f"{kind}_path"], results[f"{kind}_size_mb"] = str(path), mb
+                        results[f"{kind}_reduction"] = (1 - mb / size_mb) * 100
+                    except Exception as e:                        # noqa: BLE001
+                        logger.error("%s quantization failed: %s", kind.upper(), e)
+                        results[f"{kind}_error"] = str(e)
+                return results
+            except Exception as e:                                # noqa: BLE001
+                logger.exception("Export failed: %s", e)
+                return {"success": False, "error": str(e)}
+        finally:
+            if was_training:
+                self.model.train()
+
+    def _write_fp16(self, output_path: Path, header: dict, state: dict, config: ExportConfig) -> Path:
+        path = output_path.parent / f"{output_path.stem}_fp16.npz"
+        return write_bundle(path, dict(header, kind="fp16"), float_arrays(state, fp16=True))
+
+    def _write_int8(self, output_path: Path, header: dict, state: dict, config: ExportConfig) -> Path:
+        if header["architecture"] != "cnn_small":
+            raise QuantizationError(f"int8 export covers cnn_small only, not {header['architecture']!r}")
+        if self.calibration is None:
+            raise QuantizationError("int8 export needs calibration data (ModelExporter(..., calibration=batches)); "
+                                    "it is never calibrated on random input")
+        F, T = self.sample_input_shape[-2:]
+        fe = self.feature_extractor
+        if fe is None:
+            from ..data.feature_extraction import FeatureExtractor
+            fe = FeatureExtractor(n_mels=F, device=self.device)
+        cal = calibrate_cnn_small(self.model, self.calibration, (F, T), self.device, fe)
+        if config.verbose:
+            logger.info("calibrated ranges: %s", cal)
+        arrays, scales = quantize_cnn_small(state, (F, T), cal["x_min"], cal["x_max"], cal["a_max"], cal["p_max"],
+                                            eps=self.model.stem.bn.eps)
+        h = dict(header, kind="int8", layers=CONVS + ["pool", "fc"], feature_shape=[int(F), int(T)], scales=scales,
+                 calibration=cal)
+        check_bundle(h, arrays)
+        path = output_path.parent / f"{output_path.stem}_int8.npz"
+        return write_bundle(path, h, arrays)
+
+
+def export_model(checkpoint_path: Path, output_path: Path, opset_version: int = 14, dynamic_batch: bool = True,
+                 quantize_fp16: bool = False, quantize_int8: bool = False, device: str = "cuda", calibration=None) -> Dict:
+    """Checkpoint -> bundles (``onnx_exporter.py:257-347``); the checkpoint is read by ``load_model_for_evaluation``."""
+    from ..evaluation.evaluator import load_model_for_evaluation
+    model, info = load_model_for_evaluation(Path(checkpoint_path), device)
+    config = info["config"]
+    sample_rate, duration = config.data.sample_rate, config.data.audio_duration
+    n_frames = int(sample_rate * duration) // config.data.hop_length + 1
+    shape = (1, 1, config.data.n_mels, n_frames)
+    from ..data.feature_extraction import FeatureExtractor
+    fe = FeatureExtractor(sample_rate=sample_rate, n_mels=config.data.n_mels, n_fft=getattr(config.data, "n_fft", 1024),
+                          hop_length=config.data.hop_length, device=device)
+    exporter = ModelExporter(model, shape, device, calibration=calibration, feature_extractor=fe,
+                             architecture=config.model.architecture)
+    results = exporter.export(ExportConfig(output_path=Path(output_path), opset_version=opset_version,
+                                           dynamic_batch=dynamic_batch, quantize_fp16=quantize_fp16,
+                                           quantize_int8=quantize_int8, optimize=True, verbose=False))
+    results.update(architecture=config.model.architecture, sample_rate=sample_rate, duration=duration, input_shape=shape)
+    return results
+
+
+def load_exported_model(path: Path, device: str = "cuda") -> nn.Module:
+    """A bundle as a module in eval mode on ``device``: the factory's architecture with the stored weights (fp16 widened to
+    fp32) or, for an int8 bundle, ``QuantizedCNNSmall``.  ``ModelEvaluator`` and ``RecordingScanner`` take either."""
+    header, arrays = load_bundle(path)
+    check_bundle(header, arrays)
+    if header["kind"] == "int8":
+        return QuantizedCNNSmall(header, arrays).to(device)
+    from ..models import create_model
+    model = create_model(architecture=header["architecture"], num_classes=header["num_classes"], pretrained=False)
+    state = {}
+    for k, v in arrays.items():
+        if k.startswith(STATE_PREFIX):
+            t = torch.from_numpy(np.ascontiguousarray(v))
+            state[k[len(STATE_PREFIX):]] = t.float() if t.is_floating_point() else t
+    model.load_state_dict(state)
+    model.to(device)
+    model.eval()
+    return model
+
+
+def validate_exported_model(path: Path, pytorch_model: Optional[nn.Module] = None, sample_input: Optional[torch.Tensor] = None,
+                            device: str = "cuda") -> Dict:
+    """The reference's ``validate_onnx_model`` (``:350-438``) and its keys; never raises on a malformed bundle."""
+    results: Dict[str, Any] = {"valid": False, "error": None}
+    try:
+        path = Path(path)
+        header, arrays = load_bundle(path)
+        check_bundle(header, arrays)
+        results["valid"] = True
+        results["graph"] = len(header["layers"])
+        results["inputs"] = [("input", [0] + list(header["input_shape"][1:]))]      # 0: the batch dimension is free
+        results["outputs"] = [("output", [0, header["num_classes"]])]
+        results["file_size_mb"] = path.stat().st_size / (1024 * 1024)
+        if sample_input is not None:
+            model = load_exported_model(path, device)
+            with torch.no_grad():
+                out = model(sample_input.to(device)).cpu().numpy()
+            results["inference_success"] = True
+            results["output_shape"] = out.shape
+            if pytorch_model is not None:
+                pytorch_model.eval()
+                pytorch_model.to(device)
+                with torch.no_grad():
+                    ref = pytorch_model(sample_input.to(device)).cpu().numpy()
+                results["max_difference"] = float(np.abs(ref - out).max())
+                results["mean_difference"] = float(np.abs(ref - out).mean())
+                results["numerically_equivalent"] = bool(results["max_difference"] < 1e-3)
+    except Exception as e:                                        # noqa: BLE001 -- as the reference: any failure is the answer
+        logger.error("Validation failed: %s", e)
+        results["valid"] = False
+        results["error"] = str(e)
+    return results
+
+
+def _time_forwards(model, x, num_runs: int) -> float:
+    """ms per forward: device events around ``num_runs`` forwards after 10 warm-up runs, one synchronisation at the end."""
+    with torch.no_grad():
+        for _ in range(10):
+            model(x)
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(num_runs):
+            model(x)
+        end.record()
+    end.synchronize()
+    return start.elapsed_time(end) / num_runs
+
+
+def benchmark_exported_model(path: Path, pytorch_model: nn.Module, sample_input: torch.Tensor, num_runs: int = 100,
+                             device: str = "cuda") -> Dict:
+    """The reference's ``benchmark_onnx_model`` (``:441-517``); ``onnx_time_ms`` repeats ``exported_time_ms`` for callers
+    that read the reference's key."""
+    if num_runs < 1:
+        raise ValueError("num_runs must be at least 1")
+    pytorch_model.eval()
+    pytorch_model.to(device)
+    x = sample_input.to(device)
+    exported = load_exported_model(path, device)
+    t_torch = _time_forwards(pytorch_model, x, num_runs)
+    t_exp = _time_forwards(exported, x, num_runs)
+    return {"pytorch_time_ms": t_torch, "exported_time_ms": t_exp, "onnx_time_ms": t_exp, "speedup": t_torch / t_exp,
+            "num_runs": num_runs}
+
+
+ONNXExporter = ModelExporter
+export_model_to_onnx = export_model
+validate_onnx_model = validate_exported_model
+benchmark_onnx_model = benchmark_exported_model
+__all__ = ["ExportConfig", "ModelExporter", "ONNXExporter", "export_model", "export_model_to_onnx", "load_exported_model",
+           "validate_exported_model", "validate_onnx_model", "benchmark_exported_model", "benchmark_onnx_model",
+           "QuantizedCNNSmall", "BundleError", "QuantizationError", "calibrate_cnn_small"]

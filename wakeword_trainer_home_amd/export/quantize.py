@@ -1,0 +1,127 @@
+"""The export side of the int8 law (DESIGN.md "Export"): BatchNorm folding, scales, integer weights, biases and multipliers
+of ``cnn_small``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does with the result."""
+import math
+from typing import Dict, Sequence
+
+import numpy as np
+
+from .reference import BLOCKS, CONVS
+
+A_MAX_FLOOR = 255.0 * 2.0 ** -20       # a calibrated maximum at or below zero (a dead layer) counts as this: s_out = 2^-20
+ACC_MAX_3X3 = 9 * 127 * 255            # largest |sum q_w (q_in - z_in)| of the stem and the depthwise convs
+ACC_MAX_1X1 = 64 * 127 * 255           # ... of the pointwise convs and the classifier
+INT32_MAX = 2 ** 31 - 1
+
+
+class QuantizationError(ValueError):
+    """The model or its calibration cannot be expressed in the int8 law; the message names the layer and channel."""
+
+
+def encode_multiplier(r: float, what: str = "multiplier"):
+    """(m, sh) with 2^30 <= m < 2^31, 1 <= sh <= 62 and m * 2^-sh the nearest such value to ``r`` (ties to the even m)."""
+    r = float(r)
+    if not (math.isfinite(r) and r > 0.0):
+        raise QuantizationError(f"{what}: the real multiplier {r!r} is not positive and finite")
+    f, e = math.frexp(r)                         # r = f * 2^e, 0.5 <= f < 1
+    m = int(np.rint(f * 2.0 ** 31))              # exact product, one rounding
+    if m == 2 ** 31:
+        m, e = 2 ** 30, e + 1
+    sh = 31 - e
+    if not 1 <= sh <= 62:
+        raise QuantizationError(f"{what}: the real multiplier {r!r} needs a shift of {sh}, outside [1, 62]")
+    return m, sh
+
+
+def fold_bn(w, gamma, beta, mean, var, eps):
+    """W' = W g / sqrt(var + eps) per output channel, b' = beta - mean g / sqrt(var + eps); float64."""
+    w, gamma, beta, mean, var = (np.asarray(t, np.float64) for t in (w, gamma, beta, mean, var))
+    k = gamma / np.sqrt(var + float(eps))
+    return w.reshape(w.shape[0], -1) * k[:, None], beta - mean * k
+
+
+def quantize_weights(wf):
+    """wf float64 (C,K) -> (int8 (C,K), s_w float64 (C,)): s_w = max|row| / 127, an all-zero row takes 1."""
+    amax = np.abs(wf).max(axis=1)
+    s_w = np.where(amax > 0, amax / 127.0, 1.0)
+    return np.clip(np.rint(wf / s_w[:, None]), -127, 127).astype(np.int8), s_w
+
+
+def quantize_bias(bf, s_in, s_w, acc_max, layer):
+    q = np.rint(np.asarray(bf, np.float64) / (s_in * s_w))
+    bad = np.nonzero(~(np.abs(q) + acc_max <= INT32_MAX))[0]       # (a NaN is bad too)
+    if bad.size:
+        c = int(bad[0])
+        raise QuantizationError(f"{layer}, channel {c}: bias {q[c]!r} plus an accumulator of up to {acc_max} leaves int32")
+    return q.astype(np.int32)
+
+
+def input_qparams(x_min, x_max):
+    """(s_x as float32, z_x) from the calibrated range, widened to contain 0; an empty range counts as [0, 1]."""
+    lo, hi = min(float(x_min), 0.0), max(float(x_max), 0.0)
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise QuantizationError(f"input: the calibrated range [{x_min!r}, {x_max!r}] is not finite")
+    if hi - lo <= 0.0:
+        hi = 1.0
+    s = np.float32((hi - lo) / 255.0)
+    if not (np.isfinite(s) and s > 0):
+        raise QuantizationError(f"input: the scale of the range [{lo!r}, {hi!r}] is not a positive float32")
+    z = int(np.clip(np.rint(-128.0 - lo / float(s)), -128, 127))
+    return s, z
+
+
+def out_scale(a_max):
+    a = float(a_max)
+    if math.isnan(a) or math.isinf(a):
+        raise QuantizationError(f"a calibrated maximum of {a!r} is not finite")
+    return max(a, A_MAX_FLOOR) / 255.0
+
+
+def cnn_small_float_layers(state: Dict[str, np.ndarray], eps: float = 1e-5):
+    """{conv name: (W' (64,K), b' (64,))} of a cnn_small state_dict, BatchNorm folded; plus ``fc``."""
+    def bn(prefix):
+        return [state[f"{prefix}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")]
+    layers = {"stem": fold_bn(state["stem.conv.weight"], *bn("stem.bn"), eps)}
+    for k in range(BLOCKS):
+        layers[f"dw{k}"] = fold_bn(state[f"blocks.{k}.dw.weight"], *bn(f"blocks.{k}.dw_bn"), eps)
+        layers[f"pw{k}"] = fold_bn(state[f"blocks.{k}.pw.weight"], *bn(f"blocks.{k}.pw_bn"), eps)
+    layers["fc"] = (np.asarray(state["classifier.weight"], np.float64), np.asarray(state["classifier.bias"], np.float64))
+    return layers
+
+
+def quantize_cnn_small(state: Dict[str, np.ndarray], feature_shape: Sequence[int], x_min: float, x_max: float,
+                       a_max: Sequence[float], p_max: float, eps: float = 1e-5):
+    """The arrays of an int8 bundle and its scales.  ``a_max``: the calibrated maximum of each conv's post-ReLU output, in
+    ``CONVS`` order; ``p_max``: that of the pooled vector.  Raises ``QuantizationError`` where the law refuses."""
+    F, T = int(feature_shape[0]), int(feature_shape[1])
+    H, W = (F + 1) // 2, (T + 1) // 2
+    if len(a_max) != len(CONVS):
+        raise QuantizationError(f"{len(a_max)} calibrated maxima for {len(CONVS)} convs")
+    layers = cnn_small_float_layers(state, eps)
+    if layers["fc"][0].shape != (2, 64):
+        raise QuantizationError(f"the int8 path has a Linear(64,2) classifier, got weights of shape {layers['fc'][0].shape}")
+    s_x, z_x = input_qparams(x_min, x_max)
+    arrays = {"input_scale": np.array([s_x], np.float32), "input_zero": np.array([z_x], np.int32)}
+    scales = {"input": float(s_x)}
+    s_in = float(s_x)
+    for name, am in zip(CONVS, a_max):
+        wf, bf = layers[name]
+        acc_max = ACC_MAX_1X1 if name.startswith("pw") else ACC_MAX_3X3
+        q_w, s_w = quantize_weights(wf)
+        s_out = out_scale(am)
+        ms = [encode_multiplier(s_in * s_w[c] / s_out, f"{name}, channel {c}") for c in range(64)]
+        arrays[name + ".w"] = q_w
+        arrays[name + ".b"] = quantize_bias(bf, s_in, s_w, acc_max, name)
+        arrays[name + ".m"] = np.array([m for m, _ in ms], np.int32)
+        arrays[name + ".sh"] = np.array([s for _, s in ms], np.int32)
+        scales[name] = s_out
+        s_in = s_out
+    s_p = out_scale(p_max)
+    m_p, sh_p = encode_multiplier(s_in / (H * W * s_p), "pool")
+    arrays["pool.m"], arrays["pool.sh"] = np.array([m_p], np.int32), np.array([sh_p], np.int32)
+    scales["pool"] = s_p
+    wf, bf = layers["fc"]
+    q_w, s_w = quantize_weights(wf)
+    arrays["fc.w"] = q_w
+    arrays["fc.b"] = quantize_bias(bf, s_p, s_w, ACC_MAX_1X1, "classifier")
+    arrays["fc.scale"] = (s_p * s_w).astype(np.float32)
+    return arrays, scales

@@ -1,0 +1,101 @@
+"""``QuantizedCNNSmall``: an int8 bundle on the device, run with integer arithmetic only (``ww_q8_cnn_small_fwd``)."""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _native as nat
+from .bundle import check_bundle
+from .reference import CONVS
+
+
+def effective_bias(q_b: np.ndarray, q_w: np.ndarray, z_in: int) -> np.ndarray:
+    """q_b - z_in * sum(q_w) per output channel, wrapped to int32: what the kernels add to sum q_w q_in (include/wwhip.h)."""
+    return (q_b.astype(np.int64) - int(z_in) * q_w.astype(np.int64).sum(axis=1)).astype(np.int32)
+
+
+def device_conv(arrays: dict, name: str, z_in: int):
+    """The four tensors of one conv as the kernels read them: w (taps,64) for the 3x3 convs, (64,64) [out][in] for 1x1."""
+    w = arrays[name + ".w"]
+    return (np.ascontiguousarray(w if name.startswith("pw") else w.T), effective_bias(arrays[name + ".b"], w, z_in),
+            arrays[name + ".m"], arrays[name + ".sh"])
+
+
+class QuantizedCNNSmall(nn.Module):
+    """``forward((B,1,F,T) float32 on the device) -> (B,2) float32``: one native call, no host synchronisation.
+
+    Eval only, no parameters.  The bundle is for ONE feature shape (the pooling multiplier holds 1/HW): another shape is
+    refused.  ``form``: ``"pair"`` runs depthwise and pointwise as two launches, ``"fused"`` as one; both give the same bits.
+    """
+
+    hip_backed = True
+    FORMS = {"pair": nat.Q8_PAIR, "fused": nat.Q8_FUSED}
+    DEFAULT_FORM = "fused"
+
+    def __init__(self, header: dict, arrays: dict, form: str = None):
+        super().__init__()
+        check_bundle(header, arrays)
+        if header["kind"] != "int8":
+            raise ValueError(f"QuantizedCNNSmall needs an int8 bundle, got kind {header['kind']!r}")
+        self.header = dict(header)
+        self.feature_shape = tuple(int(v) for v in header["feature_shape"])
+        self.num_classes = 2
+        self.set_form(form or self.DEFAULT_FORM)
+        z_x = int(arrays["input_zero"][0])
+        self.io = nat.Q8Io(float(arrays["input_scale"][0]), z_x, int(arrays["pool.m"][0]), int(arrays["pool.sh"][0]))
+        self._names = []
+        for name in CONVS:
+            for suffix, a in zip(("w", "b", "m", "sh"), device_conv(arrays, name, z_x if name == "stem" else -128)):
+                self._add(f"{name}_{suffix}", a)
+        for key in ("fc.w", "fc.b", "fc.scale"):
+            self._add(key.replace(".", "_"), arrays[key])
+        assert len(self._names) == nat.Q8_NPTR
+        self._tab, self._key, self._ws = None, None, {}
+        self.eval()
+
+    def _add(self, name, a):
+        self.register_buffer(name, torch.from_numpy(np.ascontiguousarray(a).copy()), persistent=False)
+        self._names.append(name)
+
+    def set_form(self, form: str):
+        if form not in self.FORMS:
+            raise ValueError(f"form must be one of {sorted(self.FORMS)}, got {form!r}")
+        self.form = form
+        return self
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise RuntimeError("QuantizedCNNSmall is an inference network: it has no training mode")
+        return super().train(False)
+
+    def conv(self, name):
+        """(w, bias_eff, mult, shift) of one conv, for the per-layer entry points."""
+        return tuple(getattr(self, f"{name}_{s}") for s in ("w", "b", "m", "sh"))
+
+    def _table(self):
+        tensors = [getattr(self, n) for n in self._names]
+        key = tuple(t.data_ptr() for t in tensors)
+        if self._key != key:
+            self._tab, self._key = nat.ptr_array(tensors), key
+        return self._tab
+
+    def workspace(self, B):
+        """The uint8 workspace of the last forward at this batch size (``_native.q8_workspace_views`` names its parts)."""
+        return self._ws[B]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() == 4 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 3 or tuple(x.shape[1:]) != self.feature_shape:
+            raise ValueError(f"this int8 bundle is for features of shape {self.feature_shape}, got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"features must be float32, got {x.dtype}")
+        if not x.is_contiguous() or x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.contiguous_format)
+        B, (F, T) = x.shape[0], self.feature_shape
+        dev = nat._dev(x, self.fc_w)
+        ws = self._ws.get(B)
+        if ws is None or ws.device != dev:
+            ws = self._ws[B] = torch.empty(nat.q8_cnn_small_workspace_bytes(B, F, T), dtype=torch.uint8, device=dev)
+        logits = torch.empty((B, 2), dtype=torch.float32, device=dev)
+        nat.q8_cnn_small_fwd(self._table(), self.io, x, ws, logits, self.FORMS[self.form])
+        return logits
