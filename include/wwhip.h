@@ -33,7 +33,7 @@ extern "C" {
 
 /* 17: ww_pass_plan / ww_loader_plan (host-only pass plans of the capped-grid support launches) were added; no existing
  * signature, struct, constant or result changed.  ww_dw_plan / ww_ctx_set_dw_wide_addr came later under the same number: pure
- * additions again. */
+ * additions again, as is ww_gemm_plan. */
 #define WW_ABI_VERSION 17
 
 #define WW_OK 0
@@ -544,6 +544,27 @@ int ww_loader_plan(int B, int n_out, int *out);
  * segment, items, waves (item pairs) of the launch, how many of them take the interior body (both strips have all six window
  * columns inside the image; no column clamps, selects or guards), address form: 32 or 64}.                                      */
 int ww_dw_plan(int B, int H, int W, int act_dtype, int wide, long *out);
+/* Host-only: what ww_linear_mfma_fwd (which = 0) / ww_linear_mfma_bwd (which = 1) launch for (M, K, N) in `mode`, from the
+ * functions the launchers themselves decide through; no context, no device (ABI 17, additive).  full_epilogue: forward 1 when a
+ * pre-activation copy, an activation or dropout is requested (the EPI 1 kernels), backward 1 when an activation or dropout is
+ * (k_linear_dpre runs).  aligned: 1 when every base pointer is on a 16-byte boundary; the leading-dimension half of the float4
+ * rule follows from the shape.  need_dx: backward, 0 when dx is NULL.  A block tile cfg is 0 = 64 x 64, 1 = 128 x 64,
+ * 2 = 128 x 128; shallow = the 32-deep K stage of the 16-bit modes.  out[24], unused entries 0:
+ *   forward:  {0 EPI kind 1 / 2, 1 cfg, 2 shallow, 3 K per LDS stage, 4 vecA (x), 5 vecB (w), 6-8 grid x / y / z}
+ *   backward: {0 k_linear_dpre runs, 1 its grid, 2 dX and dW in one k_gemm_pair launch, 3 the rule that refused the pair
+ *              (WW_PAIR_*), 4 dX cfg as launched (after the tall remap), 5 dX shallow, 6 dW cfg, 7 dW shallow, 8 contraction rows
+ *              per dW split, 9 dW splits nz, 10 workgroups of the dW side nbw, 11 of the dX side nbx (0 without dx), 12
+ *              k_splitk_sum is launched (or its sum queued when the context defers), 13 its grid, 14-16 WW_GEMM_PAIR,
+ *              WW_GEMM_PAIR_TALL and the effective WW_DW_MIN_ROWS as the library read them, 17 dX cfg before the remap, 18 splits
+ *              asked for, 19-22 vec of dX's A (dpre) and B (w), dW's A (dpre) and B (x), 23 workgroups of the bias-gradient sum} */
+#define WW_PAIR_OK 0          /* paired */
+#define WW_PAIR_OFF 1         /* WW_GEMM_PAIR=0 */
+#define WW_PAIR_DX_CFG2 2     /* dX wants 128 x 128 tiles */
+#define WW_PAIR_DW_TILE 3     /* dW wants a tile other than 64 x 64 */
+#define WW_PAIR_DW_SHALLOW 4  /* dW wants the shallow stage (M <= 32, 16-bit modes) */
+#define WW_PAIR_TALL_OFF 5    /* a tall deep dX under WW_GEMM_PAIR_TALL=0 */
+#define WW_PAIR_NO_DX 6       /* dx == NULL: dW alone */
+int ww_gemm_plan(int which, int mode, int M, int K, int N, int full_epilogue, int aligned, int need_dx, long *out);
 
 /* ------------------------------------------------------------------ conv front-end of the CRNN
  * cnn_small's conv stack (stem + 4 depthwise-separable blocks) without GAP / classifier, followed by the mean over the

@@ -22,17 +22,9 @@ def _rel(a, b):
                                    (4096, 64, 1024), (8192, 24, 20), (8192, 200, 64), (300, 30, 300)])
 @pytest.mark.parametrize("mode", ["fp32", "bf16", "fp16"])
 def test_linear_fwd_bwd_matches_torch(M, K, N, mode):
-    """Each mode against its restatement (operands rounded to the matrix type, wide sums).  The launch_gemm / gemm_plan choice
-    each shape reaches in the 16-bit modes (fwd = x W^T over K, dX = dY W over N, dW = dY^T x over M split dw_splits ways):
-      (4096, 64, 1024)  fwd cfg 2 (128 x 128 tiles: both extents >= 128, 256 tiles); dW 32 splits in the paired dX+dW launch
-      (2048, 576, 1024) dW cfg 2 with 8 K splits + k_splitk_sum, dX cfg 0, issued as two launches (the pair refuses cfg 2)
-      (8192, 200, 64)   fwd cfg 1 (M >= 8192); paired launch with a tall dX (128-row plan remapped to 64 rows), dW 64 splits
-      (8192, 24, 20)    fwd cfg 1 shallow (K <= 32: one 32-deep stage); paired launch with a cfg 1 shallow dX, dW 64 splits
-      (1, 7, 3)         fwd / dX / dW all cfg 0 shallow, unaligned (K = 7: vec = 0), dX and dW separately (the pair refuses a
-                        shallow dW)
-      (300, 30, 300)    fwd cfg 0 shallow with vec = 0 (K = 30); dW 2 splits with unaligned rows in the pair
-      (130, 40, 2), (200, 1024, 2)  paired launch with a shallow dX over N = 2, unaligned dpre (vec = 0)
-      (77, 576, 1024), (64, 64, 64) the paired launch, cfg 0, one split"""
+    """Each mode against its restatement (operands rounded to the matrix type, wide sums).  The launch_gemm / pair choice each
+    shape reaches in the 16-bit modes is data now: tests/gemm_cases.py LEGACY_CLAIMS, asserted through ww_gemm_plan by
+    test_gemm_paths_host.py::test_what_the_older_linear_test_reaches (per launch path and bit for bit: test_gemm_paths_gpu.py)."""
     from wakeword_trainer_home_amd import _native as nat
     g = torch.Generator().manual_seed(M * 7 + N)
     x = torch.randn(M, K, generator=g)

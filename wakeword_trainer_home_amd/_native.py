@@ -213,6 +213,7 @@ _SIGS = {
     "ww_pass_plan": (C.c_int, [_i, C.c_long, C.POINTER(C.c_long)]),
     "ww_dw_plan": (C.c_int, [_i, _i, _i, _i, _i, C.POINTER(C.c_long)]),
     "ww_loader_plan": (C.c_int, [_i, _i, C.POINTER(C.c_int)]),
+    "ww_gemm_plan": (C.c_int, [_i] * 8 + [C.POINTER(C.c_long)]),
     "ww_gru_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ww_gru_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, C.c_long, _vp, _vp, _sz, _vp]),
     "ww_gru_bidir_fwd": (C.c_int, [_vp, _i, _vp, C.c_long, _vp, _i, _i, _i, _i, _vp, C.c_long, _sz, _vp]),
@@ -1449,6 +1450,25 @@ def plan_dw_strips(B, H, W, dtype=torch.float32, wide=False):
     out = (C.c_long * 7)()
     _check(load().ww_dw_plan(int(B), int(H), int(W), act_code(dtype), int(bool(wide)), out), "ww_dw_plan")
     return dict(zip(("ncs", "nseg", "hs_len", "items", "waves", "interior_waves", "addr_bits"), out))
+
+
+GEMM_PLAN_FWD = ("epi", "cfg", "shallow", "stage_k", "vecA", "vecB", "gx", "gy", "gz")
+GEMM_PLAN_BWD = ("dpre", "dpre_grid", "paired", "refused", "dx_cfg", "dx_shallow", "dw_cfg", "dw_shallow", "kps", "nz", "nbw", "nbx",
+                 "splitk_sum", "splitk_grid", "env_pair", "env_pair_tall", "dw_min_rows", "dx_cfg_plain", "splits", "dx_vecA",
+                 "dx_vecB", "dw_vecA", "dw_vecB", "db_grid")
+PAIR_REFUSALS = ("paired", "off", "dx_cfg2", "dw_tile", "dw_shallow", "tall_off", "no_dx")       # WW_PAIR_* of include/wwhip.h, in order
+
+
+def plan_gemm(which, M, K, N, mode=torch.float32, full_epilogue=False, aligned=True, need_dx=True):
+    """What linear_mfma_fwd (which = "fwd") / linear_mfma_bwd ("bwd") launch for (M, K, N) (ww_gemm_plan: the launchers' own
+    dispatch code, no device) -> a dict of GEMM_PLAN_FWD / GEMM_PLAN_BWD; "refused" is one of PAIR_REFUSALS."""
+    out = (C.c_long * 24)()
+    _check(load().ww_gemm_plan(("fwd", "bwd").index(which), act_code(mode), int(M), int(K), int(N), int(bool(full_epilogue)),
+                               int(bool(aligned)), int(bool(need_dx)), out), "ww_gemm_plan")
+    p = dict(zip(GEMM_PLAN_FWD if which == "fwd" else GEMM_PLAN_BWD, out))
+    if which == "bwd":
+        p["refused"] = PAIR_REFUSALS[p["refused"]]
+    return p
 
 
 def plan_loader(B, n_out):

@@ -476,28 +476,54 @@ static inline int gemm_tile_cfg(int epi, int mode, long rowsA, long rowsB, int n
     const long tiles128 = ((rowsA + 127) / 128) * ((rowsB + 127) / 128) * nz;
     return (epi != 1 && mode != WW_ACT_F32 && rowsA >= 128 && rowsB >= 128 && tiles128 >= 256) ? 2 : (rowsA >= 8192 ? 1 : 0);
 }
-// splits > 1: partial products into `part` (splits x rows x cols), then summed in fixed order into C
-template <bool KCA, bool KCB, int EPI, bool A16 = false, bool SEG = false>
-int launch_gemm(int mode, const GemmOperand &A, const GemmOperand &B, int K, float *C, long ldc, const Epilogue &e,
-                hipStream_t st, int splits = 1, float *part = nullptr, int *row_tile_out = nullptr, ww_ctx *defer_ctx = nullptr) {
-    auto aligned = [](const GemmOperand &o, bool kc) {
-        const long ld = kc ? o.s_row : o.s_k;
-        return (int)((((uintptr_t)o.p | (uintptr_t)o.p2) & (o.h16 ? 7 : 15)) == 0 && (ld & 3) == 0);
-    };
-    const int vecA = aligned(A, KCA), vecB = aligned(B, KCB);
-    int kps = K;
+// ---- the host's dispatch rules, one copy each: launch_gemm, launch_gemm_pair and ww_gemm_plan (wwhip.h) decide through these
+// float4 (16-bit operands: four-element) loads of an operand: its base on a 16-byte (8-byte) boundary and its leading dimension
+// -- the stride of the coordinate that is NOT contiguous in memory -- a multiple of 4
+static inline int operand_vec(const GemmOperand &o, bool kc) {
+    const long ld = kc ? o.s_row : o.s_k;
+    return (int)((((uintptr_t)o.p | (uintptr_t)o.p2) & (o.h16 ? 7 : 15)) == 0 && (ld & 3) == 0);
+}
+// what launch_gemm launches for rowsA x rowsB outputs over K in `splits` K splits with epilogue kind epi: K per split and the
+// split count, the block tile, the shallow 32-deep stage of the 16-bit modes, the grid
+struct GemmPlan { int cfg, kps, nz; bool shallow; int gx, gy; };
+static inline void gemm_plan_grid(GemmPlan &p, long rowsA, long rowsB) {
+    const int RA = p.cfg ? 128 : 64, RBt = p.cfg == 2 ? 128 : 64;
+    p.gx = (int)((rowsB + RBt - 1) / RBt);
+    p.gy = (int)((rowsA + RA - 1) / RA);
+}
+static inline GemmPlan gemm_plan(int epi, int mode, long rowsA, long rowsB, int K, int splits) {
+    GemmPlan p;
+    p.kps = K;
     const int kt = mode != WW_ACT_F32 ? GKH : GK;      // a multiple of every stage depth in use (128, 64, 32)
-    if (splits > 1) kps = ((K + splits - 1) / splits + kt - 1) / kt * kt;
-    const int nz = (K + kps - 1) / kps;
+    if (splits > 1) p.kps = ((K + splits - 1) / splits + kt - 1) / kt * kt;
+    p.nz = (K + p.kps - 1) / p.kps;
     // Block tile: 64 x 64 by default; 128 x 128 (each staged byte feeds twice the MFMA work: these GEMMs are bound by operand
     // traffic, not by the matrix cores) when both extents allow it and enough workgroups remain; 128 x 64 for very tall ones
     // (the 128 x 128 form pays in bf16 mode only: in fp32 mode its 64 accumulator + 32 prefetch registers cost occupancy, 72 vs 82 TF)
     // (the dense head's full epilogue -- EPI = 1 -- stays off the 128 x 128 form: with 64 accumulators beside the Philox dropout
     // the kernel spilled scalar registers and carried a scratch segment; the head's GEMMs are far too small to miss that tile)
-    const int cfg = gemm_tile_cfg(EPI, mode, A.rows, B.rows, nz);
-    const int RA = cfg ? 128 : 64, RBt = cfg == 2 ? 128 : 64;
-    if (row_tile_out) *row_tile_out = RA;
-    dim3 grid((B.rows + RBt - 1) / RBt, (A.rows + RA - 1) / RA, nz);
+    p.cfg = gemm_tile_cfg(epi, mode, rowsA, rowsB, p.nz);
+    p.shallow = K <= 32 && p.nz == 1 && p.cfg != 2 && mode != WW_ACT_F32;   // 16-bit modes: one 32-deep stage instead of a 128-deep one
+    gemm_plan_grid(p, rowsA, rowsB);
+    return p;
+}
+// K per LDS stage of the instantiation a plan selects (GemmLds' own constant)
+static inline int gemm_stage_k(int mode, const GemmPlan &p) {
+    if (mode == WW_ACT_F32) return GemmLds<0, true, true, 1, 1, 0>::KT;
+    if (p.shallow) return GemmLds<1, true, true, 1, 1, 32>::KT;
+    return p.cfg == 2 ? GemmLds<1, true, true, 2, 2, 0>::KT : p.cfg == 1 ? GemmLds<1, true, true, 2, 1, 0>::KT : GemmLds<1, true, true, 1, 1, 0>::KT;
+}
+static inline int splitk_grid(long n) { return (int)std::min<long>((n / 4 + 255) / 256 + 1, 2048); }      // k_splitk_sum over n sums
+static inline int dpre_grid(long n) { return (int)std::min<long>((n + 255) / 256, 256 * 16); }           // k_linear_dpre over n elements
+// splits > 1: partial products into `part` (splits x rows x cols), then summed in fixed order into C
+template <bool KCA, bool KCB, int EPI, bool A16 = false, bool SEG = false>
+int launch_gemm(int mode, const GemmOperand &A, const GemmOperand &B, int K, float *C, long ldc, const Epilogue &e,
+                hipStream_t st, int splits = 1, float *part = nullptr, int *row_tile_out = nullptr, ww_ctx *defer_ctx = nullptr) {
+    const int vecA = operand_vec(A, KCA), vecB = operand_vec(B, KCB);
+    const GemmPlan pl = gemm_plan(EPI, mode, A.rows, B.rows, K, splits);
+    const int kps = pl.kps, nz = pl.nz, cfg = pl.cfg;
+    if (row_tile_out) *row_tile_out = cfg ? 128 : 64;
+    dim3 grid(pl.gx, pl.gy, nz);
     float *dst = nz > 1 ? part : C;
     const long sstride = (long)A.rows * ldc;
 #define WW_GEMM_LAUNCH(BF, TM_, TN_) \
@@ -505,7 +531,7 @@ int launch_gemm(int mode, const GemmOperand &A, const GemmOperand &B, int K, flo
         hipLaunchKernelGGL((k_gemm<BF, KCA, KCB, EPI, TM_, TN_, 0, (A16 && BF != 0), SEG>), grid, dim3(256), 0, st, A, B, K, kps, dst, ldc, sstride, vecA, vecB, e); } while (0)
 #define WW_GEMM_LAUNCH_K32(BF, TM_) \
     hipLaunchKernelGGL((k_gemm<BF, KCA, KCB, EPI, TM_, 1, 32, (A16 && BF != 0), SEG>), grid, dim3(256), 0, st, A, B, K, kps, dst, ldc, sstride, vecA, vecB, e)
-    const bool shallow = K <= 32 && nz == 1 && cfg != 2;       // 16-bit modes: one 32-deep stage instead of a 128-deep one
+    const bool shallow = pl.shallow;
     if (mode == WW_ACT_BF16) {
         if (shallow) { if (cfg == 1) WW_GEMM_LAUNCH_K32(1, 2); else WW_GEMM_LAUNCH_K32(1, 1); }
         else if (cfg == 2) WW_GEMM_LAUNCH(1, 2, 2); else if (cfg == 1) WW_GEMM_LAUNCH(1, 2, 1); else WW_GEMM_LAUNCH(1, 1, 1);
@@ -520,54 +546,62 @@ int launch_gemm(int mode, const GemmOperand &A, const GemmOperand &B, int K, flo
     WW_LAUNCH_CHECK();
     if (nz > 1 && !(ldc == B.rows && ww_defer(defer_ctx, part, C, sstride, nz, e.accumulate))) {
         const long n = sstride;
-        const int g = (int)std::min<long>((n / 4 + 255) / 256 + 1, 2048);
-        hipLaunchKernelGGL(k_splitk_sum, dim3(g), dim3(256), 0, st, part, n, nz, C, e.accumulate);
+        hipLaunchKernelGGL(k_splitk_sum, dim3(splitk_grid(n)), dim3(256), 0, st, part, n, nz, C, e.accumulate);
         WW_LAUNCH_CHECK();
     }
     return WW_OK;
 }
 
+// ---- the operands of the dense layer's three products (the launchers and ww_gemm_plan build them here)
+struct GemmSides { GemmOperand A, B; };
+static inline GemmSides fwd_sides(const float *x, const float *w, int M, int K, int N) {       // y[m][n] = sum_k x[m][k] w[n][k]
+    return GemmSides{GemmOperand{x, K, 1, M}, GemmOperand{w, K, 1, N}};
+}
+static inline GemmSides dx_sides(const float *dpre, const float *w, int M, int K, int N) {     // dx[m][k] = sum_n dpre[m][n] w[n][k]
+    return GemmSides{GemmOperand{dpre, N, 1, M}, GemmOperand{w, 1, K, K}};    // A = dpre (n contiguous), B(k, n) = w[n][k]
+}
+static inline GemmSides dw_sides(const float *dpre, const float *x, int M, int K, int N) {     // dw[n][k] = sum_m dpre[m][n] x[m][k]
+    return GemmSides{GemmOperand{dpre, 1, N, N}, GemmOperand{x, 1, K, K}};    // A(n, m) = dpre[m][n], B(k, m) = x[m][k]
+}
 // ---- the paired launch of ww_linear_mfma_bwd: dW (N x K) = dpre^T x split over the M rows, and dX (M x K) = dpre W
-struct GemmPlan { int cfg, kps, nz; bool shallow; };
-GemmPlan gemm_plan(int mode, const GemmOperand &A, const GemmOperand &B, int K, int splits) {      // launch_gemm's choices
-    GemmPlan p;
-    p.kps = K;
-    const int kt = mode != WW_ACT_F32 ? GKH : GK;
-    if (splits > 1) p.kps = ((K + splits - 1) / splits + kt - 1) / kt * kt;
-    p.nz = (K + p.kps - 1) / p.kps;
-    p.cfg = gemm_tile_cfg(0, mode, A.rows, B.rows, p.nz);
-    p.shallow = K <= 32 && p.nz == 1 && p.cfg != 2 && mode != WW_ACT_F32;
+static inline int env_gemm_pair() { static const int v = ww_env_int("WW_GEMM_PAIR", 1); return v; }
+static inline int env_gemm_pair_tall() { static const int v = ww_env_int("WW_GEMM_PAIR_TALL", 1); return v; }
+// The pair / refuse / remap decision and the grids of both sides.  refused: 0 = paired, else the first rule that said no (the
+// caller then issues the two products separately, by px and pw as they stand): the paired kernel carries 64 x 64 dW tiles with a
+// deep stage and 64- or 128-row x 64 dX tiles, nothing else (WW_PAIR_*: wwhip.h)
+struct PairPlan { int refused; GemmPlan px, pw; int px_cfg_plain, nbw, nbx; };
+static inline PairPlan pair_plan(int mode, int M, int K, int N, int splits) {
+    PairPlan p = {};
+    p.px = gemm_plan(0, mode, M, K, N, 1);
+    p.pw = gemm_plan(0, mode, N, K, M, splits);
+    p.px_cfg_plain = p.px.cfg;
+    // tall dX products (128-row tiles) with a deep K stage: the paired kernel's 128-row form needs 480 registers (one wave per
+    // SIMD: 43 us against 31 for the two separate launches at M = 194 560) -- WW_GEMM_PAIR_TALL: 0 = launch them separately,
+    // 1 = pair with 64-row dX tiles, 2 = pair with 128-row tiles
+    const bool tall_deep = p.px.cfg == 1 && !p.px.shallow;
+    if (!env_gemm_pair()) p.refused = WW_PAIR_OFF;
+    else if (p.px.cfg == 2) p.refused = WW_PAIR_DX_CFG2;
+    else if (p.pw.cfg != 0) p.refused = WW_PAIR_DW_TILE;
+    else if (p.pw.shallow) p.refused = WW_PAIR_DW_SHALLOW;
+    else if (tall_deep && env_gemm_pair_tall() == 0) p.refused = WW_PAIR_TALL_OFF;
+    else if (tall_deep && env_gemm_pair_tall() == 1) { p.px.cfg = 0; gemm_plan_grid(p.px, M, K); }
+    p.nbw = p.pw.gx * p.pw.gy * p.pw.nz;
+    p.nbx = p.px.gx * p.px.gy;
     return p;
 }
 // returns 1 when the pair was launched (dW partials in `part` when nz > 1, their sum queued on ctx or launched), 0 when the
 // shapes want tile forms the paired kernel does not carry (the caller then issues the two products separately), < 0 on error
 int launch_gemm_pair(ww_ctx *ctx, int mode, const float *dpre, const float *x, const float *w, int M, int K, int N, float *dx,
                      float *dw, int splits, float *part, hipStream_t st) {
-    static const int enabled = ww_env_int("WW_GEMM_PAIR", 1);
-    if (!enabled) return 0;
-    const GemmOperand Ax{dpre, N, 1, M}, Bx{w, 1, K, K};            // dx[m][k] = sum_n dpre[m][n] w[n][k]
-    const GemmOperand Aw{dpre, 1, N, N}, Bw{x, 1, K, K};            // dw[n][k] = sum_m dpre[m][n] x[m][k]
-    GemmPlan px = gemm_plan(mode, Ax, Bx, N, 1);
-    const GemmPlan pw = gemm_plan(mode, Aw, Bw, M, splits);
-    if (px.cfg == 2 || pw.cfg != 0 || pw.shallow) return 0;
-    // tall dX products (128-row tiles) with a deep K stage: the paired kernel's 128-row form needs 480 registers (one wave per
-    // SIMD: 43 us against 31 for the two separate launches at M = 194 560) -- WW_GEMM_PAIR_TALL: 0 = launch them separately,
-    // 1 = pair with 64-row dX tiles, 2 = pair with 128-row tiles
-    static const int tall = ww_env_int("WW_GEMM_PAIR_TALL", 1);
-    if (px.cfg == 1 && !px.shallow) {
-        if (tall == 0) return 0;
-        if (tall == 1) px.cfg = 0;
-    }
-    auto aligned = [](const GemmOperand &o, bool kc) {
-        const long ld = kc ? o.s_row : o.s_k;
-        return (int)((((uintptr_t)o.p | (uintptr_t)o.p2) & (o.h16 ? 7 : 15)) == 0 && (ld & 3) == 0);
-    };
-    const int RAx = px.cfg ? 128 : 64;
-    PairSide sw{Aw, Bw, M, pw.kps, pw.nz > 1 ? part : dw, (long)K, (long)N * K, aligned(Aw, false), aligned(Bw, false),
-                (K + 63) / 64, (N + 63) / 64, pw.nz};
-    PairSide sx{Ax, Bx, N, N, dx, (long)K, 0, aligned(Ax, true), aligned(Bx, false), (K + 63) / 64, (M + RAx - 1) / RAx, 1};
-    const int nbw = sw.gx * sw.gy * sw.nz, nbx = sx.gx * sx.gy;
-    const dim3 grid(nbw + nbx);
+    const PairPlan pp = pair_plan(mode, M, K, N, splits);
+    if (pp.refused) return 0;
+    const GemmPlan &px = pp.px, &pw = pp.pw;
+    const GemmSides X = dx_sides(dpre, w, M, K, N), W = dw_sides(dpre, x, M, K, N);
+    PairSide sw{W.A, W.B, M, pw.kps, pw.nz > 1 ? part : dw, (long)K, (long)N * K, operand_vec(W.A, false), operand_vec(W.B, false),
+                pw.gx, pw.gy, pw.nz};
+    PairSide sx{X.A, X.B, N, N, dx, (long)K, 0, operand_vec(X.A, true), operand_vec(X.B, false), px.gx, px.gy, 1};
+    const int nbw = pp.nbw;
+    const dim3 grid(pp.nbw + pp.nbx);
 #define WW_PAIR(MODE_) \
     do { \
         if (px.shallow) { if (px.cfg) hipLaunchKernelGGL((k_gemm_pair<MODE_, 2, 32>), grid, dim3(256), 0, st, sw, sx, nbw); \
@@ -583,8 +617,7 @@ int launch_gemm_pair(ww_ctx *ctx, int mode, const float *dpre, const float *x, c
     WW_LAUNCH_CHECK();
     if (pw.nz > 1 && !ww_defer(ctx, part, dw, (long)N * K, pw.nz, 0)) {
         const long n = (long)N * K;
-        const int g = (int)std::min<long>((n / 4 + 255) / 256 + 1, 2048);
-        hipLaunchKernelGGL(k_splitk_sum, dim3(g), dim3(256), 0, st, part, n, pw.nz, dw, 0);
+        hipLaunchKernelGGL(k_splitk_sum, dim3(splitk_grid(n)), dim3(256), 0, st, part, n, pw.nz, dw, 0);
         WW_LAUNCH_CHECK();
     }
     return 1;
@@ -677,10 +710,10 @@ extern "C" int ww_linear_mfma_fwd(ww_ctx *ctx, int mode, const float *x, const f
     if (rc) return rc;
     Epilogue e;
     if ((rc = make_epilogue(ctx, epi, bias, pre, &e))) return rc;
-    const GemmOperand A{x, K, 1, M}, B{w, K, 1, N};
+    const GemmSides S = fwd_sides(x, w, M, K, N);
     ww_prof_scope ps_(ctx, WW_K_LINEAR, (hipStream_t)stream);
-    if (e.pre || e.act != WW_LIN_NONE || e.use_dropout) return launch_gemm<true, true, 1>(mode, A, B, K, y, N, e, (hipStream_t)stream);
-    return launch_gemm<true, true, 2>(mode, A, B, K, y, N, e, (hipStream_t)stream);
+    if (e.pre || e.act != WW_LIN_NONE || e.use_dropout) return launch_gemm<true, true, 1>(mode, S.A, S.B, K, y, N, e, (hipStream_t)stream);
+    return launch_gemm<true, true, 2>(mode, S.A, S.B, K, y, N, e, (hipStream_t)stream);
 }
 
 // Conv2dNormActivation with a 1x1 (or im2col'ed) convolution in training mode: y = x W^T on the matrix cores with the BatchNorm
@@ -720,11 +753,12 @@ extern "C" int ww_conv1x1_row_tile(int mode, int M, int K, int N) {
 // K splits of the weight-gradient product dW (N x K) = dpre^T x: its contraction runs over the M rows (batch x pixels), which
 // for a 1x1 convolution is hundreds of thousands while N x K is a handful of 64 x 64 tiles -- the splits are what fills the
 // chip: enough of them for ~1024 workgroups, each at least 512 rows deep
+static int dw_min_rows() { static const int v = std::max(128, ww_env_int("WW_DW_MIN_ROWS", 128)); return v; }
 static int dw_splits(int M, int K, int N) {
     // rows of the contraction per split: ONE 128-deep K stage.  A split's time is a chain of dependent stages (fetch -> LDS ->
     // MFMA, ~3 us each at these sizes), so shallower splits finish sooner and the deferred reduction sums the extra partials for
     // free (MobileNetV3 B=256, WW_DW_MIN_ROWS = 512 / 256 / 128: 2.694 / 2.579 / 2.566 ms per step, profiles/r03_e_*)
-    static const int min_rows = std::max(128, ww_env_int("WW_DW_MIN_ROWS", 128));
+    const int min_rows = dw_min_rows();
     const long tiles = (long)((N + 63) / 64) * ((K + 63) / 64);
     long s = (1024 + tiles - 1) / tiles;
     s = std::min<long>(s, M / min_rows);
@@ -750,27 +784,65 @@ extern "C" int ww_linear_mfma_bwd(ww_ctx *ctx, int mode, const float *x, const f
     const float *dpre = dy;
     if (e.act != WW_LIN_NONE || e.use_dropout) {
         const long n = (long)M * N;
-        const int grid = (int)std::min<long>((n + 255) / 256, 256 * 16);
-        hipLaunchKernelGGL(k_linear_dpre, dim3(grid), dim3(256), 0, st, dy, pre, (long)M, N, e, (float *)scratch);
+        hipLaunchKernelGGL(k_linear_dpre, dim3(dpre_grid(n)), dim3(256), 0, st, dy, pre, (long)M, N, e, (float *)scratch);
         WW_LAUNCH_CHECK();
         dpre = (const float *)scratch;
     }
     const Epilogue none = {};
+    // The split-K partials follow dpre's M*N floats.  Partial z starts at part0 + z*N*K, so k_splitk_sum's float4 reads of the
+    // partials are only 4-byte aligned whenever M*N or N*K is no multiple of 4 (its reads and writes of dW stay on 16 bytes).  A
+    // 4-byte-aligned global_load_dwordx4 is a legal access on gfx950 and returns the same bytes: accepted as it is, and pinned
+    // bit for bit by the (257, 33, 71) case of tests/gemm_cases.py (M*N odd, N*K % 4 == 3).  Rounding part0 up to 16 bytes would
+    // not remove these reads (z*N*K stays off the boundary).  The deferred flush (k_reduce_items) checks the alignment itself.
     float *const part0 = (float *)scratch + (size_t)M * N;
     const int paired = dx ? launch_gemm_pair(ctx, mode, dpre, x, w, M, K, N, dx, dw, dw_splits(M, K, N), part0, st) : 0;
     if (paired < 0) return paired;
-    if (dx && !paired) {   // dx[m][k] = sum_n dpre[m][n] w[n][k] : A = dpre (n contiguous), B(k, n) = w[n][k] (row index contiguous)
-        const GemmOperand A{dpre, N, 1, M}, B{w, 1, K, K};
-        if ((rc = launch_gemm<true, false, 0>(mode, A, B, N, dx, K, none, st))) return rc;
+    if (dx && !paired) {
+        const GemmSides S = dx_sides(dpre, w, M, K, N);
+        if ((rc = launch_gemm<true, false, 0>(mode, S.A, S.B, N, dx, K, none, st))) return rc;
     }
-    if (!paired) {   // dw[n][k] = sum_m dpre[m][n] x[m][k] : A(n, m) = dpre[m][n], B(k, m) = x[m][k]
-        const GemmOperand A{dpre, 1, N, N}, B{x, 1, K, K};
-        float *part = (float *)scratch + (size_t)M * N;
-        if ((rc = launch_gemm<false, false, 0>(mode, A, B, M, dw, K, none, st, dw_splits(M, K, N), part, nullptr, ctx))) return rc;
+    if (!paired) {
+        const GemmSides S = dw_sides(dpre, x, M, K, N);
+        if ((rc = launch_gemm<false, false, 0>(mode, S.A, S.B, M, dw, K, none, st, dw_splits(M, K, N), part0, nullptr, ctx))) return rc;
     }
     if (db) {
         hipLaunchKernelGGL(k_colsum_any, dim3((N + 63) / 64), dim3(1024), 0, st, dpre, M, N, db);
         WW_LAUNCH_CHECK();
     }
+    return WW_OK;
+}
+
+// host-only: what ww_linear_mfma_fwd (which = 0) / ww_linear_mfma_bwd (which = 1) launch, from the functions the launchers call
+// (wwhip.h lists out[24])
+extern "C" int ww_gemm_plan(int which, int mode, int M, int K, int N, int full_epilogue, int aligned, int need_dx, long *out) {
+    WW_REQUIRE(out && (which == 0 || which == 1) && (full_epilogue == 0 || full_epilogue == 1) && (aligned == 0 || aligned == 1) &&
+               (need_dx == 0 || need_dx == 1), WW_E_INVALID, "ww_gemm_plan: bad argument");
+    int rc = check_dims("ww_gemm_plan", mode, M, K, N);
+    if (rc) return rc;
+    for (int i = 0; i < 24; ++i) out[i] = 0;
+    // stand-in base pointers, never dereferenced: on or off the 16-byte grid as the caller says its tensors are
+    const float *base = reinterpret_cast<const float *>((uintptr_t)(aligned ? 16 : 4));
+    if (which == 0) {
+        const int epi = full_epilogue ? 1 : 2;
+        const GemmSides S = fwd_sides(base, base, M, K, N);
+        const GemmPlan p = gemm_plan(epi, mode, S.A.rows, S.B.rows, K, 1);
+        out[0] = epi; out[1] = p.cfg; out[2] = p.shallow; out[3] = gemm_stage_k(mode, p);
+        out[4] = operand_vec(S.A, true); out[5] = operand_vec(S.B, true);
+        out[6] = p.gx; out[7] = p.gy; out[8] = p.nz;
+        return WW_OK;
+    }
+    const int splits = dw_splits(M, K, N);
+    PairPlan pp = pair_plan(mode, M, K, N, splits);
+    if (!need_dx) { pp.refused = WW_PAIR_NO_DX; pp.nbx = 0; }      // ww_linear_mfma_bwd does not ask launch_gemm_pair then
+    const GemmSides X = dx_sides(base, base, M, K, N), W = dw_sides(base, base, M, K, N);
+    out[0] = full_epilogue; out[1] = full_epilogue ? dpre_grid((long)M * N) : 0;
+    out[2] = pp.refused == WW_PAIR_OK; out[3] = pp.refused;
+    out[4] = pp.px.cfg; out[5] = pp.px.shallow; out[6] = pp.pw.cfg; out[7] = pp.pw.shallow;
+    out[8] = pp.pw.kps; out[9] = pp.pw.nz; out[10] = pp.nbw; out[11] = pp.nbx;
+    out[12] = pp.pw.nz > 1; out[13] = pp.pw.nz > 1 ? splitk_grid((long)N * K) : 0;
+    out[14] = env_gemm_pair(); out[15] = env_gemm_pair_tall(); out[16] = dw_min_rows();
+    out[17] = pp.px_cfg_plain; out[18] = splits;
+    out[19] = operand_vec(X.A, true); out[20] = operand_vec(X.B, false); out[21] = operand_vec(W.A, false); out[22] = operand_vec(W.B, false);
+    out[23] = (N + 63) / 64;
     return WW_OK;
 }
