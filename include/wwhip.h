@@ -937,6 +937,50 @@ size_t ww_q8_cnn_small_workspace_bytes(int B, int F, int T);
 int ww_q8_cnn_small_fwd(ww_ctx *ctx, const void *const *tab, const ww_q8_io *io, const float *x, int B, int F, int T, int form,
                         void *ws, size_t ws_bytes, float *logits, ww_stream_t stream);
 
+/* ------------------------------------------------------------------ int8 inference of an exported TCNWakeword bundle
+ * The same law with one more rule, the residual add (DESIGN.md "Export", subsection "TCN"); ww_q8_tcn.hip.  Activations are int8
+ * rows (B*T, Cp), Cp = the channel count rounded up to 64; pad channels hold the tensor's zero point (z_x for the quantised
+ * features, -128 for everything a conv or an add writes).  Every tensor is 16-byte aligned.  Per conv (k taps, dilation d):
+ *   w      int8 (Cpo, k, Cpi) [out][tap][in]; pad rows and pad columns are zero
+ *   bias   int32 (Cpo): the EFFECTIVE bias q_b - z_in * sum(q_w); mult int32 (Cpo) in [2^30, 2^31), shift int32 (Cpo) in [1, 62];
+ *          pad channels: bias 0, mult 2^30, shift 31, so they come out as -128
+ *   acc[t][n] = sum_j sum_c w[n][j][c] * in[t - (k-1-j) d][c] + bias[n], a source time below 0 reading `zero`
+ *   residual == NULL:  out = clamp(-128 + R(acc, mult, shift), -128, 127), R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh
+ *   residual (N, Cpo): out = clamp(-128 + R(acc, mult, shift) + R(residual + 128, res_mult, res_shift), -128, 127) -- the
+ *          downsample conv carrying the block's add and last ReLU
+ * ww_tq8_quantize_bt: x fp32 (B,F,T) -> int8 (B*T, Fp), the input rule of ww_q8_quantize, transposed; pad channels = zero.
+ * ww_tq8_skip_add_fwd: out = clamp(-128 + R(in - zero, skip_mult, skip_shift) + R(h2 + 128, add_mult, add_shift), -128, 127).
+ * ww_tq8_pool_fc_fwd: S[c] = sum_t (q + 128); pool_out int8 (B, C) = the requantised S; logits (B, num_classes) =
+ *   float32(sum_c fc_w[k][c] (pool[c] + 128) + fc_bias[k]) * fc_scale[k]; fc_w int8 (num_classes, C), UNPADDED, fc_bias the law's q_b.
+ * The whole model: tab = per block WW_TQ8_BLOCK_NPTR device pointers [conv1 w, bias, mult, shift, conv2 .., downsample ..] (the last
+ * four NULL for an identity skip), then [fc_w, fc_bias, fc_scale]; io on the host.  Block i has dilation 2^i.  The workspace holds,
+ * each rounded up to 256 bytes: xq (B*T*Fp), then per block h1, h2, out (B*T*Cp_i each), then pool (B*C_last) -- that sum is what
+ * the workspace-size entry point returns.  Nothing synchronises with the host. */
+#define WW_TQ8_MAX_BLOCKS 8
+#define WW_TQ8_BLOCK_NPTR 12
+typedef struct {
+    float in_scale;                         /* s_x */
+    int32_t in_zero;                        /* z_x */
+    int32_t pool_mult, pool_shift;
+    int32_t n_blocks, kernel_size, input_size, num_classes;
+    int32_t channels[WW_TQ8_MAX_BLOCKS];    /* unpadded */
+    int32_t add_mult[WW_TQ8_MAX_BLOCKS], add_shift[WW_TQ8_MAX_BLOCKS];
+    int32_t skip_mult[WW_TQ8_MAX_BLOCKS], skip_shift[WW_TQ8_MAX_BLOCKS];   /* identity skips only */
+} ww_tq8_io;
+int ww_tq8_quantize_bt(ww_ctx *ctx, const float *x, int B, int F, int T, int Fp, float scale, int zero, int8_t *out,
+                       ww_stream_t stream);
+int ww_tq8_conv1d_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, const int32_t *bias, const int32_t *mult,
+                      const int32_t *shift, int B, int T, int Cpi, int Cpo, int k, int dilation, int zero, const int8_t *residual,
+                      int res_mult, int res_shift, int8_t *out, ww_stream_t stream);
+int ww_tq8_skip_add_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *h2, long N, int Cp, int zero, int skip_mult, int skip_shift,
+                        int add_mult, int add_shift, int8_t *out, ww_stream_t stream);
+int ww_tq8_pool_fc_fwd(ww_ctx *ctx, const int8_t *in, int B, int T, int C, int Cp, int pool_mult, int pool_shift, const int8_t *fc_w,
+                       const int32_t *fc_bias, const float *fc_scale, int num_classes, int8_t *pool_out, float *logits,
+                       ww_stream_t stream);
+size_t ww_tq8_tcn_workspace_bytes(int B, int F, int T, int n_blocks, const int32_t *channels);
+int ww_tq8_tcn_fwd(ww_ctx *ctx, const void *const *tab, const ww_tq8_io *io, const float *x, int B, int T, void *ws, size_t ws_bytes,
+                   float *logits, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ collectives: deliberately NOT in this ABI
  * SURVEY.md §8b sketched two more entry points, `ww_comm_init` (ctx, nccl_unique_id, rank, world) and `ww_allreduce_f32`
  * (ctx, buf, n, avg, comm_stream).

@@ -124,6 +124,17 @@ class Q8Io(C.Structure):
 
 
 Q8_NPTR, Q8_NACT, Q8_PAIR, Q8_FUSED = 39, 9, 0, 1
+TQ8_MAX_BLOCKS, TQ8_BLOCK_NPTR = 8, 12
+
+
+class Tq8Io(C.Structure):
+    """ww_tq8_io: the scalars of an int8 TCNWakeword bundle (include/wwhip.h)."""
+    _fields_ = [("in_scale", C.c_float), ("in_zero", C.c_int32), ("pool_mult", C.c_int32), ("pool_shift", C.c_int32),
+                ("n_blocks", C.c_int32), ("kernel_size", C.c_int32), ("input_size", C.c_int32), ("num_classes", C.c_int32),
+                ("channels", C.c_int32 * TQ8_MAX_BLOCKS), ("add_mult", C.c_int32 * TQ8_MAX_BLOCKS),
+                ("add_shift", C.c_int32 * TQ8_MAX_BLOCKS), ("skip_mult", C.c_int32 * TQ8_MAX_BLOCKS),
+                ("skip_shift", C.c_int32 * TQ8_MAX_BLOCKS)]
+
 
 _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 _SIGS = {
@@ -268,6 +279,12 @@ _SIGS = {
     "ww_q8_gap_fc_fwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ww_q8_cnn_small_workspace_bytes": (_sz, [_i, _i, _i]),
     "ww_q8_cnn_small_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Q8Io), _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "ww_tq8_quantize_bt": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp]),
+    "ww_tq8_conv1d_fwd": (C.c_int, [_vp] * 6 + [_i] * 7 + [_vp, _i, _i, _vp, _vp]),
+    "ww_tq8_skip_add_fwd": (C.c_int, [_vp, _vp, _vp, C.c_long] + [_i] * 6 + [_vp, _vp]),
+    "ww_tq8_pool_fc_fwd": (C.c_int, [_vp, _vp] + [_i] * 6 + [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ww_tq8_tcn_workspace_bytes": (_sz, [_i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "ww_tq8_tcn_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Tq8Io), _vp, _i, _i, _vp, _sz, _vp, _vp]),
     "ww_prof_num_classes": (C.c_int, []),
     "ww_prof_class_name": (C.c_char_p, [_i]),
     "ww_ctx_set_deferred_reduce": (C.c_int, [_vp, _i]),
@@ -2255,6 +2272,109 @@ def q8_workspace_views(ws, B, F, T):
         out[name] = i8[off:off + act].view(B, H, W, 64)
         off += r256(act)
     out["pool"] = i8[off:off + B * 64].view(B, 64)
+    return out
+
+
+# ---- int8 inference of an exported TCNWakeword bundle (ww_q8_tcn.hip).  Activations are int8 (B,T,Cp) rows, Cp a multiple of 64;
+# conv arguments are (w (Cpo,k,Cpi), bias_eff, mult, shift), padded as include/wwhip.h lays them out.
+def tq8_pad(c):
+    return (int(c) + 63) // 64 * 64
+
+
+def _tq8_act_check(a, what):
+    if a.dtype != torch.int8 or a.dim() != 3 or a.shape[2] % 64:
+        raise ValueError(f"{what}: int8 activations are (B,T,Cp), Cp a multiple of 64")
+
+
+def tq8_quantize_bt(x, scale, zero):
+    """x float32 (B,F,T) -> int8 (B,T,Fp); the pad channels hold ``zero``."""
+    dev = _dev(x)
+    if x.dtype != torch.float32 or x.dim() != 3:
+        raise ValueError("tq8_quantize_bt: float32 (B,F,T) features")
+    B, F, T = x.shape
+    out = torch.empty((B, T, tq8_pad(F)), dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_tq8_quantize_bt(ctx(dev), _p(x), B, F, T, out.shape[2], float(scale), int(zero), _p(out), _stream(dev)),
+               "ww_tq8_quantize_bt")
+    return out
+
+
+def tq8_conv1d_fwd(a, w, bias, mult, shift, dilation, zero=-128, residual=None, res_mult=0, res_shift=0):
+    """``residual`` (B,T,Cpo) with its multiplier and shift selects the epilogue that carries the block's add and last ReLU."""
+    dev = _dev(a, w, bias, mult, shift, residual)
+    _tq8_act_check(a, "tq8_conv1d_fwd")
+    if w.dtype != torch.int8 or w.dim() != 3 or w.shape[2] != a.shape[2] or w.shape[0] % 64 or \
+            any(t.dtype != torch.int32 or t.numel() != w.shape[0] for t in (bias, mult, shift)):
+        raise ValueError("tq8_conv1d_fwd: w int8 (Cpo,k,Cpi), bias / mult / shift int32 (Cpo)")
+    B, T, Cpi = a.shape
+    Cpo, k = w.shape[0], w.shape[1]
+    if residual is not None and (residual.dtype != torch.int8 or tuple(residual.shape) != (B, T, Cpo)):
+        raise ValueError("tq8_conv1d_fwd: residual int8 (B,T,Cpo)")
+    out = torch.empty((B, T, Cpo), dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_tq8_conv1d_fwd(ctx(dev), _p(a), _p(w), _p(bias), _p(mult), _p(shift), B, T, Cpi, Cpo, k, int(dilation),
+                                        int(zero), _p(residual), int(res_mult), int(res_shift), _p(out), _stream(dev)),
+               "ww_tq8_conv1d_fwd")
+    return out
+
+
+def tq8_skip_add_fwd(a, h2, zero, skip_mult, skip_shift, add_mult, add_shift):
+    dev = _dev(a, h2)
+    _tq8_act_check(a, "tq8_skip_add_fwd")
+    if h2.dtype != torch.int8 or h2.shape != a.shape:
+        raise ValueError("tq8_skip_add_fwd: h2 int8 of the input's shape")
+    out = torch.empty_like(a)
+    with _guard(dev):
+        _check(load().ww_tq8_skip_add_fwd(ctx(dev), _p(a), _p(h2), a.shape[0] * a.shape[1], a.shape[2], int(zero), int(skip_mult),
+                                          int(skip_shift), int(add_mult), int(add_shift), _p(out), _stream(dev)),
+               "ww_tq8_skip_add_fwd")
+    return out
+
+
+def tq8_pool_fc_fwd(a, C_real, pool_mult, pool_shift, fc_w, fc_bias, fc_scale):
+    """a int8 (B,T,Cp) with ``C_real`` channels -> (pool int8 (B,C_real), logits float32 (B,num_classes))."""
+    dev = _dev(a, fc_w, fc_bias, fc_scale)
+    _tq8_act_check(a, "tq8_pool_fc_fwd")
+    nc = fc_w.shape[0]
+    if (fc_w.dtype, fc_bias.dtype, fc_scale.dtype) != (torch.int8, torch.int32, torch.float32) or \
+            tuple(fc_w.shape) != (nc, C_real) or fc_bias.numel() != nc or fc_scale.numel() != nc:
+        raise ValueError("tq8_pool_fc_fwd: fc_w int8 (num_classes,C), fc_bias int32 (num_classes), fc_scale float32 (num_classes)")
+    B, T, Cp = a.shape
+    pool = torch.empty((B, C_real), dtype=torch.int8, device=dev)
+    logits = torch.empty((B, nc), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_tq8_pool_fc_fwd(ctx(dev), _p(a), B, T, int(C_real), Cp, int(pool_mult), int(pool_shift), _p(fc_w), _p(fc_bias),
+                                         _p(fc_scale), nc, _p(pool), _p(logits), _stream(dev)), "ww_tq8_pool_fc_fwd")
+    return pool, logits
+
+
+def tq8_tcn_workspace_bytes(B, F, T, channels):
+    ch = (C.c_int32 * len(channels))(*[int(c) for c in channels])
+    return load().ww_tq8_tcn_workspace_bytes(B, F, T, len(channels), ch)
+
+
+def tq8_tcn_fwd(tab, io: Tq8Io, x, ws, logits):
+    """``tab``: ``ptr_array`` of the bundle's tensors (TQ8_BLOCK_NPTR per block, then fc_w, fc_bias, fc_scale); x float32
+    (B,F,T) or (B,1,F,T); ws uint8; logits float32 (B,num_classes)."""
+    dev = _dev(x, ws, logits)
+    with _guard(dev):
+        _check(load().ww_tq8_tcn_fwd(ctx(dev), tab, C.byref(io), _p(x), x.shape[0], x.shape[-1], _p(ws),
+                                     ws.numel() * ws.element_size(), _p(logits), _stream(dev)), "ww_tq8_tcn_fwd")
+
+
+def tq8_workspace_views(ws, B, F, T, channels):
+    """The tensors ww_tq8_tcn_fwd left in ``ws`` (uint8), by stage name, PADDED: xq (B,T,Fp), per block b{i}.h1, b{i}.h2, b{i}.out
+    (B,T,Cp_i), pool (B,C_last) -- the layout include/wwhip.h states."""
+    r256 = lambda n: (n + 255) // 256 * 256       # noqa: E731
+    i8 = ws.view(torch.int8)
+    Fp = tq8_pad(F)
+    out, off = {"xq": i8[:B * T * Fp].view(B, T, Fp)}, r256(B * T * Fp)
+    for i, c in enumerate(channels):
+        n = B * T * tq8_pad(c)
+        for s in ("h1", "h2", "out"):
+            out[f"b{i}.{s}"] = i8[off:off + n].view(B, T, tq8_pad(c))
+            off += r256(n)
+    out["pool"] = i8[off:off + B * channels[-1]].view(B, channels[-1])
     return out
 
 

@@ -66,6 +66,50 @@ def _check_mult(arrays, prefix, n):
         raise BundleError(f"{prefix}.sh: a shift outside [1, 62]")
 
 
+def check_tcn_entry(header: dict):
+    """The header's ``tcn`` entry as (input_size, [channels], kernel_size), within the limits of the int8 TCN path."""
+    tcn = header.get("tcn")
+    if not (isinstance(tcn, dict) and all(k in tcn for k in ("input_size", "num_channels", "kernel_size"))):
+        raise BundleError(f"the tcn entry {tcn!r} is not {{input_size, num_channels, kernel_size}}")
+    F, ch, k = tcn["input_size"], tcn["num_channels"], tcn["kernel_size"]
+    if not (isinstance(ch, list) and 1 <= len(ch) <= 8 and all(isinstance(c, int) for c in ch) and isinstance(F, int)
+            and isinstance(k, int)):
+        raise BundleError(f"the tcn entry {tcn!r}: 1..8 integer channel counts, an integer input_size and kernel_size")
+    if any(c < 4 or c % 4 for c in [F] + ch) or not 1 <= k <= 8:
+        raise BundleError(f"the tcn entry {tcn!r}: channel counts are positive multiples of 4, 1 <= kernel_size <= 8")
+    return F, ch, k
+
+
+def _check_tcn(header, arrays, fs):
+    F, ch, k = check_tcn_entry(header)
+    nc = header["num_classes"]
+    if not (isinstance(nc, int) and 2 <= nc <= 64):
+        raise BundleError(f"num_classes {nc!r} is outside [2, 64]")
+    if fs[0] != F:
+        raise BundleError(f"feature_shape {fs!r} does not have the TCN's {F} features per frame")
+    cin = F
+    for i, c in enumerate(ch):
+        convs = [("conv1", cin, k), ("conv2", c, k)] + ([("down", cin, 1)] if cin != c else [])
+        for name, ci, kk in convs:
+            p = f"b{i}.{name}"
+            w = _need(arrays, p + ".w", np.int8, (c, ci, kk))
+            if (w == -128).any():
+                raise BundleError(f"{p}.w holds -128: weights are symmetric, in [-127, 127]")
+            _need(arrays, p + ".b", np.int32, (c,))
+            _check_mult(arrays, p, c)
+        if cin == c:
+            _check_mult(arrays, f"b{i}.skip", 1)
+        _check_mult(arrays, f"b{i}.add", 1)
+        cin = c
+    _check_mult(arrays, "pool", 1)
+    w = _need(arrays, "fc.w", np.int8, (nc, cin))
+    if (w == -128).any():
+        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
+    _need(arrays, "fc.b", np.int32, (nc,))
+    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
+        raise BundleError("fc.scale is not finite")
+
+
 def check_bundle(header: dict, arrays: dict) -> None:
     """Raises ``BundleError`` unless the bundle is complete and every value is in the range its law gives it."""
     if not isinstance(header, dict) or header.get("format") != FORMAT_NAME:
@@ -89,8 +133,8 @@ def check_bundle(header: dict, arrays: dict) -> None:
         return
     if kind != "int8":
         raise BundleError(f"unknown bundle kind {kind!r}")
-    if header["architecture"] != "cnn_small":
-        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small has an int8 form")
+    if header["architecture"] not in ("cnn_small", "TCNWakeword"):
+        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small and TCNWakeword have an int8 form")
     fs = header.get("feature_shape")
     if not (isinstance(fs, list) and len(fs) == 2 and all(isinstance(v, int) and v >= 1 for v in fs)):
         raise BundleError(f"feature_shape {fs!r} is not [F, T]")
@@ -100,6 +144,8 @@ def check_bundle(header: dict, arrays: dict) -> None:
     z = _need(arrays, "input_zero", np.int32, (1,))
     if not -128 <= int(z[0]) <= 127:
         raise BundleError("input_zero is outside int8")
+    if header["architecture"] == "TCNWakeword":
+        return _check_tcn(header, arrays, fs)
     for name in CONVS:
         w = _need(arrays, name + ".w", np.int8, (64, 64 if name.startswith("pw") else 9))
         if (w == -128).any():

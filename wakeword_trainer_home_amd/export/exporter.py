@@ -1,8 +1,8 @@
 """The reference's export panel (``src/export/onnx_exporter.py``) without ONNX: neither an ONNX writer nor a runtime exists
 on the build machine, so ``export`` writes self-describing bundles (``bundle.py``) instead -- fp32, fp16 (weights only, as
-the reference's ``QFloat16`` call) and int8 (``cnn_small`` only; the law is DESIGN.md "Export") -- and the int8 bundle runs on
-the device with integer arithmetic (``runtime.QuantizedCNNSmall``).  Names, signatures, result keys and failure behaviour are
-the reference's; ``ONNXExporter``, ``export_model_to_onnx``, ``validate_onnx_model`` and ``benchmark_onnx_model`` stay as
+the reference's ``QFloat16`` call) and int8 (``cnn_small`` and ``TCNWakeword``; the law is DESIGN.md "Export") -- and the int8
+bundle runs on the device with integer arithmetic (``runtime.QuantizedCNNSmall``, ``runtime.QuantizedTCN``).  Names,
+signatures, result keys and failure behaviour are the reference's; ``ONNXExporter``, ``export_model_to_onnx``, ``validate_onnx_model`` and ``benchmark_onnx_model`` stay as
 aliases.  Parity with onnxruntime's ``quantize_dynamic`` is not claimed."""
 import logging
 from dataclasses import dataclass
@@ -15,9 +15,9 @@ import torch.nn as nn
 
 from .. import _native as nat
 from .bundle import STATE_PREFIX, BundleError, check_bundle, float_arrays, load_bundle, make_header, write_bundle
-from .quantize import QuantizationError, quantize_cnn_small
+from .quantize import QuantizationError, check_tcn_args, quantize_cnn_small, quantize_tcn
 from .reference import CONVS
-from .runtime import QuantizedCNNSmall
+from .runtime import QuantizedCNNSmall, QuantizedTCN
 
 logger = logging.getLogger(__name__)
 
@@ -98,6 +98,58 @@ def calibrate_cnn_small(model, batches: Iterable[torch.Tensor], feature_shape, d
             "samples": seen}
 
 
+def tcn_entry(model) -> dict:
+    """The header's ``tcn`` entry of a ``TCNWakeword``: what its constructor needs besides ``num_classes``."""
+    blocks = list(model.tcn.network)
+    return {"input_size": int(model.input_size), "num_channels": [int(b.conv1.out_channels) for b in blocks],
+            "kernel_size": int(blocks[0].conv1.kernel_size)}
+
+
+def calibrate_tcn(model, batches: Iterable[torch.Tensor], feature_shape, device, feature_extractor=None) -> dict:
+    """Ranges of the fp32 ``TCNWakeword`` in eval mode over the calibration batches: the input's minimum and maximum, per block
+    the maxima of h1, h2 and the block output (``a_max``, three per block), and that of the pooled vector.  Runs the model's own
+    layer entry points (``ww_tconv1d_fwd``, ``ww_add_relu_fwd``, its time mean) on fp32 activations, no dropout; the maxima are
+    torch reductions on the device and come to the host once, at the end."""
+    F, T = feature_shape
+    dev = torch.device(device)
+    blocks = list(model.tcn.network)
+    lo = torch.full((), float("inf"), device=dev)
+    hi = torch.full((), float("-inf"), device=dev)
+    a_max = torch.full((3 * len(blocks),), float("-inf"), device=dev)
+    p_max = torch.full((), float("-inf"), device=dev)
+    seen = 0
+    with torch.no_grad():
+        for x in batches:
+            x = torch.as_tensor(x).to(dev)
+            if x.dim() == 2:
+                if feature_extractor is None:
+                    raise QuantizationError("calibration waveforms need a feature_extractor")
+                x = feature_extractor(x)
+            if x.dim() == 3:
+                x = x[:, None]
+            if x.dim() != 4 or tuple(x.shape[1:]) != (1, F, T):
+                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{T})")
+            x = x.float().contiguous()
+            lo, hi = torch.minimum(lo, x.min()), torch.maximum(hi, x.max())
+            h = x[:, 0].transpose(1, 2).contiguous()
+            for i, blk in enumerate(blocks):
+                d, mode = blk.dilation, blk.mode
+                h1 = nat.tconv1d_fwd(h, blk.conv1.weight, blk.conv1.bias, d, relu=True, mode=mode)
+                h2 = nat.tconv1d_fwd(h1, blk.conv2.weight, blk.conv2.bias, d, relu=True, mode=mode)
+                if blk.downsample is not None:
+                    h = nat.tconv1d_fwd(h, blk.downsample.weight, blk.downsample.bias, 1, relu=True, residual=h2, mode=mode)
+                else:
+                    h = nat.add_relu_fwd(h2, h)
+                for j, t in enumerate((h1, h2, h)):
+                    a_max[3 * i + j] = torch.maximum(a_max[3 * i + j], t.max())
+            p_max = torch.maximum(p_max, model.fc[0](h).max())
+            seen += x.shape[0]
+    if seen == 0:
+        raise QuantizationError("the calibration data is empty")
+    return {"x_min": float(lo), "x_max": float(hi), "a_max": [float(v) for v in a_max.cpu()], "p_max": float(p_max),
+            "samples": seen}
+
+
 class ModelExporter:
     """The reference's ``ONNXExporter`` (``onnx_exporter.py:37-193``).  ``calibration``: an iterable of feature batches
     ``(B,1,F,T)`` -- or of waveforms ``(B,N)``, which go through ``feature_extractor`` (default: a mel ``FeatureExtractor``
@@ -135,8 +187,9 @@ class ModelExporter:
                         return {"success": False, "error": "Model outputs contain NaN or Inf"}
                 arch = self.architecture or _architecture(self.model)
                 state = _state_numpy(self.model)
+                more = {"tcn": tcn_entry(self.model)} if arch == "TCNWakeword" and hasattr(self.model, "tcn") else {}
                 header = make_header("fp32", arch, int(test_output.shape[1]), self.sample_input_shape,
-                                     [k for k in state if k.endswith("weight")], config)
+                                     [k for k in state if k.endswith("weight")], config, **more)
                 write_bundle(output_path, header, float_arrays(state, fp16=False))
                 if not output_path.exists():
                     return {"success": False, "error": "Export completed but file not found"}
@@ -168,8 +221,9 @@ class ModelExporter:
         return write_bundle(path, dict(header, kind="fp16"), float_arrays(state, fp16=True))
 
     def _write_int8(self, output_path: Path, header: dict, state: dict, config: ExportConfig) -> Path:
-        if header["architecture"] != "cnn_small":
-            raise QuantizationError(f"int8 export covers cnn_small only, not {header['architecture']!r}")
+        if header["architecture"] not in ("cnn_small", "TCNWakeword"):
+            raise QuantizationError("int8 export covers cnn_small only among the factory's architectures, and TCNWakeword; "
+                                    f"not {header['architecture']!r}")
         if self.calibration is None:
             raise QuantizationError("int8 export needs calibration data (ModelExporter(..., calibration=batches)); "
                                     "it is never calibrated on random input")
@@ -178,6 +232,16 @@ class ModelExporter:
         if fe is None:
             from ..data.feature_extraction import FeatureExtractor
             fe = FeatureExtractor(n_mels=F, device=self.device)
+        if header["architecture"] == "TCNWakeword":
+            check_tcn_args(header["tcn"], header["num_classes"])
+            cal = calibrate_tcn(self.model, self.calibration, (F, T), self.device, fe)
+            if config.verbose:
+                logger.info("calibrated ranges: %s", cal)
+            arrays, scales = quantize_tcn(state, header["tcn"], (F, T), cal["x_min"], cal["x_max"], cal["a_max"], cal["p_max"])
+            layers = [k[:-2] for k in arrays if k.endswith(".w") and k.startswith("b")] + ["pool", "fc"]
+            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
+            check_bundle(h, arrays)
+            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
         cal = calibrate_cnn_small(self.model, self.calibration, (F, T), self.device, fe)
         if config.verbose:
             logger.info("calibrated ranges: %s", cal)
@@ -213,13 +277,21 @@ def export_model(checkpoint_path: Path, output_path: Path, opset_version: int = 
 
 def load_exported_model(path: Path, device: str = "cuda") -> nn.Module:
     """A bundle as a module in eval mode on ``device``: the factory's architecture with the stored weights (fp16 widened to
-    fp32) or, for an int8 bundle, ``QuantizedCNNSmall``.  ``ModelEvaluator`` and ``RecordingScanner`` take either."""
+    fp32) or, for an int8 bundle, ``QuantizedCNNSmall`` / ``QuantizedTCN``.  A ``TCNWakeword`` bundle is built from its header's
+    ``tcn`` entry (the factory does not offer that class).  ``ModelEvaluator`` and ``RecordingScanner`` take any of them."""
     header, arrays = load_bundle(path)
     check_bundle(header, arrays)
     if header["kind"] == "int8":
-        return QuantizedCNNSmall(header, arrays).to(device)
-    from ..models import create_model
-    model = create_model(architecture=header["architecture"], num_classes=header["num_classes"], pretrained=False)
+        cls = QuantizedTCN if header["architecture"] == "TCNWakeword" else QuantizedCNNSmall
+        return cls(header, arrays).to(device)
+    if header["architecture"] == "TCNWakeword":
+        from ..models import TCNWakeword
+        from .bundle import check_tcn_entry
+        F, channels, k = check_tcn_entry(header)
+        model = TCNWakeword(input_size=F, num_channels=channels, kernel_size=k, num_classes=header["num_classes"])
+    else:
+        from ..models import create_model
+        model = create_model(architecture=header["architecture"], num_classes=header["num_classes"], pretrained=False)
     state = {}
     for k, v in arrays.items():
         if k.startswith(STATE_PREFIX):
@@ -301,4 +373,4 @@ validate_onnx_model = validate_exported_model
 benchmark_onnx_model = benchmark_exported_model
 __all__ = ["ExportConfig", "ModelExporter", "ONNXExporter", "export_model", "export_model_to_onnx", "load_exported_model",
            "validate_exported_model", "validate_onnx_model", "benchmark_exported_model", "benchmark_onnx_model",
-           "QuantizedCNNSmall", "BundleError", "QuantizationError", "calibrate_cnn_small"]
+           "QuantizedCNNSmall", "QuantizedTCN", "BundleError", "QuantizationError", "calibrate_cnn_small", "calibrate_tcn"]

@@ -1,11 +1,12 @@
 """The export side of the int8 law (DESIGN.md "Export"): BatchNorm folding, scales, integer weights, biases and multipliers
-of ``cnn_small``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does with the result."""
+of ``cnn_small`` and ``TCNWakeword``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does
+with the result."""
 import math
 from typing import Dict, Sequence
 
 import numpy as np
 
-from .reference import BLOCKS, CONVS
+from .reference import BLOCKS, CONVS, tcn_blocks
 
 A_MAX_FLOOR = 255.0 * 2.0 ** -20       # a calibrated maximum at or below zero (a dead layer) counts as this: s_out = 2^-20
 ACC_MAX_3X3 = 9 * 127 * 255            # largest |sum q_w (q_in - z_in)| of the stem and the depthwise convs
@@ -123,5 +124,87 @@ def quantize_cnn_small(state: Dict[str, np.ndarray], feature_shape: Sequence[int
     q_w, s_w = quantize_weights(wf)
     arrays["fc.w"] = q_w
     arrays["fc.b"] = quantize_bias(bf, s_p, s_w, ACC_MAX_1X1, "classifier")
+    arrays["fc.scale"] = (s_p * s_w).astype(np.float32)
+    return arrays, scales
+
+
+TCN_MAX_BLOCKS, TCN_MAX_KERNEL, TCN_MAX_CLASSES = 8, 8, 64
+
+
+def check_tcn_args(tcn_args, num_classes=2):
+    """The limits of the TCN int8 path: the model's own (channel counts multiples of 4, 1 <= k <= 8, at most 8 blocks) and
+    2 <= num_classes <= 64.  -> (input_size, [channels], kernel_size) as ints."""
+    F, ch, k = int(tcn_args["input_size"]), [int(c) for c in tcn_args["num_channels"]], int(tcn_args["kernel_size"])
+    if not 1 <= len(ch) <= TCN_MAX_BLOCKS:
+        raise QuantizationError(f"the int8 TCN takes 1..{TCN_MAX_BLOCKS} blocks, got {len(ch)}")
+    if not 1 <= k <= TCN_MAX_KERNEL:
+        raise QuantizationError(f"the int8 TCN takes 1 <= kernel_size <= {TCN_MAX_KERNEL}, got {k}")
+    if any(c < 4 or c % 4 for c in [F] + ch):
+        raise QuantizationError(f"the int8 TCN takes channel counts that are positive multiples of 4, got {[F] + ch}")
+    if not 2 <= int(num_classes) <= TCN_MAX_CLASSES:
+        raise QuantizationError(f"the int8 TCN takes 2..{TCN_MAX_CLASSES} classes, got {num_classes}")
+    return F, ch, k
+
+
+def _quantize_conv1d(arrays, name, wf, bf, s_in, s_out):
+    """One Conv1d (Cout, Cin, k) of the TCN: weights, bias with the refusal, one multiplier per output channel."""
+    cout, cin, k = wf.shape
+    q_w, s_w = quantize_weights(wf.reshape(cout, cin * k))
+    ms = [encode_multiplier(s_in * s_w[c] / s_out, f"{name}, channel {c}") for c in range(cout)]
+    arrays[name + ".w"] = q_w.reshape(cout, cin, k)
+    arrays[name + ".b"] = quantize_bias(bf, s_in, s_w, k * cin * 127 * 255, name)
+    arrays[name + ".m"] = np.array([m for m, _ in ms], np.int32)
+    arrays[name + ".sh"] = np.array([s for _, s in ms], np.int32)
+
+
+def _one_multiplier(arrays, name, r):
+    m, sh = encode_multiplier(r, name)
+    arrays[name + ".m"], arrays[name + ".sh"] = np.array([m], np.int32), np.array([sh], np.int32)
+
+
+def quantize_tcn(state: Dict[str, np.ndarray], tcn_args: dict, feature_shape: Sequence[int], x_min: float, x_max: float,
+                 a_max: Sequence[float], p_max: float):
+    """The arrays of an int8 TCNWakeword bundle and its scales (the law's subsection "TCN").  ``tcn_args``: ``input_size``,
+    ``num_channels``, ``kernel_size``; ``a_max``: per block the calibrated maxima of h1, h2 and the block output, in that order;
+    ``p_max``: that of the pooled vector.  Arrays are unpadded.  Raises ``QuantizationError`` where the law refuses."""
+    F, T = int(feature_shape[0]), int(feature_shape[1])
+    st = {k: np.asarray(v, np.float64) for k, v in state.items()}
+    if "fc.3.weight" not in st:
+        raise QuantizationError("the state holds no TCNWakeword classifier (fc.3.weight)")
+    num_classes = st["fc.3.weight"].shape[0]
+    in_size, channels, k = check_tcn_args(tcn_args, num_classes)
+    if in_size != F:
+        raise QuantizationError(f"the TCN reads {in_size} features per frame, the feature shape has {F}")
+    if len(a_max) != 3 * len(channels):
+        raise QuantizationError(f"{len(a_max)} calibrated maxima for {len(channels)} blocks of three tensors")
+    s_x, z_x = input_qparams(x_min, x_max)
+    arrays = {"input_scale": np.array([s_x], np.float32), "input_zero": np.array([z_x], np.int32)}
+    scales = {"input": float(s_x)}
+    s_in = float(s_x)
+    for i, cin, cout, _, down in tcn_blocks(tcn_args):
+        p, q = f"tcn.network.{i}.", f"b{i}."
+        for key, shape in ((p + "conv1.weight", (cout, cin, k)), (p + "conv2.weight", (cout, cout, k))):
+            if key not in st or st[key].shape != shape:
+                raise QuantizationError(f"{key}: expected weights of shape {shape}")
+        if down and (p + "downsample.weight" not in st or st[p + "downsample.weight"].shape != (cout, cin, 1)):
+            raise QuantizationError(f"{p}downsample.weight: expected weights of shape {(cout, cin, 1)}")
+        s_h1, s_h2, s_out = (out_scale(v) for v in a_max[3 * i:3 * i + 3])
+        _quantize_conv1d(arrays, q + "conv1", st[p + "conv1.weight"], st[p + "conv1.bias"], s_in, s_h1)
+        _quantize_conv1d(arrays, q + "conv2", st[p + "conv2.weight"], st[p + "conv2.bias"], s_h1, s_h2)
+        if down:
+            _quantize_conv1d(arrays, q + "down", st[p + "downsample.weight"], st[p + "downsample.bias"], s_in, s_out)
+        else:
+            _one_multiplier(arrays, q + "skip", s_in / s_out)
+        _one_multiplier(arrays, q + "add", s_h2 / s_out)
+        scales.update({q + "h1": s_h1, q + "h2": s_h2, q + "out": s_out})
+        s_in = s_out
+    s_p = out_scale(p_max)
+    _one_multiplier(arrays, "pool", s_in / (T * s_p))
+    scales["pool"] = s_p
+    if st["fc.3.weight"].shape != (num_classes, channels[-1]):
+        raise QuantizationError(f"fc.3.weight: expected weights of shape {(num_classes, channels[-1])}")
+    q_w, s_w = quantize_weights(st["fc.3.weight"])
+    arrays["fc.w"] = q_w
+    arrays["fc.b"] = quantize_bias(st["fc.3.bias"], s_p, s_w, channels[-1] * 127 * 255, "classifier")
     arrays["fc.scale"] = (s_p * s_w).astype(np.float32)
     return arrays, scales

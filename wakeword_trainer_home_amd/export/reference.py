@@ -6,6 +6,9 @@ bundle to another runtime can be checked against it, tensor by tensor.  It runs 
     header, arrays = load_bundle("model_int8.npz")
     out = run_int8(header, arrays, features)          # features (B,1,F,T) or (B,F,T) float32
     out["logits"]                                     # (B,2) float32; the other keys are the int8 tensors of every stage
+
+``run_int8`` dispatches on the header's architecture: ``cnn_small`` (NHWC tensors) or ``TCNWakeword`` (``run_int8_tcn``: (B,T,C)
+tensors ``xq``, each block's ``b{i}.h1``, ``b{i}.h2``, ``b{i}.out``, then ``pool`` and ``logits`` (B,num_classes)).
 """
 import json
 
@@ -61,8 +64,88 @@ def _conv3x3(q, zero, w, stride):
     return acc
 
 
-def run_int8(header, arrays, x):
-    """Every stage of the int8 network on features ``x``; -> dict of STAGES (int8 NHWC tensors, ``pool`` (B,64), ``logits``)."""
+def round_shift(a, mult, shift):
+    """R(a, m, sh) = (int64(a) * m + 2^(sh-1)) >> sh: arithmetic shift, round half up; no offset, no clamp."""
+    a, mult, shift = np.asarray(a, np.int64), np.asarray(mult, np.int64), np.asarray(shift, np.int64)
+    return (a * mult + (np.int64(1) << (shift - 1))) >> shift
+
+
+def _clamp8(v):
+    """clamp(-128 + v, -128, 127)"""
+    return (np.clip(v, 0, 255) - 128).astype(np.int8)
+
+
+def tcn_blocks(tcn):
+    """[(block, Cin, Cout, dilation, has a downsample conv)] of a header's ``tcn`` entry."""
+    out, cin = [], int(tcn["input_size"])
+    for i, c in enumerate(tcn["num_channels"]):
+        out.append((i, cin, int(c), 2 ** i, cin != int(c)))
+        cin = int(c)
+    return out
+
+
+def tcn_stages(tcn):
+    return ["xq"] + [f"b{i}.{s}" for i in range(len(tcn["num_channels"])) for s in ("h1", "h2", "out")] + ["pool", "logits"]
+
+
+def _causal_conv(q, zero, w, dilation):
+    """sum_j sum_c w[n,c,j] (q[b, t - (k-1-j) d, c] - zero) -> int64 (B,T,Cout); source times below 0 contribute nothing.
+    The channel sums are float64 matrix products of integers below 2^8 -- at most k Cin 127 255 < 2^53 in all, so exact."""
+    B, T, _ = q.shape
+    k = w.shape[2]
+    d = q.astype(np.float64) - float(zero)
+    acc = np.zeros((B, T, w.shape[0]), np.float64)
+    for j in range(k):
+        off = (k - 1 - j) * dilation
+        if off < T:
+            acc[:, off:] += d[:, :T - off] @ w[:, :, j].astype(np.float64).T
+    return acc.astype(np.int64)
+
+
+def run_int8_tcn(header, arrays, x, want_acc=False):
+    """Every stage of an int8 TCNWakeword bundle: ``xq`` (B,T,F), each block's ``b{i}.h1``, ``b{i}.h2``, ``b{i}.out`` (B,T,C),
+    ``pool`` (B,C), ``logits`` float32; with ``want_acc`` also the int64 accumulators ``acc/b{i}.conv1|conv2|down``."""
+    x = np.asarray(x, np.float32)
+    if x.ndim == 4:
+        x = x[:, 0]
+    F, T = header["feature_shape"]
+    if x.ndim != 3 or tuple(x.shape[1:]) != (F, T):
+        raise ValueError(f"this bundle is for features of shape ({F},{T}), got {tuple(x.shape)}")
+    a, out = arrays, {}
+    zero = int(a["input_zero"][0])
+    q = np.ascontiguousarray(quantize_input(x, a["input_scale"][0], zero).transpose(0, 2, 1))
+    out["xq"] = q
+    for i, _, _, d, down in tcn_blocks(header["tcn"]):
+        p = f"b{i}."
+        acc1 = _wrap32(_causal_conv(q, zero, a[p + "conv1.w"], d) + a[p + "conv1.b"].astype(np.int64))
+        h1 = requantize(acc1, a[p + "conv1.m"], a[p + "conv1.sh"])
+        acc2 = _wrap32(_causal_conv(h1, -128, a[p + "conv2.w"], d) + a[p + "conv2.b"].astype(np.int64))
+        h2 = requantize(acc2, a[p + "conv2.m"], a[p + "conv2.sh"])
+        if down:
+            accd = _wrap32(_causal_conv(q, zero, a[p + "down.w"], 1) + a[p + "down.b"].astype(np.int64))
+            skip = round_shift(accd, a[p + "down.m"], a[p + "down.sh"])
+        else:
+            skip = round_shift(q.astype(np.int64) - zero, a[p + "skip.m"][0], a[p + "skip.sh"][0])
+        q = _clamp8(skip + round_shift(h2.astype(np.int64) + 128, a[p + "add.m"][0], a[p + "add.sh"][0]))
+        zero = -128
+        out[p + "h1"], out[p + "h2"], out[p + "out"] = h1, h2, q
+        if want_acc:
+            out["acc/" + p + "conv1"], out["acc/" + p + "conv2"] = acc1, acc2
+            if down:
+                out["acc/" + p + "down"] = accd
+    S = _wrap32((q.astype(np.int64) + 128).sum(axis=1))
+    pool = requantize(S, a["pool.m"][0], a["pool.sh"][0])
+    out["pool"] = pool
+    acc = _wrap32((pool.astype(np.int64) + 128) @ a["fc.w"].astype(np.int64).T + a["fc.b"].astype(np.int64))
+    out["logits"] = acc.astype(np.float32) * a["fc.scale"].astype(np.float32)
+    return out
+
+
+def run_int8(header, arrays, x, want_acc=False):
+    """Every stage of the int8 network on features ``x``, by the bundle's architecture.  ``cnn_small``: dict of STAGES (int8
+    NHWC tensors, ``pool`` (B,64), ``logits``); ``TCNWakeword``: ``run_int8_tcn``.  ``want_acc`` adds the accumulators."""
+    if header.get("architecture") == "TCNWakeword":
+        return run_int8_tcn(header, arrays, x, want_acc)
     x = np.asarray(x, np.float32)
     if x.ndim == 4:
         x = x[:, 0]
@@ -86,6 +169,8 @@ def run_int8(header, arrays, x):
         acc = _wrap32(acc + a[name + ".b"].astype(np.int64))
         q, zero = requantize(acc, a[name + ".m"], a[name + ".sh"]), -128
         out[name] = q
+        if want_acc:
+            out["acc/" + name] = acc
     S = _wrap32((q.astype(np.int64) + 128).sum(axis=(1, 2)))
     p = requantize(S, a["pool.m"][0], a["pool.sh"][0])
     out["pool"] = p

@@ -1,11 +1,12 @@
-"""``QuantizedCNNSmall``: an int8 bundle on the device, run with integer arithmetic only (``ww_q8_cnn_small_fwd``)."""
+"""``QuantizedCNNSmall`` and ``QuantizedTCN``: an int8 bundle on the device, run with integer arithmetic only
+(``ww_q8_cnn_small_fwd``, ``ww_tq8_tcn_fwd``)."""
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _native as nat
 from .bundle import check_bundle
-from .reference import CONVS
+from .reference import CONVS, tcn_blocks
 
 
 def effective_bias(q_b: np.ndarray, q_w: np.ndarray, z_in: int) -> np.ndarray:
@@ -18,6 +19,108 @@ def device_conv(arrays: dict, name: str, z_in: int):
     w = arrays[name + ".w"]
     return (np.ascontiguousarray(w if name.startswith("pw") else w.T), effective_bias(arrays[name + ".b"], w, z_in),
             arrays[name + ".m"], arrays[name + ".sh"])
+
+
+def device_tcn_conv(arrays: dict, name: str, z_in: int):
+    """The four tensors of one TCN conv as ``ww_tq8_conv1d_fwd`` reads them: w (Cpo,k,Cpi) [out][tap][in], zero in its pad rows
+    and columns; the effective bias, mult and shift (Cpo), the pad channels 0, 2^30 and 31 (they come out as -128)."""
+    w = arrays[name + ".w"]
+    cout, cin, k = w.shape
+    cpo, cpi = nat.tq8_pad(cout), nat.tq8_pad(cin)
+    wd = np.zeros((cpo, k, cpi), np.int8)
+    wd[:cout, :, :cin] = w.transpose(0, 2, 1)
+    bias, mult, shift = np.zeros(cpo, np.int32), np.full(cpo, 2 ** 30, np.int32), np.full(cpo, 31, np.int32)
+    bias[:cout] = effective_bias(arrays[name + ".b"], w.reshape(cout, cin * k), z_in)
+    mult[:cout], shift[:cout] = arrays[name + ".m"], arrays[name + ".sh"]
+    return wd, bias, mult, shift
+
+
+class QuantizedTCN(nn.Module):
+    """An int8 ``TCNWakeword`` bundle on the device: ``forward((B,1,F,T) float32) -> (B,num_classes) float32`` is one native
+    call (``ww_tq8_tcn_fwd``), no host synchronisation.  Eval only, no parameters.  The bundle is for ONE feature shape (the
+    pooling multiplier holds 1/T): another shape is refused."""
+
+    hip_backed = True
+
+    def __init__(self, header: dict, arrays: dict):
+        super().__init__()
+        check_bundle(header, arrays)
+        if header["kind"] != "int8" or header["architecture"] != "TCNWakeword":
+            raise ValueError(f"QuantizedTCN needs an int8 TCNWakeword bundle, got kind {header['kind']!r} of "
+                             f"{header['architecture']!r}")
+        self.header = dict(header)
+        self.feature_shape = tuple(int(v) for v in header["feature_shape"])
+        self.num_classes = int(header["num_classes"])
+        tcn = header["tcn"]
+        self.input_size, self.kernel_size = int(tcn["input_size"]), int(tcn["kernel_size"])
+        self.channels = [int(c) for c in tcn["num_channels"]]
+        if self.channels[-1] > 1024:
+            raise ValueError(f"the pooling kernel sums at most 1024 channels, got {self.channels[-1]}")
+        z_x = int(arrays["input_zero"][0])
+        io = nat.Tq8Io(float(arrays["input_scale"][0]), z_x, int(arrays["pool.m"][0]), int(arrays["pool.sh"][0]),
+                       len(self.channels), self.kernel_size, self.input_size, self.num_classes)
+        self._names = []
+        for i, cin, cout, _, down in tcn_blocks(tcn):
+            z_in = z_x if i == 0 else -128
+            io.channels[i] = cout
+            io.add_mult[i], io.add_shift[i] = int(arrays[f"b{i}.add.m"][0]), int(arrays[f"b{i}.add.sh"][0])
+            if not down:
+                io.skip_mult[i], io.skip_shift[i] = int(arrays[f"b{i}.skip.m"][0]), int(arrays[f"b{i}.skip.sh"][0])
+            for conv, z in (("conv1", z_in), ("conv2", -128), ("down", z_in)):
+                tensors = device_tcn_conv(arrays, f"b{i}.{conv}", z) if conv != "down" or down else (None,) * 4
+                for suffix, a in zip(("w", "b", "m", "sh"), tensors):
+                    self._add(f"b{i}_{conv}_{suffix}", a)
+        for key in ("fc.w", "fc.b", "fc.scale"):
+            self._add(key.replace(".", "_"), arrays[key])
+        assert len(self._names) == nat.TQ8_BLOCK_NPTR * len(self.channels) + 3
+        self.io = io
+        self._tab, self._key, self._ws = None, None, {}
+        self.eval()
+
+    def _add(self, name, a):
+        if a is None:
+            setattr(self, name, None)
+        else:
+            self.register_buffer(name, torch.from_numpy(np.ascontiguousarray(a).copy()), persistent=False)
+        self._names.append(name)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise RuntimeError("QuantizedTCN is an inference network: it has no training mode")
+        return super().train(False)
+
+    def conv(self, block, name):
+        """(w, bias_eff, mult, shift) of ``conv1`` / ``conv2`` / ``down`` of a block, for the per-layer entry points."""
+        return tuple(getattr(self, f"b{block}_{name}_{s}") for s in ("w", "b", "m", "sh"))
+
+    def _table(self):
+        tensors = [getattr(self, n) for n in self._names]
+        key = tuple(None if t is None else t.data_ptr() for t in tensors)
+        if self._key != key:
+            self._tab, self._key = nat.ptr_array(tensors), key
+        return self._tab
+
+    def workspace(self, B):
+        """The uint8 workspace of the last forward at this batch size (``_native.tq8_workspace_views`` names its parts)."""
+        return self._ws[B]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() == 4 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 3 or tuple(x.shape[1:]) != self.feature_shape:
+            raise ValueError(f"this int8 bundle is for features of shape {self.feature_shape}, got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"features must be float32, got {x.dtype}")
+        if not x.is_contiguous():
+            x = x.contiguous()
+        B, (F, T) = x.shape[0], self.feature_shape
+        dev = nat._dev(x, self.fc_w)
+        ws = self._ws.get(B)
+        if ws is None or ws.device != dev:
+            ws = self._ws[B] = torch.empty(nat.tq8_tcn_workspace_bytes(B, F, T, self.channels), dtype=torch.uint8, device=dev)
+        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
+        nat.tq8_tcn_fwd(self._table(), self.io, x, ws, logits)
+        return logits
 
 
 class QuantizedCNNSmall(nn.Module):
