@@ -981,6 +981,44 @@ size_t ww_tq8_tcn_workspace_bytes(int B, int F, int T, int n_blocks, const int32
 int ww_tq8_tcn_fwd(ww_ctx *ctx, const void *const *tab, const ww_tq8_io *io, const float *x, int B, int T, void *ws, size_t ws_bytes,
                    float *logits, ww_stream_t stream);
 
+/* ------------------------------------------------------------------ int8 inference of an exported ResNet18Wakeword bundle
+ * The same law with the rules of its subsection "ResNet18" (DESIGN.md "Export"); ww_q8_resnet.hip.  Activations are int8 NHWC
+ * (B,H,W,C), C a multiple of 64; every tensor is 16-byte aligned.  Per conv (k = 1 or 3, stride 1 or 2, pad k / 2):
+ *   w      int8 (Cout, k*k, Cin) [out][tap kh*k+kw][in]
+ *   bias   int32 (Cout): the EFFECTIVE bias q_b - z_in * sum(q_w); mult int32 (Cout) in [2^30, 2^31), shift int32 (Cout) in [1, 62]
+ *   acc[b,ho,wo,n] = sum_{kh,kw,c} w[n][kh*k+kw][c] * in[b, ho s - p + kh, wo s - p + kw, c] + bias[n], a source pixel outside the
+ *   image reading `zero`;  R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh
+ *   WW_RQ8_RELU:   out = clamp(-128 + R(acc, mult, shift), -128, 127)
+ *   WW_RQ8_SIGNED: out = clamp(R(acc, mult, shift), -128, 127)                                    (the downsample conv, z_out = 0)
+ *   WW_RQ8_ADD:    out = clamp(-128 + R(acc, mult, shift) + R(residual - res_zero, res_mult, res_shift), -128, 127), residual (N, Cout)
+ * ww_rq8_stem_fwd: xq int8 (B,F,T) -> (B,(F-1)/2+1,(T-1)/2+1,64), 7x7 stride 2 pad 3, RELU epilogue; w (64,64) [channel][tap kh*7+kw],
+ *   the taps 49..63 zero: a pixel's window padded to 64 bytes is one K chunk of the matrix instruction.
+ * ww_rq8_maxpool_fwd: 3x3 stride 2 pad 1, the maximum over the window positions inside the image.
+ * The whole model: tab = WW_RQ8_NPTR device pointers [stem w, bias, mult, shift] + 8 x [conv1 w, bias, mult, shift, conv2 ..,
+ * downsample ..] (the last four NULL except in blocks 2, 4 and 6) + [fc_w, fc_bias, fc_scale]; io on the host.  Quantisation is
+ * ww_q8_quantize, pooling and the classifier ww_tq8_pool_fc_fwd.  The workspace holds, each rounded up to 256 bytes: xq (B*F*T),
+ * stem, pool0, then per block h1, ds (blocks 2, 4, 6 only) and out, then pool (B*512).  Nothing synchronises with the host. */
+#define WW_RQ8_NPTR 103
+#define WW_RQ8_RELU 0
+#define WW_RQ8_SIGNED 1
+#define WW_RQ8_ADD 2
+typedef struct {
+    float in_scale;                         /* s_x */
+    int32_t in_zero;                        /* z_x */
+    int32_t pool_mult, pool_shift;
+    int32_t num_classes;
+    int32_t res_mult[8], res_shift[8];      /* m_r, sh_r of each block's add */
+} ww_rq8_io;
+int ww_rq8_conv2d_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, const int32_t *bias, const int32_t *mult,
+                      const int32_t *shift, int B, int H, int W, int Cin, int Cout, int k, int stride, int zero, int epilogue,
+                      const int8_t *residual, int res_zero, int res_mult, int res_shift, int8_t *out, ww_stream_t stream);
+int ww_rq8_stem_fwd(ww_ctx *ctx, const int8_t *xq, const int8_t *w, const int32_t *bias, const int32_t *mult, const int32_t *shift,
+                    int B, int F, int T, int zero, int8_t *out, ww_stream_t stream);
+int ww_rq8_maxpool_fwd(ww_ctx *ctx, const int8_t *in, int B, int H, int W, int C, int8_t *out, ww_stream_t stream);
+size_t ww_rq8_resnet18_workspace_bytes(int B, int F, int T);
+int ww_rq8_resnet18_fwd(ww_ctx *ctx, const void *const *tab, const ww_rq8_io *io, const float *x, int B, int F, int T, void *ws,
+                        size_t ws_bytes, float *logits, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ collectives: deliberately NOT in this ABI
  * SURVEY.md §8b sketched two more entry points, `ww_comm_init` (ctx, nccl_unique_id, rank, world) and `ww_allreduce_f32`
  * (ctx, buf, n, avg, comm_stream).

@@ -136,6 +136,16 @@ class Tq8Io(C.Structure):
                 ("skip_shift", C.c_int32 * TQ8_MAX_BLOCKS)]
 
 
+RQ8_NPTR, RQ8_RELU, RQ8_SIGNED, RQ8_ADD = 103, 0, 1, 2
+RQ8_PLANES = (64, 128, 256, 512)
+
+
+class Rq8Io(C.Structure):
+    """ww_rq8_io: the scalars of an int8 ResNet18Wakeword bundle (include/wwhip.h)."""
+    _fields_ = [("in_scale", C.c_float), ("in_zero", C.c_int32), ("pool_mult", C.c_int32), ("pool_shift", C.c_int32),
+                ("num_classes", C.c_int32), ("res_mult", C.c_int32 * 8), ("res_shift", C.c_int32 * 8)]
+
+
 _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 _SIGS = {
     "ww_abi_version": (C.c_int, []),
@@ -285,6 +295,11 @@ _SIGS = {
     "ww_tq8_pool_fc_fwd": (C.c_int, [_vp, _vp] + [_i] * 6 + [_vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "ww_tq8_tcn_workspace_bytes": (_sz, [_i, _i, _i, _i, C.POINTER(C.c_int32)]),
     "ww_tq8_tcn_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Tq8Io), _vp, _i, _i, _vp, _sz, _vp, _vp]),
+    "ww_rq8_conv2d_fwd": (C.c_int, [_vp] * 6 + [_i] * 9 + [_vp, _i, _i, _i, _vp, _vp]),
+    "ww_rq8_stem_fwd": (C.c_int, [_vp] * 6 + [_i] * 4 + [_vp, _vp]),
+    "ww_rq8_maxpool_fwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "ww_rq8_resnet18_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ww_rq8_resnet18_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Rq8Io), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "ww_prof_num_classes": (C.c_int, []),
     "ww_prof_class_name": (C.c_char_p, [_i]),
     "ww_ctx_set_deferred_reduce": (C.c_int, [_vp, _i]),
@@ -2375,6 +2390,110 @@ def tq8_workspace_views(ws, B, F, T, channels):
             out[f"b{i}.{s}"] = i8[off:off + n].view(B, T, tq8_pad(c))
             off += r256(n)
     out["pool"] = i8[off:off + B * channels[-1]].view(B, channels[-1])
+    return out
+
+
+# ---- int8 inference of an exported ResNet18Wakeword bundle (ww_q8_resnet.hip).  Activations are int8 NHWC (B,H,W,C), C a multiple
+# of 64; conv arguments are (w (Cout,k*k,Cin), bias_eff, mult, shift) as include/wwhip.h lays them out.
+def rq8_half(n):
+    """The output size of every stride-2 layer of the model: (7, pad 3), (3, pad 1) and (1, pad 0) all give (n - 1) // 2 + 1."""
+    return (int(n) - 1) // 2 + 1
+
+
+def rq8_conv2d_fwd(a, w, bias, mult, shift, k, stride, zero=-128, epilogue=RQ8_RELU, residual=None, res_zero=-128, res_mult=0,
+                   res_shift=0):
+    """``epilogue``: RQ8_RELU, RQ8_SIGNED (the downsample conv, z_out = 0) or RQ8_ADD with ``residual`` (B,Ho,Wo,Cout), its zero
+    point, multiplier and shift: conv2 carrying the block's add and last ReLU."""
+    dev = _dev(a, w, bias, mult, shift, residual)
+    if a.dtype != torch.int8 or a.dim() != 4 or a.shape[3] % 64:
+        raise ValueError("rq8_conv2d_fwd: int8 activations are (B,H,W,C), C a multiple of 64")
+    if w.dtype != torch.int8 or w.dim() != 3 or w.shape[2] != a.shape[3] or w.shape[1] != k * k or w.shape[0] % 64 or \
+            any(t.dtype != torch.int32 or t.numel() != w.shape[0] for t in (bias, mult, shift)):
+        raise ValueError("rq8_conv2d_fwd: w int8 (Cout,k*k,Cin), bias / mult / shift int32 (Cout)")
+    B, H, W, Cin = a.shape
+    Cout = w.shape[0]
+    Ho, Wo = (rq8_half(H), rq8_half(W)) if stride == 2 else (H, W)
+    if residual is not None and (residual.dtype != torch.int8 or tuple(residual.shape) != (B, Ho, Wo, Cout)):
+        raise ValueError("rq8_conv2d_fwd: residual int8 (B,Ho,Wo,Cout)")
+    out = torch.empty((B, Ho, Wo, Cout), dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_rq8_conv2d_fwd(ctx(dev), _p(a), _p(w), _p(bias), _p(mult), _p(shift), B, H, W, Cin, Cout, int(k), int(stride),
+                                        int(zero), int(epilogue), _p(residual), int(res_zero), int(res_mult), int(res_shift), _p(out),
+                                        _stream(dev)), "ww_rq8_conv2d_fwd")
+    return out
+
+
+def rq8_stem_fwd(xq, w, bias, mult, shift, zero):
+    dev = _dev(xq, w, bias, mult, shift)
+    if xq.dtype != torch.int8 or xq.dim() != 3:
+        raise ValueError("rq8_stem_fwd: int8 (B,F,T) features")
+    if w.dtype != torch.int8 or tuple(w.shape) != (64, 64) or any(t.dtype != torch.int32 or t.numel() != 64 for t in (bias, mult, shift)):
+        raise ValueError("rq8_stem_fwd: w int8 (64,64) [channel][tap, 49 padded to 64], bias / mult / shift int32 (64)")
+    B, F, T = xq.shape
+    out = torch.empty((B, rq8_half(F), rq8_half(T), 64), dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_rq8_stem_fwd(ctx(dev), _p(xq), _p(w), _p(bias), _p(mult), _p(shift), B, F, T, int(zero), _p(out),
+                                      _stream(dev)), "ww_rq8_stem_fwd")
+    return out
+
+
+def rq8_maxpool_fwd(a):
+    dev = _dev(a)
+    if a.dtype != torch.int8 or a.dim() != 4 or a.shape[3] % 16:
+        raise ValueError("rq8_maxpool_fwd: int8 activations are (B,H,W,C), C a multiple of 16")
+    B, H, W, Cn = a.shape
+    out = torch.empty((B, rq8_half(H), rq8_half(W), Cn), dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_rq8_maxpool_fwd(ctx(dev), _p(a), B, H, W, Cn, _p(out), _stream(dev)), "ww_rq8_maxpool_fwd")
+    return out
+
+
+def rq8_resnet18_workspace_bytes(B, F, T):
+    return load().ww_rq8_resnet18_workspace_bytes(B, F, T)
+
+
+def rq8_resnet18_fwd(tab, io: Rq8Io, x, ws, logits):
+    """``tab``: ``ptr_array`` of the RQ8_NPTR bundle tensors; x float32 (B,F,T) or (B,1,F,T); ws uint8; logits float32
+    (B,num_classes)."""
+    dev = _dev(x, ws, logits)
+    with _guard(dev):
+        _check(load().ww_rq8_resnet18_fwd(ctx(dev), tab, C.byref(io), _p(x), x.shape[0], x.shape[-2], x.shape[-1], _p(ws),
+                                          ws.numel() * ws.element_size(), _p(logits), _stream(dev)), "ww_rq8_resnet18_fwd")
+
+
+def rq8_stage_shapes(F, T):
+    """[(H, W)] of the stem output, then of stages 1..4 (stage 1 is the max pool's output size)."""
+    out = [(rq8_half(F), rq8_half(T))]
+    for _ in range(4):
+        out.append((rq8_half(out[-1][0]), rq8_half(out[-1][1])))
+    return out
+
+
+def rq8_workspace_views(ws, B, F, T):
+    """The tensors ww_rq8_resnet18_fwd left in ``ws`` (uint8), by stage name: xq (B,F,T), stem, pool0, per block l{s}.{b}.h1,
+    l{s}.{b}.ds (blocks 0 of stages 2-4) and l{s}.{b}.out, all (B,H,W,C), then pool (B,512) -- the layout include/wwhip.h states."""
+    r256 = lambda n: (n + 255) // 256 * 256       # noqa: E731
+    i8 = ws.view(torch.int8)
+    hw = rq8_stage_shapes(F, T)
+    out, off = {}, 0
+
+    def take(name, *shape):
+        nonlocal off
+        n = 1
+        for v in shape:
+            n *= v
+        out[name] = i8[off:off + n].view(*shape)
+        off += r256(n)
+    take("xq", B, F, T)
+    take("stem", B, *hw[0], 64)
+    take("pool0", B, *hw[1], 64)
+    for s, planes in enumerate(RQ8_PLANES):
+        for b in range(2):
+            take(f"l{s + 1}.{b}.h1", B, *hw[s + 1], planes)
+            if s > 0 and b == 0:
+                take(f"l{s + 1}.{b}.ds", B, *hw[s + 1], planes)
+            take(f"l{s + 1}.{b}.out", B, *hw[s + 1], planes)
+    take("pool", B, 512)
     return out
 
 

@@ -5,7 +5,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .reference import CONVS, FORMAT_NAME, FORMAT_VERSION, load_bundle  # noqa: F401  (load_bundle is re-exported)
+from .reference import CONVS, FORMAT_NAME, FORMAT_VERSION, load_bundle, resnet_blocks  # noqa: F401  (load_bundle is re-exported)
 
 STATE_PREFIX = "state/"
 FP16_MAX = 65504.0
@@ -110,6 +110,29 @@ def _check_tcn(header, arrays, fs):
         raise BundleError("fc.scale is not finite")
 
 
+def _check_resnet18(header, arrays):
+    nc = header["num_classes"]
+    if not (isinstance(nc, int) and 2 <= nc <= 64):
+        raise BundleError(f"num_classes {nc!r} is outside [2, 64]")
+    convs = [("stem", 64, 1, 7)]
+    for name, cin, cout, _, down in resnet_blocks():
+        convs += [(name + ".conv1", cout, cin, 3), (name + ".conv2", cout, cout, 3)] + ([(name + ".down", cout, cin, 1)] if down else [])
+        _check_mult(arrays, name + ".res", 1)
+    for p, cout, cin, k in convs:
+        w = _need(arrays, p + ".w", np.int8, (cout, cin, k, k))
+        if (w == -128).any():
+            raise BundleError(f"{p}.w holds -128: weights are symmetric, in [-127, 127]")
+        _need(arrays, p + ".b", np.int32, (cout,))
+        _check_mult(arrays, p, cout)
+    _check_mult(arrays, "pool", 1)
+    w = _need(arrays, "fc.w", np.int8, (nc, 512))
+    if (w == -128).any():
+        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
+    _need(arrays, "fc.b", np.int32, (nc,))
+    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
+        raise BundleError("fc.scale is not finite")
+
+
 def check_bundle(header: dict, arrays: dict) -> None:
     """Raises ``BundleError`` unless the bundle is complete and every value is in the range its law gives it."""
     if not isinstance(header, dict) or header.get("format") != FORMAT_NAME:
@@ -133,8 +156,9 @@ def check_bundle(header: dict, arrays: dict) -> None:
         return
     if kind != "int8":
         raise BundleError(f"unknown bundle kind {kind!r}")
-    if header["architecture"] not in ("cnn_small", "TCNWakeword"):
-        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small and TCNWakeword have an int8 form")
+    if header["architecture"] not in ("cnn_small", "TCNWakeword", "ResNet18Wakeword"):
+        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small, TCNWakeword and ResNet18Wakeword have an "
+                          "int8 form")
     fs = header.get("feature_shape")
     if not (isinstance(fs, list) and len(fs) == 2 and all(isinstance(v, int) and v >= 1 for v in fs)):
         raise BundleError(f"feature_shape {fs!r} is not [F, T]")
@@ -146,6 +170,8 @@ def check_bundle(header: dict, arrays: dict) -> None:
         raise BundleError("input_zero is outside int8")
     if header["architecture"] == "TCNWakeword":
         return _check_tcn(header, arrays, fs)
+    if header["architecture"] == "ResNet18Wakeword":
+        return _check_resnet18(header, arrays)
     for name in CONVS:
         w = _need(arrays, name + ".w", np.int8, (64, 64 if name.startswith("pw") else 9))
         if (w == -128).any():

@@ -1,7 +1,8 @@
 """The reference's export panel (``src/export/onnx_exporter.py``) without ONNX: neither an ONNX writer nor a runtime exists
 on the build machine, so ``export`` writes self-describing bundles (``bundle.py``) instead -- fp32, fp16 (weights only, as
-the reference's ``QFloat16`` call) and int8 (``cnn_small`` and ``TCNWakeword``; the law is DESIGN.md "Export") -- and the int8
-bundle runs on the device with integer arithmetic (``runtime.QuantizedCNNSmall``, ``runtime.QuantizedTCN``).  Names,
+the reference's ``QFloat16`` call) and int8 (``cnn_small``, ``TCNWakeword`` and ``ResNet18Wakeword``; the law is DESIGN.md
+"Export") -- and the int8 bundle runs on the device with integer arithmetic (``runtime.QuantizedCNNSmall``,
+``runtime.QuantizedTCN``, ``runtime.QuantizedResNet18``).  Names,
 signatures, result keys and failure behaviour are the reference's; ``ONNXExporter``, ``export_model_to_onnx``, ``validate_onnx_model`` and ``benchmark_onnx_model`` stay as
 aliases.  Parity with onnxruntime's ``quantize_dynamic`` is not claimed."""
 import logging
@@ -15,9 +16,9 @@ import torch.nn as nn
 
 from .. import _native as nat
 from .bundle import STATE_PREFIX, BundleError, check_bundle, float_arrays, load_bundle, make_header, write_bundle
-from .quantize import QuantizationError, check_tcn_args, quantize_cnn_small, quantize_tcn
+from .quantize import QuantizationError, check_tcn_args, quantize_cnn_small, quantize_resnet18, quantize_tcn
 from .reference import CONVS
-from .runtime import QuantizedCNNSmall, QuantizedTCN
+from .runtime import QuantizedCNNSmall, QuantizedResNet18, QuantizedTCN
 
 logger = logging.getLogger(__name__)
 
@@ -150,6 +151,62 @@ def calibrate_tcn(model, batches: Iterable[torch.Tensor], feature_shape, device,
             "samples": seen}
 
 
+def calibrate_resnet18(model, batches: Iterable[torch.Tensor], feature_shape, device, feature_extractor=None) -> dict:
+    """Ranges of the ``ResNet18Wakeword`` in eval mode, on fp32 activations, over the calibration batches: the input's minimum and
+    maximum, the stem's post-ReLU maximum, per block the maxima of h1 and of the block output, max |ds| of the three downsample
+    outputs, and the pooled vector's maximum.  Runs the model's own layer entry points (``ww_conv2d_stem_fwd``, ``ww_bn_act_fwd``
+    with running statistics, ``ww_maxpool3x3s2_fwd``, ``ww_conv2d_fwd``, ``ww_add_relu_fwd``, ``ww_pool_hw_fwd``); the ranges are
+    torch reductions on the device and come to the host once, at the end."""
+    F, T = feature_shape
+    dev = torch.device(device)
+    net = model.resnet
+    blocks = [blk for i in range(4) for blk in getattr(net, f"layer{i + 1}")]
+
+    def bn(mod, y, act):
+        bnp = nat.make_bn(mod.weight, mod.bias, mod.running_mean, mod.running_var, momentum=mod.momentum, eps=mod.eps, training=False)
+        return nat.bn_act_fwd(y, bnp, act, y.shape[-1])[0]
+    lo = torch.full((), float("inf"), device=dev)
+    hi = torch.full((), float("-inf"), device=dev)
+    m = {k: torch.full((n,), float("-inf"), device=dev) for k, n in (("stem", 1), ("h1", 8), ("ds", 3), ("out", 8), ("p", 1))}
+    seen = 0
+    with torch.no_grad():
+        for x in batches:
+            x = torch.as_tensor(x).to(dev)
+            if x.dim() == 2:
+                if feature_extractor is None:
+                    raise QuantizationError("calibration waveforms need a feature_extractor")
+                x = feature_extractor(x)
+            if x.dim() == 3:
+                x = x[:, None]
+            if x.dim() != 4 or tuple(x.shape[1:]) != (1, F, T):
+                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{T})")
+            x = x.float().contiguous()
+            lo, hi = torch.minimum(lo, x.min()), torch.maximum(hi, x.max())
+            a = bn(net.bn1, nat.conv2d_stem_fwd(x[:, 0].contiguous(), net.conv1.weight, net.conv1.stride), nat.LIN_RELU)
+            m["stem"][0] = torch.maximum(m["stem"][0], a.max())
+            h = nat.maxpool3x3s2_fwd(a)
+            n_ds = 0
+            for i, blk in enumerate(blocks):
+                h1 = bn(blk.bn1, nat.conv2d_fwd(h, blk.conv1.weight, blk.stride, mode=blk.mode), nat.LIN_RELU)
+                o2 = bn(blk.bn2, nat.conv2d_fwd(h1, blk.conv2.weight, 1, mode=blk.mode), nat.LIN_NONE)
+                if blk.downsample is not None:
+                    idn = bn(blk.downsample[1], nat.conv2d_fwd(h, blk.downsample[0].weight, blk.stride, mode=blk.mode), nat.LIN_NONE)
+                    m["ds"][n_ds] = torch.maximum(m["ds"][n_ds], idn.abs().max())
+                    n_ds += 1
+                else:
+                    idn = h
+                h = nat.add_relu_fwd(o2, idn)
+                m["h1"][i], m["out"][i] = torch.maximum(m["h1"][i], h1.max()), torch.maximum(m["out"][i], h.max())
+            B, H, W, Cn = h.shape
+            m["p"][0] = torch.maximum(m["p"][0], nat.pool_hw_fwd(h.reshape(B, H * W, Cn)).max())
+            seen += x.shape[0]
+    if seen == 0:
+        raise QuantizationError("the calibration data is empty")
+    got = torch.cat([lo[None], hi[None]] + [m[k] for k in ("stem", "h1", "ds", "out", "p")]).cpu().tolist()      # the one read-back
+    return {"x_min": got[0], "x_max": got[1], "stem_max": got[2], "h1_max": got[3:11], "ds_max": got[11:14], "out_max": got[14:22],
+            "p_max": got[22], "samples": seen}
+
+
 class ModelExporter:
     """The reference's ``ONNXExporter`` (``onnx_exporter.py:37-193``).  ``calibration``: an iterable of feature batches
     ``(B,1,F,T)`` -- or of waveforms ``(B,N)``, which go through ``feature_extractor`` (default: a mel ``FeatureExtractor``
@@ -186,6 +243,8 @@ class ModelExporter:
                         logger.error("Model produces non-finite outputs")
                         return {"success": False, "error": "Model outputs contain NaN or Inf"}
                 arch = self.architecture or _architecture(self.model)
+                if type(self.model).__name__ == "ResNet18Wakeword":
+                    arch = "ResNet18Wakeword"                      # the factory does not build the class: bundles go by its own name
                 state = _state_numpy(self.model)
                 more = {"tcn": tcn_entry(self.model)} if arch == "TCNWakeword" and hasattr(self.model, "tcn") else {}
                 header = make_header("fp32", arch, int(test_output.shape[1]), self.sample_input_shape,
@@ -221,9 +280,9 @@ class ModelExporter:
         return write_bundle(path, dict(header, kind="fp16"), float_arrays(state, fp16=True))
 
     def _write_int8(self, output_path: Path, header: dict, state: dict, config: ExportConfig) -> Path:
-        if header["architecture"] not in ("cnn_small", "TCNWakeword"):
-            raise QuantizationError("int8 export covers cnn_small only among the factory's architectures, and TCNWakeword; "
-                                    f"not {header['architecture']!r}")
+        if header["architecture"] not in ("cnn_small", "TCNWakeword", "ResNet18Wakeword"):
+            raise QuantizationError("int8 export covers cnn_small only among the factory's architectures, and TCNWakeword and "
+                                    f"ResNet18Wakeword; not {header['architecture']!r}")
         if self.calibration is None:
             raise QuantizationError("int8 export needs calibration data (ModelExporter(..., calibration=batches)); "
                                     "it is never calibrated on random input")
@@ -239,6 +298,15 @@ class ModelExporter:
                 logger.info("calibrated ranges: %s", cal)
             arrays, scales = quantize_tcn(state, header["tcn"], (F, T), cal["x_min"], cal["x_max"], cal["a_max"], cal["p_max"])
             layers = [k[:-2] for k in arrays if k.endswith(".w") and k.startswith("b")] + ["pool", "fc"]
+            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
+            check_bundle(h, arrays)
+            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
+        if header["architecture"] == "ResNet18Wakeword":
+            cal = calibrate_resnet18(self.model, self.calibration, (F, T), self.device, fe)
+            if config.verbose:
+                logger.info("calibrated ranges: %s", cal)
+            arrays, scales = quantize_resnet18(state, (F, T), cal, eps=self.model.resnet.bn1.eps)
+            layers = [k[:-2] for k in arrays if k.endswith(".w") and k != "fc.w"] + ["pool", "fc"]
             h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
             check_bundle(h, arrays)
             return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
@@ -277,14 +345,18 @@ def export_model(checkpoint_path: Path, output_path: Path, opset_version: int = 
 
 def load_exported_model(path: Path, device: str = "cuda") -> nn.Module:
     """A bundle as a module in eval mode on ``device``: the factory's architecture with the stored weights (fp16 widened to
-    fp32) or, for an int8 bundle, ``QuantizedCNNSmall`` / ``QuantizedTCN``.  A ``TCNWakeword`` bundle is built from its header's
-    ``tcn`` entry (the factory does not offer that class).  ``ModelEvaluator`` and ``RecordingScanner`` take any of them."""
+    fp32) or, for an int8 bundle, ``QuantizedCNNSmall`` / ``QuantizedTCN`` / ``QuantizedResNet18``.  A ``TCNWakeword`` bundle is
+    built from its header's ``tcn`` entry and a ``ResNet18Wakeword`` bundle from ``num_classes`` alone (the factory does not offer
+    those classes).  ``ModelEvaluator`` and ``RecordingScanner`` take any of them."""
     header, arrays = load_bundle(path)
     check_bundle(header, arrays)
     if header["kind"] == "int8":
-        cls = QuantizedTCN if header["architecture"] == "TCNWakeword" else QuantizedCNNSmall
+        cls = {"TCNWakeword": QuantizedTCN, "ResNet18Wakeword": QuantizedResNet18}.get(header["architecture"], QuantizedCNNSmall)
         return cls(header, arrays).to(device)
-    if header["architecture"] == "TCNWakeword":
+    if header["architecture"] == "ResNet18Wakeword":
+        from ..models import ResNet18Wakeword
+        model = ResNet18Wakeword(num_classes=header["num_classes"])
+    elif header["architecture"] == "TCNWakeword":
         from ..models import TCNWakeword
         from .bundle import check_tcn_entry
         F, channels, k = check_tcn_entry(header)
@@ -373,4 +445,5 @@ validate_onnx_model = validate_exported_model
 benchmark_onnx_model = benchmark_exported_model
 __all__ = ["ExportConfig", "ModelExporter", "ONNXExporter", "export_model", "export_model_to_onnx", "load_exported_model",
            "validate_exported_model", "validate_onnx_model", "benchmark_exported_model", "benchmark_onnx_model",
-           "QuantizedCNNSmall", "QuantizedTCN", "BundleError", "QuantizationError", "calibrate_cnn_small", "calibrate_tcn"]
+           "QuantizedCNNSmall", "QuantizedTCN", "QuantizedResNet18", "BundleError", "QuantizationError", "calibrate_cnn_small",
+           "calibrate_tcn", "calibrate_resnet18"]

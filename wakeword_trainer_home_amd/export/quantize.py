@@ -1,12 +1,12 @@
 """The export side of the int8 law (DESIGN.md "Export"): BatchNorm folding, scales, integer weights, biases and multipliers
-of ``cnn_small`` and ``TCNWakeword``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does
+of ``cnn_small``, ``TCNWakeword`` and ``ResNet18Wakeword``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does
 with the result."""
 import math
 from typing import Dict, Sequence
 
 import numpy as np
 
-from .reference import BLOCKS, CONVS, tcn_blocks
+from .reference import BLOCKS, CONVS, resnet_blocks, resnet_half, tcn_blocks
 
 A_MAX_FLOOR = 255.0 * 2.0 ** -20       # a calibrated maximum at or below zero (a dead layer) counts as this: s_out = 2^-20
 ACC_MAX_3X3 = 9 * 127 * 255            # largest |sum q_w (q_in - z_in)| of the stem and the depthwise convs
@@ -124,6 +124,87 @@ def quantize_cnn_small(state: Dict[str, np.ndarray], feature_shape: Sequence[int
     q_w, s_w = quantize_weights(wf)
     arrays["fc.w"] = q_w
     arrays["fc.b"] = quantize_bias(bf, s_p, s_w, ACC_MAX_1X1, "classifier")
+    arrays["fc.scale"] = (s_p * s_w).astype(np.float32)
+    return arrays, scales
+
+
+DS_MAX_FLOOR = 127.0 * 2.0 ** -20      # a calibrated max|ds| at or below zero counts as this: s_ds = 2^-20
+RESNET_MAX_CLASSES = 64
+
+
+def signed_scale(a_max):
+    """The scale of a signed tensor (zero point 0) from its calibrated max |value|: the ResNet's downsample output."""
+    a = float(a_max)
+    if math.isnan(a) or math.isinf(a):
+        raise QuantizationError(f"a calibrated maximum of {a!r} is not finite")
+    return max(a, DS_MAX_FLOOR) / 127.0
+
+
+def _quantize_conv2d(arrays, name, wf, bf, shape, s_in, s_out):
+    """One BatchNorm-folded Conv2d of the ResNet: ``wf`` float64 (Cout, Cin k k), ``shape`` = (Cout, Cin, k, k)."""
+    cout, cin, k, _ = shape
+    q_w, s_w = quantize_weights(wf)
+    ms = [encode_multiplier(s_in * s_w[c] / s_out, f"{name}, channel {c}") for c in range(cout)]
+    arrays[name + ".w"] = q_w.reshape(shape)
+    arrays[name + ".b"] = quantize_bias(bf, s_in, s_w, k * k * cin * 127 * 255, name)
+    arrays[name + ".m"] = np.array([m for m, _ in ms], np.int32)
+    arrays[name + ".sh"] = np.array([s for _, s in ms], np.int32)
+
+
+def quantize_resnet18(state: Dict[str, np.ndarray], feature_shape: Sequence[int], ranges: dict, eps: float = 1e-5):
+    """The arrays of an int8 ResNet18Wakeword bundle and its scales (the law's subsection "ResNet18").  ``ranges``: ``x_min``,
+    ``x_max``, ``stem_max``, per block (eight, in execution order) ``h1_max`` and ``out_max``, ``ds_max`` (max |ds| of the three
+    downsample outputs, stages 2-4) and ``p_max``.  Weights keep nn.Conv2d's (Cout,Cin,k,k).  Raises ``QuantizationError`` where
+    the law refuses."""
+    F, T = int(feature_shape[0]), int(feature_shape[1])
+    st = {k: np.asarray(v, np.float64) for k, v in state.items()}
+    if "resnet.fc.1.weight" not in st or "resnet.conv1.weight" not in st:
+        raise QuantizationError("the state holds no ResNet18Wakeword (resnet.conv1.weight, resnet.fc.1.weight)")
+    num_classes = st["resnet.fc.1.weight"].shape[0]
+    if not 2 <= num_classes <= RESNET_MAX_CLASSES:
+        raise QuantizationError(f"the int8 ResNet18 takes 2..{RESNET_MAX_CLASSES} classes, got {num_classes}")
+    blocks = resnet_blocks()
+    if len(ranges["h1_max"]) != 8 or len(ranges["out_max"]) != 8 or len(ranges["ds_max"]) != 3:
+        raise QuantizationError("the calibrated ranges need eight h1 and block-output maxima and three downsample maxima")
+
+    def folded(conv, bn, shape):
+        key = conv + ".weight"
+        if key not in st or st[key].shape != shape:
+            raise QuantizationError(f"{key}: expected weights of shape {shape}")
+        return fold_bn(st[key], *(st[f"{bn}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")), eps)
+    s_x, z_x = input_qparams(ranges["x_min"], ranges["x_max"])
+    arrays = {"input_scale": np.array([s_x], np.float32), "input_zero": np.array([z_x], np.int32)}
+    scales = {"input": float(s_x)}
+    s_in = out_scale(ranges["stem_max"])
+    _quantize_conv2d(arrays, "stem", *folded("resnet.conv1", "resnet.bn1", (64, 1, 7, 7)), (64, 1, 7, 7), float(s_x), s_in)
+    scales["stem"] = s_in                          # (the max pool passes scale and zero point through)
+    n_ds = 0
+    for i, (name, cin, cout, _, down) in enumerate(blocks):
+        p = f"resnet.layer{name[1]}.{name[3]}."
+        s_h1, s_out = out_scale(ranges["h1_max"][i]), out_scale(ranges["out_max"][i])
+        _quantize_conv2d(arrays, name + ".conv1", *folded(p + "conv1", p + "bn1", (cout, cin, 3, 3)), (cout, cin, 3, 3), s_in, s_h1)
+        s_res = s_in
+        if down:
+            s_res = signed_scale(ranges["ds_max"][n_ds])
+            n_ds += 1
+            _quantize_conv2d(arrays, name + ".down", *folded(p + "downsample.0", p + "downsample.1", (cout, cin, 1, 1)),
+                             (cout, cin, 1, 1), s_in, s_res)
+            scales[name + ".ds"] = s_res
+        _quantize_conv2d(arrays, name + ".conv2", *folded(p + "conv2", p + "bn2", (cout, cout, 3, 3)), (cout, cout, 3, 3), s_h1, s_out)
+        _one_multiplier(arrays, name + ".res", s_res / s_out)
+        scales.update({name + ".h1": s_h1, name + ".out": s_out})
+        s_in = s_out
+    hw = F, T
+    for _ in range(5):
+        hw = resnet_half(hw[0]), resnet_half(hw[1])
+    s_p = out_scale(ranges["p_max"])
+    _one_multiplier(arrays, "pool", s_in / (hw[0] * hw[1] * s_p))
+    scales["pool"] = s_p
+    if st["resnet.fc.1.weight"].shape != (num_classes, 512):
+        raise QuantizationError(f"resnet.fc.1.weight: expected weights of shape {(num_classes, 512)}")
+    q_w, s_w = quantize_weights(st["resnet.fc.1.weight"])
+    arrays["fc.w"] = q_w
+    arrays["fc.b"] = quantize_bias(st["resnet.fc.1.bias"], s_p, s_w, 512 * 127 * 255, "classifier")
     arrays["fc.scale"] = (s_p * s_w).astype(np.float32)
     return arrays, scales
 

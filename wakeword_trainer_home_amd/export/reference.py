@@ -141,11 +141,115 @@ def run_int8_tcn(header, arrays, x, want_acc=False):
     return out
 
 
+RESNET_PLANES = (64, 128, 256, 512)
+
+
+def resnet_half(n):
+    """The output size of a stride-2 layer of the ResNet: floor((n + 2p - k) / 2) + 1 is (n - 1) // 2 + 1 for (k, p) = (7, 3),
+    (3, 1) and (1, 0) alike."""
+    return (int(n) - 1) // 2 + 1
+
+
+def resnet_blocks():
+    """[(name 'l{s}.{b}', Cin, Cout, stride, has a downsample conv)] of the eight BasicBlocks, in execution order."""
+    out, cin = [], 64
+    for s, planes in enumerate(RESNET_PLANES):
+        for b in range(2):
+            first = b == 0 and s > 0
+            out.append((f"l{s + 1}.{b}", cin, planes, 2 if first else 1, first))
+            cin = planes
+    return out
+
+
+def resnet_stages():
+    out = ["xq", "stem", "pool0"]
+    for name, _, _, _, down in resnet_blocks():
+        out += [name + ".h1"] + ([name + ".ds"] if down else []) + [name + ".out"]
+    return out + ["pool", "logits"]
+
+
+def _conv2d(q, zero, w, stride):
+    """sum_{kh,kw,c} w[n,c,kh,kw] (q[b, ho s - p + kh, wo s - p + kw, c] - zero) -> int64 (B,Ho,Wo,Cout), p = k // 2; positions
+    outside the image contribute nothing (the padding of q - zero is 0).  The channel sums are float64 matrix products of
+    integers below 2^8 -- at most k k Cin 127 255 < 2^53 in all, so exact."""
+    B, H, W, _ = q.shape
+    k = w.shape[2]
+    p = k // 2
+    Ho, Wo = (H + 2 * p - k) // stride + 1, (W + 2 * p - k) // stride + 1
+    d = np.pad(q.astype(np.float64) - float(zero), ((0, 0), (p, p), (p, p), (0, 0)))
+    acc = np.zeros((B, Ho, Wo, w.shape[0]), np.float64)
+    for kh in range(k):
+        for kw in range(k):
+            win = d[:, kh:kh + stride * (Ho - 1) + 1:stride, kw:kw + stride * (Wo - 1) + 1:stride, :]
+            acc += win @ w[:, :, kh, kw].astype(np.float64).T
+    return acc.astype(np.int64)
+
+
+def _maxpool3x3s2(q):
+    """The maximum of q over the 3x3 stride-2 pad-1 window's positions inside the image (the padding can never win)."""
+    B, H, W, C = q.shape
+    Ho, Wo = resnet_half(H), resnet_half(W)
+    d = np.pad(q.astype(np.int16), ((0, 0), (1, 1), (1, 1), (0, 0)), constant_values=-129)
+    out = np.full((B, Ho, Wo, C), -129, np.int16)
+    for kh in range(3):
+        for kw in range(3):
+            out = np.maximum(out, d[:, kh:kh + 2 * (Ho - 1) + 1:2, kw:kw + 2 * (Wo - 1) + 1:2, :])
+    return out.astype(np.int8)
+
+
+def run_int8_resnet18(header, arrays, x, want_acc=False):
+    """Every stage of an int8 ResNet18Wakeword bundle, NHWC: ``xq`` (B,F,T), ``stem``, ``pool0``, per block ``l{s}.{b}.h1``,
+    ``l{s}.{b}.ds`` (int8 with zero point 0; blocks 0 of stages 2-4) and ``l{s}.{b}.out``, ``pool`` (B,512), ``logits`` float32;
+    with ``want_acc`` also the int64 accumulators ``acc/stem`` and ``acc/l{s}.{b}.conv1|conv2|down``."""
+    x = np.asarray(x, np.float32)
+    if x.ndim == 4:
+        x = x[:, 0]
+    F, T = header["feature_shape"]
+    if x.ndim != 3 or tuple(x.shape[1:]) != (F, T):
+        raise ValueError(f"this bundle is for features of shape ({F},{T}), got {tuple(x.shape)}")
+    a, out = arrays, {}
+    z_x = int(a["input_zero"][0])
+    xq = quantize_input(x, a["input_scale"][0], z_x)
+    out["xq"] = xq
+
+    def conv(name, q, zero, stride):
+        acc = _wrap32(_conv2d(q, zero, a[name + ".w"], stride) + a[name + ".b"].astype(np.int64))
+        if want_acc:
+            out["acc/" + name] = acc
+        return acc
+    q = requantize(conv("stem", xq[..., None], z_x, 2), a["stem.m"], a["stem.sh"])
+    out["stem"] = q
+    q = _maxpool3x3s2(q)
+    out["pool0"] = q
+    for name, _, _, stride, down in resnet_blocks():
+        h1 = requantize(conv(name + ".conv1", q, -128, stride), a[name + ".conv1.m"], a[name + ".conv1.sh"])
+        out[name + ".h1"] = h1
+        if down:
+            r = round_shift(conv(name + ".down", q, -128, stride), a[name + ".down.m"], a[name + ".down.sh"])
+            res = np.clip(r, -128, 127).astype(np.int8)
+            out[name + ".ds"] = res
+            z_res = 0
+        else:
+            res, z_res = q, -128
+        t = round_shift(conv(name + ".conv2", h1, -128, 1), a[name + ".conv2.m"], a[name + ".conv2.sh"])
+        q = _clamp8(t + round_shift(res.astype(np.int64) - z_res, a[name + ".res.m"][0], a[name + ".res.sh"][0]))
+        out[name + ".out"] = q
+    S = _wrap32((q.astype(np.int64) + 128).sum(axis=(1, 2)))
+    pool = requantize(S, a["pool.m"][0], a["pool.sh"][0])
+    out["pool"] = pool
+    acc = _wrap32((pool.astype(np.int64) + 128) @ a["fc.w"].astype(np.int64).T + a["fc.b"].astype(np.int64))
+    out["logits"] = acc.astype(np.float32) * a["fc.scale"].astype(np.float32)
+    return out
+
+
 def run_int8(header, arrays, x, want_acc=False):
     """Every stage of the int8 network on features ``x``, by the bundle's architecture.  ``cnn_small``: dict of STAGES (int8
-    NHWC tensors, ``pool`` (B,64), ``logits``); ``TCNWakeword``: ``run_int8_tcn``.  ``want_acc`` adds the accumulators."""
+    NHWC tensors, ``pool`` (B,64), ``logits``); ``TCNWakeword``: ``run_int8_tcn``; ``ResNet18Wakeword``: ``run_int8_resnet18``.
+    ``want_acc`` adds the accumulators."""
     if header.get("architecture") == "TCNWakeword":
         return run_int8_tcn(header, arrays, x, want_acc)
+    if header.get("architecture") == "ResNet18Wakeword":
+        return run_int8_resnet18(header, arrays, x, want_acc)
     x = np.asarray(x, np.float32)
     if x.ndim == 4:
         x = x[:, 0]

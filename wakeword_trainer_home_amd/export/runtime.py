@@ -1,12 +1,12 @@
-"""``QuantizedCNNSmall`` and ``QuantizedTCN``: an int8 bundle on the device, run with integer arithmetic only
-(``ww_q8_cnn_small_fwd``, ``ww_tq8_tcn_fwd``)."""
+"""``QuantizedCNNSmall``, ``QuantizedTCN`` and ``QuantizedResNet18``: an int8 bundle on the device, run with integer arithmetic
+only (``ww_q8_cnn_small_fwd``, ``ww_tq8_tcn_fwd``, ``ww_rq8_resnet18_fwd``)."""
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _native as nat
 from .bundle import check_bundle
-from .reference import CONVS, tcn_blocks
+from .reference import CONVS, resnet_blocks, tcn_blocks
 
 
 def effective_bias(q_b: np.ndarray, q_w: np.ndarray, z_in: int) -> np.ndarray:
@@ -120,6 +120,101 @@ class QuantizedTCN(nn.Module):
             ws = self._ws[B] = torch.empty(nat.tq8_tcn_workspace_bytes(B, F, T, self.channels), dtype=torch.uint8, device=dev)
         logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
         nat.tq8_tcn_fwd(self._table(), self.io, x, ws, logits)
+        return logits
+
+
+def device_resnet_conv(arrays: dict, name: str, z_in: int):
+    """The four tensors of one ResNet conv as the kernels read them: w (Cout,k*k,Cin) [out][tap][in] -- the stem's (64,64)
+    [channel][tap], its 49 taps padded with zero weights to one 64-deep K chunk -- and the effective bias, mult and shift (Cout)."""
+    w = arrays[name + ".w"]
+    cout, cin, k, _ = w.shape
+    if name == "stem":
+        wd = np.zeros((64, 64), np.int8)
+        wd[:, :49] = w.reshape(64, 49)
+    else:
+        wd = w.transpose(0, 2, 3, 1).reshape(cout, k * k, cin)
+    return (np.ascontiguousarray(wd), effective_bias(arrays[name + ".b"], w.reshape(cout, -1), z_in), arrays[name + ".m"],
+            arrays[name + ".sh"])
+
+
+class QuantizedResNet18(nn.Module):
+    """An int8 ``ResNet18Wakeword`` bundle on the device: ``forward((B,1,F,T) float32) -> (B,num_classes) float32`` is one native
+    call (``ww_rq8_resnet18_fwd``), no host synchronisation.  Eval only, no parameters.  The bundle is for ONE feature shape (the
+    pooling multiplier holds 1/HW): another shape is refused."""
+
+    hip_backed = True
+
+    def __init__(self, header: dict, arrays: dict):
+        super().__init__()
+        check_bundle(header, arrays)
+        if header["kind"] != "int8" or header["architecture"] != "ResNet18Wakeword":
+            raise ValueError(f"QuantizedResNet18 needs an int8 ResNet18Wakeword bundle, got kind {header['kind']!r} of "
+                             f"{header['architecture']!r}")
+        self.header = dict(header)
+        self.feature_shape = tuple(int(v) for v in header["feature_shape"])
+        self.num_classes = int(header["num_classes"])
+        z_x = int(arrays["input_zero"][0])
+        io = nat.Rq8Io(float(arrays["input_scale"][0]), z_x, int(arrays["pool.m"][0]), int(arrays["pool.sh"][0]), self.num_classes)
+        self._names = []
+        for suffix, a in zip(("w", "b", "m", "sh"), device_resnet_conv(arrays, "stem", z_x)):
+            self._add(f"stem_{suffix}", a)
+        self.blocks = [name for name, *_ in resnet_blocks()]
+        for i, (name, _, _, _, down) in enumerate(resnet_blocks()):
+            io.res_mult[i], io.res_shift[i] = int(arrays[name + ".res.m"][0]), int(arrays[name + ".res.sh"][0])
+            for conv in ("conv1", "conv2", "down"):
+                tensors = device_resnet_conv(arrays, f"{name}.{conv}", -128) if conv != "down" or down else (None,) * 4
+                for suffix, a in zip(("w", "b", "m", "sh"), tensors):
+                    self._add(f"{name.replace('.', '_')}_{conv}_{suffix}", a)
+        for key in ("fc.w", "fc.b", "fc.scale"):
+            self._add(key.replace(".", "_"), arrays[key])
+        assert len(self._names) == nat.RQ8_NPTR
+        self.io = io
+        self._tab, self._key, self._ws = None, None, {}
+        self.eval()
+
+    def _add(self, name, a):
+        if a is None:
+            setattr(self, name, None)
+        else:
+            self.register_buffer(name, torch.from_numpy(np.ascontiguousarray(a).copy()), persistent=False)
+        self._names.append(name)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise RuntimeError("QuantizedResNet18 is an inference network: it has no training mode")
+        return super().train(False)
+
+    def conv(self, name):
+        """(w, bias_eff, mult, shift) of ``stem`` or ``l{s}.{b}.conv1|conv2|down``, for the per-layer entry points."""
+        return tuple(getattr(self, f"{name.replace('.', '_')}_{s}") for s in ("w", "b", "m", "sh"))
+
+    def _table(self):
+        tensors = [getattr(self, n) for n in self._names]
+        key = tuple(None if t is None else t.data_ptr() for t in tensors)
+        if self._key != key:
+            self._tab, self._key = nat.ptr_array(tensors), key
+        return self._tab
+
+    def workspace(self, B):
+        """The uint8 workspace of the last forward at this batch size (``_native.rq8_workspace_views`` names its parts)."""
+        return self._ws[B]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() == 4 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 3 or tuple(x.shape[1:]) != self.feature_shape:
+            raise ValueError(f"this int8 bundle is for features of shape {self.feature_shape}, got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"features must be float32, got {x.dtype}")
+        if not x.is_contiguous() or x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.contiguous_format)
+        B, (F, T) = x.shape[0], self.feature_shape
+        dev = nat._dev(x, self.fc_w)
+        ws = self._ws.get(B)
+        if ws is None or ws.device != dev:
+            ws = self._ws[B] = torch.empty(nat.rq8_resnet18_workspace_bytes(B, F, T), dtype=torch.uint8, device=dev)
+        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
+        nat.rq8_resnet18_fwd(self._table(), self.io, x, ws, logits)
         return logits
 
 
