@@ -1019,6 +1019,49 @@ size_t ww_rq8_resnet18_workspace_bytes(int B, int F, int T);
 int ww_rq8_resnet18_fwd(ww_ctx *ctx, const void *const *tab, const ww_rq8_io *io, const float *x, int B, int F, int T, void *ws,
                         size_t ws_bytes, float *logits, ww_stream_t stream);
 
+/* ------------------------------------------------------------------ int8 inference of an exported LSTMWakeword bundle
+ * The same law with the rules of its subsection "LSTM" (DESIGN.md "Export"); ww_q8_lstm.hip.  Hidden size 128; a direction has 512
+ * gate rows in torch's order i, f, g, o; nd = 1 or 2 directions, forward first.  Every tensor is 16-byte aligned.
+ * ww_lq8_proj_fwd: the input projection of all nd directions of a layer over N = B*T rows.
+ *   in     int8 (N, Kp), Kp a multiple of 64: the quantised features (ww_tq8_quantize_bt, pad channels = z_x) or the previous
+ *          layer's y (Kp = nd * 128)
+ *   w      int8 (G, Kp), G = nd * 512, the directions stacked; pad columns are zero
+ *   bias   int32 (G): the EFFECTIVE bias q_bi - z_in * sum(q_wi); mult int32 (G) in [2^30, 2^31), shift int32 (G) in [1, 62]
+ *   u[n][r] = clamp(R(sum_k w[r][k] in[n][k] + bias[r], mult[r], shift[r]), -32768, 32767) as int16 (N, G): Q8 gate pre-activations;
+ *   R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh
+ * ww_lq8_lstm_layer_fwd: the recurrence of one layer, all directions in one launch.  w_hh int8 (G, 128); bias int32 (G) is the
+ *   law's q_bh (q_h has zero point 0); mult, shift as above; tab_sigmoid, tab_tanh int16 (4096) are the bundle's tables.  Per
+ *   direction and step, with q_h = 0 and c = 0 before the first: a = u[t] + R(sum_k w_hh[r][k] q_h[k] + bias[r], mult[r], shift[r]);
+ *   i, f, o = look(sigmoid, a), g = look(tanh, a), look(tab, a) = tab[clamp(a, -2048, 2047) + 2048];
+ *   c = clamp((f c + ((i g + 8) >> 4) + 2^14) >> 15, -32768, 32767); h16 = (o look(tanh, (c + 4) >> 3) + 2^14) >> 15;
+ *   q_h = clamp((h16 + 128) >> 8, -128, 127).  The reverse direction walks t = T-1 .. 0.  y int8 (B*T, nd*128) holds q_h of every step
+ *   in time order, the forward direction's 128 channels first; c_n int16 (B, nd*128) the cell after each direction's last step.
+ *   WW_LQ8_TABLES=global in the environment reads the tables through the caches instead of LDS (same bits; the A/B switch).
+ * ww_lq8_head_fwd: hcat int8 (B, nd*128) = [y[b][T-1][0:128], y[b][0][128:256]]; logits (B, num_classes) =
+ *   float32(sum_k fc_w[c][k] hcat[k] + fc_bias[c]) * fc_scale[c]; fc_w int8 (num_classes, nd*128), fc_bias the law's q_b.
+ * The whole model: tab = per layer WW_LQ8_LAYER_NPTR device pointers [w_ih, bias, mult, shift, w_hh, bias, mult, shift] (directions
+ * stacked, as above), then WW_LQ8_TAIL_NPTR: [fc_w, fc_bias, fc_scale, tab_sigmoid, tab_tanh]; io on the host; x fp32 (B,F,T).  The
+ * workspace holds, each rounded up to 256 bytes: xq (B*T*Fp), then per layer u (B*T*nd*512 int16), y (B*T*nd*128), c_n (B*nd*128
+ * int16), then hcat (B*nd*128) -- that sum is what the workspace-size entry point returns.  Nothing synchronises with the host. */
+#define WW_LQ8_MAX_LAYERS 8
+#define WW_LQ8_LAYER_NPTR 8
+#define WW_LQ8_TAIL_NPTR 5
+typedef struct {
+    float in_scale;                         /* s_x */
+    int32_t in_zero;                        /* z_x */
+    int32_t input_size, num_layers, num_directions, num_classes;
+} ww_lq8_io;
+int ww_lq8_proj_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, const int32_t *bias, const int32_t *mult, const int32_t *shift,
+                    long N, int Kp, int G, int16_t *u, ww_stream_t stream);
+int ww_lq8_lstm_layer_fwd(ww_ctx *ctx, const int16_t *u, const int8_t *w_hh, const int32_t *bias, const int32_t *mult,
+                          const int32_t *shift, const int16_t *tab_sigmoid, const int16_t *tab_tanh, int B, int T, int num_directions,
+                          int8_t *y, int16_t *c_n, ww_stream_t stream);
+int ww_lq8_head_fwd(ww_ctx *ctx, const int8_t *y, int B, int T, int num_directions, const int8_t *fc_w, const int32_t *fc_bias,
+                    const float *fc_scale, int num_classes, int8_t *hcat, float *logits, ww_stream_t stream);
+size_t ww_lq8_lstm_workspace_bytes(int B, int T, int input_size, int num_layers, int num_directions);
+int ww_lq8_lstm_fwd(ww_ctx *ctx, const void *const *tab, const ww_lq8_io *io, const float *x, int B, int T, void *ws, size_t ws_bytes,
+                    float *logits, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ collectives: deliberately NOT in this ABI
  * SURVEY.md §8b sketched two more entry points, `ww_comm_init` (ctx, nccl_unique_id, rank, world) and `ww_allreduce_f32`
  * (ctx, buf, n, avg, comm_stream).

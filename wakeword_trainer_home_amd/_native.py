@@ -146,6 +146,15 @@ class Rq8Io(C.Structure):
                 ("num_classes", C.c_int32), ("res_mult", C.c_int32 * 8), ("res_shift", C.c_int32 * 8)]
 
 
+LQ8_MAX_LAYERS, LQ8_LAYER_NPTR, LQ8_TAIL_NPTR, LQ8_HIDDEN = 8, 8, 5, 128
+
+
+class Lq8Io(C.Structure):
+    """ww_lq8_io: the scalars of an int8 LSTMWakeword bundle (include/wwhip.h)."""
+    _fields_ = [("in_scale", C.c_float), ("in_zero", C.c_int32), ("input_size", C.c_int32), ("num_layers", C.c_int32),
+                ("num_directions", C.c_int32), ("num_classes", C.c_int32)]
+
+
 _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 _SIGS = {
     "ww_abi_version": (C.c_int, []),
@@ -300,6 +309,11 @@ _SIGS = {
     "ww_rq8_maxpool_fwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "ww_rq8_resnet18_workspace_bytes": (_sz, [_i, _i, _i]),
     "ww_rq8_resnet18_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Rq8Io), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "ww_lq8_proj_fwd": (C.c_int, [_vp] * 6 + [C.c_long, _i, _i, _vp, _vp]),
+    "ww_lq8_lstm_layer_fwd": (C.c_int, [_vp] * 8 + [_i, _i, _i, _vp, _vp, _vp]),
+    "ww_lq8_head_fwd": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ww_lq8_lstm_workspace_bytes": (_sz, [_i] * 5),
+    "ww_lq8_lstm_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Lq8Io), _vp, _i, _i, _vp, _sz, _vp, _vp]),
     "ww_prof_num_classes": (C.c_int, []),
     "ww_prof_class_name": (C.c_char_p, [_i]),
     "ww_ctx_set_deferred_reduce": (C.c_int, [_vp, _i]),
@@ -2494,6 +2508,91 @@ def rq8_workspace_views(ws, B, F, T):
                 take(f"l{s + 1}.{b}.ds", B, *hw[s + 1], planes)
             take(f"l{s + 1}.{b}.out", B, *hw[s + 1], planes)
     take("pool", B, 512)
+    return out
+
+
+# ---- int8 inference of an exported LSTMWakeword bundle (ww_q8_lstm.hip).  Activations are int8 (B,T,Kp) rows, Kp a multiple of 64;
+# a layer's tensors are stacked over its directions, as include/wwhip.h lays them out.
+def lq8_proj_fwd(a, w, bias, mult, shift):
+    """a int8 (B,T,Kp), w int8 (G,Kp), bias (effective) / mult / shift int32 (G), G = 512 or 1024 -> u int16 (B,T,G)."""
+    dev = _dev(a, w, bias, mult, shift)
+    _tq8_act_check(a, "lq8_proj_fwd")
+    if w.dtype != torch.int8 or w.dim() != 2 or w.shape[1] != a.shape[2] or w.shape[0] not in (512, 1024) or \
+            any(t.dtype != torch.int32 or t.numel() != w.shape[0] for t in (bias, mult, shift)):
+        raise ValueError("lq8_proj_fwd: w int8 (G,Kp), G = 512 or 1024, bias / mult / shift int32 (G)")
+    B, T, Kp = a.shape
+    u = torch.empty((B, T, w.shape[0]), dtype=torch.int16, device=dev)
+    with _guard(dev):
+        _check(load().ww_lq8_proj_fwd(ctx(dev), _p(a), _p(w), _p(bias), _p(mult), _p(shift), B * T, Kp, w.shape[0], _p(u),
+                                      _stream(dev)), "ww_lq8_proj_fwd")
+    return u
+
+
+def lq8_lstm_layer_fwd(u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh):
+    """u int16 (B,T,nd*512), w_hh int8 (nd*512,128), bias / mult / shift int32 (nd*512), the two int16 (4096) tables ->
+    (y int8 (B,T,nd*128), c_n int16 (B,nd*128))."""
+    dev = _dev(u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh)
+    G = w_hh.shape[0]
+    if u.dtype != torch.int16 or u.dim() != 3 or u.shape[2] != G or G not in (512, 1024) or w_hh.dtype != torch.int8 or \
+            tuple(w_hh.shape) != (G, 128) or any(t.dtype != torch.int32 or t.numel() != G for t in (bias, mult, shift)) or \
+            any(t.dtype != torch.int16 or t.numel() != 4096 for t in (tab_sigmoid, tab_tanh)):
+        raise ValueError("lq8_lstm_layer_fwd: u int16 (B,T,G), w_hh int8 (G,128), bias / mult / shift int32 (G), tables int16 (4096)")
+    B, T, nd = u.shape[0], u.shape[1], G // 512
+    y = torch.empty((B, T, nd * 128), dtype=torch.int8, device=dev)
+    c_n = torch.empty((B, nd * 128), dtype=torch.int16, device=dev)
+    with _guard(dev):
+        _check(load().ww_lq8_lstm_layer_fwd(ctx(dev), _p(u), _p(w_hh), _p(bias), _p(mult), _p(shift), _p(tab_sigmoid), _p(tab_tanh),
+                                            B, T, nd, _p(y), _p(c_n), _stream(dev)), "ww_lq8_lstm_layer_fwd")
+    return y, c_n
+
+
+def lq8_head_fwd(y, fc_w, fc_bias, fc_scale):
+    """y int8 (B,T,nd*128) -> (hcat int8 (B,nd*128), logits float32 (B,num_classes))."""
+    dev = _dev(y, fc_w, fc_bias, fc_scale)
+    nc = fc_w.shape[0]
+    if y.dtype != torch.int8 or y.dim() != 3 or y.shape[2] not in (128, 256) or \
+            (fc_w.dtype, fc_bias.dtype, fc_scale.dtype) != (torch.int8, torch.int32, torch.float32) or \
+            tuple(fc_w.shape) != (nc, y.shape[2]) or fc_bias.numel() != nc or fc_scale.numel() != nc:
+        raise ValueError("lq8_head_fwd: y int8 (B,T,nd*128), fc_w int8 (num_classes,nd*128), fc_bias int32, fc_scale float32")
+    B, T, Cn = y.shape
+    hcat = torch.empty((B, Cn), dtype=torch.int8, device=dev)
+    logits = torch.empty((B, nc), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_lq8_head_fwd(ctx(dev), _p(y), B, T, Cn // 128, _p(fc_w), _p(fc_bias), _p(fc_scale), nc, _p(hcat), _p(logits),
+                                      _stream(dev)), "ww_lq8_head_fwd")
+    return hcat, logits
+
+
+def lq8_lstm_workspace_bytes(B, T, input_size, num_layers, num_directions):
+    return load().ww_lq8_lstm_workspace_bytes(B, T, input_size, num_layers, num_directions)
+
+
+def lq8_lstm_fwd(tab, io: Lq8Io, x, ws, logits):
+    """``tab``: ``ptr_array`` of the bundle's tensors (LQ8_LAYER_NPTR per layer, then fc_w, fc_bias, fc_scale, tab_sigmoid,
+    tab_tanh); x float32 (B,F,T); ws uint8; logits float32 (B,num_classes)."""
+    dev = _dev(x, ws, logits)
+    with _guard(dev):
+        _check(load().ww_lq8_lstm_fwd(ctx(dev), tab, C.byref(io), _p(x), x.shape[0], x.shape[-1], _p(ws),
+                                      ws.numel() * ws.element_size(), _p(logits), _stream(dev)), "ww_lq8_lstm_fwd")
+
+
+def lq8_workspace_views(ws, B, T, input_size, num_layers, num_directions):
+    """The tensors ww_lq8_lstm_fwd left in ``ws`` (uint8), by stage name: xq (B,T,Fp) PADDED, per layer l{k}.u int16 (B,T,nd*512),
+    l{k}.y int8 (B,T,nd*128) and l{k}.c int16 (B,nd*128), directions stacked, then hcat (B,nd*128) -- the layout include/wwhip.h
+    states."""
+    r256 = lambda n: (n + 255) // 256 * 256       # noqa: E731
+    i8, nd = ws.view(torch.int8), num_directions
+    Fp = tq8_pad(input_size)
+    out, off = {"xq": i8[:B * T * Fp].view(B, T, Fp)}, r256(B * T * Fp)
+    for k in range(num_layers):
+        n = B * T * nd * 512 * 2
+        out[f"l{k}.u"] = i8[off:off + n].view(torch.int16).view(B, T, nd * 512)
+        off += r256(n)
+        out[f"l{k}.y"] = i8[off:off + B * T * nd * 128].view(B, T, nd * 128)
+        off += r256(B * T * nd * 128)
+        out[f"l{k}.c"] = i8[off:off + B * nd * 256].view(torch.int16).view(B, nd * 128)
+        off += r256(B * nd * 256)
+    out["hcat"] = i8[off:off + B * nd * 128].view(B, nd * 128)
     return out
 
 

@@ -5,7 +5,7 @@ from pathlib import Path
 
 import numpy as np
 
-from .reference import CONVS, FORMAT_NAME, FORMAT_VERSION, load_bundle, resnet_blocks  # noqa: F401  (load_bundle is re-exported)
+from .reference import CONVS, FORMAT_NAME, FORMAT_VERSION, LSTM_DIRS, LSTM_HIDDEN, LSTM_TABLE, load_bundle, resnet_blocks  # noqa: F401  (load_bundle is re-exported)
 
 STATE_PREFIX = "state/"
 FP16_MAX = 65504.0
@@ -133,6 +133,48 @@ def _check_resnet18(header, arrays):
         raise BundleError("fc.scale is not finite")
 
 
+def check_lstm_entry(header: dict):
+    """The header's ``lstm`` entry as (input_size, num_layers, num_directions), within the limits of ``LSTMWakeword``."""
+    e = header.get("lstm")
+    keys = ("input_size", "hidden_size", "num_layers", "bidirectional")
+    if not (isinstance(e, dict) and all(k in e for k in keys)):
+        raise BundleError(f"the lstm entry {e!r} is not {{input_size, hidden_size, num_layers, bidirectional}}")
+    I, H, L, bi = (e[k] for k in keys)
+    if not (all(isinstance(v, int) and not isinstance(v, bool) for v in (I, H, L)) and isinstance(bi, bool)):
+        raise BundleError(f"the lstm entry {e!r}: integer input_size, hidden_size and num_layers, a boolean bidirectional")
+    if H != LSTM_HIDDEN or not 1 <= L <= 8 or I < 1:
+        raise BundleError(f"the lstm entry {e!r}: hidden_size {LSTM_HIDDEN}, 1..8 layers, a positive input_size")
+    return I, L, 2 if bi else 1
+
+
+def _check_lstm(header, arrays, fs):
+    I, L, nd = check_lstm_entry(header)
+    nc, H = header["num_classes"], LSTM_HIDDEN
+    if not (isinstance(nc, int) and 2 <= nc <= 64):
+        raise BundleError(f"num_classes {nc!r} is outside [2, 64]")
+    if fs[0] != I:
+        raise BundleError(f"feature_shape {fs!r} does not have the LSTM's {I} features per frame")
+    for layer in range(L):
+        for d in LSTM_DIRS[:nd]:
+            for part, K in (("ih", I if layer == 0 else nd * H), ("hh", H)):
+                p = f"l{layer}.{d}.{part}"
+                w = _need(arrays, p + ".w", np.int8, (4 * H, K))
+                if (w == -128).any():
+                    raise BundleError(f"{p}.w holds -128: weights are symmetric, in [-127, 127]")
+                _need(arrays, p + ".b", np.int32, (4 * H,))
+                _check_mult(arrays, p, 4 * H)
+    for name, lo in (("tab.sigmoid", 0), ("tab.tanh", -32767)):
+        t = _need(arrays, name, np.int16, (LSTM_TABLE,)).astype(np.int64)
+        if (np.diff(t) < 0).any() or t.min() < lo or t.max() > 32767:
+            raise BundleError(f"{name} is not a non-decreasing table within [{lo}, 32767]")
+    w = _need(arrays, "fc.w", np.int8, (nc, nd * H))
+    if (w == -128).any():
+        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
+    _need(arrays, "fc.b", np.int32, (nc,))
+    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
+        raise BundleError("fc.scale is not finite")
+
+
 def check_bundle(header: dict, arrays: dict) -> None:
     """Raises ``BundleError`` unless the bundle is complete and every value is in the range its law gives it."""
     if not isinstance(header, dict) or header.get("format") != FORMAT_NAME:
@@ -156,9 +198,9 @@ def check_bundle(header: dict, arrays: dict) -> None:
         return
     if kind != "int8":
         raise BundleError(f"unknown bundle kind {kind!r}")
-    if header["architecture"] not in ("cnn_small", "TCNWakeword", "ResNet18Wakeword"):
-        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small, TCNWakeword and ResNet18Wakeword have an "
-                          "int8 form")
+    if header["architecture"] not in ("cnn_small", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
+        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small, TCNWakeword, ResNet18Wakeword and "
+                          "LSTMWakeword have an int8 form")
     fs = header.get("feature_shape")
     if not (isinstance(fs, list) and len(fs) == 2 and all(isinstance(v, int) and v >= 1 for v in fs)):
         raise BundleError(f"feature_shape {fs!r} is not [F, T]")
@@ -172,6 +214,8 @@ def check_bundle(header: dict, arrays: dict) -> None:
         return _check_tcn(header, arrays, fs)
     if header["architecture"] == "ResNet18Wakeword":
         return _check_resnet18(header, arrays)
+    if header["architecture"] == "LSTMWakeword":
+        return _check_lstm(header, arrays, fs)
     for name in CONVS:
         w = _need(arrays, name + ".w", np.int8, (64, 64 if name.startswith("pw") else 9))
         if (w == -128).any():

@@ -1,8 +1,8 @@
 """The reference's export panel (``src/export/onnx_exporter.py``) without ONNX: neither an ONNX writer nor a runtime exists
 on the build machine, so ``export`` writes self-describing bundles (``bundle.py``) instead -- fp32, fp16 (weights only, as
-the reference's ``QFloat16`` call) and int8 (``cnn_small``, ``TCNWakeword`` and ``ResNet18Wakeword``; the law is DESIGN.md
-"Export") -- and the int8 bundle runs on the device with integer arithmetic (``runtime.QuantizedCNNSmall``,
-``runtime.QuantizedTCN``, ``runtime.QuantizedResNet18``).  Names,
+the reference's ``QFloat16`` call) and int8 (``cnn_small``, ``TCNWakeword``, ``ResNet18Wakeword`` and ``LSTMWakeword``; the law is
+DESIGN.md "Export") -- and the int8 bundle runs on the device with integer arithmetic (``runtime.QuantizedCNNSmall``,
+``runtime.QuantizedTCN``, ``runtime.QuantizedResNet18``, ``runtime.QuantizedLSTM``).  Names,
 signatures, result keys and failure behaviour are the reference's; ``ONNXExporter``, ``export_model_to_onnx``, ``validate_onnx_model`` and ``benchmark_onnx_model`` stay as
 aliases.  Parity with onnxruntime's ``quantize_dynamic`` is not claimed."""
 import logging
@@ -16,9 +16,10 @@ import torch.nn as nn
 
 from .. import _native as nat
 from .bundle import STATE_PREFIX, BundleError, check_bundle, float_arrays, load_bundle, make_header, write_bundle
-from .quantize import QuantizationError, check_tcn_args, quantize_cnn_small, quantize_resnet18, quantize_tcn
+from .quantize import (QuantizationError, check_lstm_args, check_tcn_args, quantize_cnn_small, quantize_lstm, quantize_resnet18,
+                       quantize_tcn)
 from .reference import CONVS
-from .runtime import QuantizedCNNSmall, QuantizedResNet18, QuantizedTCN
+from .runtime import QuantizedCNNSmall, QuantizedLSTM, QuantizedResNet18, QuantizedTCN
 
 logger = logging.getLogger(__name__)
 
@@ -207,6 +208,42 @@ def calibrate_resnet18(model, batches: Iterable[torch.Tensor], feature_shape, de
             "p_max": got[22], "samples": seen}
 
 
+def lstm_entry(model) -> dict:
+    """The header's ``lstm`` entry of an ``LSTMWakeword``: what its constructor needs besides ``num_classes``."""
+    return {"input_size": int(model.lstm.input_size), "hidden_size": int(model.hidden_size), "num_layers": int(model.num_layers),
+            "bidirectional": bool(model.bidirectional)}
+
+
+def calibrate_lstm(model, batches: Iterable[torch.Tensor], input_size, device, feature_extractor=None) -> dict:
+    """The input's minimum and maximum over the calibration batches -- all an ``LSTMWakeword`` bundle calibrates: hidden state,
+    gates and cell have fixed scales.  Batches are (B,1,F,T) features, (B,T,F) sequences or (B,N) waveforms, which go through
+    ``feature_extractor``; T may differ from batch to batch.  Torch reductions on the device and one read-back."""
+    dev = torch.device(device)
+    F = int(input_size)
+    lo = torch.full((), float("inf"), device=dev)
+    hi = torch.full((), float("-inf"), device=dev)
+    seen = 0
+    with torch.no_grad():
+        for x in batches:
+            x = torch.as_tensor(x).to(dev)
+            if x.dim() == 2:
+                if feature_extractor is None:
+                    raise QuantizationError("calibration waveforms need a feature_extractor")
+                x = feature_extractor(x)
+                if x.dim() == 3:
+                    x = x[:, None]
+            ok = (x.dim() == 4 and x.shape[1] == 1 and x.shape[2] == F) or (x.dim() == 3 and x.shape[2] == F)
+            if not ok or x.numel() == 0:
+                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},T) or (B,T,{F})")
+            x = x.float()
+            lo, hi = torch.minimum(lo, x.min()), torch.maximum(hi, x.max())
+            seen += x.shape[0]
+    if seen == 0:
+        raise QuantizationError("the calibration data is empty")
+    got = torch.stack([lo, hi]).cpu().tolist()                    # the one read-back
+    return {"x_min": got[0], "x_max": got[1], "samples": seen}
+
+
 class ModelExporter:
     """The reference's ``ONNXExporter`` (``onnx_exporter.py:37-193``).  ``calibration``: an iterable of feature batches
     ``(B,1,F,T)`` -- or of waveforms ``(B,N)``, which go through ``feature_extractor`` (default: a mel ``FeatureExtractor``
@@ -246,7 +283,11 @@ class ModelExporter:
                 if type(self.model).__name__ == "ResNet18Wakeword":
                     arch = "ResNet18Wakeword"                      # the factory does not build the class: bundles go by its own name
                 state = _state_numpy(self.model)
+                if type(self.model).__name__ == "LSTMWakeword":
+                    arch = "LSTMWakeword"                          # likewise: create_model("lstm") is switched off
                 more = {"tcn": tcn_entry(self.model)} if arch == "TCNWakeword" and hasattr(self.model, "tcn") else {}
+                if arch == "LSTMWakeword" and hasattr(self.model, "lstm"):
+                    more = {"lstm": lstm_entry(self.model)}
                 header = make_header("fp32", arch, int(test_output.shape[1]), self.sample_input_shape,
                                      [k for k in state if k.endswith("weight")], config, **more)
                 write_bundle(output_path, header, float_arrays(state, fp16=False))
@@ -280,9 +321,9 @@ class ModelExporter:
         return write_bundle(path, dict(header, kind="fp16"), float_arrays(state, fp16=True))
 
     def _write_int8(self, output_path: Path, header: dict, state: dict, config: ExportConfig) -> Path:
-        if header["architecture"] not in ("cnn_small", "TCNWakeword", "ResNet18Wakeword"):
-            raise QuantizationError("int8 export covers cnn_small only among the factory's architectures, and TCNWakeword and "
-                                    f"ResNet18Wakeword; not {header['architecture']!r}")
+        if header["architecture"] not in ("cnn_small", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
+            raise QuantizationError("int8 export covers cnn_small only among the factory's architectures, and TCNWakeword, "
+                                    f"ResNet18Wakeword and LSTMWakeword; not {header['architecture']!r}")
         if self.calibration is None:
             raise QuantizationError("int8 export needs calibration data (ModelExporter(..., calibration=batches)); "
                                     "it is never calibrated on random input")
@@ -298,6 +339,16 @@ class ModelExporter:
                 logger.info("calibrated ranges: %s", cal)
             arrays, scales = quantize_tcn(state, header["tcn"], (F, T), cal["x_min"], cal["x_max"], cal["a_max"], cal["p_max"])
             layers = [k[:-2] for k in arrays if k.endswith(".w") and k.startswith("b")] + ["pool", "fc"]
+            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
+            check_bundle(h, arrays)
+            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
+        if header["architecture"] == "LSTMWakeword":
+            check_lstm_args(header["lstm"], header["num_classes"])
+            cal = calibrate_lstm(self.model, self.calibration, F, self.device, fe)
+            if config.verbose:
+                logger.info("calibrated ranges: %s", cal)
+            arrays, scales = quantize_lstm(state, header["lstm"], cal["x_min"], cal["x_max"])
+            layers = [k[:-2] for k in arrays if k.endswith(".w")]
             h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
             check_bundle(h, arrays)
             return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
@@ -345,17 +396,25 @@ def export_model(checkpoint_path: Path, output_path: Path, opset_version: int = 
 
 def load_exported_model(path: Path, device: str = "cuda") -> nn.Module:
     """A bundle as a module in eval mode on ``device``: the factory's architecture with the stored weights (fp16 widened to
-    fp32) or, for an int8 bundle, ``QuantizedCNNSmall`` / ``QuantizedTCN`` / ``QuantizedResNet18``.  A ``TCNWakeword`` bundle is
-    built from its header's ``tcn`` entry and a ``ResNet18Wakeword`` bundle from ``num_classes`` alone (the factory does not offer
-    those classes).  ``ModelEvaluator`` and ``RecordingScanner`` take any of them."""
+    fp32) or, for an int8 bundle, ``QuantizedCNNSmall`` / ``QuantizedTCN`` / ``QuantizedResNet18`` / ``QuantizedLSTM``.  A
+    ``TCNWakeword`` bundle is built from its header's ``tcn`` entry, an ``LSTMWakeword`` bundle from its ``lstm`` entry and a
+    ``ResNet18Wakeword`` bundle from ``num_classes`` alone (the factory does not offer those classes).  ``ModelEvaluator`` and ``RecordingScanner`` take any of them."""
     header, arrays = load_bundle(path)
     check_bundle(header, arrays)
     if header["kind"] == "int8":
-        cls = {"TCNWakeword": QuantizedTCN, "ResNet18Wakeword": QuantizedResNet18}.get(header["architecture"], QuantizedCNNSmall)
+        cls = {"TCNWakeword": QuantizedTCN, "ResNet18Wakeword": QuantizedResNet18,
+               "LSTMWakeword": QuantizedLSTM}.get(header["architecture"], QuantizedCNNSmall)
         return cls(header, arrays).to(device)
     if header["architecture"] == "ResNet18Wakeword":
         from ..models import ResNet18Wakeword
         model = ResNet18Wakeword(num_classes=header["num_classes"])
+    elif header["architecture"] == "LSTMWakeword":
+        from ..models import LSTMWakeword
+        from .bundle import check_lstm_entry
+        check_lstm_entry(header)
+        e = header["lstm"]
+        model = LSTMWakeword(input_size=e["input_size"], hidden_size=e["hidden_size"], num_layers=e["num_layers"],
+                             num_classes=header["num_classes"], bidirectional=e["bidirectional"])
     elif header["architecture"] == "TCNWakeword":
         from ..models import TCNWakeword
         from .bundle import check_tcn_entry
@@ -445,5 +504,5 @@ validate_onnx_model = validate_exported_model
 benchmark_onnx_model = benchmark_exported_model
 __all__ = ["ExportConfig", "ModelExporter", "ONNXExporter", "export_model", "export_model_to_onnx", "load_exported_model",
            "validate_exported_model", "validate_onnx_model", "benchmark_exported_model", "benchmark_onnx_model",
-           "QuantizedCNNSmall", "QuantizedTCN", "QuantizedResNet18", "BundleError", "QuantizationError", "calibrate_cnn_small",
-           "calibrate_tcn", "calibrate_resnet18"]
+           "QuantizedCNNSmall", "QuantizedTCN", "QuantizedResNet18", "QuantizedLSTM", "BundleError", "QuantizationError",
+           "calibrate_cnn_small", "calibrate_tcn", "calibrate_resnet18", "calibrate_lstm"]

@@ -1,12 +1,12 @@
 """The export side of the int8 law (DESIGN.md "Export"): BatchNorm folding, scales, integer weights, biases and multipliers
-of ``cnn_small``, ``TCNWakeword`` and ``ResNet18Wakeword``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does
+of ``cnn_small``, ``TCNWakeword``, ``ResNet18Wakeword`` and ``LSTMWakeword``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does
 with the result."""
 import math
 from typing import Dict, Sequence
 
 import numpy as np
 
-from .reference import BLOCKS, CONVS, resnet_blocks, resnet_half, tcn_blocks
+from .reference import BLOCKS, CONVS, LSTM_DIRS, LSTM_HIDDEN, LSTM_TABLE, resnet_blocks, resnet_half, tcn_blocks
 
 A_MAX_FLOOR = 255.0 * 2.0 ** -20       # a calibrated maximum at or below zero (a dead layer) counts as this: s_out = 2^-20
 ACC_MAX_3X3 = 9 * 127 * 255            # largest |sum q_w (q_in - z_in)| of the stem and the depthwise convs
@@ -47,12 +47,12 @@ def quantize_weights(wf):
     return np.clip(np.rint(wf / s_w[:, None]), -127, 127).astype(np.int8), s_w
 
 
-def quantize_bias(bf, s_in, s_w, acc_max, layer):
+def quantize_bias(bf, s_in, s_w, acc_max, layer, unit="channel"):
     q = np.rint(np.asarray(bf, np.float64) / (s_in * s_w))
     bad = np.nonzero(~(np.abs(q) + acc_max <= INT32_MAX))[0]       # (a NaN is bad too)
     if bad.size:
         c = int(bad[0])
-        raise QuantizationError(f"{layer}, channel {c}: bias {q[c]!r} plus an accumulator of up to {acc_max} leaves int32")
+        raise QuantizationError(f"{layer}, {unit} {c}: bias {q[c]!r} plus an accumulator of up to {acc_max} leaves int32")
     return q.astype(np.int32)
 
 
@@ -288,4 +288,80 @@ def quantize_tcn(state: Dict[str, np.ndarray], tcn_args: dict, feature_shape: Se
     arrays["fc.w"] = q_w
     arrays["fc.b"] = quantize_bias(st["fc.3.bias"], s_p, s_w, channels[-1] * 127 * 255, "classifier")
     arrays["fc.scale"] = (s_p * s_w).astype(np.float32)
+    return arrays, scales
+
+
+LSTM_MAX_LAYERS, LSTM_MAX_CLASSES = 8, 64
+S_H = 2.0 ** -7                        # the fixed scale of the hidden operand q_h (zero point 0)
+
+
+def check_lstm_args(lstm_args, num_classes=2):
+    """The limits of the LSTM int8 path: hidden size 128 (the implemented size of ``LSTMWakeword``), 1..8 layers, a positive
+    input size, 2 <= num_classes <= 64.  -> (input_size, num_layers, num_directions) as ints."""
+    I, H, L = int(lstm_args["input_size"]), int(lstm_args["hidden_size"]), int(lstm_args["num_layers"])
+    if H != LSTM_HIDDEN:
+        raise QuantizationError(f"the int8 LSTM implements hidden_size == {LSTM_HIDDEN}, got hidden_size {H}")
+    if not 1 <= L <= LSTM_MAX_LAYERS:
+        raise QuantizationError(f"the int8 LSTM takes 1..{LSTM_MAX_LAYERS} layers, got num_layers {L}")
+    if I < 1:
+        raise QuantizationError(f"the int8 LSTM takes a positive input_size, got {I}")
+    if not 2 <= int(num_classes) <= LSTM_MAX_CLASSES:
+        raise QuantizationError(f"the int8 LSTM takes 2..{LSTM_MAX_CLASSES} classes, got num_classes {num_classes}")
+    return I, L, 2 if lstm_args["bidirectional"] else 1
+
+
+def lstm_tables():
+    """(tab.sigmoid, tab.tanh): int16 (4096,), entry j the function at j / 256 - 8 in Q15, from float64; the sigmoid capped at
+    32767, the tanh at +-32767.  Written into the bundle: a runtime reads them, it never recomputes them."""
+    x = np.arange(LSTM_TABLE, dtype=np.float64) / 256.0 - 8.0
+    sig = np.minimum(np.rint(2.0 ** 15 / (1.0 + np.exp(-x))), 32767)
+    tanh = np.clip(np.rint(np.tanh(x) * 2.0 ** 15), -32767, 32767)
+    return sig.astype(np.int16), tanh.astype(np.int16)
+
+
+def _quantize_gates(arrays, name, wf, bf, s_in, acc_max):
+    """One weight matrix (4H, K) of a direction with its bias: per-row weights, the int32 bias with the refusal, and the
+    multiplier that brings the accumulator to Q8 gate pre-activations, m 2^-sh ~ s_in s_w 2^8."""
+    if not np.isfinite(wf).all():
+        raise QuantizationError(f"{name}: a weight is not finite")
+    q_w, s_w = quantize_weights(wf)
+    ms = [encode_multiplier(s_in * s_w[n] * 256.0, f"{name}, row {n}") for n in range(wf.shape[0])]
+    arrays[name + ".w"] = q_w
+    arrays[name + ".b"] = quantize_bias(bf, s_in, s_w, acc_max, name, unit="row")
+    arrays[name + ".m"] = np.array([m for m, _ in ms], np.int32)
+    arrays[name + ".sh"] = np.array([s for _, s in ms], np.int32)
+
+
+def quantize_lstm(state: Dict[str, np.ndarray], lstm_args: dict, x_min: float, x_max: float):
+    """The arrays of an int8 LSTMWakeword bundle and its scales (the law's subsection "LSTM").  ``lstm_args``: ``input_size``,
+    ``hidden_size``, ``num_layers``, ``bidirectional``.  Only the input range is calibrated: hidden state, gates and cell have
+    fixed power-of-two scales.  Arrays are unpadded.  Raises ``QuantizationError`` where the law refuses."""
+    st = {k: np.asarray(v, np.float64) for k, v in state.items()}
+    if "fc.1.weight" not in st or "lstm.weight_ih_l0" not in st:
+        raise QuantizationError("the state holds no LSTMWakeword (lstm.weight_ih_l0, fc.1.weight)")
+    num_classes = st["fc.1.weight"].shape[0]
+    I, L, nd = check_lstm_args(lstm_args, num_classes)
+    H = LSTM_HIDDEN
+    s_x, z_x = input_qparams(x_min, x_max)
+    arrays = {"input_scale": np.array([s_x], np.float32), "input_zero": np.array([z_x], np.int32)}
+    scales = {"input": float(s_x), "hidden": S_H}
+    for layer in range(L):
+        K, s_in = (I, float(s_x)) if layer == 0 else (nd * H, S_H)
+        for d in range(nd):
+            sfx, name = f"_l{layer}" + ("_reverse" if d else ""), f"l{layer}.{LSTM_DIRS[d]}"
+            for key, shape in ((f"lstm.weight_ih{sfx}", (4 * H, K)), (f"lstm.weight_hh{sfx}", (4 * H, H)),
+                               (f"lstm.bias_ih{sfx}", (4 * H,)), (f"lstm.bias_hh{sfx}", (4 * H,))):
+                if key not in st or st[key].shape != shape:
+                    raise QuantizationError(f"{key}: expected a tensor of shape {shape}")
+            _quantize_gates(arrays, name + ".ih", st[f"lstm.weight_ih{sfx}"], st[f"lstm.bias_ih{sfx}"], s_in, K * 127 * 255)
+            _quantize_gates(arrays, name + ".hh", st[f"lstm.weight_hh{sfx}"], st[f"lstm.bias_hh{sfx}"], S_H, H * 127 * 128)
+    if st["fc.1.weight"].shape != (num_classes, nd * H):
+        raise QuantizationError(f"fc.1.weight: expected weights of shape {(num_classes, nd * H)}")
+    if not np.isfinite(st["fc.1.weight"]).all():
+        raise QuantizationError("classifier: a weight is not finite")
+    q_w, s_w = quantize_weights(st["fc.1.weight"])
+    arrays["fc.w"] = q_w
+    arrays["fc.b"] = quantize_bias(st["fc.1.bias"], S_H, s_w, nd * H * 127 * 128, "classifier", unit="row")
+    arrays["fc.scale"] = (S_H * s_w).astype(np.float32)
+    arrays["tab.sigmoid"], arrays["tab.tanh"] = lstm_tables()
     return arrays, scales

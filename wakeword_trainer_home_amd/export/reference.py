@@ -7,8 +7,9 @@ bundle to another runtime can be checked against it, tensor by tensor.  It runs 
     out = run_int8(header, arrays, features)          # features (B,1,F,T) or (B,F,T) float32
     out["logits"]                                     # (B,2) float32; the other keys are the int8 tensors of every stage
 
-``run_int8`` dispatches on the header's architecture: ``cnn_small`` (NHWC tensors) or ``TCNWakeword`` (``run_int8_tcn``: (B,T,C)
-tensors ``xq``, each block's ``b{i}.h1``, ``b{i}.h2``, ``b{i}.out``, then ``pool`` and ``logits`` (B,num_classes)).
+``run_int8`` dispatches on the header's architecture: ``cnn_small`` (NHWC tensors), ``TCNWakeword`` (``run_int8_tcn``: (B,T,C)
+tensors ``xq``, each block's ``b{i}.h1``, ``b{i}.h2``, ``b{i}.out``, then ``pool`` and ``logits`` (B,num_classes)),
+``ResNet18Wakeword`` (``run_int8_resnet18``) or ``LSTMWakeword`` (``run_int8_lstm``: any number of frames T).
 """
 import json
 
@@ -242,10 +243,80 @@ def run_int8_resnet18(header, arrays, x, want_acc=False):
     return out
 
 
+LSTM_HIDDEN, LSTM_TABLE, LSTM_DIRS = 128, 4096, ("fwd", "rev")
+
+
+def lstm_stages(lstm):
+    """``xq``, per layer and direction ``l{l}.{fwd|rev}.u``, ``.y`` and ``.c``, then ``hcat`` and ``logits``."""
+    dirs = LSTM_DIRS if lstm["bidirectional"] else LSTM_DIRS[:1]
+    return ["xq"] + [f"l{k}.{d}.{s}" for k in range(int(lstm["num_layers"])) for d in dirs for s in ("u", "y", "c")] + ["hcat", "logits"]
+
+
+def look(tab, a):
+    """tab[clamp(a, -2048, 2047) + 2048] as int64: the bundle's int16 table is data, never recomputed."""
+    return tab[np.clip(a, -2048, 2047) + 2048].astype(np.int64)
+
+
+def _exact_matmul(q, w):
+    """q (.., K) x w (N, K)^T of integers below 2^8 as a float64 matrix product: at most K 127 255 < 2^53, so exact."""
+    return (q.astype(np.float64) @ w.astype(np.float64).T).astype(np.int64)
+
+
+def run_int8_lstm(header, arrays, x, want_acc=False):
+    """Every stage of an int8 LSTMWakeword bundle on (B,1,F,T) features or (B,T,F) sequences, any T >= 1: ``xq`` (B,T,F) int8; per
+    layer and direction ``l{l}.{fwd|rev}.u`` (B,T,512) int16 (the input projection in Q8, gate order i, f, g, o), ``.y`` (B,T,128)
+    int8 (q_h at every step, in time order) and ``.c`` (B,128) int16 (the cell after the direction's last step); ``hcat``
+    (B, nd 128) int8; ``logits`` float32.  ``want_acc`` adds nothing: the law has no hidden accumulators beyond ``u``."""
+    x = np.asarray(x, np.float32)
+    lstm = header["lstm"]
+    F, L, H = int(lstm["input_size"]), int(lstm["num_layers"]), LSTM_HIDDEN
+    if x.ndim == 4 and x.shape[1] == 1:
+        x = x[:, 0].transpose(0, 2, 1)
+    if x.ndim != 3 or x.shape[2] != F or x.shape[1] < 1:
+        raise ValueError(f"this bundle is for features of shape (B,1,{F},T) or sequences (B,T,{F}), got {tuple(x.shape)}")
+    a, out = arrays, {}
+    dirs = LSTM_DIRS if lstm["bidirectional"] else LSTM_DIRS[:1]
+    sig, tanh = a["tab.sigmoid"], a["tab.tanh"]
+    z_in = int(a["input_zero"][0])
+    q_in = np.ascontiguousarray(quantize_input(x, a["input_scale"][0], z_in))
+    out["xq"] = q_in
+    B, T, _ = q_in.shape
+    hcat = []
+    for k in range(L):
+        ys = []
+        for d in dirs:
+            p = f"l{k}.{d}"
+            acc = _wrap32(_exact_matmul(q_in.astype(np.int64) - z_in, a[p + ".ih.w"]) + a[p + ".ih.b"].astype(np.int64))
+            u = np.clip(round_shift(acc, a[p + ".ih.m"], a[p + ".ih.sh"]), -32768, 32767)
+            y = np.zeros((B, T, H), np.int8)
+            q_h, c = np.zeros((B, H), np.int64), np.zeros((B, H), np.int64)
+            for t in (range(T) if d == "fwd" else range(T - 1, -1, -1)):
+                acc = _wrap32(_exact_matmul(q_h, a[p + ".hh.w"]) + a[p + ".hh.b"].astype(np.int64))
+                g_in = u[:, t] + round_shift(acc, a[p + ".hh.m"], a[p + ".hh.sh"])
+                i, f = look(sig, g_in[:, :H]), look(sig, g_in[:, H:2 * H])
+                g, o = look(tanh, g_in[:, 2 * H:3 * H]), look(sig, g_in[:, 3 * H:])
+                c = np.clip((f * c + ((i * g + 8) >> 4) + 2 ** 14) >> 15, -32768, 32767)
+                h16 = (o * look(tanh, (c + 4) >> 3) + 2 ** 14) >> 15
+                q_h = np.clip((h16 + 128) >> 8, -128, 127)
+                y[:, t] = q_h
+            out[p + ".u"], out[p + ".y"], out[p + ".c"] = u.astype(np.int16), y, c.astype(np.int16)
+            ys.append(y)
+            if k == L - 1:
+                hcat.append(y[:, T - 1] if d == "fwd" else y[:, 0])
+        q_in, z_in = np.concatenate(ys, axis=2), 0
+    hcat = np.concatenate(hcat, axis=1)
+    out["hcat"] = hcat
+    acc = _wrap32(_exact_matmul(hcat, a["fc.w"]) + a["fc.b"].astype(np.int64))
+    out["logits"] = acc.astype(np.float32) * a["fc.scale"].astype(np.float32)
+    return out
+
+
 def run_int8(header, arrays, x, want_acc=False):
     """Every stage of the int8 network on features ``x``, by the bundle's architecture.  ``cnn_small``: dict of STAGES (int8
-    NHWC tensors, ``pool`` (B,64), ``logits``); ``TCNWakeword``: ``run_int8_tcn``; ``ResNet18Wakeword``: ``run_int8_resnet18``.
-    ``want_acc`` adds the accumulators."""
+    NHWC tensors, ``pool`` (B,64), ``logits``); ``TCNWakeword``: ``run_int8_tcn``; ``ResNet18Wakeword``: ``run_int8_resnet18``;
+    ``LSTMWakeword``: ``run_int8_lstm``.  ``want_acc`` adds the accumulators."""
+    if header.get("architecture") == "LSTMWakeword":
+        return run_int8_lstm(header, arrays, x, want_acc)
     if header.get("architecture") == "TCNWakeword":
         return run_int8_tcn(header, arrays, x, want_acc)
     if header.get("architecture") == "ResNet18Wakeword":

@@ -1,12 +1,12 @@
-"""``QuantizedCNNSmall``, ``QuantizedTCN`` and ``QuantizedResNet18``: an int8 bundle on the device, run with integer arithmetic
-only (``ww_q8_cnn_small_fwd``, ``ww_tq8_tcn_fwd``, ``ww_rq8_resnet18_fwd``)."""
+"""``QuantizedCNNSmall``, ``QuantizedTCN``, ``QuantizedResNet18`` and ``QuantizedLSTM``: an int8 bundle on the device, run with
+integer arithmetic only (``ww_q8_cnn_small_fwd``, ``ww_tq8_tcn_fwd``, ``ww_rq8_resnet18_fwd``, ``ww_lq8_lstm_fwd``)."""
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _native as nat
 from .bundle import check_bundle
-from .reference import CONVS, resnet_blocks, tcn_blocks
+from .reference import CONVS, LSTM_DIRS, LSTM_HIDDEN, resnet_blocks, tcn_blocks
 
 
 def effective_bias(q_b: np.ndarray, q_w: np.ndarray, z_in: int) -> np.ndarray:
@@ -215,6 +215,103 @@ class QuantizedResNet18(nn.Module):
             ws = self._ws[B] = torch.empty(nat.rq8_resnet18_workspace_bytes(B, F, T), dtype=torch.uint8, device=dev)
         logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
         nat.rq8_resnet18_fwd(self._table(), self.io, x, ws, logits)
+        return logits
+
+
+def device_lstm_layer(arrays: dict, layer: int, num_directions: int, z_in: int):
+    """The eight tensors of one LSTM layer as ``ww_lq8_proj_fwd`` and ``ww_lq8_lstm_layer_fwd`` read them, the directions stacked
+    (forward first): w_ih (nd*512, Kp) with zero pad columns, its EFFECTIVE bias, mult, shift; w_hh (nd*512, 128), the law's q_bh,
+    mult, shift."""
+    names = [f"l{layer}.{d}" for d in LSTM_DIRS[:num_directions]]
+    w_ih = np.concatenate([arrays[n + ".ih.w"] for n in names])
+    wd = np.zeros((w_ih.shape[0], nat.tq8_pad(w_ih.shape[1])), np.int8)
+    wd[:, :w_ih.shape[1]] = w_ih
+    cat = lambda key: np.concatenate([arrays[n + key] for n in names])       # noqa: E731
+    return (wd, effective_bias(cat(".ih.b"), w_ih, z_in), cat(".ih.m"), cat(".ih.sh"),
+            np.ascontiguousarray(cat(".hh.w")), cat(".hh.b"), cat(".hh.m"), cat(".hh.sh"))
+
+
+class QuantizedLSTM(nn.Module):
+    """An int8 ``LSTMWakeword`` bundle on the device: ``forward`` takes (B,1,F,T) float32 features or (B,T,F) sequences, any
+    T >= 1, and returns (B,num_classes) float32 from one native call (``ww_lq8_lstm_fwd``), no host synchronisation.  Eval only,
+    no parameters.  The bundle is for one ``input_size``; it is not tied to one T (its law holds no 1/T)."""
+
+    hip_backed = True
+
+    def __init__(self, header: dict, arrays: dict):
+        super().__init__()
+        check_bundle(header, arrays)
+        if header["kind"] != "int8" or header["architecture"] != "LSTMWakeword":
+            raise ValueError(f"QuantizedLSTM needs an int8 LSTMWakeword bundle, got kind {header['kind']!r} of "
+                             f"{header['architecture']!r}")
+        self.header = dict(header)
+        e = header["lstm"]
+        self.input_size, self.num_layers = int(e["input_size"]), int(e["num_layers"])
+        self.num_directions, self.hidden_size = 2 if e["bidirectional"] else 1, LSTM_HIDDEN
+        self.num_classes = int(header["num_classes"])
+        z_x = int(arrays["input_zero"][0])
+        self.io = nat.Lq8Io(float(arrays["input_scale"][0]), z_x, self.input_size, self.num_layers, self.num_directions,
+                            self.num_classes)
+        self._names = []
+        for k in range(self.num_layers):
+            tensors = device_lstm_layer(arrays, k, self.num_directions, z_x if k == 0 else 0)
+            for suffix, a in zip(("ih_w", "ih_b", "ih_m", "ih_sh", "hh_w", "hh_b", "hh_m", "hh_sh"), tensors):
+                self._add(f"l{k}_{suffix}", a)
+        for key in ("fc.w", "fc.b", "fc.scale", "tab.sigmoid", "tab.tanh"):
+            self._add(key.replace(".", "_"), arrays[key])
+        assert len(self._names) == nat.LQ8_LAYER_NPTR * self.num_layers + nat.LQ8_TAIL_NPTR
+        self._tab, self._key, self._ws = None, None, {}
+        self.eval()
+
+    def _add(self, name, a):
+        self.register_buffer(name, torch.from_numpy(np.ascontiguousarray(a).copy()), persistent=False)
+        self._names.append(name)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise RuntimeError("QuantizedLSTM is an inference network: it has no training mode")
+        return super().train(False)
+
+    def layer(self, k):
+        """(w_ih, bias_eff, mult, shift, w_hh, bias, mult, shift) of layer ``k``, for the per-kernel entry points."""
+        return tuple(getattr(self, f"l{k}_{s}") for s in ("ih_w", "ih_b", "ih_m", "ih_sh", "hh_w", "hh_b", "hh_m", "hh_sh"))
+
+    def _table(self):
+        tensors = [getattr(self, n) for n in self._names]
+        key = tuple(t.data_ptr() for t in tensors)
+        if self._key != key:
+            self._tab, self._key = nat.ptr_array(tensors), key
+        return self._tab
+
+    def workspace(self, B, T):
+        """The uint8 workspace of the last forward at this batch size and length (``_native.lq8_workspace_views`` names its
+        parts)."""
+        return self._ws[(B, T)]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        F = self.input_size
+        if x.dim() == 4 and x.shape[1] == 1 and x.shape[2] == F:
+            x = x[:, 0]
+        elif x.dim() == 3 and x.shape[2] == F:
+            x = x.transpose(1, 2)                                  # (B,T,F) sequences -> (B,F,T): the kernel's input form
+        else:
+            raise ValueError(f"this int8 bundle is for features of shape (B,1,{F},T) or sequences (B,T,{F}), got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"features must be float32, got {x.dtype}")
+        if x.shape[0] < 1 or x.shape[2] < 1:
+            raise ValueError(f"an empty batch or sequence: {tuple(x.shape)}")
+        if not x.is_contiguous():
+            x = x.contiguous()
+        B, T = x.shape[0], x.shape[2]
+        dev = nat._dev(x, self.fc_w)
+        ws = self._ws.get((B, T))
+        if ws is None or ws.device != dev:
+            if len(self._ws) >= 4:                                 # T is free: keep a few shapes, not every one ever seen
+                self._ws.clear()
+            ws = self._ws[(B, T)] = torch.empty(nat.lq8_lstm_workspace_bytes(B, T, F, self.num_layers, self.num_directions),
+                                                dtype=torch.uint8, device=dev)
+        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
+        nat.lq8_lstm_fwd(self._table(), self.io, x, ws, logits)
         return logits
 
 
