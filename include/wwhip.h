@@ -1025,7 +1025,8 @@ int ww_rq8_resnet18_fwd(ww_ctx *ctx, const void *const *tab, const ww_rq8_io *io
  * ww_lq8_proj_fwd: the input projection of all nd directions of a layer over N = B*T rows.
  *   in     int8 (N, Kp), Kp a multiple of 64: the quantised features (ww_tq8_quantize_bt, pad channels = z_x) or the previous
  *          layer's y (Kp = nd * 128)
- *   w      int8 (G, Kp), G = nd * 512, the directions stacked; pad columns are zero
+ *   w      int8 (G, Kp), G = nd * 512, the directions stacked; pad columns are zero.  G = nd * 384 is accepted too: the same
+ *          projection over a GRU's r, z, n rows (ww_cq8_* below)
  *   bias   int32 (G): the EFFECTIVE bias q_bi - z_in * sum(q_wi); mult int32 (G) in [2^30, 2^31), shift int32 (G) in [1, 62]
  *   u[n][r] = clamp(R(sum_k w[r][k] in[n][k] + bias[r], mult[r], shift[r]), -32768, 32767) as int16 (N, G): Q8 gate pre-activations;
  *   R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh
@@ -1061,6 +1062,49 @@ int ww_lq8_head_fwd(ww_ctx *ctx, const int8_t *y, int B, int T, int num_directio
 size_t ww_lq8_lstm_workspace_bytes(int B, int T, int input_size, int num_layers, int num_directions);
 int ww_lq8_lstm_fwd(ww_ctx *ctx, const void *const *tab, const ww_lq8_io *io, const float *x, int B, int T, void *ws, size_t ws_bytes,
                     float *logits, ww_stream_t stream);
+
+/* ------------------------------------------------------------------ int8 inference of an exported CRNNWakeword bundle
+ * The same law with the rules of its subsections "GRU" and "CRNN" (DESIGN.md "Export"); ww_q8_crnn.hip.  The conv stack is
+ * cnn_small's (ww_q8_quantize, ww_q8_stem_fwd, ww_q8_dwpw_fwd), the projection ww_lq8_proj_fwd at G = nd * 384, the head
+ * ww_lq8_head_fwd.  Hidden size 128; a direction has 384 gate rows in torch's order r, z, n; nd = 1 or 2 directions, forward first.
+ * Every tensor is 16-byte aligned.
+ * ww_cq8_fmean_fwd: the frequency mean.  in int8 NHWC (B,H,W,64), z = -128 (H the frequency axis, W the time axis);
+ *   S[b][w][c] = sum_h (in[b][h][w][c] + 128); out int8 (B*W, 64) rows = clamp(-128 + R(S, mult, shift), -128, 127);
+ *   R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh.  Persistent; honours ww_ctx_set_grid_cap.
+ * ww_cq8_gru_layer_fwd: the recurrence of one GRU layer, all directions in one launch.  u int16 (B*T, G), G = nd * 384: the Q8
+ *   input projection; w_hh int8 (G, 128); bias int32 (G) is the law's q_bh (q_h has zero point 0); mult int32 (G) in [2^30, 2^31),
+ *   shift int32 (G) in [1, 62]; tab_sigmoid, tab_tanh int16 (4096) are the bundle's tables.  Per direction and step, with q_h = 0
+ *   and h16 = 0 before the first: v = R(sum_k w_hh[row][k] q_h[k] + bias[row], mult[row], shift[row]) in int64, unclamped;
+ *   r = look(sigmoid, u_r + v_r), z = look(sigmoid, u_z + v_z), n = look(tanh, u_n + ((r v_n + 2^14) >> 15)), the product in int64,
+ *   look(tab, a) = tab[clamp(a, -2048, 2047) + 2048]; h16 = ((32768 - z) n + z h16 + 2^14) >> 15 (|h16| <= 32767, no clamp);
+ *   q_h = clamp((h16 + 128) >> 8, -128, 127).  The reverse direction walks t = T-1 .. 0.  y int8 (B*T, nd*128) holds q_h of every step
+ *   in time order, the forward direction's 128 channels first; h_n int16 (B, nd*128) is h16 after each direction's last step.
+ * The whole model: tab = WW_CQ8_CONV_NPTR device pointers [stem w, bias, mult, shift] + 4 x [dw w, bias, mult, shift, pw w, bias,
+ * mult, shift] (as ww_q8_cnn_small_fwd), then per layer WW_CQ8_LAYER_NPTR [w_ih, bias, mult, shift, w_hh, bias, mult, shift]
+ * (directions stacked, w_ih's bias the EFFECTIVE bias, as ww_lq8_lstm_fwd), then WW_CQ8_TAIL_NPTR: [fc_w, fc_bias, fc_scale,
+ * tab_sigmoid, tab_tanh]; io on the host; x fp32 (B,F,T), any T >= 1.  Launches: quantize, stem, 4 x dwpw, fmean, per layer
+ * (projection, recurrence), head.  With H' = (F+1)/2, W' = (T+1)/2 the workspace holds, each rounded up to 256 bytes: xq (B*F*T),
+ * WW_CQ8_NACT activation tensors of B*H'*W'*64 (stem, pw0 .. pw3: the depthwise outputs stay in registers), seq (B*W'*64), per
+ * layer u (B*W'*nd*384 int16), y (B*W'*nd*128), h_n (B*nd*128 int16), then hcat (B*nd*128) -- that sum is what the
+ * workspace-size entry point returns.  Nothing synchronises with the host. */
+#define WW_CQ8_MAX_LAYERS 8
+#define WW_CQ8_CONV_NPTR 36
+#define WW_CQ8_LAYER_NPTR 8
+#define WW_CQ8_TAIL_NPTR 5
+#define WW_CQ8_NACT 5
+typedef struct {
+    float in_scale;                         /* s_x */
+    int32_t in_zero;                        /* z_x */
+    int32_t fmean_mult, fmean_shift;        /* m_f, sh_f */
+    int32_t num_layers, num_directions, num_classes;
+} ww_cq8_io;
+int ww_cq8_fmean_fwd(ww_ctx *ctx, const int8_t *in, int B, int H, int W, int mult, int shift, int8_t *out, ww_stream_t stream);
+int ww_cq8_gru_layer_fwd(ww_ctx *ctx, const int16_t *u, const int8_t *w_hh, const int32_t *bias, const int32_t *mult,
+                         const int32_t *shift, const int16_t *tab_sigmoid, const int16_t *tab_tanh, int B, int T, int num_directions,
+                         int8_t *y, int16_t *h_n, ww_stream_t stream);
+size_t ww_cq8_crnn_workspace_bytes(int B, int F, int T, int num_layers, int num_directions);
+int ww_cq8_crnn_fwd(ww_ctx *ctx, const void *const *tab, const ww_cq8_io *io, const float *x, int B, int F, int T, void *ws,
+                    size_t ws_bytes, float *logits, ww_stream_t stream);
 
 /* ------------------------------------------------------------------ collectives: deliberately NOT in this ABI
  * SURVEY.md §8b sketched two more entry points, `ww_comm_init` (ctx, nccl_unique_id, rank, world) and `ww_allreduce_f32`

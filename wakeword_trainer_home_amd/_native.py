@@ -155,6 +155,15 @@ class Lq8Io(C.Structure):
                 ("num_directions", C.c_int32), ("num_classes", C.c_int32)]
 
 
+CQ8_MAX_LAYERS, CQ8_CONV_NPTR, CQ8_LAYER_NPTR, CQ8_TAIL_NPTR, CQ8_NACT, CQ8_HIDDEN = 8, 36, 8, 5, 5, 128
+
+
+class Cq8Io(C.Structure):
+    """ww_cq8_io: the scalars of an int8 CRNNWakeword bundle (include/wwhip.h)."""
+    _fields_ = [("in_scale", C.c_float), ("in_zero", C.c_int32), ("fmean_mult", C.c_int32), ("fmean_shift", C.c_int32),
+                ("num_layers", C.c_int32), ("num_directions", C.c_int32), ("num_classes", C.c_int32)]
+
+
 _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 _SIGS = {
     "ww_abi_version": (C.c_int, []),
@@ -314,6 +323,10 @@ _SIGS = {
     "ww_lq8_head_fwd": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "ww_lq8_lstm_workspace_bytes": (_sz, [_i] * 5),
     "ww_lq8_lstm_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Lq8Io), _vp, _i, _i, _vp, _sz, _vp, _vp]),
+    "ww_cq8_fmean_fwd": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ww_cq8_gru_layer_fwd": (C.c_int, [_vp] * 8 + [_i, _i, _i, _vp, _vp, _vp]),
+    "ww_cq8_crnn_workspace_bytes": (_sz, [_i] * 5),
+    "ww_cq8_crnn_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Cq8Io), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "ww_prof_num_classes": (C.c_int, []),
     "ww_prof_class_name": (C.c_char_p, [_i]),
     "ww_ctx_set_deferred_reduce": (C.c_int, [_vp, _i]),
@@ -2514,12 +2527,13 @@ def rq8_workspace_views(ws, B, F, T):
 # ---- int8 inference of an exported LSTMWakeword bundle (ww_q8_lstm.hip).  Activations are int8 (B,T,Kp) rows, Kp a multiple of 64;
 # a layer's tensors are stacked over its directions, as include/wwhip.h lays them out.
 def lq8_proj_fwd(a, w, bias, mult, shift):
-    """a int8 (B,T,Kp), w int8 (G,Kp), bias (effective) / mult / shift int32 (G), G = 512 or 1024 -> u int16 (B,T,G)."""
+    """a int8 (B,T,Kp), w int8 (G,Kp), bias (effective) / mult / shift int32 (G), G = 512 or 1024 (an LSTM's gate rows) or 384 or
+    768 (a GRU's) -> u int16 (B,T,G)."""
     dev = _dev(a, w, bias, mult, shift)
     _tq8_act_check(a, "lq8_proj_fwd")
-    if w.dtype != torch.int8 or w.dim() != 2 or w.shape[1] != a.shape[2] or w.shape[0] not in (512, 1024) or \
+    if w.dtype != torch.int8 or w.dim() != 2 or w.shape[1] != a.shape[2] or w.shape[0] not in (384, 512, 768, 1024) or \
             any(t.dtype != torch.int32 or t.numel() != w.shape[0] for t in (bias, mult, shift)):
-        raise ValueError("lq8_proj_fwd: w int8 (G,Kp), G = 512 or 1024, bias / mult / shift int32 (G)")
+        raise ValueError("lq8_proj_fwd: w int8 (G,Kp), G = 512 or 1024 (384 or 768 for a GRU), bias / mult / shift int32 (G)")
     B, T, Kp = a.shape
     u = torch.empty((B, T, w.shape[0]), dtype=torch.int16, device=dev)
     with _guard(dev):
@@ -2591,6 +2605,77 @@ def lq8_workspace_views(ws, B, T, input_size, num_layers, num_directions):
         out[f"l{k}.y"] = i8[off:off + B * T * nd * 128].view(B, T, nd * 128)
         off += r256(B * T * nd * 128)
         out[f"l{k}.c"] = i8[off:off + B * nd * 256].view(torch.int16).view(B, nd * 128)
+        off += r256(B * nd * 256)
+    out["hcat"] = i8[off:off + B * nd * 128].view(B, nd * 128)
+    return out
+
+
+# ---- int8 inference of an exported CRNNWakeword bundle (ww_q8_crnn.hip).  The conv stack is the q8_* family's, the projection
+# lq8_proj_fwd at G = nd*384, the head lq8_head_fwd; a layer's tensors are stacked over its directions.
+def cq8_fmean_fwd(a, mult, shift):
+    """a int8 (B,H,W,64), z = -128 -> the frequency mean, int8 (B,W,64) rows."""
+    dev = _dev(a)
+    _q8_act_check(a)
+    if not a.is_contiguous():
+        raise ValueError("cq8_fmean_fwd: contiguous activations")
+    B, H, W, _ = a.shape
+    out = torch.empty((B, W, 64), dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_cq8_fmean_fwd(ctx(dev), _p(a), B, H, W, int(mult), int(shift), _p(out), _stream(dev)), "ww_cq8_fmean_fwd")
+    return out
+
+
+def cq8_gru_layer_fwd(u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh):
+    """u int16 (B,T,nd*384), w_hh int8 (nd*384,128), bias / mult / shift int32 (nd*384), the two int16 (4096) tables ->
+    (y int8 (B,T,nd*128), h_n int16 (B,nd*128))."""
+    dev = _dev(u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh)
+    G = w_hh.shape[0]
+    if u.dtype != torch.int16 or u.dim() != 3 or u.shape[2] != G or G not in (384, 768) or w_hh.dtype != torch.int8 or \
+            tuple(w_hh.shape) != (G, 128) or any(t.dtype != torch.int32 or t.numel() != G for t in (bias, mult, shift)) or \
+            any(t.dtype != torch.int16 or t.numel() != 4096 for t in (tab_sigmoid, tab_tanh)) or not u.is_contiguous():
+        raise ValueError("cq8_gru_layer_fwd: u int16 (B,T,G), w_hh int8 (G,128), bias / mult / shift int32 (G), tables int16 (4096)")
+    B, T, nd = u.shape[0], u.shape[1], G // 384
+    y = torch.empty((B, T, nd * 128), dtype=torch.int8, device=dev)
+    h_n = torch.empty((B, nd * 128), dtype=torch.int16, device=dev)
+    with _guard(dev):
+        _check(load().ww_cq8_gru_layer_fwd(ctx(dev), _p(u), _p(w_hh), _p(bias), _p(mult), _p(shift), _p(tab_sigmoid), _p(tab_tanh),
+                                           B, T, nd, _p(y), _p(h_n), _stream(dev)), "ww_cq8_gru_layer_fwd")
+    return y, h_n
+
+
+def cq8_crnn_workspace_bytes(B, F, T, num_layers, num_directions):
+    return load().ww_cq8_crnn_workspace_bytes(B, F, T, num_layers, num_directions)
+
+
+def cq8_crnn_fwd(tab, io: Cq8Io, x, ws, logits):
+    """``tab``: ``ptr_array`` of the bundle's tensors (CQ8_CONV_NPTR of the conv stack, CQ8_LAYER_NPTR per layer, then fc_w,
+    fc_bias, fc_scale, tab_sigmoid, tab_tanh); x float32 (B,F,T); ws uint8; logits float32 (B,num_classes)."""
+    dev = _dev(x, ws, logits)
+    with _guard(dev):
+        _check(load().ww_cq8_crnn_fwd(ctx(dev), tab, C.byref(io), _p(x), x.shape[0], x.shape[-2], x.shape[-1], _p(ws),
+                                      ws.numel() * ws.element_size(), _p(logits), _stream(dev)), "ww_cq8_crnn_fwd")
+
+
+def cq8_workspace_views(ws, B, F, T, num_layers, num_directions):
+    """The tensors ww_cq8_crnn_fwd left in ``ws`` (uint8), by stage name: xq (B,F,T), front.stem and front.pw0 .. front.pw3
+    (B,H',W',64), seq (B,W',64), per layer l{k}.u int16 (B,W',nd*384), l{k}.y int8 (B,W',nd*128) and l{k}.h int16 (B,nd*128),
+    directions stacked, then hcat (B,nd*128) -- the layout include/wwhip.h states."""
+    r256 = lambda n: (n + 255) // 256 * 256       # noqa: E731
+    i8, nd = ws.view(torch.int8), num_directions
+    H, W = (F + 1) // 2, (T + 1) // 2
+    out, off, act = {"xq": i8[:B * F * T].view(B, F, T)}, r256(B * F * T), B * H * W * 64
+    for name in ["stem"] + [f"pw{j}" for j in range(4)]:
+        out["front." + name] = i8[off:off + act].view(B, H, W, 64)
+        off += r256(act)
+    out["seq"] = i8[off:off + B * W * 64].view(B, W, 64)
+    off += r256(B * W * 64)
+    for k in range(num_layers):
+        n = B * W * nd * 384 * 2
+        out[f"l{k}.u"] = i8[off:off + n].view(torch.int16).view(B, W, nd * 384)
+        off += r256(n)
+        out[f"l{k}.y"] = i8[off:off + B * W * nd * 128].view(B, W, nd * 128)
+        off += r256(B * W * nd * 128)
+        out[f"l{k}.h"] = i8[off:off + B * nd * 256].view(torch.int16).view(B, nd * 128)
         off += r256(B * nd * 256)
     out["hcat"] = i8[off:off + B * nd * 128].view(B, nd * 128)
     return out

@@ -244,7 +244,8 @@ extern "C" int ww_lq8_proj_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, c
     WW_REQUIRE(ctx && in && w && bias && mult && shift && u, WW_E_INVALID, "ww_lq8_proj_fwd: null argument");
     WW_REQUIRE(N >= 1 && N <= (1l << 40), WW_E_INVALID, "ww_lq8_proj_fwd: N=%ld", N);
     WW_REQUIRE(Kp >= 64 && Kp % 64 == 0 && Kp <= (1 << 16), WW_E_INVALID, "ww_lq8_proj_fwd: Kp=%d must be a multiple of 64", Kp);
-    WW_REQUIRE(G == LQ_G || G == 2 * LQ_G, WW_E_INVALID, "ww_lq8_proj_fwd: G=%d gate rows, expected %d or %d", G, LQ_G, 2 * LQ_G);
+    WW_REQUIRE(G == LQ_G || G == 2 * LQ_G || G == 3 * LQ_H || G == 6 * LQ_H, WW_E_INVALID,
+               "ww_lq8_proj_fwd: G=%d gate rows, expected %d or %d (LSTM), %d or %d (GRU)", G, LQ_G, 2 * LQ_G, 3 * LQ_H, 6 * LQ_H);
     WW_REQUIRE(aligned16(in) && aligned16(w) && aligned16(bias) && aligned16(mult) && aligned16(shift) && aligned16(u), WW_E_INVALID,
                "ww_lq8_proj_fwd: tensors must be 16-byte aligned");
     lq8_proj_args a{in, w, bias, mult, shift, u, N, Kp, G};

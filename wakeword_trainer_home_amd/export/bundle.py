@@ -175,6 +175,58 @@ def _check_lstm(header, arrays, fs):
         raise BundleError("fc.scale is not finite")
 
 
+def check_crnn_entry(header: dict):
+    """The header's ``crnn`` entry as (num_layers, num_directions), within the limits of the int8 GRU stack."""
+    e = header.get("crnn")
+    keys = ("hidden_size", "num_layers", "bidirectional")
+    if not (isinstance(e, dict) and all(k in e for k in keys)):
+        raise BundleError(f"the crnn entry {e!r} is not {{hidden_size, num_layers, bidirectional}}")
+    H, L, bi = (e[k] for k in keys)
+    if not (all(isinstance(v, int) and not isinstance(v, bool) for v in (H, L)) and isinstance(bi, bool)):
+        raise BundleError(f"the crnn entry {e!r}: integer hidden_size and num_layers, a boolean bidirectional")
+    if H != LSTM_HIDDEN or not 1 <= L <= 8:
+        raise BundleError(f"the crnn entry {e!r}: hidden_size {LSTM_HIDDEN}, 1..8 layers")
+    return L, 2 if bi else 1
+
+
+def _check_tables(arrays):
+    for name, lo in (("tab.sigmoid", 0), ("tab.tanh", -32767)):
+        t = _need(arrays, name, np.int16, (LSTM_TABLE,)).astype(np.int64)
+        if (np.diff(t) < 0).any() or t.min() < lo or t.max() > 32767:
+            raise BundleError(f"{name} is not a non-decreasing table within [{lo}, 32767]")
+
+
+def _check_crnn(header, arrays):
+    L, nd = check_crnn_entry(header)
+    nc, H = header["num_classes"], LSTM_HIDDEN
+    if not (isinstance(nc, int) and 2 <= nc <= 64):
+        raise BundleError(f"num_classes {nc!r} is outside [2, 64]")
+    for name in CONVS:
+        p = "front." + name
+        w = _need(arrays, p + ".w", np.int8, (64, 64 if name.startswith("pw") else 9))
+        if (w == -128).any():
+            raise BundleError(f"{p}.w holds -128: weights are symmetric, in [-127, 127]")
+        _need(arrays, p + ".b", np.int32, (64,))
+        _check_mult(arrays, p, 64)
+    _check_mult(arrays, "fmean", 1)
+    for layer in range(L):
+        for d in LSTM_DIRS[:nd]:
+            for part, K in (("ih", 64 if layer == 0 else nd * H), ("hh", H)):
+                p = f"l{layer}.{d}.{part}"
+                w = _need(arrays, p + ".w", np.int8, (3 * H, K))
+                if (w == -128).any():
+                    raise BundleError(f"{p}.w holds -128: weights are symmetric, in [-127, 127]")
+                _need(arrays, p + ".b", np.int32, (3 * H,))
+                _check_mult(arrays, p, 3 * H)
+    _check_tables(arrays)
+    w = _need(arrays, "fc.w", np.int8, (nc, nd * H))
+    if (w == -128).any():
+        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
+    _need(arrays, "fc.b", np.int32, (nc,))
+    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
+        raise BundleError("fc.scale is not finite")
+
+
 def check_bundle(header: dict, arrays: dict) -> None:
     """Raises ``BundleError`` unless the bundle is complete and every value is in the range its law gives it."""
     if not isinstance(header, dict) or header.get("format") != FORMAT_NAME:
@@ -198,8 +250,8 @@ def check_bundle(header: dict, arrays: dict) -> None:
         return
     if kind != "int8":
         raise BundleError(f"unknown bundle kind {kind!r}")
-    if header["architecture"] not in ("cnn_small", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
-        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small, TCNWakeword, ResNet18Wakeword and "
+    if header["architecture"] not in ("cnn_small", "crnn", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
+        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small, crnn, TCNWakeword, ResNet18Wakeword and "
                           "LSTMWakeword have an int8 form")
     fs = header.get("feature_shape")
     if not (isinstance(fs, list) and len(fs) == 2 and all(isinstance(v, int) and v >= 1 for v in fs)):
@@ -216,6 +268,8 @@ def check_bundle(header: dict, arrays: dict) -> None:
         return _check_resnet18(header, arrays)
     if header["architecture"] == "LSTMWakeword":
         return _check_lstm(header, arrays, fs)
+    if header["architecture"] == "crnn":
+        return _check_crnn(header, arrays)
     for name in CONVS:
         w = _need(arrays, name + ".w", np.int8, (64, 64 if name.startswith("pw") else 9))
         if (w == -128).any():

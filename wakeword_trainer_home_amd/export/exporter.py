@@ -1,8 +1,8 @@
 """The reference's export panel (``src/export/onnx_exporter.py``) without ONNX: neither an ONNX writer nor a runtime exists
 on the build machine, so ``export`` writes self-describing bundles (``bundle.py``) instead -- fp32, fp16 (weights only, as
-the reference's ``QFloat16`` call) and int8 (``cnn_small``, ``TCNWakeword``, ``ResNet18Wakeword`` and ``LSTMWakeword``; the law is
-DESIGN.md "Export") -- and the int8 bundle runs on the device with integer arithmetic (``runtime.QuantizedCNNSmall``,
-``runtime.QuantizedTCN``, ``runtime.QuantizedResNet18``, ``runtime.QuantizedLSTM``).  Names,
+the reference's ``QFloat16`` call) and int8 (``cnn_small``, ``crnn``, ``TCNWakeword``, ``ResNet18Wakeword`` and ``LSTMWakeword``; the
+law is DESIGN.md "Export") -- and the int8 bundle runs on the device with integer arithmetic (``runtime.QuantizedCNNSmall``,
+``runtime.QuantizedTCN``, ``runtime.QuantizedResNet18``, ``runtime.QuantizedLSTM``, ``runtime.QuantizedCRNN``).  Names,
 signatures, result keys and failure behaviour are the reference's; ``ONNXExporter``, ``export_model_to_onnx``, ``validate_onnx_model`` and ``benchmark_onnx_model`` stay as
 aliases.  Parity with onnxruntime's ``quantize_dynamic`` is not claimed."""
 import logging
@@ -16,10 +16,10 @@ import torch.nn as nn
 
 from .. import _native as nat
 from .bundle import STATE_PREFIX, BundleError, check_bundle, float_arrays, load_bundle, make_header, write_bundle
-from .quantize import (QuantizationError, check_lstm_args, check_tcn_args, quantize_cnn_small, quantize_lstm, quantize_resnet18,
-                       quantize_tcn)
+from .quantize import (QuantizationError, check_crnn_args, check_lstm_args, check_tcn_args, quantize_cnn_small, quantize_crnn,
+                       quantize_lstm, quantize_resnet18, quantize_tcn)
 from .reference import CONVS
-from .runtime import QuantizedCNNSmall, QuantizedLSTM, QuantizedResNet18, QuantizedTCN
+from .runtime import QuantizedCNNSmall, QuantizedCRNN, QuantizedLSTM, QuantizedResNet18, QuantizedTCN
 
 logger = logging.getLogger(__name__)
 
@@ -53,21 +53,21 @@ def _state_numpy(model: nn.Module) -> Dict[str, np.ndarray]:
     return {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
 
 
-def calibrate_cnn_small(model, batches: Iterable[torch.Tensor], feature_shape, device, feature_extractor=None) -> dict:
-    """Ranges of the fp32 model in eval mode over the calibration batches: the input's minimum and maximum, the maximum of
-    every conv's post-ReLU output and of the pooled vector.  Runs the model's own per-layer entry points with
-    ``training = 0``; the maxima are torch reductions on the device and come to the host once, at the end."""
+def _calibrate_conv_stack(model, batches, feature_shape, dev, feature_extractor, whole=None):
+    """The loop ``calibrate_cnn_small`` and ``calibrate_crnn`` share, over a ``CNNSmallWakeword`` conv stack in eval mode: the
+    input's minimum and maximum and the maximum of every conv's post-ReLU output, through the model's own per-layer entry points
+    with ``training = 0``.  ``feature_shape``: (F, T), T ``None`` for any length.  One more maximum per batch: that of ``whole(x)``
+    (a forward of the model itself, run before the layers) or, without ``whole``, that of the pooled vector.
+    -> (lo, hi, a_max (9), that maximum, samples), tensors on the device."""
     F, T = feature_shape
-    dev = torch.device(device)
     convs = [(model.stem.conv, model.stem.bn)]
     for blk in model.blocks:
         convs += [(blk.dw, blk.dw_bn), (blk.pw, blk.pw_bn)]
-    bns = [nat.make_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, 0.1, bn.eps, training=False) for _, bn in convs]
     scratch = nat.layer_scratch(dev)
     lo = torch.full((), float("inf"), device=dev)
     hi = torch.full((), float("-inf"), device=dev)
     a_max = torch.full((len(convs),), float("-inf"), device=dev)
-    p_max = torch.full((), float("-inf"), device=dev)
+    t_max = torch.full((), float("-inf"), device=dev)
     seen = 0
     with torch.no_grad():
         for x in batches:
@@ -78,10 +78,15 @@ def calibrate_cnn_small(model, batches: Iterable[torch.Tensor], feature_shape, d
                 x = feature_extractor(x)
             if x.dim() == 3:
                 x = x[:, None]
-            if x.dim() != 4 or tuple(x.shape[1:]) != (1, F, T):
-                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{T})")
+            if x.dim() != 4 or tuple(x.shape[1:3]) != (1, F) or (x.shape[3] != T if T is not None else x.shape[3] < 1):
+                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{'T' if T is None else T})")
             x = x.float().contiguous()
             lo, hi = torch.minimum(lo, x.min()), torch.maximum(hi, x.max())
+            if whole is not None:
+                t_max = torch.maximum(t_max, whole(x).max())
+            # built per batch, after ``whole``: a model's first forward may move its parameters into a flat bucket (FlatBuckets),
+            # and these structs hold their addresses
+            bns = [nat.make_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, 0.1, bn.eps, training=False) for _, bn in convs]
             y = ss = mr = None
             for i, ((conv, _), bn) in enumerate(zip(convs, bns)):
                 if i == 0:
@@ -91,13 +96,45 @@ def calibrate_cnn_small(model, batches: Iterable[torch.Tensor], feature_shape, d
                 else:
                     y, ss, mr = nat.pwconv1x1_fwd(y, ss, conv.weight, bn, scratch)
                 a_max[i] = torch.maximum(a_max[i], torch.relu(y * ss[:64] + ss[64:]).max())
-            pool = nat.gap_fwd(y, ss, mr)
-            p_max = torch.maximum(p_max, (pool[:, 0, :] / float(y.shape[1] * y.shape[2])).max())
+            if whole is None:
+                t_max = torch.maximum(t_max, (nat.gap_fwd(y, ss, mr)[:, 0, :] / float(y.shape[1] * y.shape[2])).max())
             seen += x.shape[0]
     if seen == 0:
         raise QuantizationError("the calibration data is empty")
+    return lo, hi, a_max, t_max, seen
+
+
+def calibrate_cnn_small(model, batches: Iterable[torch.Tensor], feature_shape, device, feature_extractor=None) -> dict:
+    """Ranges of the fp32 model in eval mode over the calibration batches: the input's minimum and maximum, the maximum of
+    every conv's post-ReLU output and of the pooled vector.  Runs the model's own per-layer entry points with
+    ``training = 0``; the maxima are torch reductions on the device and come to the host once, at the end."""
+    dev = torch.device(device)
+    lo, hi, a_max, p_max, seen = _calibrate_conv_stack(model, batches, tuple(feature_shape), dev, feature_extractor)
     return {"x_min": float(lo), "x_max": float(hi), "a_max": [float(v) for v in a_max.cpu()], "p_max": float(p_max),
             "samples": seen}
+
+
+def crnn_entry(model) -> dict:
+    """The header's ``crnn`` entry of a ``CRNNWakeword``: what its constructor needs besides ``num_classes``."""
+    return {"hidden_size": int(model.rnn.hidden_size), "num_layers": int(model.rnn.num_layers),
+            "bidirectional": bool(model.rnn.bidirectional)}
+
+
+def calibrate_crnn(model, batches: Iterable[torch.Tensor], feature_rows, device, feature_extractor=None) -> dict:
+    """Ranges of the fp32 ``CRNNWakeword`` in eval mode over the calibration batches: the input's minimum and maximum, the nine
+    conv maxima of ``model.front`` (through the per-layer entry points ``calibrate_cnn_small`` uses) and ``f_max``, the maximum
+    of ``model.front``'s output sequence.  The GRU stack has fixed scales.  T may differ from batch to batch.  Torch reductions
+    on the device and one read-back."""
+    dev = torch.device(device)
+    front = model.front
+    was_training = front.training
+    front.eval()
+    try:
+        lo, hi, a_max, f_max, seen = _calibrate_conv_stack(front, batches, (int(feature_rows), None), dev, feature_extractor, front)
+    finally:
+        front.train(was_training)
+    got = torch.cat([lo[None], hi[None], a_max, f_max[None]]).cpu().tolist()                    # the one read-back
+    return {"x_min": got[0], "x_max": got[1], "a_max": got[2:11], "f_max": got[11], "samples": seen}
 
 
 def tcn_entry(model) -> dict:
@@ -288,6 +325,8 @@ class ModelExporter:
                 more = {"tcn": tcn_entry(self.model)} if arch == "TCNWakeword" and hasattr(self.model, "tcn") else {}
                 if arch == "LSTMWakeword" and hasattr(self.model, "lstm"):
                     more = {"lstm": lstm_entry(self.model)}
+                if arch == "crnn" and hasattr(self.model, "rnn") and hasattr(self.model, "front"):
+                    more = {"crnn": crnn_entry(self.model)}
                 header = make_header("fp32", arch, int(test_output.shape[1]), self.sample_input_shape,
                                      [k for k in state if k.endswith("weight")], config, **more)
                 write_bundle(output_path, header, float_arrays(state, fp16=False))
@@ -321,9 +360,10 @@ class ModelExporter:
         return write_bundle(path, dict(header, kind="fp16"), float_arrays(state, fp16=True))
 
     def _write_int8(self, output_path: Path, header: dict, state: dict, config: ExportConfig) -> Path:
-        if header["architecture"] not in ("cnn_small", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
-            raise QuantizationError("int8 export covers cnn_small only among the factory's architectures, and TCNWakeword, "
-                                    f"ResNet18Wakeword and LSTMWakeword; not {header['architecture']!r}")
+        if header["architecture"] not in ("cnn_small", "crnn", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
+            raise QuantizationError("int8 export covers cnn_small only among the factory's architectures -- with crnn, whose conv "
+                                    "stack is cnn_small's -- and TCNWakeword, ResNet18Wakeword and LSTMWakeword; not "
+                                    f"{header['architecture']!r}")
         if self.calibration is None:
             raise QuantizationError("int8 export needs calibration data (ModelExporter(..., calibration=batches)); "
                                     "it is never calibrated on random input")
@@ -349,6 +389,18 @@ class ModelExporter:
                 logger.info("calibrated ranges: %s", cal)
             arrays, scales = quantize_lstm(state, header["lstm"], cal["x_min"], cal["x_max"])
             layers = [k[:-2] for k in arrays if k.endswith(".w")]
+            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
+            check_bundle(h, arrays)
+            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
+        if header["architecture"] == "crnn":
+            if "crnn" not in header:
+                raise QuantizationError("the header of a crnn bundle holds no crnn entry (hidden_size, num_layers, bidirectional)")
+            check_crnn_args(header["crnn"], header["num_classes"])
+            cal = calibrate_crnn(self.model, self.calibration, F, self.device, fe)
+            if config.verbose:
+                logger.info("calibrated ranges: %s", cal)
+            arrays, scales = quantize_crnn(state, header["crnn"], F, cal, eps=self.model.front.stem.bn.eps)
+            layers = [k[:-2] for k in arrays if k.endswith(".w") and k != "fc.w"] + ["fmean", "fc"]
             h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
             check_bundle(h, arrays)
             return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
@@ -396,14 +448,15 @@ def export_model(checkpoint_path: Path, output_path: Path, opset_version: int = 
 
 def load_exported_model(path: Path, device: str = "cuda") -> nn.Module:
     """A bundle as a module in eval mode on ``device``: the factory's architecture with the stored weights (fp16 widened to
-    fp32) or, for an int8 bundle, ``QuantizedCNNSmall`` / ``QuantizedTCN`` / ``QuantizedResNet18`` / ``QuantizedLSTM``.  A
+    fp32) or, for an int8 bundle, ``QuantizedCNNSmall`` / ``QuantizedTCN`` / ``QuantizedResNet18`` / ``QuantizedLSTM`` /
+    ``QuantizedCRNN``.  A ``crnn`` bundle is built from its header's ``crnn`` entry where it has one.  A
     ``TCNWakeword`` bundle is built from its header's ``tcn`` entry, an ``LSTMWakeword`` bundle from its ``lstm`` entry and a
     ``ResNet18Wakeword`` bundle from ``num_classes`` alone (the factory does not offer those classes).  ``ModelEvaluator`` and ``RecordingScanner`` take any of them."""
     header, arrays = load_bundle(path)
     check_bundle(header, arrays)
     if header["kind"] == "int8":
-        cls = {"TCNWakeword": QuantizedTCN, "ResNet18Wakeword": QuantizedResNet18,
-               "LSTMWakeword": QuantizedLSTM}.get(header["architecture"], QuantizedCNNSmall)
+        cls = {"TCNWakeword": QuantizedTCN, "ResNet18Wakeword": QuantizedResNet18, "LSTMWakeword": QuantizedLSTM,
+               "crnn": QuantizedCRNN}.get(header["architecture"], QuantizedCNNSmall)
         return cls(header, arrays).to(device)
     if header["architecture"] == "ResNet18Wakeword":
         from ..models import ResNet18Wakeword
@@ -415,6 +468,13 @@ def load_exported_model(path: Path, device: str = "cuda") -> nn.Module:
         e = header["lstm"]
         model = LSTMWakeword(input_size=e["input_size"], hidden_size=e["hidden_size"], num_layers=e["num_layers"],
                              num_classes=header["num_classes"], bidirectional=e["bidirectional"])
+    elif header["architecture"] == "crnn" and "crnn" in header:
+        from ..models import create_model
+        from .bundle import check_crnn_entry
+        check_crnn_entry(header)
+        e = header["crnn"]
+        model = create_model(architecture="crnn", num_classes=header["num_classes"], pretrained=False, hidden_size=e["hidden_size"],
+                             num_layers=e["num_layers"], bidirectional=e["bidirectional"])
     elif header["architecture"] == "TCNWakeword":
         from ..models import TCNWakeword
         from .bundle import check_tcn_entry
@@ -505,4 +565,4 @@ benchmark_onnx_model = benchmark_exported_model
 __all__ = ["ExportConfig", "ModelExporter", "ONNXExporter", "export_model", "export_model_to_onnx", "load_exported_model",
            "validate_exported_model", "validate_onnx_model", "benchmark_exported_model", "benchmark_onnx_model",
            "QuantizedCNNSmall", "QuantizedTCN", "QuantizedResNet18", "QuantizedLSTM", "BundleError", "QuantizationError",
-           "calibrate_cnn_small", "calibrate_tcn", "calibrate_resnet18", "calibrate_lstm"]
+           "calibrate_cnn_small", "calibrate_tcn", "calibrate_resnet18", "calibrate_lstm", "QuantizedCRNN", "calibrate_crnn"]

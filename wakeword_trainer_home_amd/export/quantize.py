@@ -1,5 +1,5 @@
 """The export side of the int8 law (DESIGN.md "Export"): BatchNorm folding, scales, integer weights, biases and multipliers
-of ``cnn_small``, ``TCNWakeword``, ``ResNet18Wakeword`` and ``LSTMWakeword``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does
+of ``cnn_small``, ``TCNWakeword``, ``ResNet18Wakeword``, ``LSTMWakeword`` and ``CRNNWakeword``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does
 with the result."""
 import math
 from typing import Dict, Sequence
@@ -85,7 +85,8 @@ def cnn_small_float_layers(state: Dict[str, np.ndarray], eps: float = 1e-5):
     for k in range(BLOCKS):
         layers[f"dw{k}"] = fold_bn(state[f"blocks.{k}.dw.weight"], *bn(f"blocks.{k}.dw_bn"), eps)
         layers[f"pw{k}"] = fold_bn(state[f"blocks.{k}.pw.weight"], *bn(f"blocks.{k}.pw_bn"), eps)
-    layers["fc"] = (np.asarray(state["classifier.weight"], np.float64), np.asarray(state["classifier.bias"], np.float64))
+    if "classifier.weight" in state:                 # (the CRNN's front end is the conv stack alone)
+        layers["fc"] = (np.asarray(state["classifier.weight"], np.float64), np.asarray(state["classifier.bias"], np.float64))
     return layers
 
 
@@ -98,8 +99,9 @@ def quantize_cnn_small(state: Dict[str, np.ndarray], feature_shape: Sequence[int
     if len(a_max) != len(CONVS):
         raise QuantizationError(f"{len(a_max)} calibrated maxima for {len(CONVS)} convs")
     layers = cnn_small_float_layers(state, eps)
-    if layers["fc"][0].shape != (2, 64):
-        raise QuantizationError(f"the int8 path has a Linear(64,2) classifier, got weights of shape {layers['fc'][0].shape}")
+    if "fc" not in layers or layers["fc"][0].shape != (2, 64):
+        shape = layers["fc"][0].shape if "fc" in layers else None
+        raise QuantizationError(f"the int8 path has a Linear(64,2) classifier, got weights of shape {shape}")
     s_x, z_x = input_qparams(x_min, x_max)
     arrays = {"input_scale": np.array([s_x], np.float32), "input_zero": np.array([z_x], np.int32)}
     scales = {"input": float(s_x)}
@@ -320,7 +322,7 @@ def lstm_tables():
 
 
 def _quantize_gates(arrays, name, wf, bf, s_in, acc_max):
-    """One weight matrix (4H, K) of a direction with its bias: per-row weights, the int32 bias with the refusal, and the
+    """One weight matrix (4H, K) of an LSTM direction, or (3H, K) of a GRU direction, with its bias: per-row weights, the int32 bias with the refusal, and the
     multiplier that brings the accumulator to Q8 gate pre-activations, m 2^-sh ~ s_in s_w 2^8."""
     if not np.isfinite(wf).all():
         raise QuantizationError(f"{name}: a weight is not finite")
@@ -364,4 +366,87 @@ def quantize_lstm(state: Dict[str, np.ndarray], lstm_args: dict, x_min: float, x
     arrays["fc.b"] = quantize_bias(st["fc.1.bias"], S_H, s_w, nd * H * 127 * 128, "classifier", unit="row")
     arrays["fc.scale"] = (S_H * s_w).astype(np.float32)
     arrays["tab.sigmoid"], arrays["tab.tanh"] = lstm_tables()
+    return arrays, scales
+
+
+GRU_MAX_LAYERS, GRU_MAX_CLASSES = 8, 64
+
+
+def check_crnn_args(crnn_args, num_classes=2):
+    """The limits of the CRNN int8 path: hidden size 128 (the implemented size of the GRU stack), 1..8 layers,
+    2 <= num_classes <= 64.  -> (num_layers, num_directions) as ints."""
+    H, L = int(crnn_args["hidden_size"]), int(crnn_args["num_layers"])
+    if H != LSTM_HIDDEN:
+        raise QuantizationError(f"the int8 CRNN implements hidden_size == {LSTM_HIDDEN}, got hidden_size {H}")
+    if not 1 <= L <= GRU_MAX_LAYERS:
+        raise QuantizationError(f"the int8 CRNN takes 1..{GRU_MAX_LAYERS} layers, got num_layers {L}")
+    if not 2 <= int(num_classes) <= GRU_MAX_CLASSES:
+        raise QuantizationError(f"the int8 CRNN takes 2..{GRU_MAX_CLASSES} classes, got num_classes {num_classes}")
+    return L, 2 if crnn_args["bidirectional"] else 1
+
+
+def quantize_gru_stack(arrays, st, prefix, input_size, num_layers, num_directions, s_in0):
+    """The GRU stack of the law's subsection "GRU" into ``arrays``: per layer and direction ``l{l}.{fwd|rev}.{ih,hh}.{w,b,m,sh}``
+    (gate rows r, z, n), then ``fc.*`` and ``tab.*``.  ``st``: float64 state; ``prefix``: where the stack lives in it (``gru.*`` and
+    ``fc.1.*`` below it); ``s_in0``: the scale of the layer-0 input.  Raises ``QuantizationError`` where the law refuses."""
+    H, nd = LSTM_HIDDEN, num_directions
+    for layer in range(num_layers):
+        K, s_in = (input_size, float(s_in0)) if layer == 0 else (nd * H, S_H)
+        for d in range(nd):
+            sfx, name = f"_l{layer}" + ("_reverse" if d else ""), f"l{layer}.{LSTM_DIRS[d]}"
+            for key, shape in ((f"{prefix}gru.weight_ih{sfx}", (3 * H, K)), (f"{prefix}gru.weight_hh{sfx}", (3 * H, H)),
+                               (f"{prefix}gru.bias_ih{sfx}", (3 * H,)), (f"{prefix}gru.bias_hh{sfx}", (3 * H,))):
+                if key not in st or st[key].shape != shape:
+                    raise QuantizationError(f"{key}: expected a tensor of shape {shape}")
+            _quantize_gates(arrays, name + ".ih", st[f"{prefix}gru.weight_ih{sfx}"], st[f"{prefix}gru.bias_ih{sfx}"], s_in, K * 127 * 255)
+            _quantize_gates(arrays, name + ".hh", st[f"{prefix}gru.weight_hh{sfx}"], st[f"{prefix}gru.bias_hh{sfx}"], S_H, H * 127 * 128)
+    fw, fb = st.get(prefix + "fc.1.weight"), st.get(prefix + "fc.1.bias")
+    if fw is None or fb is None or fw.ndim != 2 or fw.shape[1] != nd * H or fb.shape != (fw.shape[0],):
+        raise QuantizationError(f"{prefix}fc.1.weight: expected weights of shape (num_classes, {nd * H}) and their bias")
+    if not np.isfinite(fw).all():
+        raise QuantizationError("classifier: a weight is not finite")
+    q_w, s_w = quantize_weights(fw)
+    arrays["fc.w"] = q_w
+    arrays["fc.b"] = quantize_bias(fb, S_H, s_w, nd * H * 127 * 128, "classifier", unit="row")
+    arrays["fc.scale"] = (S_H * s_w).astype(np.float32)
+    arrays["tab.sigmoid"], arrays["tab.tanh"] = lstm_tables()
+
+
+def quantize_crnn(state: Dict[str, np.ndarray], crnn_args: dict, F: int, ranges: dict, eps: float = 1e-5):
+    """The arrays of an int8 CRNNWakeword bundle and its scales (the law's subsections "GRU" and "CRNN").  ``crnn_args``:
+    ``hidden_size``, ``num_layers``, ``bidirectional``; ``F``: the feature rows of the bundle; ``ranges``: ``x_min``, ``x_max``,
+    ``a_max`` (the nine conv maxima in ``CONVS`` order) and ``f_max`` (the maximum of the float front end's output sequence).
+    Arrays are unpadded: ``front.<conv>.{w,b,m,sh}``, ``fmean.{m,sh}``, the stack's, ``fc.*``, ``tab.*``."""
+    st = {k: np.asarray(v, np.float64) for k, v in state.items() if np.asarray(v).dtype.kind == "f"}
+    if "front.stem.conv.weight" not in st or "rnn.gru.weight_ih_l0" not in st or "rnn.fc.1.weight" not in st:
+        raise QuantizationError("the state holds no CRNNWakeword (front.stem.conv.weight, rnn.gru.weight_ih_l0, rnn.fc.1.weight)")
+    L, nd = check_crnn_args(crnn_args, st["rnn.fc.1.weight"].shape[0])
+    F = int(F)
+    if F < 1:
+        raise QuantizationError(f"the int8 CRNN takes a positive number of feature rows, got {F}")
+    a_max = list(ranges["a_max"])
+    if len(a_max) != len(CONVS):
+        raise QuantizationError(f"{len(a_max)} calibrated maxima for {len(CONVS)} convs")
+    layers = cnn_small_float_layers({k[len("front."):]: v for k, v in st.items() if k.startswith("front.")}, eps)
+    s_x, z_x = input_qparams(ranges["x_min"], ranges["x_max"])
+    arrays = {"input_scale": np.array([s_x], np.float32), "input_zero": np.array([z_x], np.int32)}
+    scales = {"input": float(s_x), "hidden": S_H}
+    s_in = float(s_x)
+    for name, am in zip(CONVS, a_max):
+        wf, bf = layers[name]
+        if not np.isfinite(wf).all():
+            raise QuantizationError(f"front.{name}: a weight is not finite")
+        q_w, s_w = quantize_weights(wf)
+        s_out = out_scale(am)
+        ms = [encode_multiplier(s_in * s_w[c] / s_out, f"front.{name}, channel {c}") for c in range(64)]
+        arrays[f"front.{name}.w"] = q_w
+        arrays[f"front.{name}.b"] = quantize_bias(bf, s_in, s_w, ACC_MAX_1X1 if name.startswith("pw") else ACC_MAX_3X3, "front." + name)
+        arrays[f"front.{name}.m"] = np.array([m for m, _ in ms], np.int32)
+        arrays[f"front.{name}.sh"] = np.array([s for _, s in ms], np.int32)
+        scales["front." + name] = s_out
+        s_in = s_out
+    s_f = out_scale(ranges["f_max"])
+    _one_multiplier(arrays, "fmean", s_in / (((F + 1) // 2) * s_f))
+    scales["fmean"] = s_f
+    quantize_gru_stack(arrays, st, "rnn.", 64, L, nd, s_f)
     return arrays, scales

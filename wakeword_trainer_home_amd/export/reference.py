@@ -9,7 +9,8 @@ bundle to another runtime can be checked against it, tensor by tensor.  It runs 
 
 ``run_int8`` dispatches on the header's architecture: ``cnn_small`` (NHWC tensors), ``TCNWakeword`` (``run_int8_tcn``: (B,T,C)
 tensors ``xq``, each block's ``b{i}.h1``, ``b{i}.h2``, ``b{i}.out``, then ``pool`` and ``logits`` (B,num_classes)),
-``ResNet18Wakeword`` (``run_int8_resnet18``) or ``LSTMWakeword`` (``run_int8_lstm``: any number of frames T).
+``ResNet18Wakeword`` (``run_int8_resnet18``), ``LSTMWakeword`` (``run_int8_lstm``: any number of frames T) or ``crnn``
+(``run_int8_crnn``: cnn_small's conv stack, the frequency mean, a GRU stack -- ``run_int8_gru_stack`` --; any T).
 """
 import json
 
@@ -311,10 +312,100 @@ def run_int8_lstm(header, arrays, x, want_acc=False):
     return out
 
 
+GRU_GATES = 3                          # gate rows of a GRU direction: r, z, n, 3 H in all
+
+
+def gru_stack_stages(args):
+    """Per layer and direction ``l{l}.{fwd|rev}.u``, ``.y`` and ``.h``."""
+    dirs = LSTM_DIRS if args["bidirectional"] else LSTM_DIRS[:1]
+    return [f"l{k}.{d}.{s}" for k in range(int(args["num_layers"])) for d in dirs for s in ("u", "y", "h")]
+
+
+def crnn_stages(crnn):
+    return ["xq"] + ["front." + c for c in CONVS] + ["seq"] + gru_stack_stages(crnn) + ["hcat", "logits"]
+
+
+def run_int8_gru_stack(arrays, q_in, z_in, args):
+    """The GRU stack of the law's subsection "GRU" on int8 rows ``q_in`` (B,T,K) with zero point ``z_in``; ``args``:
+    ``num_layers``, ``bidirectional``.  -> ({``l{l}.{fwd|rev}.u`` (B,T,384) int16 (the input projection in Q8, gate order r, z, n),
+    ``.y`` (B,T,128) int8 (q_h at every step, in time order), ``.h`` (B,128) int16 (h16 after the direction's last step)},
+    hcat (B, nd 128) int8)."""
+    a, out, H = arrays, {}, LSTM_HIDDEN
+    dirs = LSTM_DIRS if args["bidirectional"] else LSTM_DIRS[:1]
+    sig, tanh = a["tab.sigmoid"], a["tab.tanh"]
+    L = int(args["num_layers"])
+    q_in, z_in = np.asarray(q_in), int(z_in)
+    B, T, _ = q_in.shape
+    hcat = []
+    for k in range(L):
+        ys = []
+        for d in dirs:
+            p = f"l{k}.{d}"
+            acc = _wrap32(_exact_matmul(q_in.astype(np.int64) - z_in, a[p + ".ih.w"]) + a[p + ".ih.b"].astype(np.int64))
+            u = np.clip(round_shift(acc, a[p + ".ih.m"], a[p + ".ih.sh"]), -32768, 32767)
+            y = np.zeros((B, T, H), np.int8)
+            q_h, h16 = np.zeros((B, H), np.int64), np.zeros((B, H), np.int64)
+            for t in (range(T) if d == "fwd" else range(T - 1, -1, -1)):
+                acc = _wrap32(_exact_matmul(q_h, a[p + ".hh.w"]) + a[p + ".hh.b"].astype(np.int64))
+                v = round_shift(acc, a[p + ".hh.m"], a[p + ".hh.sh"])
+                r, z = look(sig, u[:, t, :H] + v[:, :H]), look(sig, u[:, t, H:2 * H] + v[:, H:2 * H])
+                n = look(tanh, u[:, t, 2 * H:] + ((r * v[:, 2 * H:] + 2 ** 14) >> 15))
+                h16 = ((32768 - z) * n + z * h16 + 2 ** 14) >> 15
+                q_h = np.clip((h16 + 128) >> 8, -128, 127)
+                y[:, t] = q_h
+            out[p + ".u"], out[p + ".y"], out[p + ".h"] = u.astype(np.int16), y, h16.astype(np.int16)
+            ys.append(y)
+            if k == L - 1:
+                hcat.append(y[:, T - 1] if d == "fwd" else y[:, 0])
+        q_in, z_in = np.concatenate(ys, axis=2), 0
+    return out, np.concatenate(hcat, axis=1)
+
+
+def run_int8_crnn(header, arrays, x, want_acc=False):
+    """Every stage of an int8 CRNNWakeword bundle on (B,1,F,T) or (B,F,T) features, F the bundle's, any T >= 1: ``xq`` (B,F,T)
+    int8; the nine conv tensors ``front.<conv>`` (B,H',W',64) int8 NHWC; ``seq`` (B,W',64) int8, the frequency mean; the GRU stack's
+    tensors (``run_int8_gru_stack``); ``hcat``; ``logits`` float32.  With ``want_acc`` also ``acc/front.<conv>``."""
+    x = np.asarray(x, np.float32)
+    if x.ndim == 4 and x.shape[1] == 1:
+        x = x[:, 0]
+    F = int(header["feature_shape"][0])
+    if x.ndim != 3 or x.shape[1] != F or x.shape[2] < 1:
+        raise ValueError(f"this bundle is for features of shape (B,1,{F},T), got {tuple(x.shape)}")
+    a, out = arrays, {}
+    z_x = int(a["input_zero"][0])
+    q = quantize_input(x, a["input_scale"][0], z_x)
+    out["xq"] = q
+    q, zero = q[..., None], z_x
+    for name in CONVS:
+        w = a[f"front.{name}.w"]
+        if name == "stem":
+            acc = _conv3x3(q, zero, w, 2)
+        elif name.startswith("dw"):
+            acc = _conv3x3(q, zero, w, 1)
+        else:
+            acc = (q.astype(np.int64) - zero) @ w.astype(np.int64).T
+        acc = _wrap32(acc + a[f"front.{name}.b"].astype(np.int64))
+        q, zero = requantize(acc, a[f"front.{name}.m"], a[f"front.{name}.sh"]), -128
+        out["front." + name] = q
+        if want_acc:
+            out["acc/front." + name] = acc
+    S = _wrap32((q.astype(np.int64) + 128).sum(axis=1))                  # over the frequency axis H': (B,W',64)
+    seq = requantize(S, a["fmean.m"][0], a["fmean.sh"][0])
+    out["seq"] = seq
+    stack, hcat = run_int8_gru_stack(a, seq, -128, header["crnn"])
+    out.update(stack)
+    out["hcat"] = hcat
+    acc = _wrap32(_exact_matmul(hcat, a["fc.w"]) + a["fc.b"].astype(np.int64))
+    out["logits"] = acc.astype(np.float32) * a["fc.scale"].astype(np.float32)
+    return out
+
+
 def run_int8(header, arrays, x, want_acc=False):
     """Every stage of the int8 network on features ``x``, by the bundle's architecture.  ``cnn_small``: dict of STAGES (int8
     NHWC tensors, ``pool`` (B,64), ``logits``); ``TCNWakeword``: ``run_int8_tcn``; ``ResNet18Wakeword``: ``run_int8_resnet18``;
-    ``LSTMWakeword``: ``run_int8_lstm``.  ``want_acc`` adds the accumulators."""
+    ``LSTMWakeword``: ``run_int8_lstm``; ``crnn``: ``run_int8_crnn``.  ``want_acc`` adds the accumulators."""
+    if header.get("architecture") == "crnn":
+        return run_int8_crnn(header, arrays, x, want_acc)
     if header.get("architecture") == "LSTMWakeword":
         return run_int8_lstm(header, arrays, x, want_acc)
     if header.get("architecture") == "TCNWakeword":

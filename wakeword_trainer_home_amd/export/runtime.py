@@ -1,5 +1,6 @@
-"""``QuantizedCNNSmall``, ``QuantizedTCN``, ``QuantizedResNet18`` and ``QuantizedLSTM``: an int8 bundle on the device, run with
-integer arithmetic only (``ww_q8_cnn_small_fwd``, ``ww_tq8_tcn_fwd``, ``ww_rq8_resnet18_fwd``, ``ww_lq8_lstm_fwd``)."""
+"""``QuantizedCNNSmall``, ``QuantizedTCN``, ``QuantizedResNet18``, ``QuantizedLSTM`` and ``QuantizedCRNN``: an int8 bundle on the
+device, run with integer arithmetic only (``ww_q8_cnn_small_fwd``, ``ww_tq8_tcn_fwd``, ``ww_rq8_resnet18_fwd``, ``ww_lq8_lstm_fwd``,
+``ww_cq8_crnn_fwd``)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -312,6 +313,102 @@ class QuantizedLSTM(nn.Module):
                                                 dtype=torch.uint8, device=dev)
         logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
         nat.lq8_lstm_fwd(self._table(), self.io, x, ws, logits)
+        return logits
+
+
+def device_gru_layer(arrays: dict, layer: int, num_directions: int, z_in: int):
+    """The eight tensors of one GRU layer as ``ww_lq8_proj_fwd`` and ``ww_cq8_gru_layer_fwd`` read them, the directions stacked
+    (forward first): w_ih (nd*384, Kp) with zero pad columns, its EFFECTIVE bias, mult, shift; w_hh (nd*384, 128), the law's q_bh,
+    mult, shift."""
+    return device_lstm_layer(arrays, layer, num_directions, z_in)       # the layout does not depend on the gate count
+
+
+class QuantizedCRNN(nn.Module):
+    """An int8 ``CRNNWakeword`` bundle on the device: ``forward((B,1,F,T) float32) -> (B,num_classes) float32`` is one native
+    call (``ww_cq8_crnn_fwd``) on the current stream, no host synchronisation.  Eval only, no parameters.  The bundle is for ONE
+    number of feature rows F (the frequency-mean multiplier holds 1/H'); it takes any T >= 1."""
+
+    hip_backed = True
+
+    def __init__(self, header: dict, arrays: dict):
+        super().__init__()
+        check_bundle(header, arrays)
+        if header["kind"] != "int8" or header["architecture"] != "crnn":
+            raise ValueError(f"QuantizedCRNN needs an int8 crnn bundle, got kind {header['kind']!r} of {header['architecture']!r}")
+        self.header = dict(header)
+        e = header["crnn"]
+        self.feature_rows, self.num_layers = int(header["feature_shape"][0]), int(e["num_layers"])
+        self.num_directions, self.hidden_size = 2 if e["bidirectional"] else 1, LSTM_HIDDEN
+        self.num_classes = int(header["num_classes"])
+        z_x = int(arrays["input_zero"][0])
+        self.io = nat.Cq8Io(float(arrays["input_scale"][0]), z_x, int(arrays["fmean.m"][0]), int(arrays["fmean.sh"][0]),
+                            self.num_layers, self.num_directions, self.num_classes)
+        front = {k[len("front."):]: v for k, v in arrays.items() if k.startswith("front.")}
+        self._names = []
+        for name in CONVS:
+            for suffix, a in zip(("w", "b", "m", "sh"), device_conv(front, name, z_x if name == "stem" else -128)):
+                self._add(f"{name}_{suffix}", a)
+        for k in range(self.num_layers):
+            tensors = device_gru_layer(arrays, k, self.num_directions, -128 if k == 0 else 0)
+            for suffix, a in zip(("ih_w", "ih_b", "ih_m", "ih_sh", "hh_w", "hh_b", "hh_m", "hh_sh"), tensors):
+                self._add(f"l{k}_{suffix}", a)
+        for key in ("fc.w", "fc.b", "fc.scale", "tab.sigmoid", "tab.tanh"):
+            self._add(key.replace(".", "_"), arrays[key])
+        assert len(self._names) == nat.CQ8_CONV_NPTR + nat.CQ8_LAYER_NPTR * self.num_layers + nat.CQ8_TAIL_NPTR
+        self._tab, self._key, self._ws = None, None, {}
+        self.eval()
+
+    def _add(self, name, a):
+        self.register_buffer(name, torch.from_numpy(np.ascontiguousarray(a).copy()), persistent=False)
+        self._names.append(name)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise RuntimeError("QuantizedCRNN is an inference network: it has no training mode")
+        return super().train(False)
+
+    def conv(self, name):
+        """(w, bias_eff, mult, shift) of one conv of the front end, for the per-layer entry points."""
+        return tuple(getattr(self, f"{name}_{s}") for s in ("w", "b", "m", "sh"))
+
+    def layer(self, k):
+        """(w_ih, bias_eff, mult, shift, w_hh, bias, mult, shift) of GRU layer ``k``, for the per-kernel entry points."""
+        return tuple(getattr(self, f"l{k}_{s}") for s in ("ih_w", "ih_b", "ih_m", "ih_sh", "hh_w", "hh_b", "hh_m", "hh_sh"))
+
+    def _table(self):
+        tensors = [getattr(self, n) for n in self._names]
+        key = tuple(t.data_ptr() for t in tensors)
+        if self._key != key:
+            self._tab, self._key = nat.ptr_array(tensors), key
+        return self._tab
+
+    def workspace(self, B, T):
+        """The uint8 workspace of the last forward at this batch size and length (``_native.cq8_workspace_views`` names its
+        parts)."""
+        return self._ws[(B, T)]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        F = self.feature_rows
+        if x.dim() == 4 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 3 or x.shape[1] != F:
+            raise ValueError(f"this int8 bundle is for features of shape (B,1,{F},T), got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"features must be float32, got {x.dtype}")
+        if x.shape[0] < 1 or x.shape[2] < 1:
+            raise ValueError(f"an empty batch or sequence: {tuple(x.shape)}")
+        dev = nat._dev(x, self.fc_w)
+        if not x.is_contiguous() or x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.contiguous_format)
+        B, T = x.shape[0], x.shape[2]
+        ws = self._ws.get((B, T))
+        if ws is None or ws.device != dev:
+            if len(self._ws) >= 4:                                 # T is free: keep a few shapes, not every one ever seen
+                self._ws.clear()
+            ws = self._ws[(B, T)] = torch.empty(nat.cq8_crnn_workspace_bytes(B, F, T, self.num_layers, self.num_directions),
+                                                dtype=torch.uint8, device=dev)
+        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
+        nat.cq8_crnn_fwd(self._table(), self.io, x, ws, logits)
         return logits
 
 
