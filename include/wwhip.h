@@ -1106,6 +1106,69 @@ size_t ww_cq8_crnn_workspace_bytes(int B, int F, int T, int num_layers, int num_
 int ww_cq8_crnn_fwd(ww_ctx *ctx, const void *const *tab, const ww_cq8_io *io, const float *x, int B, int F, int T, void *ws,
                     size_t ws_bytes, float *logits, ww_stream_t stream);
 
+/* ------------------------------------------------------------------ int8 inference of a MobileNetV3Wakeword bundle (ww_q8_mobilenet.hip)
+ * The int8 law's subsection "MobileNetV3" (DESIGN.md 5.6).  Activations are int8 NHWC (B,H,W,Cp), Cp = the channel count rounded up
+ * to 64; pad channels hold the tensor's zero point and meet zero weights, pad OUTPUT channels have zero weights, a zero bias, mult 2^30
+ * and shift 31, so they come out as the zero point of the tensor written.  Conv bias arguments are the EFFECTIVE bias
+ * q_b - z_in * sum(q_w); the squeeze-excitation's and classifier.3's are the law's q_b.  Epilogues, R as everywhere:
+ *   WW_MQ8_RELU:   out = clamp(-128 + R(acc, mult, shift), -128, 127)
+ *   WW_MQ8_HSWISH: u = clamp(zero_u + R(acc, mult, shift), -128, 127), out = tab[u + 128]          (tab: the layer's int8 table, 256)
+ *   WW_MQ8_SIGNED: out = clamp(R(acc, mult, shift) [+ R(residual, res_mult, res_shift)], -128, 127) (z_out = 0; residual (N, Cout), z = 0)
+ * conv1x1: in (N, Cin), w (Cout, Cin), a GEMM on v_mfma_i32_16x16x64_i8, persistent under the grid cap; rows are pixels of the whole batch.
+ * dwconv: w (k k, Cp) [tap][channel], k = 3 or 5, stride 1 or 2, pad k / 2, output (n - 1) / 2 + 1 at stride 2; window positions outside
+ * the image read as `zero`.  stem: xq (B,F,T) -> (B,(F-1)/2+1,(T-1)/2+1,Cp), 3x3 stride 2 pad 1, w (9, Cp), Hardswish epilogue.
+ * se: one workgroup per image -- pool = clamp(zero + R(sum_hw (q - zero), pool_mult, pool_shift)) (B, Cp), h = fc1 + ReLU (B, Csq),
+ * gate = clamp(R(fc2 acc, m2, sh2), 0, 255) uint8 (B, Cp), pad gates 0; w1 (Csq, C), w2 (C, Csq) unpadded.
+ * gate: y = clamp(zero + R((q - zero) * gate, gate_mult, gate_shift), -128, 127) -- the PASS form of the gate multiply.  The FUSED form:
+ * conv1x1 with `gate` (N / HW, Cin) applies the same expression to the pixel fragments it loads (signed epilogue only), so `in` is the
+ * un-gated tensor and no y is stored; both forms give the same bits.  The whole forward picks by WW_MQ8_GATE=pass | fused in the
+ * environment, read at every call (default: pass); in the fused form the workspace's y tensors are not written.
+ * head: in (B, HW, 576) -> pool (B, 576), hidden (B, 1024) = classifier.0 under the Hardswish epilogue (w0 (1024, 576), effective
+ * bias), logits[c] = float(sum w[c] (hidden - zero_h) + fc_bias[c]) * fc_scale[c].
+ * The whole model: tab = WW_MQ8_NPTR device pointers [stem w, bias, mult, shift, tab] + 11 x [expand w, bias, mult, shift, tab,
+ * dw w, bias, mult, shift, tab, fc1 w, b, m, sh, fc2 w, b, m, sh, project w, bias, mult, shift] + [last w, bias, mult, shift, tab,
+ * cls0 w, bias, mult, shift, tab, fc w, bias, scale]; entries a block does not have (no expand conv, no squeeze-excitation, the table
+ * of a ReLU layer) are NULL.  The workspace keeps every tensor the launches write, each at a 256-byte boundary, in the order xq, stem,
+ * per block [expand], dw, [pool, h, gate, y], out, then last, pool, hidden. */
+#define WW_MQ8_BLOCKS 11
+#define WW_MQ8_BLOCK_NPTR 22
+#define WW_MQ8_NPTR 260
+#define WW_MQ8_LAST 576
+#define WW_MQ8_HIDDEN 1024
+#define WW_MQ8_RELU 0
+#define WW_MQ8_HSWISH 1
+#define WW_MQ8_SIGNED 2
+typedef struct {
+    float in_scale;
+    int32_t in_zero, num_classes;
+    int32_t stem_zu, stem_zo, last_zu, last_zo, cls_zu, cls_zo;   /* zero points of the Hardswish pre-activations and outputs */
+    int32_t pool_mult, pool_shift;
+    int32_t exp_zu[WW_MQ8_BLOCKS], exp_zo[WW_MQ8_BLOCKS], dw_zu[WW_MQ8_BLOCKS], dw_zo[WW_MQ8_BLOCKS];
+    int32_t sepool_mult[WW_MQ8_BLOCKS], sepool_shift[WW_MQ8_BLOCKS], gate_mult[WW_MQ8_BLOCKS], gate_shift[WW_MQ8_BLOCKS];
+    int32_t res_mult[WW_MQ8_BLOCKS], res_shift[WW_MQ8_BLOCKS];
+} ww_mq8_io;
+int ww_mq8_conv1x1_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, const int32_t *bias, const int32_t *mult, const int32_t *shift,
+                       long N, int Cin, int Cout, int zero, int epilogue, int zero_u, const int8_t *tab, const int8_t *residual,
+                       int res_mult, int res_shift, const uint8_t *gate /* nullable */, int HW, int gate_mult, int gate_shift, int8_t *out,
+                       ww_stream_t stream);
+int ww_mq8_dwconv_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, const int32_t *bias, const int32_t *mult, const int32_t *shift,
+                      int B, int H, int W, int Cp, int k, int stride, int zero, int epilogue, int zero_u, const int8_t *tab, int8_t *out,
+                      ww_stream_t stream);
+int ww_mq8_stem_fwd(ww_ctx *ctx, const int8_t *xq, const int8_t *w, const int32_t *bias, const int32_t *mult, const int32_t *shift,
+                    int B, int F, int T, int Cp, int zero, int zero_u, const int8_t *tab, int8_t *out, ww_stream_t stream);
+int ww_mq8_se_fwd(ww_ctx *ctx, const int8_t *in, int B, int HW, int C, int Cp, int Csq, int zero, int pool_mult, int pool_shift,
+                  const int8_t *w1, const int32_t *b1, const int32_t *m1, const int32_t *sh1, const int8_t *w2, const int32_t *b2,
+                  const int32_t *m2, const int32_t *sh2, int8_t *pool_out, int8_t *h_out, uint8_t *gate_out, ww_stream_t stream);
+int ww_mq8_gate_fwd(ww_ctx *ctx, const int8_t *in, const uint8_t *gate, int B, int HW, int Cp, int zero, int gate_mult, int gate_shift,
+                    int8_t *out, ww_stream_t stream);
+int ww_mq8_head_fwd(ww_ctx *ctx, const int8_t *in, int B, int HW, int zero, int pool_mult, int pool_shift, const int8_t *w0,
+                    const int32_t *b0, const int32_t *m0, const int32_t *sh0, int zero_u, const int8_t *tab, int zero_h,
+                    const int8_t *fc_w, const int32_t *fc_bias, const float *fc_scale, int num_classes, int8_t *pool_out,
+                    int8_t *hidden_out, float *logits, ww_stream_t stream);
+size_t ww_mq8_mobilenetv3_workspace_bytes(int B, int F, int T);
+int ww_mq8_mobilenetv3_fwd(ww_ctx *ctx, const void *const *tab, const ww_mq8_io *io, const float *x, int B, int F, int T, void *ws,
+                           size_t ws_bytes, float *logits, ww_stream_t stream);
+
 /* ------------------------------------------------------------------ collectives: deliberately NOT in this ABI
  * SURVEY.md §8b sketched two more entry points, `ww_comm_init` (ctx, nccl_unique_id, rank, world) and `ww_allreduce_f32`
  * (ctx, buf, n, avg, comm_stream).

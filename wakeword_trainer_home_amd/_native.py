@@ -164,6 +164,17 @@ class Cq8Io(C.Structure):
                 ("num_layers", C.c_int32), ("num_directions", C.c_int32), ("num_classes", C.c_int32)]
 
 
+MQ8_BLOCKS, MQ8_BLOCK_NPTR, MQ8_NPTR, MQ8_LAST, MQ8_HIDDEN, MQ8_RELU, MQ8_HSWISH, MQ8_SIGNED = 11, 22, 260, 576, 1024, 0, 1, 2
+
+
+class Mq8Io(C.Structure):
+    """ww_mq8_io: the scalars of an int8 MobileNetV3Wakeword bundle (include/wwhip.h)."""
+    _fields_ = [("in_scale", C.c_float), ("in_zero", C.c_int32), ("num_classes", C.c_int32)] + \
+               [(k, C.c_int32) for k in ("stem_zu", "stem_zo", "last_zu", "last_zo", "cls_zu", "cls_zo", "pool_mult", "pool_shift")] + \
+               [(k, C.c_int32 * MQ8_BLOCKS) for k in ("exp_zu", "exp_zo", "dw_zu", "dw_zo", "sepool_mult", "sepool_shift", "gate_mult",
+                                                      "gate_shift", "res_mult", "res_shift")]
+
+
 _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 _SIGS = {
     "ww_abi_version": (C.c_int, []),
@@ -327,6 +338,14 @@ _SIGS = {
     "ww_cq8_gru_layer_fwd": (C.c_int, [_vp] * 8 + [_i, _i, _i, _vp, _vp, _vp]),
     "ww_cq8_crnn_workspace_bytes": (_sz, [_i] * 5),
     "ww_cq8_crnn_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Cq8Io), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "ww_mq8_conv1x1_fwd": (C.c_int, [_vp] * 6 + [C.c_long] + [_i] * 5 + [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "ww_mq8_dwconv_fwd": (C.c_int, [_vp] * 6 + [_i] * 9 + [_vp, _vp, _vp]),
+    "ww_mq8_stem_fwd": (C.c_int, [_vp] * 6 + [_i] * 6 + [_vp, _vp, _vp]),
+    "ww_mq8_se_fwd": (C.c_int, [_vp, _vp] + [_i] * 8 + [_vp] * 12),
+    "ww_mq8_gate_fwd": (C.c_int, [_vp, _vp, _vp] + [_i] * 6 + [_vp, _vp]),
+    "ww_mq8_head_fwd": (C.c_int, [_vp, _vp] + [_i] * 5 + [_vp] * 4 + [_i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ww_mq8_mobilenetv3_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ww_mq8_mobilenetv3_fwd": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(Mq8Io), _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "ww_prof_num_classes": (C.c_int, []),
     "ww_prof_class_name": (C.c_char_p, [_i]),
     "ww_ctx_set_deferred_reduce": (C.c_int, [_vp, _i]),
@@ -2678,6 +2697,169 @@ def cq8_workspace_views(ws, B, F, T, num_layers, num_directions):
         out[f"l{k}.h"] = i8[off:off + B * nd * 256].view(torch.int16).view(B, nd * 128)
         off += r256(B * nd * 256)
     out["hcat"] = i8[off:off + B * nd * 128].view(B, nd * 128)
+    return out
+
+
+# ---- int8 inference of an exported MobileNetV3Wakeword bundle (ww_q8_mobilenet.hip).  Activations are int8 NHWC (B,H,W,Cp), Cp the
+# channel count rounded up to 64; conv arguments are (w, bias_eff, mult, shift[, tab]) as include/wwhip.h lays them out.
+def _mq8_conv_check(what, w, bias, mult, shift, tab, epilogue):
+    n = w.shape[0 if what == "conv1x1" else -1]
+    if w.dtype != torch.int8 or any(t.dtype != torch.int32 or t.numel() != n for t in (bias, mult, shift)):
+        raise ValueError(f"mq8_{what}_fwd: w int8, bias / mult / shift int32, one per output channel")
+    if (tab is not None) != (epilogue == MQ8_HSWISH) or (tab is not None and (tab.dtype != torch.int8 or tab.numel() != 256)):
+        raise ValueError(f"mq8_{what}_fwd: the Hardswish epilogue, and only it, takes an int8 table of 256 entries")
+
+
+def mq8_conv1x1_fwd(a, w, bias, mult, shift, zero=-128, epilogue=MQ8_RELU, zero_u=0, tab=None, residual=None, res_mult=0, res_shift=0,
+                    gate=None, gate_mult=0, gate_shift=0):
+    """a int8 (..., Cin) -> (..., Cout); w int8 (Cout, Cin), both multiples of 64.  ``residual`` (..., Cout) with its multiplier and
+    shift goes with MQ8_SIGNED: the projection conv carrying the block's skip connection.  ``gate`` uint8 (B, Cin) with a (B,H,W,Cin)
+    selects the fused gate form: the conv reads clamp(zero + R((a - zero) gate, gate_mult, gate_shift)) in place of a."""
+    dev = _dev(a, w, bias, mult, shift, tab, residual, gate)
+    if gate is not None and (a.dim() != 4 or gate.dtype != torch.uint8 or tuple(gate.shape) != (a.shape[0], a.shape[3])):
+        raise ValueError("mq8_conv1x1_fwd: the fused gate form takes a (B,H,W,Cin) and gate uint8 (B,Cin)")
+    if a.dtype != torch.int8 or a.shape[-1] % 64 or w.dim() != 2 or w.shape[1] != a.shape[-1] or w.shape[0] % 64:
+        raise ValueError("mq8_conv1x1_fwd: int8 activations (..., Cin), w int8 (Cout, Cin), channel counts multiples of 64")
+    _mq8_conv_check("conv1x1", w, bias, mult, shift, tab, epilogue)
+    out = torch.empty((*a.shape[:-1], w.shape[0]), dtype=torch.int8, device=dev)
+    if residual is not None and (residual.dtype != torch.int8 or residual.shape != out.shape):
+        raise ValueError("mq8_conv1x1_fwd: residual int8 of the output's shape")
+    with _guard(dev):
+        _check(load().ww_mq8_conv1x1_fwd(ctx(dev), _p(a), _p(w), _p(bias), _p(mult), _p(shift), a.numel() // a.shape[-1], a.shape[-1],
+                                         w.shape[0], int(zero), int(epilogue), int(zero_u), _p(tab), _p(residual), int(res_mult),
+                                         int(res_shift), _p(gate), a.shape[1] * a.shape[2] if gate is not None else 0, int(gate_mult),
+                                         int(gate_shift), _p(out), _stream(dev)), "ww_mq8_conv1x1_fwd")
+    return out
+
+
+def mq8_dwconv_fwd(a, w, bias, mult, shift, k, stride, zero=-128, epilogue=MQ8_RELU, zero_u=0, tab=None):
+    """a int8 (B,H,W,Cp); w int8 (k*k, Cp) [tap][channel]."""
+    dev = _dev(a, w, bias, mult, shift, tab)
+    if a.dtype != torch.int8 or a.dim() != 4 or a.shape[3] % 16 or tuple(w.shape) != (k * k, a.shape[3]):
+        raise ValueError("mq8_dwconv_fwd: int8 activations (B,H,W,Cp), Cp a multiple of 16, w int8 (k*k, Cp)")
+    _mq8_conv_check("dwconv", w, bias, mult, shift, tab, epilogue)
+    B, H, W, Cp = a.shape
+    Ho, Wo = (rq8_half(H), rq8_half(W)) if stride == 2 else (H, W)
+    out = torch.empty((B, Ho, Wo, Cp), dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_mq8_dwconv_fwd(ctx(dev), _p(a), _p(w), _p(bias), _p(mult), _p(shift), B, H, W, Cp, int(k), int(stride), int(zero),
+                                        int(epilogue), int(zero_u), _p(tab), _p(out), _stream(dev)), "ww_mq8_dwconv_fwd")
+    return out
+
+
+def mq8_stem_fwd(xq, w, bias, mult, shift, zero, zero_u, tab):
+    """xq int8 (B,F,T); w int8 (9, Cp) [tap][channel] -> (B,(F-1)//2+1,(T-1)//2+1,Cp), the Hardswish epilogue."""
+    dev = _dev(xq, w, bias, mult, shift, tab)
+    if xq.dtype != torch.int8 or xq.dim() != 3 or w.dim() != 2 or w.shape[0] != 9 or w.shape[1] % 16:
+        raise ValueError("mq8_stem_fwd: int8 (B,F,T) features, w int8 (9, Cp), Cp a multiple of 16")
+    _mq8_conv_check("stem", w, bias, mult, shift, tab, MQ8_HSWISH)
+    B, F, T = xq.shape
+    out = torch.empty((B, rq8_half(F), rq8_half(T), w.shape[1]), dtype=torch.int8, device=dev)
+    with _guard(dev):
+        _check(load().ww_mq8_stem_fwd(ctx(dev), _p(xq), _p(w), _p(bias), _p(mult), _p(shift), B, F, T, w.shape[1], int(zero), int(zero_u),
+                                      _p(tab), _p(out), _stream(dev)), "ww_mq8_stem_fwd")
+    return out
+
+
+def mq8_se_fwd(a, C_real, zero, pool_mult, pool_shift, fc1, fc2):
+    """a int8 (B,H,W,Cp) with ``C_real`` channels; ``fc1`` = (w (Csq,C), q_b, mult, shift), ``fc2`` = (w (C,Csq), q_b, mult, shift), the
+    law's own biases -> (pool int8 (B,Cp), h int8 (B,Csq), gate uint8 (B,Cp))."""
+    dev = _dev(a, *fc1, *fc2)
+    if a.dtype != torch.int8 or a.dim() != 4 or a.shape[3] != tq8_pad(C_real):
+        raise ValueError("mq8_se_fwd: int8 activations (B,H,W,Cp), Cp = C rounded up to 64")
+    Csq = fc1[0].shape[0]
+    if tuple(fc1[0].shape) != (Csq, C_real) or tuple(fc2[0].shape) != (C_real, Csq) or fc1[0].dtype != torch.int8 or \
+            fc2[0].dtype != torch.int8 or any(t.dtype != torch.int32 or t.numel() != n for ts, n in ((fc1[1:], Csq), (fc2[1:], C_real)) for t in ts):
+        raise ValueError("mq8_se_fwd: fc1 (w int8 (Csq,C), b / m / sh int32 (Csq)), fc2 (w int8 (C,Csq), b / m / sh int32 (C))")
+    B, H, W, Cp = a.shape
+    pool = torch.empty((B, Cp), dtype=torch.int8, device=dev)
+    h = torch.empty((B, Csq), dtype=torch.int8, device=dev)
+    gate = torch.empty((B, Cp), dtype=torch.uint8, device=dev)
+    with _guard(dev):
+        _check(load().ww_mq8_se_fwd(ctx(dev), _p(a), B, H * W, int(C_real), Cp, Csq, int(zero), int(pool_mult), int(pool_shift),
+                                    *[_p(t) for t in fc1], *[_p(t) for t in fc2], _p(pool), _p(h), _p(gate), _stream(dev)), "ww_mq8_se_fwd")
+    return pool, h, gate
+
+
+def mq8_gate_fwd(a, gate, zero, gate_mult, gate_shift):
+    dev = _dev(a, gate)
+    if a.dtype != torch.int8 or a.dim() != 4 or a.shape[3] % 16 or gate.dtype != torch.uint8 or tuple(gate.shape) != (a.shape[0], a.shape[3]):
+        raise ValueError("mq8_gate_fwd: int8 activations (B,H,W,Cp), gate uint8 (B,Cp)")
+    out = torch.empty_like(a)
+    with _guard(dev):
+        _check(load().ww_mq8_gate_fwd(ctx(dev), _p(a), _p(gate), a.shape[0], a.shape[1] * a.shape[2], a.shape[3], int(zero), int(gate_mult),
+                                      int(gate_shift), _p(out), _stream(dev)), "ww_mq8_gate_fwd")
+    return out
+
+
+def mq8_head_fwd(a, zero, pool_mult, pool_shift, cls0, zero_u, tab, zero_h, fc_w, fc_bias, fc_scale):
+    """a int8 (B,H,W,576); ``cls0`` = (w (1024,576), bias_eff, mult, shift) -> (pool int8 (B,576), hidden int8 (B,1024), logits)."""
+    dev = _dev(a, *cls0, tab, fc_w, fc_bias, fc_scale)
+    nc = fc_w.shape[0]
+    if a.dtype != torch.int8 or a.dim() != 4 or a.shape[3] != MQ8_LAST or tuple(cls0[0].shape) != (MQ8_HIDDEN, MQ8_LAST):
+        raise ValueError("mq8_head_fwd: int8 activations (B,H,W,576), classifier.0 weights int8 (1024,576)")
+    _mq8_conv_check("conv1x1", *cls0, tab, MQ8_HSWISH)
+    if (fc_w.dtype, fc_bias.dtype, fc_scale.dtype) != (torch.int8, torch.int32, torch.float32) or \
+            tuple(fc_w.shape) != (nc, MQ8_HIDDEN) or fc_bias.numel() != nc or fc_scale.numel() != nc:
+        raise ValueError("mq8_head_fwd: fc_w int8 (num_classes,1024), fc_bias int32 (num_classes), fc_scale float32 (num_classes)")
+    B = a.shape[0]
+    pool = torch.empty((B, MQ8_LAST), dtype=torch.int8, device=dev)
+    hidden = torch.empty((B, MQ8_HIDDEN), dtype=torch.int8, device=dev)
+    logits = torch.empty((B, nc), dtype=torch.float32, device=dev)
+    with _guard(dev):
+        _check(load().ww_mq8_head_fwd(ctx(dev), _p(a), B, a.shape[1] * a.shape[2], int(zero), int(pool_mult), int(pool_shift),
+                                      *[_p(t) for t in cls0], int(zero_u), _p(tab), int(zero_h), _p(fc_w), _p(fc_bias), _p(fc_scale), nc,
+                                      _p(pool), _p(hidden), _p(logits), _stream(dev)), "ww_mq8_head_fwd")
+    return pool, hidden, logits
+
+
+def mq8_mobilenetv3_workspace_bytes(B, F, T):
+    return load().ww_mq8_mobilenetv3_workspace_bytes(B, F, T)
+
+
+def mq8_mobilenetv3_fwd(tab, io: Mq8Io, x, ws, logits):
+    """``tab``: ``ptr_array`` of the MQ8_NPTR bundle tensors (None where a block has none); x float32 (B,F,T) or (B,1,F,T); ws uint8;
+    logits float32 (B,num_classes)."""
+    dev = _dev(x, ws, logits)
+    with _guard(dev):
+        _check(load().ww_mq8_mobilenetv3_fwd(ctx(dev), tab, C.byref(io), _p(x), x.shape[0], x.shape[-2], x.shape[-1], _p(ws),
+                                             ws.numel() * ws.element_size(), _p(logits), _stream(dev)), "ww_mq8_mobilenetv3_fwd")
+
+
+def mq8_workspace_views(ws, B, F, T):
+    """The tensors ww_mq8_mobilenetv3_fwd left in ``ws`` (uint8), by stage name, PADDED to 64 channels: xq (B,F,T), stem, per block
+    b{i}.expand (where the block has one), b{i}.dw, the squeeze-excitation's b{i}.pool (B,Cp), b{i}.h (B,Csq), b{i}.gate uint8 (B,Cp)
+    and b{i}.y, b{i}.out; last, pool (B,576), hidden (B,1024) -- the layout include/wwhip.h states."""
+    from .export.reference import mbv3_blocks
+    r256 = lambda n: (n + 255) // 256 * 256       # noqa: E731
+    i8 = ws.view(torch.int8)
+    out, off = {}, 0
+
+    def take(name, *shape):
+        nonlocal off
+        n = 1
+        for v in shape:
+            n *= v
+        out[name] = i8[off:off + n].view(*shape)
+        off += r256(n)
+    take("xq", B, F, T)
+    take("stem", B, rq8_half(F), rq8_half(T), 64)
+    blocks = mbv3_blocks(F, T)
+    for i, b in enumerate(blocks):
+        ep = tq8_pad(b["exp"])
+        if b["expand"]:
+            take(f"b{i}.expand", B, *b["hw_in"], ep)
+        take(f"b{i}.dw", B, *b["hw"], ep)
+        if b["se"]:
+            take(f"b{i}.pool", B, ep)
+            take(f"b{i}.h", B, b["se"])
+            take(f"b{i}.gate", B, ep)
+            out[f"b{i}.gate"] = out[f"b{i}.gate"].view(torch.uint8)
+            take(f"b{i}.y", B, *b["hw"], ep)
+        take(f"b{i}.out", B, *b["hw"], tq8_pad(b["cout"]))
+    take("last", B, *blocks[-1]["hw"], MQ8_LAST)
+    take("pool", B, MQ8_LAST)
+    take("hidden", B, MQ8_HIDDEN)
     return out
 
 

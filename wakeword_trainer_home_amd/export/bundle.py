@@ -5,7 +5,8 @@ from pathlib import Path
 
 import numpy as np
 
-from .reference import CONVS, FORMAT_NAME, FORMAT_VERSION, LSTM_DIRS, LSTM_HIDDEN, LSTM_TABLE, load_bundle, resnet_blocks  # noqa: F401  (load_bundle is re-exported)
+from .reference import (CONVS, FORMAT_NAME, FORMAT_VERSION, LSTM_DIRS, LSTM_HIDDEN, LSTM_TABLE, MBV3_HIDDEN, MBV3_LAST, MBV3_STEM,
+                        load_bundle, mbv3_blocks, resnet_blocks)  # noqa: F401  (load_bundle is re-exported)
 
 STATE_PREFIX = "state/"
 FP16_MAX = 65504.0
@@ -227,6 +228,56 @@ def _check_crnn(header, arrays):
         raise BundleError("fc.scale is not finite")
 
 
+def _check_mbv3_layer(arrays, p, cout, k_in, hs=False):
+    w = _need(arrays, p + ".w", np.int8, (cout, k_in))
+    if (w == -128).any():
+        raise BundleError(f"{p}.w holds -128: weights are symmetric, in [-127, 127]")
+    _need(arrays, p + ".b", np.int32, (cout,))
+    _check_mult(arrays, p, cout)
+    if hs:
+        _need(arrays, p + ".tab", np.int8, (256,))
+        for z in (".zu", ".zo"):
+            if not -128 <= int(_need(arrays, p + z, np.int32, (1,))[0]) <= 127:
+                raise BundleError(f"{p}{z} is outside int8")
+
+
+def _check_mbv3_pool(arrays, p, hw):
+    _check_mult(arrays, p, 1)
+    got = int(_need(arrays, p + ".hw", np.int32, (1,))[0])
+    if got != hw:
+        raise BundleError(f"{p}.hw is {got}: the feature_shape reduces to {hw} pixels there")
+
+
+def _check_mobilenetv3(header, arrays, fs):
+    nc = header["num_classes"]
+    if not (isinstance(nc, int) and not isinstance(nc, bool) and 2 <= nc <= 64):
+        raise BundleError(f"num_classes {nc!r} is outside [2, 64]")
+    _check_mbv3_layer(arrays, "stem", MBV3_STEM, 9, hs=True)
+    blocks = mbv3_blocks(*fs)
+    for i, b in enumerate(blocks):
+        p = f"b{i}."
+        if b["expand"]:
+            _check_mbv3_layer(arrays, p + "expand", b["exp"], b["cin"], b["hs"])
+        _check_mbv3_layer(arrays, p + "dw", b["exp"], b["k"] ** 2, b["hs"])
+        if b["se"]:
+            _check_mbv3_pool(arrays, p + "pool", b["hw"][0] * b["hw"][1])
+            _check_mbv3_layer(arrays, p + "fc1", b["se"], b["exp"])
+            _check_mbv3_layer(arrays, p + "fc2", b["exp"], b["se"])
+            _check_mult(arrays, p + "gate", 1)
+        _check_mbv3_layer(arrays, p + "project", b["cout"], b["exp"])
+        if b["res"]:
+            _check_mult(arrays, p + "res", 1)
+    _check_mbv3_layer(arrays, "last", MBV3_LAST, blocks[-1]["cout"], hs=True)
+    _check_mbv3_pool(arrays, "pool", blocks[-1]["hw"][0] * blocks[-1]["hw"][1])
+    _check_mbv3_layer(arrays, "cls0", MBV3_HIDDEN, MBV3_LAST, hs=True)
+    w = _need(arrays, "fc.w", np.int8, (nc, MBV3_HIDDEN))
+    if (w == -128).any():
+        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
+    _need(arrays, "fc.b", np.int32, (nc,))
+    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
+        raise BundleError("fc.scale is not finite")
+
+
 def check_bundle(header: dict, arrays: dict) -> None:
     """Raises ``BundleError`` unless the bundle is complete and every value is in the range its law gives it."""
     if not isinstance(header, dict) or header.get("format") != FORMAT_NAME:
@@ -250,9 +301,9 @@ def check_bundle(header: dict, arrays: dict) -> None:
         return
     if kind != "int8":
         raise BundleError(f"unknown bundle kind {kind!r}")
-    if header["architecture"] not in ("cnn_small", "crnn", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
-        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small, crnn, TCNWakeword, ResNet18Wakeword and "
-                          "LSTMWakeword have an int8 form")
+    if header["architecture"] not in ("cnn_small", "crnn", "mobilenetv3", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
+        raise BundleError(f"an int8 bundle of {header['architecture']!r}: only cnn_small, crnn, mobilenetv3, TCNWakeword, "
+                          "ResNet18Wakeword and LSTMWakeword have an int8 form")
     fs = header.get("feature_shape")
     if not (isinstance(fs, list) and len(fs) == 2 and all(isinstance(v, int) and v >= 1 for v in fs)):
         raise BundleError(f"feature_shape {fs!r} is not [F, T]")
@@ -270,6 +321,8 @@ def check_bundle(header: dict, arrays: dict) -> None:
         return _check_lstm(header, arrays, fs)
     if header["architecture"] == "crnn":
         return _check_crnn(header, arrays)
+    if header["architecture"] == "mobilenetv3":
+        return _check_mobilenetv3(header, arrays, fs)
     for name in CONVS:
         w = _need(arrays, name + ".w", np.int8, (64, 64 if name.startswith("pw") else 9))
         if (w == -128).any():

@@ -1,8 +1,9 @@
 """The reference's export panel (``src/export/onnx_exporter.py``) without ONNX: neither an ONNX writer nor a runtime exists
 on the build machine, so ``export`` writes self-describing bundles (``bundle.py``) instead -- fp32, fp16 (weights only, as
-the reference's ``QFloat16`` call) and int8 (``cnn_small``, ``crnn``, ``TCNWakeword``, ``ResNet18Wakeword`` and ``LSTMWakeword``; the
-law is DESIGN.md "Export") -- and the int8 bundle runs on the device with integer arithmetic (``runtime.QuantizedCNNSmall``,
-``runtime.QuantizedTCN``, ``runtime.QuantizedResNet18``, ``runtime.QuantizedLSTM``, ``runtime.QuantizedCRNN``).  Names,
+the reference's ``QFloat16`` call) and int8 (``cnn_small``, ``crnn``, ``mobilenetv3``, ``TCNWakeword``, ``ResNet18Wakeword`` and
+``LSTMWakeword``; the law is DESIGN.md "Export") -- and the int8 bundle runs on the device with integer arithmetic
+(``runtime.QuantizedCNNSmall``, ``runtime.QuantizedTCN``, ``runtime.QuantizedResNet18``, ``runtime.QuantizedLSTM``,
+``runtime.QuantizedCRNN``, ``runtime.QuantizedMobileNetV3``).  Names,
 signatures, result keys and failure behaviour are the reference's; ``ONNXExporter``, ``export_model_to_onnx``, ``validate_onnx_model`` and ``benchmark_onnx_model`` stay as
 aliases.  Parity with onnxruntime's ``quantize_dynamic`` is not claimed."""
 import logging
@@ -17,9 +18,9 @@ import torch.nn as nn
 from .. import _native as nat
 from .bundle import STATE_PREFIX, BundleError, check_bundle, float_arrays, load_bundle, make_header, write_bundle
 from .quantize import (QuantizationError, check_crnn_args, check_lstm_args, check_tcn_args, quantize_cnn_small, quantize_crnn,
-                       quantize_lstm, quantize_resnet18, quantize_tcn)
-from .reference import CONVS
-from .runtime import QuantizedCNNSmall, QuantizedCRNN, QuantizedLSTM, QuantizedResNet18, QuantizedTCN
+                       quantize_lstm, quantize_mobilenetv3, quantize_resnet18, quantize_tcn)
+from .reference import CONVS, mbv3_range_names
+from .runtime import QuantizedCNNSmall, QuantizedCRNN, QuantizedLSTM, QuantizedMobileNetV3, QuantizedResNet18, QuantizedTCN
 
 logger = logging.getLogger(__name__)
 
@@ -245,6 +246,88 @@ def calibrate_resnet18(model, batches: Iterable[torch.Tensor], feature_shape, de
             "p_max": got[22], "samples": seen}
 
 
+def calibrate_mobilenetv3(model, batches: Iterable[torch.Tensor], feature_shape, device, feature_extractor=None) -> dict:
+    """Ranges of the fp32 ``MobileNetV3Wakeword`` in eval mode over the calibration batches: the input's minimum and maximum and
+    ``ranges``, {name: [min, max]} over ``reference.mbv3_range_names()`` -- every conv's output, the Hardswish layers' pre-activations
+    (``<layer>.u``), each squeeze-excitation's hidden vector, each block's output, the head's hidden vector.  Runs the model's own
+    eval entry points (``ww_im2col3x3s2`` + ``ww_linear_mfma_fwd`` for the stem, ``ww_dwconv_nhwc_fwd``, ``ww_linear_mfma_fwd`` for
+    the 1x1 convs and the Linears, ``ww_bn_act_fwd`` with running statistics -- ``LIN_NONE`` where the pre-activation is wanted,
+    Hardswish then being a torch op --, ``ww_pool_hw_fwd``, ``ww_scale_bc_fwd``); the ranges are torch reductions on the device
+    and come to the host once, at the end."""
+    F, T = feature_shape
+    dev = torch.device(device)
+    net = model.mobilenet
+    names = mbv3_range_names()
+    lo = torch.full((len(names) + 1,), float("inf"), device=dev)
+    hi = torch.full((len(names) + 1,), float("-inf"), device=dev)
+    at = {n: i + 1 for i, n in enumerate(names)}
+
+    def see(name, t):
+        i = at[name] if name else 0
+        lo[i], hi[i] = torch.minimum(lo[i], t.min()), torch.maximum(hi[i], t.max())
+        return t
+
+    def cba(mod, h, name, out_name=None, residual=None):
+        """one ConvBNAct in eval mode, its ranges recorded -> its output"""
+        conv, bn = mod[0], mod[1]
+        if mod.stem:
+            B, _, H, W = h.shape
+            y = nat.linear_mfma_fwd(nat.im2col3x3s2(h.reshape(B, H, W).contiguous()), conv.weight.reshape(conv.weight.shape[0], 9), None,
+                                    mode=mod.mode).reshape(B, (H + 1) // 2, (W + 1) // 2, -1)
+        elif mod.depthwise:
+            y = nat.dwconv_nhwc_fwd(h.contiguous(), conv.weight.contiguous(), conv.k, conv.stride)
+        else:
+            y = nat.linear_mfma_fwd(h.reshape(-1, h.shape[-1]), conv.weight.reshape(conv.weight.shape[0], -1), None,
+                                    mode=mod.mode).reshape(*h.shape[:-1], -1)
+        bnp = nat.make_bn(bn.weight, bn.bias, bn.running_mean, bn.running_var, momentum=bn.momentum, eps=bn.eps, training=False)
+        if mod.act == nat.LIN_HARDSWISH:
+            a = torch.nn.functional.hardswish(see(name + ".u", nat.bn_act_fwd(y, bnp, nat.LIN_NONE, y.shape[-1])[0]))
+        else:
+            a = nat.bn_act_fwd(y, bnp, mod.act, y.shape[-1])[0]
+        if residual is not None:
+            a = nat.add_f32(a, residual.contiguous())
+        return see(out_name or name, a)
+    seen = 0
+    with torch.no_grad():
+        for x in batches:
+            x = torch.as_tensor(x).to(dev)
+            if x.dim() == 2:
+                if feature_extractor is None:
+                    raise QuantizationError("calibration waveforms need a feature_extractor")
+                x = feature_extractor(x)
+            if x.dim() == 3:
+                x = x[:, None]
+            if x.dim() != 4 or tuple(x.shape[1:]) != (1, F, T):
+                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{T})")
+            x = see("", x.float().contiguous())
+            h = cba(net.features[0], x, "stem")
+            for i, blk in enumerate(list(net.features)[1:-1]):
+                p, h_in = f"b{i}.", h
+                layers = list(blk.block)
+                if len(layers) - (1 if any(hasattr(m, "fc1") for m in layers) else 0) == 3:
+                    h = cba(layers.pop(0), h, p + "expand")
+                h = cba(layers.pop(0), h, p + "dw")
+                if hasattr(layers[0], "fc1"):
+                    se = layers.pop(0)
+                    B, H, W, Cn = h.shape
+                    x3 = h.reshape(B, H * W, Cn).contiguous()
+                    w1, w2 = se.fc1.weight.reshape(se.fc1.weight.shape[0], -1), se.fc2.weight.reshape(se.fc2.weight.shape[0], -1)
+                    hid = see(p + "h", nat.linear_mfma_fwd(nat.pool_hw_fwd(x3), w1, se.fc1.bias, act=nat.LIN_RELU, mode=se.mode))
+                    gate = nat.linear_mfma_fwd(hid, w2, se.fc2.bias, act=nat.LIN_HARDSIGMOID, mode=se.mode)
+                    h = nat.scale_bc_fwd(x3, gate).reshape(B, H, W, Cn)
+                h = cba(layers[0], h, p + "project", p + "out", residual=h_in if blk.use_res_connect else None)
+            h = cba(net.features[-1], h, "last")
+            B, H, W, Cn = h.shape
+            cls = net.classifier[0]
+            pre = see("cls0.u", nat.linear_mfma_fwd(nat.pool_hw_fwd(h.reshape(B, H * W, Cn).contiguous()), cls.weight, cls.bias, mode=cls.mode))
+            see("hidden", torch.nn.functional.hardswish(pre))
+            seen += x.shape[0]
+    if seen == 0:
+        raise QuantizationError("the calibration data is empty")
+    got = torch.stack([lo, hi], dim=1).cpu().tolist()                     # the one read-back
+    return {"x_min": got[0][0], "x_max": got[0][1], "ranges": {n: got[at[n]] for n in names}, "samples": seen}
+
+
 def lstm_entry(model) -> dict:
     """The header's ``lstm`` entry of an ``LSTMWakeword``: what its constructor needs besides ``num_classes``."""
     return {"input_size": int(model.lstm.input_size), "hidden_size": int(model.hidden_size), "num_layers": int(model.num_layers),
@@ -360,9 +443,9 @@ class ModelExporter:
         return write_bundle(path, dict(header, kind="fp16"), float_arrays(state, fp16=True))
 
     def _write_int8(self, output_path: Path, header: dict, state: dict, config: ExportConfig) -> Path:
-        if header["architecture"] not in ("cnn_small", "crnn", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
+        if header["architecture"] not in ("cnn_small", "crnn", "mobilenetv3", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
             raise QuantizationError("int8 export covers cnn_small only among the factory's architectures -- with crnn, whose conv "
-                                    "stack is cnn_small's -- and TCNWakeword, ResNet18Wakeword and LSTMWakeword; not "
+                                    "stack is cnn_small's, and mobilenetv3 -- and TCNWakeword, ResNet18Wakeword and LSTMWakeword; not "
                                     f"{header['architecture']!r}")
         if self.calibration is None:
             raise QuantizationError("int8 export needs calibration data (ModelExporter(..., calibration=batches)); "
@@ -401,6 +484,15 @@ class ModelExporter:
                 logger.info("calibrated ranges: %s", cal)
             arrays, scales = quantize_crnn(state, header["crnn"], F, cal, eps=self.model.front.stem.bn.eps)
             layers = [k[:-2] for k in arrays if k.endswith(".w") and k != "fc.w"] + ["fmean", "fc"]
+            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
+            check_bundle(h, arrays)
+            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
+        if header["architecture"] == "mobilenetv3":
+            cal = calibrate_mobilenetv3(self.model, self.calibration, (F, T), self.device, fe)
+            if config.verbose:
+                logger.info("calibrated ranges: %s", cal)
+            arrays, scales = quantize_mobilenetv3(state, (F, T), cal, eps=self.model.mobilenet.features[0][1].eps)
+            layers = [k[:-2] for k in arrays if k.endswith(".w") and k != "fc.w"] + ["pool", "fc"]
             h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
             check_bundle(h, arrays)
             return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
@@ -449,14 +541,14 @@ def export_model(checkpoint_path: Path, output_path: Path, opset_version: int = 
 def load_exported_model(path: Path, device: str = "cuda") -> nn.Module:
     """A bundle as a module in eval mode on ``device``: the factory's architecture with the stored weights (fp16 widened to
     fp32) or, for an int8 bundle, ``QuantizedCNNSmall`` / ``QuantizedTCN`` / ``QuantizedResNet18`` / ``QuantizedLSTM`` /
-    ``QuantizedCRNN``.  A ``crnn`` bundle is built from its header's ``crnn`` entry where it has one.  A
+    ``QuantizedCRNN`` / ``QuantizedMobileNetV3``.  A ``crnn`` bundle is built from its header's ``crnn`` entry where it has one.  A
     ``TCNWakeword`` bundle is built from its header's ``tcn`` entry, an ``LSTMWakeword`` bundle from its ``lstm`` entry and a
     ``ResNet18Wakeword`` bundle from ``num_classes`` alone (the factory does not offer those classes).  ``ModelEvaluator`` and ``RecordingScanner`` take any of them."""
     header, arrays = load_bundle(path)
     check_bundle(header, arrays)
     if header["kind"] == "int8":
         cls = {"TCNWakeword": QuantizedTCN, "ResNet18Wakeword": QuantizedResNet18, "LSTMWakeword": QuantizedLSTM,
-               "crnn": QuantizedCRNN}.get(header["architecture"], QuantizedCNNSmall)
+               "crnn": QuantizedCRNN, "mobilenetv3": QuantizedMobileNetV3}.get(header["architecture"], QuantizedCNNSmall)
         return cls(header, arrays).to(device)
     if header["architecture"] == "ResNet18Wakeword":
         from ..models import ResNet18Wakeword
@@ -565,4 +657,5 @@ benchmark_onnx_model = benchmark_exported_model
 __all__ = ["ExportConfig", "ModelExporter", "ONNXExporter", "export_model", "export_model_to_onnx", "load_exported_model",
            "validate_exported_model", "validate_onnx_model", "benchmark_exported_model", "benchmark_onnx_model",
            "QuantizedCNNSmall", "QuantizedTCN", "QuantizedResNet18", "QuantizedLSTM", "BundleError", "QuantizationError",
-           "calibrate_cnn_small", "calibrate_tcn", "calibrate_resnet18", "calibrate_lstm", "QuantizedCRNN", "calibrate_crnn"]
+           "calibrate_cnn_small", "calibrate_tcn", "calibrate_resnet18", "calibrate_lstm", "QuantizedCRNN", "calibrate_crnn",
+           "QuantizedMobileNetV3", "calibrate_mobilenetv3"]

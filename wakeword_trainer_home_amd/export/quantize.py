@@ -1,5 +1,5 @@
 """The export side of the int8 law (DESIGN.md "Export"): BatchNorm folding, scales, integer weights, biases and multipliers
-of ``cnn_small``, ``TCNWakeword``, ``ResNet18Wakeword``, ``LSTMWakeword`` and ``CRNNWakeword``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does
+of ``cnn_small``, ``TCNWakeword``, ``ResNet18Wakeword``, ``LSTMWakeword``, ``CRNNWakeword`` and ``MobileNetV3Wakeword``, all in float64 NumPy on the host.  ``reference.py`` is the other half: what a runtime does
 with the result."""
 import math
 from typing import Dict, Sequence
@@ -449,4 +449,135 @@ def quantize_crnn(state: Dict[str, np.ndarray], crnn_args: dict, F: int, ranges:
     _one_multiplier(arrays, "fmean", s_in / (((F + 1) // 2) * s_f))
     scales["fmean"] = s_f
     quantize_gru_stack(arrays, st, "rnn.", 64, L, nd, s_f)
+    return arrays, scales
+
+
+MBV3_MAX_CLASSES = 64
+
+
+def asym_qparams(lo, hi, what):
+    """The *input rule* on a calibrated (min, max) for any asymmetric tensor: (s as float32, z); the range is widened to contain 0."""
+    try:
+        return input_qparams(lo, hi)
+    except QuantizationError as e:
+        raise QuantizationError(f"{what}: {str(e)[len('input: '):]}") from None
+
+
+def hardswish_table(s_u, z_u, s_out, z_out):
+    """T[i] = clamp(rne(hs((i - 128 - z_u) s_u) / s_out) + z_out, -128, 127), hs(v) = v min(max(v + 3, 0), 6) / 6: int8 (256,), in
+    float64.  A runtime reads it from the bundle and never recomputes it."""
+    v = (np.arange(256, dtype=np.float64) - 128.0 - float(z_u)) * float(s_u)
+    hs = v * np.minimum(np.maximum(v + 3.0, 0.0), 6.0) / 6.0
+    return np.clip(np.rint(hs / float(s_out)) + float(z_out), -128, 127).astype(np.int8)
+
+
+def _quantize_mbv3_layer(arrays, scales, name, wf, bf, s_in, acc_max, kind, rng, rng_u=None, bias_shift=0.0, real=None):
+    """One weight matrix ``wf`` (Cout, K) with its float bias under one of the law's epilogues.  ``kind``: ``relu`` (``rng[1]`` is
+    the calibrated maximum), ``signed`` (max |.| of ``rng``), ``hs`` (the Hardswish rule: ``rng_u`` is the pre-activation's range,
+    ``rng`` the output's) or ``gate`` (fc2 with Hardsigmoid: +3 folded into the bias, the multiplier aims at 255 / 6).
+    -> (s_out, z_out) of the tensor the layer writes."""
+    wf = np.asarray(wf, np.float64)
+    if not (np.isfinite(wf).all() and np.isfinite(np.asarray(bf, np.float64)).all()):
+        raise QuantizationError(f"{name}: a weight or folded bias is not finite")
+    q_w, s_w = quantize_weights(wf)
+    if kind == "hs":
+        s_u, z_u = asym_qparams(max(float(rng_u[0]), -3.0), rng_u[1], name + " pre-activation")
+        s_o, z_o = asym_qparams(rng[0], rng[1], name + " output")
+        arrays[name + ".zu"], arrays[name + ".zo"] = np.array([z_u], np.int32), np.array([z_o], np.int32)
+        arrays[name + ".tab"] = hardswish_table(s_u, z_u, s_o, z_o)
+        s_t, s_o = float(s_u), float(s_o)
+        scales[name + ".u"] = s_t
+    elif kind == "relu":
+        s_t = s_o = out_scale(rng[1])
+        z_o = -128
+    elif kind == "signed":
+        s_t = s_o = signed_scale(max(abs(float(rng[0])), abs(float(rng[1]))))
+        z_o = 0
+    else:
+        s_t, s_o, z_o = 6.0 / 255.0, 1.0 / 255.0, 0
+    ms = [encode_multiplier(s_in * s_w[c] / s_t, f"{name}, channel {c}") for c in range(wf.shape[0])]
+    arrays[name + ".w"] = q_w
+    arrays[name + ".b"] = quantize_bias(np.asarray(bf, np.float64) + bias_shift, s_in, s_w, acc_max, name)
+    arrays[name + ".m"] = np.array([m for m, _ in ms], np.int32)
+    arrays[name + ".sh"] = np.array([s for _, s in ms], np.int32)
+    scales[real or name] = s_o
+    return s_o, z_o
+
+
+def quantize_mobilenetv3(state: Dict[str, np.ndarray], feature_shape: Sequence[int], cal: dict, eps: float = 1e-3):
+    """The arrays of an int8 MobileNetV3Wakeword bundle and its scales (the law's subsection "MobileNetV3").  ``cal``: ``x_min``,
+    ``x_max`` and ``ranges``, {name: (min, max)} over ``reference.mbv3_range_names()``.  Arrays are unpadded: ``stem.*``, per block
+    ``b{i}.expand|dw|project.{w,b,m,sh}``, ``b{i}.pool.{m,sh,hw}``, ``b{i}.fc1|fc2.{w,b,m,sh}``, ``b{i}.gate.{m,sh}``,
+    ``b{i}.res.{m,sh}``; ``last.*``, ``pool.{m,sh,hw}``, ``cls0.*``, ``fc.{w,b,scale}``; every Hardswish layer carries ``.zu``, ``.zo``
+    and ``.tab``.  Raises ``QuantizationError`` where the law refuses."""
+    from .reference import MBV3_HIDDEN, MBV3_LAST, MBV3_STEM, mbv3_blocks, mbv3_range_names
+    F, T = int(feature_shape[0]), int(feature_shape[1])
+    st = {k: np.asarray(v, np.float64) for k, v in state.items() if np.asarray(v).dtype.kind == "f"}
+    pre = "mobilenet.features."
+    if pre + "0.0.weight" not in st or "mobilenet.classifier.3.weight" not in st:
+        raise QuantizationError("the state holds no MobileNetV3Wakeword (mobilenet.features.0.0.weight, mobilenet.classifier.3.weight)")
+    num_classes = st["mobilenet.classifier.3.weight"].shape[0]
+    if not 2 <= num_classes <= MBV3_MAX_CLASSES:
+        raise QuantizationError(f"the int8 MobileNetV3 takes 2..{MBV3_MAX_CLASSES} classes, got {num_classes}")
+    rng = cal["ranges"]
+    missing = [n for n in mbv3_range_names() if n not in rng]
+    if missing:
+        raise QuantizationError(f"the calibrated ranges lack {missing[:3]}")
+
+    def folded(p, shape):
+        key = p + ".0.weight"
+        if key not in st or st[key].shape != shape:
+            raise QuantizationError(f"{key}: expected weights of shape {shape}")
+        return fold_bn(st[key], *(st[f"{p}.1.{k}"] for k in ("weight", "bias", "running_mean", "running_var")), eps)
+
+    def plain(p, shape):
+        if p + ".weight" not in st or st[p + ".weight"].shape[:2] != shape or st[p + ".bias"].shape != shape[:1]:
+            raise QuantizationError(f"{p}.weight: expected weights of shape {shape} and their bias")
+        return st[p + ".weight"].reshape(shape), st[p + ".bias"]
+    s_x, z_x = input_qparams(cal["x_min"], cal["x_max"])
+    arrays = {"input_scale": np.array([s_x], np.float32), "input_zero": np.array([z_x], np.int32)}
+    scales = {"input": float(s_x)}
+    s, z = _quantize_mbv3_layer(arrays, scales, "stem", *folded(pre + "0", (MBV3_STEM, 1, 3, 3)), float(s_x), 9 * 127 * 255, "hs",
+                                rng["stem"], rng["stem.u"])
+    for i, b in enumerate(mbv3_blocks(F, T)):
+        p, q, j = f"{pre}{i + 1}.block.", f"b{i}.", 0
+        kind, s_res = "hs" if b["hs"] else "relu", s
+        if b["expand"]:
+            s, z = _quantize_mbv3_layer(arrays, scales, q + "expand", *folded(p + "0", (b["exp"], b["cin"], 1, 1)), s,
+                                        b["cin"] * 127 * 255, kind, rng[q + "expand"], rng.get(q + "expand.u"))
+            j = 1
+        s, z = _quantize_mbv3_layer(arrays, scales, q + "dw", *folded(f"{p}{j}", (b["exp"], 1, b["k"], b["k"])), s,
+                                    b["k"] ** 2 * 127 * 255, kind, rng[q + "dw"], rng.get(q + "dw.u"))
+        j += 1
+        if b["se"]:
+            hw = b["hw"][0] * b["hw"][1]
+            _one_multiplier(arrays, q + "pool", 1.0 / hw)
+            arrays[q + "pool.hw"] = np.array([hw], np.int32)
+            s_h, _ = _quantize_mbv3_layer(arrays, scales, q + "fc1", *plain(f"{p}{j}.fc1", (b["se"], b["exp"])), s, b["exp"] * 127 * 255,
+                                          "relu", rng[q + "h"], real=q + "h")
+            _quantize_mbv3_layer(arrays, scales, q + "fc2", *plain(f"{p}{j}.fc2", (b["exp"], b["se"])), s_h, b["se"] * 127 * 255,
+                                 "gate", None, bias_shift=3.0, real=q + "gate")
+            _one_multiplier(arrays, q + "gate", 1.0 / 255.0)
+            j += 1
+        s_y = s
+        s, z = _quantize_mbv3_layer(arrays, scales, q + "project", *folded(f"{p}{j}", (b["cout"], b["exp"], 1, 1)), s_y,
+                                    b["exp"] * 127 * 255, "signed", rng[q + "out"], real=q + "out")
+        if b["res"]:
+            _one_multiplier(arrays, q + "res", s_res / s)
+    last = mbv3_blocks(F, T)[-1]
+    s, z = _quantize_mbv3_layer(arrays, scales, "last", *folded(pre + "12", (MBV3_LAST, last["cout"], 1, 1)), s, last["cout"] * 127 * 255,
+                                "hs", rng["last"], rng["last.u"])
+    hw = last["hw"][0] * last["hw"][1]
+    _one_multiplier(arrays, "pool", 1.0 / hw)
+    arrays["pool.hw"] = np.array([hw], np.int32)
+    scales["pool"] = s
+    s_h, _ = _quantize_mbv3_layer(arrays, scales, "cls0", *plain("mobilenet.classifier.0", (MBV3_HIDDEN, MBV3_LAST)), s, MBV3_LAST * 127 * 255,
+                                  "hs", rng["hidden"], rng["cls0.u"], real="hidden")
+    fw, fb = plain("mobilenet.classifier.3", (num_classes, MBV3_HIDDEN))
+    if not np.isfinite(fw).all():
+        raise QuantizationError("classifier: a weight is not finite")
+    q_w, s_w = quantize_weights(fw)
+    arrays["fc.w"] = q_w
+    arrays["fc.b"] = quantize_bias(fb, s_h, s_w, MBV3_HIDDEN * 127 * 255, "classifier")
+    arrays["fc.scale"] = (s_h * s_w).astype(np.float32)
     return arrays, scales

@@ -10,7 +10,8 @@ bundle to another runtime can be checked against it, tensor by tensor.  It runs 
 ``run_int8`` dispatches on the header's architecture: ``cnn_small`` (NHWC tensors), ``TCNWakeword`` (``run_int8_tcn``: (B,T,C)
 tensors ``xq``, each block's ``b{i}.h1``, ``b{i}.h2``, ``b{i}.out``, then ``pool`` and ``logits`` (B,num_classes)),
 ``ResNet18Wakeword`` (``run_int8_resnet18``), ``LSTMWakeword`` (``run_int8_lstm``: any number of frames T) or ``crnn``
-(``run_int8_crnn``: cnn_small's conv stack, the frequency mean, a GRU stack -- ``run_int8_gru_stack`` --; any T).
+(``run_int8_crnn``: cnn_small's conv stack, the frequency mean, a GRU stack -- ``run_int8_gru_stack`` --; any T) or ``mobilenetv3``
+(``run_int8_mobilenetv3``: Hardswish by table, squeeze-excitation with a uint8 gate, signed bottleneck outputs).
 """
 import json
 
@@ -400,12 +401,142 @@ def run_int8_crnn(header, arrays, x, want_acc=False):
     return out
 
 
+MBV3_CONF = ((16, 3, 16, 16, True, "RE", 2), (16, 3, 72, 24, False, "RE", 2), (24, 3, 88, 24, False, "RE", 1),
+             (24, 5, 96, 40, True, "HS", 2), (40, 5, 240, 40, True, "HS", 1), (40, 5, 240, 40, True, "HS", 1),
+             (40, 5, 120, 48, True, "HS", 1), (48, 5, 144, 48, True, "HS", 1), (48, 5, 288, 96, True, "HS", 2),
+             (96, 5, 576, 96, True, "HS", 1), (96, 5, 576, 96, True, "HS", 1))      # mobilenet_v3_small: cin, k, exp, cout, SE, act, stride
+MBV3_STEM, MBV3_LAST, MBV3_HIDDEN = 16, 576, 1024
+GATE_MULT, GATE_SHIFT = 1077952576, 38         # the encoding of 1 / 255
+
+
+def mbv3_blocks(F, T):
+    """[dict] of the eleven inverted-residual blocks on (F, T) features, in execution order: ``cin``, ``k``, ``exp``, ``cout``,
+    ``se`` (its squeeze width, or 0), ``hs`` (Hardswish, else ReLU), ``stride``, ``expand`` (has an expand conv), ``res`` (has a
+    skip connection), ``hw_in`` and ``hw`` (the image before and after the depthwise conv)."""
+    hw, out = (resnet_half(F), resnet_half(T)), []
+    for cin, k, exp, cout, se, act, stride in MBV3_CONF:
+        nxt = (resnet_half(hw[0]), resnet_half(hw[1])) if stride == 2 else hw
+        sq = max(8, (exp // 4 + 4) // 8 * 8)
+        if sq < 0.9 * (exp // 4):
+            sq += 8
+        out.append({"cin": cin, "k": k, "exp": exp, "cout": cout, "se": sq if se else 0, "hs": act == "HS", "stride": stride,
+                    "expand": exp != cin, "res": stride == 1 and cin == cout, "hw_in": hw, "hw": nxt})
+        hw = nxt
+    return out
+
+
+def mbv3_stages(want=("expand", "dw", "pool", "h", "gate", "y", "out")):
+    """The stage tensors of ``run_int8_mobilenetv3`` in execution order."""
+    out = ["xq", "stem"]
+    for i, b in enumerate(mbv3_blocks(1, 1)):
+        have = {"expand": b["expand"], "dw": True, "pool": b["se"], "h": b["se"], "gate": b["se"], "y": b["se"], "out": True}
+        out += [f"b{i}.{s}" for s in want if have[s]]
+    return out + ["last", "pool", "hidden", "logits"]
+
+
+def mbv3_range_names():
+    """The calibrated tensors of a MobileNetV3 bundle, in execution order; ``<layer>.u`` is a Hardswish pre-activation."""
+    out = ["stem.u", "stem"]
+    for i, b in enumerate(mbv3_blocks(1, 1)):
+        for layer in (["expand"] if b["expand"] else []) + ["dw"]:
+            out += ([f"b{i}.{layer}.u"] if b["hs"] else []) + [f"b{i}.{layer}"]
+        out += ([f"b{i}.h"] if b["se"] else []) + [f"b{i}.out"]
+    return out + ["last.u", "last", "cls0.u", "hidden"]
+
+
+def _dwconv(q, zero, w, k, stride):
+    """sum_{kh,kw} w[c, kh k + kw] (q[b, ho s - p + kh, wo s - p + kw, c] - zero) -> int64 (B,Ho,Wo,C), p = k // 2; positions outside
+    the image contribute nothing.  q has C channels, or one (the stem: every output channel reads it)."""
+    B, H, W, _ = q.shape
+    p = k // 2
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    d = np.pad(q.astype(np.int64) - int(zero), ((0, 0), (p, p), (p, p), (0, 0)))
+    acc = np.zeros((B, Ho, Wo, w.shape[0]), np.int64)
+    for kh in range(k):
+        for kw in range(k):
+            win = d[:, kh:kh + stride * (Ho - 1) + 1:stride, kw:kw + stride * (Wo - 1) + 1:stride, :]
+            acc += win * w[:, kh * k + kw].astype(np.int64)
+    return acc
+
+
+def run_int8_mobilenetv3(header, arrays, x, want_acc=False):
+    """Every stage of an int8 MobileNetV3Wakeword bundle, NHWC (the law's subsection "MobileNetV3"): ``xq`` (B,F,T), ``stem``, per
+    block ``b{i}.expand`` (where the block has one), ``b{i}.dw``, the squeeze-excitation's ``b{i}.pool`` (B,C), ``b{i}.h`` (B,Csq),
+    ``b{i}.gate`` (B,C) uint8 and ``b{i}.y``, ``b{i}.out`` (zero point 0); ``last``, ``pool`` (B,576), ``hidden`` (B,1024), ``logits``
+    float32.  With ``want_acc`` also the accumulators ``acc/<layer>`` and the Hardswish pre-activations ``u/<layer>``."""
+    x = np.asarray(x, np.float32)
+    if x.ndim == 4:
+        x = x[:, 0]
+    F, T = header["feature_shape"]
+    if x.ndim != 3 or tuple(x.shape[1:]) != (F, T):
+        raise ValueError(f"this bundle is for features of shape ({F},{T}), got {tuple(x.shape)}")
+    a, out = arrays, {}
+
+    def finish(name, acc, kind, res=None):
+        """the three epilogues: -> (int8 tensor, its zero point)"""
+        acc = _wrap32(acc + a[name + ".b"].astype(np.int64))
+        if want_acc:
+            out["acc/" + name] = acc
+        r = round_shift(acc, a[name + ".m"], a[name + ".sh"])
+        if kind == "relu":
+            return _clamp8(r), -128
+        if kind == "signed":
+            return np.clip(r if res is None else r + res, -128, 127).astype(np.int8), 0
+        u = np.clip(int(a[name + ".zu"][0]) + r, -128, 127)
+        if want_acc:
+            out["u/" + name] = u.astype(np.int8)
+        return a[name + ".tab"][u + 128], int(a[name + ".zo"][0])
+
+    def pool(q, zero, name):
+        S = _wrap32((q.astype(np.int64) - zero).sum(axis=(1, 2)))
+        return np.clip(zero + round_shift(S, a[name + ".m"][0], a[name + ".sh"][0]), -128, 127).astype(np.int8)
+    z_x = int(a["input_zero"][0])
+    xq = quantize_input(x, a["input_scale"][0], z_x)
+    out["xq"] = xq
+    q, z = finish("stem", _dwconv(xq[..., None], z_x, a["stem.w"], 3, 2), "hs")
+    out["stem"] = q
+    for i, b in enumerate(mbv3_blocks(F, T)):
+        p, act, q_in = f"b{i}.", "hs" if b["hs"] else "relu", q
+        if b["expand"]:
+            q, z = finish(p + "expand", _exact_matmul(q.astype(np.int64) - z, a[p + "expand.w"]), act)
+            out[p + "expand"] = q
+        q, z = finish(p + "dw", _dwconv(q, z, a[p + "dw.w"], b["k"], b["stride"]), act)
+        out[p + "dw"] = q
+        if b["se"]:
+            sq = pool(q, z, p + "pool")
+            h, _ = finish(p + "fc1", _exact_matmul(sq.astype(np.int64) - z, a[p + "fc1.w"]), "relu")
+            acc2 = _wrap32(_exact_matmul(h.astype(np.int64) + 128, a[p + "fc2.w"]) + a[p + "fc2.b"].astype(np.int64))
+            gate = np.clip(round_shift(acc2, a[p + "fc2.m"], a[p + "fc2.sh"]), 0, 255)
+            y = (q.astype(np.int64) - z) * gate[:, None, None, :]
+            q = np.clip(z + round_shift(y, a[p + "gate.m"][0], a[p + "gate.sh"][0]), -128, 127).astype(np.int8)
+            out[p + "pool"], out[p + "h"], out[p + "gate"], out[p + "y"] = sq, h, gate.astype(np.uint8), q
+            if want_acc:
+                out["acc/" + p + "fc2"] = acc2
+        res = round_shift(q_in.astype(np.int64), a[p + "res.m"][0], a[p + "res.sh"][0]) if b["res"] else None
+        q, z = finish(p + "project", _exact_matmul(q.astype(np.int64) - z, a[p + "project.w"]), "signed", res)
+        out[p + "out"] = q
+    q, z = finish("last", _exact_matmul(q.astype(np.int64), a["last.w"]), "hs")
+    out["last"] = q
+    pq = pool(q, z, "pool")
+    out["pool"] = pq
+    hid, z_h = finish("cls0", _exact_matmul(pq.astype(np.int64) - z, a["cls0.w"]), "hs")
+    out["hidden"] = hid
+    acc = _wrap32(_exact_matmul(hid.astype(np.int64) - z_h, a["fc.w"]) + a["fc.b"].astype(np.int64))
+    if want_acc:
+        out["acc/fc"] = acc
+    out["logits"] = acc.astype(np.float32) * a["fc.scale"].astype(np.float32)
+    return out
+
+
 def run_int8(header, arrays, x, want_acc=False):
     """Every stage of the int8 network on features ``x``, by the bundle's architecture.  ``cnn_small``: dict of STAGES (int8
     NHWC tensors, ``pool`` (B,64), ``logits``); ``TCNWakeword``: ``run_int8_tcn``; ``ResNet18Wakeword``: ``run_int8_resnet18``;
-    ``LSTMWakeword``: ``run_int8_lstm``; ``crnn``: ``run_int8_crnn``.  ``want_acc`` adds the accumulators."""
+    ``LSTMWakeword``: ``run_int8_lstm``; ``crnn``: ``run_int8_crnn``; ``mobilenetv3``: ``run_int8_mobilenetv3``.  ``want_acc`` adds the
+    accumulators."""
     if header.get("architecture") == "crnn":
         return run_int8_crnn(header, arrays, x, want_acc)
+    if header.get("architecture") == "mobilenetv3":
+        return run_int8_mobilenetv3(header, arrays, x, want_acc)
     if header.get("architecture") == "LSTMWakeword":
         return run_int8_lstm(header, arrays, x, want_acc)
     if header.get("architecture") == "TCNWakeword":

@@ -1,13 +1,13 @@
-"""``QuantizedCNNSmall``, ``QuantizedTCN``, ``QuantizedResNet18``, ``QuantizedLSTM`` and ``QuantizedCRNN``: an int8 bundle on the
-device, run with integer arithmetic only (``ww_q8_cnn_small_fwd``, ``ww_tq8_tcn_fwd``, ``ww_rq8_resnet18_fwd``, ``ww_lq8_lstm_fwd``,
-``ww_cq8_crnn_fwd``)."""
+"""``QuantizedCNNSmall``, ``QuantizedTCN``, ``QuantizedResNet18``, ``QuantizedLSTM``, ``QuantizedCRNN`` and ``QuantizedMobileNetV3``: an
+int8 bundle on the device, run with integer arithmetic only (``ww_q8_cnn_small_fwd``, ``ww_tq8_tcn_fwd``, ``ww_rq8_resnet18_fwd``,
+``ww_lq8_lstm_fwd``, ``ww_cq8_crnn_fwd``, ``ww_mq8_mobilenetv3_fwd``)."""
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _native as nat
 from .bundle import check_bundle
-from .reference import CONVS, LSTM_DIRS, LSTM_HIDDEN, resnet_blocks, tcn_blocks
+from .reference import CONVS, LSTM_DIRS, LSTM_HIDDEN, mbv3_blocks, resnet_blocks, tcn_blocks
 
 
 def effective_bias(q_b: np.ndarray, q_w: np.ndarray, z_in: int) -> np.ndarray:
@@ -409,6 +409,130 @@ class QuantizedCRNN(nn.Module):
                                                 dtype=torch.uint8, device=dev)
         logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
         nat.cq8_crnn_fwd(self._table(), self.io, x, ws, logits)
+        return logits
+
+
+def device_mbv3_conv(arrays: dict, name: str, z_in: int, kind: str):
+    """The tensors of one MobileNetV3 conv as the ``ww_mq8_*`` kernels read them, channel counts padded to 64 (``kind``: ``pw`` --
+    w (Cpo, Cpi) [out][in] -- or ``dw`` / ``stem`` -- w (taps, Cp) [tap][channel]): zero weights in the pad rows and columns; the
+    effective bias, mult and shift, the pad channels 0, 2^30 and 31 (they come out as the output's zero point); the layer's
+    Hardswish table, or None."""
+    w = arrays[name + ".w"]
+    cout = w.shape[0]
+    cpo = nat.tq8_pad(cout)
+    if kind == "pw":
+        wd = np.zeros((cpo, nat.tq8_pad(w.shape[1])), np.int8)
+        wd[:cout, :w.shape[1]] = w
+    else:
+        wd = np.zeros((w.shape[1], cpo), np.int8)
+        wd[:, :cout] = w.T
+    bias, mult, shift = np.zeros(cpo, np.int32), np.full(cpo, 2 ** 30, np.int32), np.full(cpo, 31, np.int32)
+    bias[:cout] = effective_bias(arrays[name + ".b"], w, z_in)
+    mult[:cout], shift[:cout] = arrays[name + ".m"], arrays[name + ".sh"]
+    return wd, bias, mult, shift, arrays.get(name + ".tab")
+
+
+class QuantizedMobileNetV3(nn.Module):
+    """An int8 ``MobileNetV3Wakeword`` bundle on the device: ``forward((B,1,F,T) float32) -> (B,num_classes) float32`` is one native
+    call (``ww_mq8_mobilenetv3_fwd``) on the current stream, no host synchronisation.  Eval only, no parameters.  The bundle is for
+    ONE feature shape (its pooling multipliers hold 1/HW): another shape is refused."""
+
+    hip_backed = True
+
+    def __init__(self, header: dict, arrays: dict):
+        super().__init__()
+        check_bundle(header, arrays)
+        if header["kind"] != "int8" or header["architecture"] != "mobilenetv3":
+            raise ValueError(f"QuantizedMobileNetV3 needs an int8 mobilenetv3 bundle, got kind {header['kind']!r} of "
+                             f"{header['architecture']!r}")
+        self.header = dict(header)
+        self.feature_shape = tuple(int(v) for v in header["feature_shape"])
+        self.num_classes = int(header["num_classes"])
+        one = lambda key: int(arrays[key][0])        # noqa: E731
+        io = nat.Mq8Io(float(arrays["input_scale"][0]), one("input_zero"), self.num_classes, one("stem.zu"), one("stem.zo"),
+                       one("last.zu"), one("last.zo"), one("cls0.zu"), one("cls0.zo"), one("pool.m"), one("pool.sh"))
+        self._names = []
+        self._add_conv("stem", device_mbv3_conv(arrays, "stem", io.in_zero, "stem"))
+        z = io.stem_zo
+        self.blocks = mbv3_blocks(*self.feature_shape)
+        for i, b in enumerate(self.blocks):
+            p = f"b{i}."
+            for layer, kind in (("expand", "pw"), ("dw", "dw")):
+                if layer == "expand" and not b["expand"]:
+                    self._add_conv(f"b{i}_expand", (None,) * 5)
+                    continue
+                self._add_conv(f"b{i}_{layer}", device_mbv3_conv(arrays, p + layer, z, kind))
+                z = one(p + layer + ".zo") if b["hs"] else -128
+                if b["hs"]:
+                    getattr(io, "exp_zu" if layer == "expand" else "dw_zu")[i] = one(p + layer + ".zu")
+                    getattr(io, "exp_zo" if layer == "expand" else "dw_zo")[i] = z
+            for fc in ("fc1", "fc2"):
+                for s in ("w", "b", "m", "sh"):
+                    self._add(f"b{i}_{fc}_{s}", arrays[f"{p}{fc}.{s}"] if b["se"] else None)
+            if b["se"]:
+                io.sepool_mult[i], io.sepool_shift[i] = one(p + "pool.m"), one(p + "pool.sh")
+                io.gate_mult[i], io.gate_shift[i] = one(p + "gate.m"), one(p + "gate.sh")
+            self._add_conv(f"b{i}_project", device_mbv3_conv(arrays, p + "project", z, "pw")[:4])
+            if b["res"]:
+                io.res_mult[i], io.res_shift[i] = one(p + "res.m"), one(p + "res.sh")
+            z = 0
+        self._add_conv("last", device_mbv3_conv(arrays, "last", 0, "pw"))
+        self._add_conv("cls0", device_mbv3_conv(arrays, "cls0", io.last_zo, "pw"))
+        for key in ("fc.w", "fc.b", "fc.scale"):
+            self._add(key.replace(".", "_"), arrays[key])
+        assert len(self._names) == nat.MQ8_NPTR
+        self.io = io
+        self._tab, self._key, self._ws = None, None, {}
+        self.eval()
+
+    def _add(self, name, a):
+        if a is None:
+            setattr(self, name, None)
+        else:
+            self.register_buffer(name, torch.from_numpy(np.ascontiguousarray(a).copy()), persistent=False)
+        self._names.append(name)
+
+    def _add_conv(self, name, tensors):
+        for suffix, a in zip(("w", "b", "m", "sh", "tab"), tensors):
+            self._add(f"{name}_{suffix}", a)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise RuntimeError("QuantizedMobileNetV3 is an inference network: it has no training mode")
+        return super().train(False)
+
+    def conv(self, name):
+        """(w, bias_eff, mult, shift, tab) of ``stem``, ``b{i}.expand|dw|project``, ``last`` or ``cls0``; (w, q_b, mult, shift) of
+        ``b{i}.fc1|fc2``: what the per-layer entry points take."""
+        return tuple(getattr(self, f"{name.replace('.', '_')}_{s}", None) for s in ("w", "b", "m", "sh", "tab"))
+
+    def _table(self):
+        tensors = [getattr(self, n) for n in self._names]
+        key = tuple(None if t is None else t.data_ptr() for t in tensors)
+        if self._key != key:
+            self._tab, self._key = nat.ptr_array(tensors), key
+        return self._tab
+
+    def workspace(self, B):
+        """The uint8 workspace of the last forward at this batch size (``_native.mq8_workspace_views`` names its parts)."""
+        return self._ws[B]
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dim() == 4 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 3 or tuple(x.shape[1:]) != self.feature_shape:
+            raise ValueError(f"this int8 bundle is for features of shape {self.feature_shape}, got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"features must be float32, got {x.dtype}")
+        if not x.is_contiguous() or x.data_ptr() % 16:
+            x = x.clone(memory_format=torch.contiguous_format)
+        B, (F, T) = x.shape[0], self.feature_shape
+        dev = nat._dev(x, self.fc_w)
+        ws = self._ws.get(B)
+        if ws is None or ws.device != dev:
+            ws = self._ws[B] = torch.empty(nat.mq8_mobilenetv3_workspace_bytes(B, F, T), dtype=torch.uint8, device=dev)
+        logits = torch.empty((B, self.num_classes), dtype=torch.float32, device=dev)
+        nat.mq8_mobilenetv3_fwd(self._table(), self.io, x, ws, logits)
         return logits
 
 
