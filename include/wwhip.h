@@ -33,7 +33,8 @@ extern "C" {
 
 /* 17: ww_pass_plan / ww_loader_plan (host-only pass plans of the capped-grid support launches) were added; no existing
  * signature, struct, constant or result changed.  ww_dw_plan / ww_ctx_set_dw_wide_addr came later under the same number: pure
- * additions again, as is ww_gemm_plan. */
+ * additions again, as is ww_gemm_plan, and as are the detection scan's entry points (ww_wave_windows_at, ww_feat_windows,
+ * ww_detect_accumulate). */
 #define WW_ABI_VERSION 17
 
 #define WW_OK 0
@@ -863,6 +864,51 @@ int ww_eval_accumulate_classes(ww_ctx *ctx, const float *logits, int num_classes
  * holding a NaN is copied unscaled (np.max returns the NaN and NaN > 0 is false) and its peak is NaN.  W must be the rule's. */
 long ww_wave_num_windows(long S, int chunk);
 int ww_wave_windows(ww_ctx *ctx, const float *wave, long S, int chunk, int W, float *out, float *peaks, ww_stream_t stream);
+
+/* ------------------------------------------------------------------ evaluation: the dense detection scan
+ * What the reference does not have: windows at any hop, a smoothed posterior, a refractory period after a trigger, triggers
+ * matched to labelled keyword occurrences, counted at every threshold of a table -- false alarms per hour against miss rate.
+ * One read-back per recording (DESIGN.md "Evaluation", evaluation/detection.py restates every law below in NumPy).
+ *
+ * Windows at a free hop, by slab.  W = 0 if S < chunk else (S - chunk)/hop + 1, 1 <= hop <= chunk (host only: the first
+ * function below, 0 for a hop outside that range).  Window w0 + i = wave[(w0+i)*hop .. +chunk) for i in [0, n), 0 <= w0,
+ * w0 + n <= W: out (n,chunk), peaks (n).  peaks[i] = max|x| of the window, NaN if it holds a NaN, always written.
+ * normalize = 1: ww_wave_windows' law -- divided by its peak when that is > 0, correctly rounded; a zero window stays zero; a
+ * window holding a NaN is copied unscaled.  normalize = 0: a plain copy.  An hour of windows is never materialised: the
+ * caller cuts a slab, runs it through the front end and the model, and reuses the buffer.  One workgroup per window and
+ * trip; honours ww_ctx_set_grid_cap, as ww_feat_windows does.  A window of more than WW_WAVE_SPLIT_CHUNK samples -- a whole
+ * recording divided by its own peak is ONE window with chunk = hop = S -- is spread over a workgroup per 8192 samples instead
+ * (an integer atomic maximum for the peak, then the division: the same bits). */
+#define WW_WAVE_SPLIT_CHUNK 32768
+long ww_wave_num_windows_hop(long S, int chunk, int hop);
+int ww_wave_windows_at(ww_ctx *ctx, const float *wave, long S, int chunk, int hop, long w0, int n, int normalize, float *out,
+                       float *peaks, ww_stream_t stream);
+/* Windows of a feature map computed once over the whole recording: feat (F,Ttot) fp32, out (n,1,F,Tw),
+ * out[i][0][f][t] = feat[f][(w0+i)*step + t], bit copied.  (w0+n-1)*step + Tw <= Ttot. */
+int ww_feat_windows(ww_ctx *ctx, const float *feat, int F, long Ttot, int Tw, int step, long w0, int n, float *out,
+                    ww_stream_t stream);
+/* The detector over the W per-window confidences of one recording (conf fp32 (W) on the device).
+ *   smoothing   1 <= M <= WW_DETECT_MAX_SMOOTH:  s_w = fp32( (0.0 + sum of fp64(conf_j), j = max(0, w-M+1) .. w, added in
+ *               ascending j) / count ), the division in fp64, count = the number of terms.  A NaN propagates.
+ *   triggers    one machine per table entry t and one for `decision`, each restarting at w = 0 on every call; R >= 1 is the
+ *               refractory length in windows.  next_ok = 0; for w = 0 .. W-1: if w >= next_ok and fp64(s_w) >= t, trigger at
+ *               w and set next_ok = w + R.  A NaN never triggers.  The comparison is fp64 on the fp32 value, as above.
+ *   matching    events int32 (E,2) on the device, E >= 0: inclusive window-index intervals [a_e, b_e], a_e <= b_e < a_{e+1}.
+ *               A trigger inside an event not yet hit by this threshold in this call is a hit, one inside an event already
+ *               hit is a duplicate, one outside every event is a false alarm: triggers = hits + false alarms + duplicates.
+ * thresholds fp64 (K) on the device, ascending, 1 <= K <= WW_EVAL_MAX_THRESHOLDS; decision: one fp64, not NaN.
+ * Outputs: smoothed fp32 (W), nullable; counts uint64 (K,4) = {triggers, hits, false alarms, duplicates} per table entry and
+ * decision_counts uint64 (4), both added to and never reset here; triggers int32 (max_triggers): the decision threshold's
+ * trigger windows in order, the first max_triggers of them; n_triggers int32 (1): their full number in this call, which may
+ * exceed max_triggers (written, not added to).  W = 0 is valid and changes nothing, n_triggers included.
+ * False alarms are NOT monotone in the threshold: a lower threshold can trigger earlier and its refractory period swallow a
+ * later false alarm, so every table entry runs its own machine -- one lane each; the smoothed sequence is staged through LDS
+ * in tiles of WW_DETECT_TILE windows, events are consumed with a per-lane cursor.  Integer counting: reproducible. */
+#define WW_DETECT_MAX_SMOOTH 64
+#define WW_DETECT_TILE 1024
+int ww_detect_accumulate(ww_ctx *ctx, const float *conf, int W, int M, int R, const double *thresholds, int K, double decision,
+                         const int32_t *events, int E, float *smoothed, uint64_t *counts, uint64_t *decision_counts,
+                         int32_t *triggers, int max_triggers, int32_t *n_triggers, ww_stream_t stream);
 
 /* ------------------------------------------------------------------ loader: batches from a device-resident clip bank
  * The reference feeds its trainer from a host DataLoader over WakewordDataset (src/data, absent from the snapshot;

@@ -307,6 +307,10 @@ _SIGS = {
     "ww_eval_accumulate_classes": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, C.c_double, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ww_wave_num_windows": (C.c_long, [C.c_long, _i]),
     "ww_wave_windows": (C.c_int, [_vp, _vp, C.c_long, _i, _i, _vp, _vp, _vp]),
+    "ww_wave_num_windows_hop": (C.c_long, [C.c_long, _i, _i]),
+    "ww_wave_windows_at": (C.c_int, [_vp, _vp, C.c_long, _i, _i, C.c_long, _i, _i, _vp, _vp, _vp]),
+    "ww_feat_windows": (C.c_int, [_vp, _vp, _i, C.c_long, _i, _i, C.c_long, _i, _vp, _vp]),
+    "ww_detect_accumulate": (C.c_int, [_vp, _vp, _i, _i, _i, _vp, _i, C.c_double, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "ww_loader_indices": (C.c_int, [_vp, _i, _i, _i, _vp, _i, _u64, _u64, _i, _i, C.c_int64, _i, _vp, _vp]),
     "ww_loader_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _u64, _u64, _i, _i, C.c_int64, _i, _i, _vp, _vp,
                                   _vp, _vp]),
@@ -2167,6 +2171,90 @@ def wave_windows(wave, chunk):
     with _guard(dev):
         _check(load().ww_wave_windows(ctx(dev), _p(wave), S, chunk, W, _p(out), _p(peaks), _stream(dev)), "ww_wave_windows")
     return out, peaks
+
+
+DETECT_MAX_SMOOTH = 64        # WW_DETECT_MAX_SMOOTH
+DETECT_TILE = 1024            # WW_DETECT_TILE: windows of the smoothed sequence staged through LDS per trip of ww_detect_accumulate
+WAVE_SPLIT_CHUNK = 32768      # WW_WAVE_SPLIT_CHUNK: windows longer than this are cut by several workgroups each
+DETECT_COUNTS = ("triggers", "hits", "false_alarms", "duplicates")
+
+
+def wave_num_windows_hop(n_samples, chunk, hop):
+    return int(load().ww_wave_num_windows_hop(int(n_samples), int(chunk), int(hop)))
+
+
+def wave_windows_at(wave, chunk, hop, w0, n, normalize=True, out=None, peaks=None):
+    """wave (S,) f32 cuda -> (out (n,chunk) f32: windows w0 .. w0+n-1 at hop `hop`, each divided by its own peak when
+    `normalize` (ww_wave_windows' law) or copied; peaks (n,) f32).  `out` / `peaks` may be passed in to be reused."""
+    dev = _dev(wave, out, peaks)
+    if wave.dim() != 1 or wave.dtype != torch.float32:
+        raise ValueError(f"recording must be a 1-D float32 tensor, got {wave.dtype} {tuple(wave.shape)}")
+    chunk, hop, w0, n = int(chunk), int(hop), int(w0), int(n)
+    if not 1 <= hop <= chunk:
+        raise ValueError(f"hop must be in [1, chunk = {chunk}], got {hop}")
+    S = wave.shape[0]
+    W = wave_num_windows_hop(S, chunk, hop)
+    if w0 < 0 or n < 0 or w0 + n > W or n >= 2 ** 31:
+        raise ValueError(f"windows [{w0}, {w0 + n}) are not among the {W} windows of {S} samples")
+    if out is None:
+        out = torch.empty((n, chunk), dtype=torch.float32, device=dev)
+    if peaks is None:
+        peaks = torch.empty((n,), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or out.shape != (n, chunk) or peaks.dtype != torch.float32 or peaks.shape != (n,):
+        raise ValueError(f"out / peaks must be float32 ({n},{chunk}) / ({n},)")
+    with _guard(dev):
+        _check(load().ww_wave_windows_at(ctx(dev), _p(wave), S, chunk, hop, w0, n, 1 if normalize else 0, _p(out), _p(peaks),
+                                         _stream(dev)), "ww_wave_windows_at")
+    return out, peaks
+
+
+def feat_windows(feat, Tw, step, w0, n, out=None):
+    """feat (F,Ttot) f32 cuda -> out (n,1,F,Tw) f32 with out[i,0,f,t] = feat[f, (w0+i)*step + t] (ww_feat_windows)."""
+    dev = _dev(feat, out)
+    if feat.dim() != 2 or feat.dtype != torch.float32:
+        raise ValueError(f"the feature map must be a 2-D float32 tensor, got {feat.dtype} {tuple(feat.shape)}")
+    Tw, step, w0, n = int(Tw), int(step), int(w0), int(n)
+    F, Ttot = feat.shape
+    if F < 1 or Tw < 1 or step < 1 or w0 < 0 or n < 0 or n >= 2 ** 31 or (n > 0 and (w0 + n - 1) * step + Tw > Ttot):
+        raise ValueError(f"windows [{w0}, {w0 + n}) of {Tw} columns at step {step} do not fit a ({F},{Ttot}) map")
+    if out is None:
+        out = torch.empty((n, 1, F, Tw), dtype=torch.float32, device=dev)
+    if out.dtype != torch.float32 or out.shape != (n, 1, F, Tw):
+        raise ValueError(f"out must be float32 ({n},1,{F},{Tw})")
+    with _guard(dev):
+        _check(load().ww_feat_windows(ctx(dev), _p(feat), F, Ttot, Tw, step, w0, n, _p(out), _stream(dev)), "ww_feat_windows")
+    return out
+
+
+def detect_accumulate(conf, M, R, thresholds, decision, events, smoothed, counts, decision_counts, triggers, n_triggers):
+    """The detector over one recording's confidences (ww_detect_accumulate), launched on the current stream; nothing is read
+    back.  conf (W,) f32; thresholds (K,) f64 ascending; events (E,2) i32 inclusive ascending window intervals or None;
+    smoothed (W,) f32 or None; counts i64 (K,4) and decision_counts i64 (4,) (DETECT_COUNTS) are added to; triggers i32
+    (max_triggers,) takes the decision threshold's first trigger windows and n_triggers i32 (1,) their full number."""
+    dev = _dev(conf, thresholds, events, smoothed, counts, decision_counts, triggers, n_triggers)
+    if conf.dim() != 1 or conf.dtype != torch.float32:
+        raise ValueError(f"conf must be a 1-D float32 tensor, got {conf.dtype} {tuple(conf.shape)}")
+    W, K = conf.shape[0], thresholds.numel()
+    if W >= 2 ** 31:
+        raise ValueError(f"{W} windows: scan the recording in pieces")
+    if thresholds.dtype != torch.float64 or thresholds.dim() != 1:
+        raise ValueError("thresholds must be a 1-D float64 tensor")
+    E = 0
+    if events is not None:
+        if events.dtype != torch.int32 or events.dim() != 2 or events.shape[1] != 2:
+            raise ValueError("events must be int32 of shape (E,2)")
+        E = events.shape[0]
+    if smoothed is not None and (smoothed.dtype != torch.float32 or smoothed.shape != (W,)):
+        raise ValueError(f"smoothed must be float32 ({W},)")
+    if counts.dtype != torch.int64 or counts.numel() != 4 * K or decision_counts.dtype != torch.int64 or decision_counts.numel() != 4:
+        raise ValueError(f"counts must be int64 with 4*K = {4 * K} elements and decision_counts int64 with 4")
+    if triggers.dtype != torch.int32 or triggers.dim() != 1 or n_triggers.dtype != torch.int32 or n_triggers.numel() != 1:
+        raise ValueError("triggers must be 1-D int32 and n_triggers int32 with one element")
+    with _guard(dev):
+        _check(load().ww_detect_accumulate(ctx(dev), _p(conf), W, int(M), int(R), _p(thresholds), K, float(decision),
+                                           _p(events) if E else None, E, _p(smoothed), _p(counts), _p(decision_counts),
+                                           _p(triggers) if triggers.numel() else None, triggers.numel(), _p(n_triggers),
+                                           _stream(dev)), "ww_detect_accumulate")
 
 
 SAMPLER_PERM, SAMPLER_TABLE = 0, 1
