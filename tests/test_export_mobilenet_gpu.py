@@ -238,6 +238,35 @@ def test_fused_gate_form_equals_the_pass_form(cases, grid_cap, monkeypatch):
         _check_forward(cases[name], skip=(".y",))                            # ... nor read
 
 
+@pytest.mark.parametrize("form", ["relu", "gated"])
+def test_conv1x1_rows_past_the_end_on_a_second_trip(grid_cap, form):
+    """64 -> 64 channels over 14 images of 5 pixels, one workgroup: 70 rows are five 16-row tiles for four waves, so one wave makes
+    a second trip, to the tile whose last ten rows lie past the end; 5 pixels an image, so every tile spans images and the gated
+    form reads up to four gate rows in one tile.  (The model cases reach the ReLU epilogue under a grid cap with whole tiles only.)"""
+    from wakeword_trainer_home_amd import _native as nat
+    g = np.random.default_rng(7)
+    B, HW, C, z = 14, 5, 64, 23
+    q = g.integers(-128, 128, (B, 1, HW, C)).astype(np.int8)
+    w = g.integers(-127, 128, (C, C)).astype(np.int8)
+    b = g.integers(-20000, 20001, C).astype(np.int32)
+    m = g.integers(2 ** 30, 2 ** 31, C).astype(np.int32)
+    sh = np.full(C, 39, np.int32)                                        # |acc| < 2^21.1 and m / 2^39 > 2^-9: r leaves [-128, 255] both ways
+    b_eff = (b.astype(np.int64) - z * w.astype(np.int64).sum(axis=1)).astype(np.int32)
+    args = [_dev(v) for v in (w, b_eff, m, sh)]
+    grid_cap(1)
+    if form == "relu":
+        want = MQ.r_clamp(MQ.r_R(MQ.r_matmul(q, z, w) + b, m, sh) - 128)
+        got = nat.mq8_conv1x1_fwd(_dev(q), *args, z, nat.MQ8_RELU)
+    else:
+        gate = g.integers(0, 256, (B, C)).astype(np.uint8)
+        gm, gsh = int(g.integers(2 ** 30, 2 ** 31)), 38                  # G / 255 is about R(G, 2^30 .. 2^31, 38)
+        y = MQ.r_clamp(z + MQ.r_R((q.astype(np.int64) - z) * gate[:, None, None, :], gm, gsh))
+        want = MQ.r_clamp(MQ.r_R(MQ.r_matmul(y, z, w) + b, m, sh))
+        got = nat.mq8_conv1x1_fwd(_dev(q), *args, z, nat.MQ8_SIGNED, gate=_dev(gate), gate_mult=gm, gate_shift=gsh)
+    assert want.min() == -128 and want.max() == 127
+    _same(got, want, None, form)
+
+
 # ------------------------------------------------------------------ the export package
 def _model(num_classes=2, seed=0):
     from wakeword_trainer_home_amd.models import create_model

@@ -18,27 +18,16 @@
 //
 // bias arguments are the EFFECTIVE bias q_b - z_in * sum(q_w) (host, once per bundle): the kernels then sum q_w * q_in with the
 // border filled with z_in, which is sum q_w (q_in - z_in) + q_b in two's complement.  All adds that may wrap are unsigned.
-#include "ww_internal.h"
+#include "ww_q8_common.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int Q8_BLOCK = 256;
 constexpr int Q8_WAVES = Q8_BLOCK / 64;
 
-// clamp(-128 + ((int64(acc) * m + 2^(sh-1)) >> sh), -128, 127); 1 <= sh <= 62, 2^30 <= m < 2^31: |acc * m| < 2^62
-__device__ __forceinline__ int q8_requant(int acc, int m, int sh) {
-    long long p = (long long)acc * (long long)m + (1ll << (sh - 1));
-    p >>= sh;
-    p = p < 0 ? 0 : (p > 255 ? 255 : p);
-    return (int)p - 128;
-}
-
-template <int J> __device__ __forceinline__ int q8_byte(int d) { return (int)(signed char)((unsigned)d >> (8 * J)); }
-
-__device__ __forceinline__ int q8_pack4(int a, int b, int c, int d) {
-    return (int)((unsigned)(a & 255) | ((unsigned)(b & 255) << 8) | ((unsigned)(c & 255) << 16) | ((unsigned)(d & 255) << 24));
-}
+// the requantisation of every tensor here is the shared law and the unsigned clamp, nothing of its own:
+// clamp(-128 + R(acc, m, sh), -128, 127)
+__device__ __forceinline__ int q8_requant(int acc, int m, int sh) { return q8_clamp(q8_round(acc, m, sh)); }
 
 struct q8_chan {                      // per-output-channel tables of one conv: (64) int32 each, 16-byte aligned
     const int *bias, *mult, *shift;
@@ -279,10 +268,6 @@ __global__ __launch_bounds__(Q8_BLOCK) void k_q8_gap_fc(const int8_t *__restrict
     }
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-inline long q8_round256(long n) { return (n + 255) / 256 * 256; }
-
 template <typename K> int q8_tile_grid(ww_ctx *ctx, K fn, long N) {
     const long want = ((N + 15) / 16 + Q8_WAVES - 1) / Q8_WAVES;
     return ww_conv_grid(ctx, (const void *)fn, Q8_BLOCK, 0, want, 1 << 20);
@@ -376,7 +361,7 @@ extern "C" int ww_q8_gap_fc_fwd(ww_ctx *ctx, const int8_t *in, int B, int HW, in
                                 ww_stream_t stream) {
     WW_REQUIRE(ctx && in && fc_w && fc_bias && fc_scale && pool_out && logits, WW_E_INVALID, "ww_q8_gap_fc_fwd: null argument");
     WW_REQUIRE(B >= 1 && HW >= 1 && HW <= (1 << 23), WW_E_INVALID, "ww_q8_gap_fc_fwd: B=%d HW=%d", B, HW);
-    WW_REQUIRE(pool_mult >= (1 << 30) && pool_shift >= 1 && pool_shift <= 62, WW_E_INVALID,
+    WW_REQUIRE(q8_mult_ok(pool_mult, pool_shift), WW_E_INVALID,
                "ww_q8_gap_fc_fwd: multiplier %d / shift %d out of range", pool_mult, pool_shift);
     WW_REQUIRE(aligned16(in), WW_E_INVALID, "ww_q8_gap_fc_fwd: the activations must be 16-byte aligned");
     ww_prof_scope prof(ctx, WW_K_GAP_FWD, (hipStream_t)stream);

@@ -17,12 +17,10 @@
 // the bundle) are copied to LDS once per launch.
 //
 // All adds that may wrap are unsigned; the law's refusal bounds keep every true sum inside int32.  R and r v_n are 64-bit.
-#include "ww_internal.h"
+#include "ww_q8_common.h"
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
 constexpr int CQ_H = 128;                      // hidden size: the implemented size of the GRU stack
 constexpr int CQ_G = 3 * CQ_H;                 // gate rows of one direction, torch's order r, z, n
 constexpr int CQ_BLOCK = 512;                  // the recurrence: 8 waves x 16 hidden units
@@ -31,22 +29,6 @@ constexpr int CQ_HROW = CQ_H + 16;             // LDS row of q_h: 144 bytes, so 
 constexpr int CQ_TAB = 4096;
 constexpr int FM_BLOCK = 256;                  // the frequency mean: 4 waves, each a tile of 16 rows per trip
 constexpr int FM_WAVES = FM_BLOCK / 64;
-
-// R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh, arithmetic shift; |a| < 2^31, 2^30 <= m < 2^31, 1 <= sh <= 62
-__device__ __forceinline__ long long cq8_round(int a, int m, int sh) {
-    return ((long long)a * (long long)m + (1ll << (sh - 1))) >> sh;
-}
-
-__device__ __forceinline__ int cq8_pack16(int a, int b) { return (int)(((unsigned)a & 0xffffu) | ((unsigned)b << 16)); }
-__device__ __forceinline__ int cq8_lo16(int d) { return (int)(short)(d & 0xffff); }
-__device__ __forceinline__ int cq8_hi16(int d) { return d >> 16; }
-template <int J> __device__ __forceinline__ int cq8_byte(int d) { return (int)(signed char)((unsigned)d >> (8 * J)); }
-
-// look(tab, a) = tab[clamp(a, -2048, 2047) + 2048]
-__device__ __forceinline__ int cq8_look(const int16_t *tab, long long a) {
-    const int i = a < -2048 ? -2048 : (a > 2047 ? 2047 : (int)a);
-    return (int)tab[i + 2048];
-}
 
 // lane l of a wave's tile: output row 16 tile + (l & 15), channels [16 g, 16 g + 16), g = l >> 4 -- the q8 lane map
 __global__ __launch_bounds__(FM_BLOCK) void k_cq8_fmean(const int8_t *__restrict__ in, int H, int W, long rows, int mult, int shift,
@@ -66,10 +48,10 @@ __global__ __launch_bounds__(FM_BLOCK) void k_cq8_fmean(const int8_t *__restrict
             const v4i q = *(const v4i *)(src + (long)h * W * 64);
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
-                sum[4 * d + 0] += cq8_byte<0>(q[d]) + 128;
-                sum[4 * d + 1] += cq8_byte<1>(q[d]) + 128;
-                sum[4 * d + 2] += cq8_byte<2>(q[d]) + 128;
-                sum[4 * d + 3] += cq8_byte<3>(q[d]) + 128;
+                sum[4 * d + 0] += q8_byte<0>(q[d]) + 128;
+                sum[4 * d + 1] += q8_byte<1>(q[d]) + 128;
+                sum[4 * d + 2] += q8_byte<2>(q[d]) + 128;
+                sum[4 * d + 3] += q8_byte<3>(q[d]) + 128;
             }
         }
         v4i o;
@@ -77,13 +59,8 @@ __global__ __launch_bounds__(FM_BLOCK) void k_cq8_fmean(const int8_t *__restrict
         for (int d = 0; d < 4; ++d) {
             int q[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                long long v = cq8_round(sum[4 * d + r], mult, shift);
-                v = v < 0 ? 0 : (v > 255 ? 255 : v);
-                q[r] = (int)v - 128;
-            }
-            o[d] = (int)((unsigned)(q[0] & 255) | ((unsigned)(q[1] & 255) << 8) | ((unsigned)(q[2] & 255) << 16) |
-                         ((unsigned)(q[3] & 255) << 24));
+            for (int r = 0; r < 4; ++r) q[r] = q8_clamp(q8_round(sum[4 * d + r], mult, shift));
+            o[d] = q8_pack4(q[0], q[1], q[2], q[3]);
         }
         *(v4i *)(out + row * 64 + 16 * g) = o;
     }
@@ -157,30 +134,26 @@ __global__ __launch_bounds__(CQ_BLOCK) void k_cq8_gru(cq8_rec_args a) {
                 long long uu[3], v[3];
 #pragma unroll
                 for (int G = 0; G < 3; ++G) {
-                    uu[G] = (e & 1) ? cq8_hi16(uc[G][e >> 1]) : cq8_lo16(uc[G][e >> 1]);
-                    v[G] = cq8_round((int)((unsigned)acc[G][e] + (unsigned)bq[G][e]), mq[G][e], sq[G][e]);
+                    uu[G] = (e & 1) ? q8_hi16(uc[G][e >> 1]) : q8_lo16(uc[G][e >> 1]);
+                    v[G] = q8_round((int)((unsigned)acc[G][e] + (unsigned)bq[G][e]), mq[G][e], sq[G][e]);
                 }
-                const int gr = cq8_look(sig, uu[0] + v[0]), gz = cq8_look(sig, uu[1] + v[1]);
+                const int gr = q8_look(sig, uu[0] + v[0]), gz = q8_look(sig, uu[1] + v[1]);
                 const long long rv = (long long)((unsigned long long)gr * (unsigned long long)v[2]);      // r v_n in 64 bits
-                const int gn = cq8_look(tnh, uu[2] + ((rv + (1ll << 14)) >> 15));
+                const int gn = q8_look(tnh, uu[2] + ((rv + (1ll << 14)) >> 15));
                 // the two weights sum to 2^15 and |n|, |h16| <= 32767: |h16'| <= 32767 and the sum stays below 2^30 + 2^14
                 const int hn = ((32768 - gz) * gn + gz * h[e] + (1 << 14)) >> 15;
                 h[e] = hn;
                 const int qh = (hn + 128) >> 8;
                 q[e] = qh < -128 ? -128 : (qh > 127 ? 127 : qh);
             }
-            const int packed = (int)((unsigned)(q[0] & 255) | ((unsigned)(q[1] & 255) << 8) | ((unsigned)(q[2] & 255) << 16) |
-                                     ((unsigned)(q[3] & 255) << 24));
+            const int packed = q8_pack4(q[0], q[1], q[2], q[3]);
             *(int *)(s_h[(s + 1) & 1] + p * CQ_HROW + unit0) = packed;
             if (live) *(int *)(yb + t * ystride) = packed;
             __syncthreads();                    // q_h[t] is whole before any wave's next product reads it
         }
-        if (live) *(v2i *)(a.h_n + (long)b * ystride + dir * CQ_H + unit0) = v2i{cq8_pack16(h[0], h[1]), cq8_pack16(h[2], h[3])};
+        if (live) *(v2i *)(a.h_n + (long)b * ystride + dir * CQ_H + unit0) = v2i{q8_pack16(h[0], h[1]), q8_pack16(h[2], h[3])};
     }
 }
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-inline long cq8_round256(long n) { return (n + 255) / 256 * 256; }
 
 }  // namespace
 
@@ -189,7 +162,7 @@ extern "C" int ww_cq8_fmean_fwd(ww_ctx *ctx, const int8_t *in, int B, int H, int
     WW_REQUIRE(ctx && in && out, WW_E_INVALID, "ww_cq8_fmean_fwd: null argument");
     WW_REQUIRE(B >= 1 && H >= 1 && W >= 1 && H <= (1 << 20) && (long)B * H * W <= (1l << 40), WW_E_INVALID,
                "ww_cq8_fmean_fwd: B=%d H=%d W=%d", B, H, W);
-    WW_REQUIRE(mult >= (1 << 30) && shift >= 1 && shift <= 62, WW_E_INVALID, "ww_cq8_fmean_fwd: multiplier %d / shift %d out of range",
+    WW_REQUIRE(q8_mult_ok(mult, shift), WW_E_INVALID, "ww_cq8_fmean_fwd: multiplier %d / shift %d out of range",
                mult, shift);
     WW_REQUIRE(aligned16(in) && aligned16(out), WW_E_INVALID, "ww_cq8_fmean_fwd: tensors must be 16-byte aligned");
     WW_REQUIRE(in != out, WW_E_INVALID, "ww_cq8_fmean_fwd: in place");
@@ -224,9 +197,9 @@ extern "C" size_t ww_cq8_crnn_workspace_bytes(int B, int F, int T, int num_layer
     if (B < 1 || F < 1 || T < 1 || num_layers < 1 || num_layers > WW_CQ8_MAX_LAYERS || num_directions < 1 || num_directions > 2)
         return 0;
     const long H = (F + 1) / 2, W = (T + 1) / 2, N = (long)B * W, nd = num_directions;
-    const long layer = cq8_round256(N * nd * CQ_G * 2) + cq8_round256(N * nd * CQ_H) + cq8_round256((long)B * nd * CQ_H * 2);
-    return (size_t)(cq8_round256((long)B * F * T) + WW_CQ8_NACT * cq8_round256((long)B * H * W * 64) + cq8_round256(N * 64) +
-                    num_layers * layer + cq8_round256((long)B * nd * CQ_H));
+    const long layer = q8_round256(N * nd * CQ_G * 2) + q8_round256(N * nd * CQ_H) + q8_round256((long)B * nd * CQ_H * 2);
+    return (size_t)(q8_round256((long)B * F * T) + WW_CQ8_NACT * q8_round256((long)B * H * W * 64) + q8_round256(N * 64) +
+                    num_layers * layer + q8_round256((long)B * nd * CQ_H));
 }
 
 extern "C" int ww_cq8_crnn_fwd(ww_ctx *ctx, const void *const *tab, const ww_cq8_io *io, const float *x, int B, int F, int T,
@@ -243,9 +216,9 @@ extern "C" int ww_cq8_crnn_fwd(ww_ctx *ctx, const void *const *tab, const ww_cq8
     auto i8 = [&](int i) { return (const int8_t *)tab[i]; };
     auto i32 = [&](int i) { return (const int32_t *)tab[i]; };
     const int H = (F + 1) / 2, W = (T + 1) / 2;
-    const long N = (long)B * W, act = cq8_round256((long)B * H * W * 64);
+    const long N = (long)B * W, act = q8_round256((long)B * H * W * 64);
     int8_t *xq = (int8_t *)ws;
-    int8_t *a0 = xq + cq8_round256((long)B * F * T);
+    int8_t *a0 = xq + q8_round256((long)B * F * T);
     int8_t *seq = a0 + WW_CQ8_NACT * act;
     int rc = ww_q8_quantize(ctx, x, (long)B * F * T, io->in_scale, io->in_zero, xq, stream);
     if (rc != WW_OK) return rc;
@@ -261,12 +234,12 @@ extern "C" int ww_cq8_crnn_fwd(ww_ctx *ctx, const void *const *tab, const ww_cq8
     if (rc != WW_OK) return rc;
     const int8_t *cur = seq;
     int Kp = 64;
-    int8_t *next = seq + cq8_round256(N * 64);
+    int8_t *next = seq + q8_round256(N * 64);
     for (int k = 0; k < L; ++k) {
         const int p = WW_CQ8_CONV_NPTR + WW_CQ8_LAYER_NPTR * k;
         int16_t *u = (int16_t *)next;
-        int8_t *y = next + cq8_round256(N * nd * CQ_G * 2);
-        int16_t *h_n = (int16_t *)(y + cq8_round256(N * nd * CQ_H));
+        int8_t *y = next + q8_round256(N * nd * CQ_G * 2);
+        int16_t *h_n = (int16_t *)(y + q8_round256(N * nd * CQ_H));
         rc = ww_lq8_proj_fwd(ctx, cur, i8(p), i32(p + 1), i32(p + 2), i32(p + 3), N, Kp, nd * CQ_G, u, stream);
         if (rc != WW_OK) return rc;
         rc = ww_cq8_gru_layer_fwd(ctx, u, i8(p + 4), i32(p + 5), i32(p + 6), i32(p + 7), (const int16_t *)tab[np + 3],
@@ -274,7 +247,7 @@ extern "C" int ww_cq8_crnn_fwd(ww_ctx *ctx, const void *const *tab, const ww_cq8
         if (rc != WW_OK) return rc;
         cur = y;
         Kp = nd * CQ_H;
-        next = (int8_t *)h_n + cq8_round256((long)B * nd * CQ_H * 2);
+        next = (int8_t *)h_n + q8_round256((long)B * nd * CQ_H * 2);
     }
     return ww_lq8_head_fwd(ctx, cur, B, W, nd, i8(np), i32(np + 1), (const float *)tab[np + 2], io->num_classes, next, logits, stream);
 }

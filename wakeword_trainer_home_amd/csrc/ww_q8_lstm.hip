@@ -1,6 +1,7 @@
 // Integer-only inference of an exported int8 LSTMWakeword bundle (DESIGN.md "Export", the int8 law, subsection "LSTM").
-//   k_lq8_proj  : the input projection of both directions over all B*T rows: an int8 GEMM on v_mfma_i32_16x16x64_i8 whose
-//                 epilogue is effective bias, R, the int16 clamp; it stores u (B*T, nd*512) int16, Q8 gate pre-activations
+//   the projection : the input projection of both directions over all B*T rows: the one-segment geometry of the int8 tap-GEMM
+//                 core (ww_q8_tap_gemm.h) with the epilogue LqInt16 -- effective bias, R, the int16 clamp; it stores
+//                 u (B*T, nd*512) int16, Q8 gate pre-activations
 //   k_lq8_lstm  : the recurrence of one layer, both directions in one launch (gridDim.y): T dependent steps of
 //                 MFMA over K = 128 -> gate arithmetic in integer C++ -> the int8 output row -> LDS -> barrier
 //   k_lq8_head  : hcat = [forward q_h[T-1], reverse q_h[0]], Linear(nd*128, num_classes), one fp32 multiply per logit
@@ -20,102 +21,42 @@
 // tools/bench_q8_lstm.py and the tests); both give the same bits.
 //
 // All adds that may wrap are unsigned; the law's refusal bounds keep every true sum inside int32.
-#include "ww_internal.h"
+#include "ww_q8_tap_gemm.h"
 
 #include <cstdlib>
 #include <cstring>
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef int v2i __attribute__((ext_vector_type(2)));
 constexpr int LQ_H = 128;                      // hidden size: the implemented size of LSTMWakeword
 constexpr int LQ_G = 4 * LQ_H;                 // gate rows of one direction, torch's order i, f, g, o
 constexpr int LQ_BLOCK = 512;                  // the recurrence: 8 waves x 16 hidden units
 constexpr int LQ_RB = 16;                      // batch rows a workgroup owns
 constexpr int LQ_HROW = LQ_H + 16;             // LDS row of q_h: 144 bytes, so the 16 rows of a ds_read_b128 group spread over banks
 constexpr int LQ_TAB = 4096;
-constexpr int PJ_BLOCK = 256;                  // the projection: 4 waves, each 64 rows x 64 gate rows per item
-constexpr int PJ_WAVES = PJ_BLOCK / 64;
-constexpr int PJ_RT = 4;
-constexpr int PJ_ROWS = 16 * PJ_RT;
+constexpr int PJ_RT = 4;                       // the projection: a wave's item is 64 rows x 64 gate rows
 
-// R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh, arithmetic shift; |a| < 2^31, 2^30 <= m < 2^31, 1 <= sh <= 62
-__device__ __forceinline__ long long lq8_round(int a, int m, int sh) {
-    return ((long long)a * (long long)m + (1ll << (sh - 1))) >> sh;
-}
-
-__device__ __forceinline__ int lq8_pack16(int a, int b) { return (int)(((unsigned)a & 0xffffu) | ((unsigned)b << 16)); }
-__device__ __forceinline__ int lq8_lo16(int d) { return (int)(short)(d & 0xffff); }
-__device__ __forceinline__ int lq8_hi16(int d) { return d >> 16; }
-
-// look(tab, a) = tab[clamp(a, -2048, 2047) + 2048]
-__device__ __forceinline__ int lq8_look(const int16_t *tab, long long a) {
-    const int i = a < -2048 ? -2048 : (a > 2047 ? 2047 : (int)a);
-    return (int)tab[i + 2048];
-}
-
-struct lq8_proj_args {
-    const int8_t *in, *w;                      // in (N, Kp); w (G, Kp), zero in its pad columns
-    const int *bias, *mult, *shift;            // (G) each; bias is the EFFECTIVE bias q_b - z_in * sum(q_w)
+// u = clamp(R(acc + bias, m, sh), -32768, 32767): the lane's sixteen gate rows c0 .. c0 + 15 of row n, two 16-byte stores
+struct LqInt16 : Q8Chan {
     int16_t *u;                                // (N, G)
-    long N;
-    int Kp, G;
-};
-
-// persistent over (row group, 64-row tile of the gate rows) items, one per wave and trip; the weights stream through L2
-__global__ __launch_bounds__(PJ_BLOCK) void k_lq8_proj(lq8_proj_args a) {
-    const int ctn = a.G / 64, kcn = a.Kp / 64;
-    const long items = (a.N + PJ_ROWS - 1) / PJ_ROWS * ctn;
-    const int lane = threadIdx.x & 63, p = lane & 15, g = lane >> 4;
-    for (long item = (long)blockIdx.x * PJ_WAVES + (threadIdx.x >> 6); item < items; item += (long)gridDim.x * PJ_WAVES) {
-        const int ct = (int)(item % ctn);
-        const long row0 = item / ctn * PJ_ROWS;
-        long n[PJ_RT];
+    __device__ void store(const v4i (&acc)[4], long n, int c0) const {
+        int q[16];
 #pragma unroll
-        for (int r = 0; r < PJ_RT; ++r) n[r] = row0 + 16 * r + p;
-        const int8_t *wrow[4];
+        for (int m = 0; m < 4; ++m) {
+            const v4i b = *(const v4i *)(bias + c0 + 4 * m);
+            const v4i mu = *(const v4i *)(mult + c0 + 4 * m);
+            const v4i sh = *(const v4i *)(shift + c0 + 4 * m);
 #pragma unroll
-        for (int m = 0; m < 4; ++m) wrow[m] = a.w + (long)(64 * ct + 16 * (p >> 2) + 4 * m + (p & 3)) * a.Kp + 16 * g;
-        v4i acc[PJ_RT][4];
-#pragma unroll
-        for (int r = 0; r < PJ_RT; ++r)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) acc[r][m] = v4i{0, 0, 0, 0};
-        for (int kc = 0; kc < kcn; ++kc) {
-            v4i wa[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) wa[m] = *(const v4i *)(wrow[m] + 64 * kc);
-#pragma unroll
-            for (int r = 0; r < PJ_RT; ++r) {
-                v4i bq = {0, 0, 0, 0};
-                if (n[r] < a.N) bq = *(const v4i *)(a.in + n[r] * a.Kp + 64 * kc + 16 * g);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[r][m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa[m], bq, acc[r][m], 0, 0, 0);
+            for (int e = 0; e < 4; ++e) {
+                const long long v = q8_round((int)((unsigned)acc[m][e] + (unsigned)b[e]), mu[e], sh[e]);
+                q[4 * m + e] = v < -32768 ? -32768 : (v > 32767 ? 32767 : (int)v);
             }
         }
-        const int c0 = 64 * ct + 16 * g;        // the lane ends with gate rows c0 .. c0 + 15 of its row
-#pragma unroll
-        for (int r = 0; r < PJ_RT; ++r) {
-            if (n[r] >= a.N) continue;
-            int q[16];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const v4i b = *(const v4i *)(a.bias + c0 + 4 * m);
-                const v4i mu = *(const v4i *)(a.mult + c0 + 4 * m);
-                const v4i sh = *(const v4i *)(a.shift + c0 + 4 * m);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const long long v = lq8_round((int)((unsigned)acc[r][m][e] + (unsigned)b[e]), mu[e], sh[e]);
-                    q[4 * m + e] = v < -32768 ? -32768 : (v > 32767 ? 32767 : (int)v);
-                }
-            }
-            int16_t *dst = a.u + n[r] * a.G + c0;
-            *(v4i *)dst = v4i{lq8_pack16(q[0], q[1]), lq8_pack16(q[2], q[3]), lq8_pack16(q[4], q[5]), lq8_pack16(q[6], q[7])};
-            *(v4i *)(dst + 8) = v4i{lq8_pack16(q[8], q[9]), lq8_pack16(q[10], q[11]), lq8_pack16(q[12], q[13]), lq8_pack16(q[14], q[15])};
-        }
+        int16_t *dst = u + n * Cout + c0;
+        *(v4i *)dst = v4i{q8_pack16(q[0], q[1]), q8_pack16(q[2], q[3]), q8_pack16(q[4], q[5]), q8_pack16(q[6], q[7])};
+        *(v4i *)(dst + 8) = v4i{q8_pack16(q[8], q[9]), q8_pack16(q[10], q[11]), q8_pack16(q[12], q[13]), q8_pack16(q[14], q[15])};
     }
-}
+};
 
 struct lq8_rec_args {
     const int16_t *u;                          // (B*T, nd*512)
@@ -189,24 +130,23 @@ template <bool TAB_LDS> __global__ __launch_bounds__(LQ_BLOCK) void k_lq8_lstm(l
                 long long pre[4];
 #pragma unroll
                 for (int G = 0; G < 4; ++G) {
-                    const int uu = (e & 1) ? lq8_hi16(uc[G][e >> 1]) : lq8_lo16(uc[G][e >> 1]);
-                    pre[G] = uu + lq8_round((int)((unsigned)acc[G][e] + (unsigned)bq[G][e]), mq[G][e], sq[G][e]);
+                    const int uu = (e & 1) ? q8_hi16(uc[G][e >> 1]) : q8_lo16(uc[G][e >> 1]);
+                    pre[G] = uu + q8_round((int)((unsigned)acc[G][e] + (unsigned)bq[G][e]), mq[G][e], sq[G][e]);
                 }
-                const int gi = lq8_look(sig, pre[0]), gf = lq8_look(sig, pre[1]), gg = lq8_look(tnh, pre[2]), go = lq8_look(sig, pre[3]);
+                const int gi = q8_look(sig, pre[0]), gf = q8_look(sig, pre[1]), gg = q8_look(tnh, pre[2]), go = q8_look(sig, pre[3]);
                 int cn = (gf * c[e] + ((gi * gg + 8) >> 4) + (1 << 14)) >> 15;      // |.| < 2^30 + 2^26 + 2^14: inside int32
                 cn = cn < -32768 ? -32768 : (cn > 32767 ? 32767 : cn);
                 c[e] = cn;
-                const int h16 = (go * lq8_look(tnh, (cn + 4) >> 3) + (1 << 14)) >> 15;
+                const int h16 = (go * q8_look(tnh, (cn + 4) >> 3) + (1 << 14)) >> 15;
                 const int qh = (h16 + 128) >> 8;
                 q[e] = qh < -128 ? -128 : (qh > 127 ? 127 : qh);
             }
-            const int packed = (int)((unsigned)(q[0] & 255) | ((unsigned)(q[1] & 255) << 8) | ((unsigned)(q[2] & 255) << 16) |
-                                     ((unsigned)(q[3] & 255) << 24));
+            const int packed = q8_pack4(q[0], q[1], q[2], q[3]);
             *(int *)(s_h[(s + 1) & 1] + p * LQ_HROW + unit0) = packed;
             if (live) *(int *)(yb + t * ystride) = packed;
             __syncthreads();                    // q_h[t] is whole before any wave's next product reads it
         }
-        if (live) *(v2i *)(a.c_n + (long)b * ystride + dir * LQ_H + unit0) = v2i{lq8_pack16(c[0], c[1]), lq8_pack16(c[2], c[3])};
+        if (live) *(v2i *)(a.c_n + (long)b * ystride + dir * LQ_H + unit0) = v2i{q8_pack16(c[0], c[1]), q8_pack16(c[2], c[3])};
     }
 }
 
@@ -233,10 +173,6 @@ __global__ __launch_bounds__(64) void k_lq8_head(const int8_t *__restrict__ y, i
     }
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-inline long lq8_round256(long n) { return (n + 255) / 256 * 256; }
-inline int lq8_pad64(int c) { return (c + 63) / 64 * 64; }
-
 }  // namespace
 
 extern "C" int ww_lq8_proj_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, const int32_t *bias, const int32_t *mult,
@@ -248,13 +184,11 @@ extern "C" int ww_lq8_proj_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, c
                "ww_lq8_proj_fwd: G=%d gate rows, expected %d or %d (LSTM), %d or %d (GRU)", G, LQ_G, 2 * LQ_G, 3 * LQ_H, 6 * LQ_H);
     WW_REQUIRE(aligned16(in) && aligned16(w) && aligned16(bias) && aligned16(mult) && aligned16(shift) && aligned16(u), WW_E_INVALID,
                "ww_lq8_proj_fwd: tensors must be 16-byte aligned");
-    lq8_proj_args a{in, w, bias, mult, shift, u, N, Kp, G};
-    const long items = (N + PJ_ROWS - 1) / PJ_ROWS * (G / 64);
-    const int grid = ww_conv_grid(ctx, (const void *)k_lq8_proj, PJ_BLOCK, 0, (items + PJ_WAVES - 1) / PJ_WAVES, 1 << 20);
+    // the pad columns of w are zero and a row past the end is not stored, so the fill value never reaches an output
+    const Q8Rows geo{in, N, Kp, 0};
+    const LqInt16 epi{{bias, mult, shift, G}, u};
     ww_prof_scope prof(ctx, WW_K_LINEAR, (hipStream_t)stream);
-    hipLaunchKernelGGL(k_lq8_proj, dim3(grid), dim3(PJ_BLOCK), 0, (hipStream_t)stream, a);
-    WW_LAUNCH_CHECK();
-    return WW_OK;
+    return q8_tap_launch_stream<Q8Rows, LqInt16, PJ_RT>(ctx, geo, epi, w, (hipStream_t)stream);
 }
 
 extern "C" int ww_lq8_lstm_layer_fwd(ww_ctx *ctx, const int16_t *u, const int8_t *w_hh, const int32_t *bias, const int32_t *mult,
@@ -301,9 +235,9 @@ extern "C" size_t ww_lq8_lstm_workspace_bytes(int B, int T, int input_size, int 
         num_directions > 2)
         return 0;
     const long N = (long)B * T;
-    const long layer = lq8_round256(N * num_directions * LQ_G * 2) + lq8_round256(N * num_directions * LQ_H) +
-                       lq8_round256((long)B * num_directions * LQ_H * 2);
-    return (size_t)(lq8_round256(N * lq8_pad64(input_size)) + num_layers * layer + lq8_round256((long)B * num_directions * LQ_H));
+    const long layer = q8_round256(N * num_directions * LQ_G * 2) + q8_round256(N * num_directions * LQ_H) +
+                       q8_round256((long)B * num_directions * LQ_H * 2);
+    return (size_t)(q8_round256(N * q8_pad64(input_size)) + num_layers * layer + q8_round256((long)B * num_directions * LQ_H));
 }
 
 extern "C" int ww_lq8_lstm_fwd(ww_ctx *ctx, const void *const *tab, const ww_lq8_io *io, const float *x, int B, int T, void *ws,
@@ -321,15 +255,15 @@ extern "C" int ww_lq8_lstm_fwd(ww_ctx *ctx, const void *const *tab, const ww_lq8
     auto i32 = [&](int i) { return (const int32_t *)tab[i]; };
     const long N = (long)B * T;
     int8_t *cur = (int8_t *)ws;
-    int Kp = lq8_pad64(F);
+    int Kp = q8_pad64(F);
     int rc = ww_tq8_quantize_bt(ctx, x, B, F, T, Kp, io->in_scale, io->in_zero, cur, stream);
     if (rc != WW_OK) return rc;
-    int8_t *next = cur + lq8_round256(N * Kp);
+    int8_t *next = cur + q8_round256(N * Kp);
     for (int k = 0; k < L; ++k) {
         const int p = WW_LQ8_LAYER_NPTR * k;
         int16_t *u = (int16_t *)next;
-        int8_t *y = next + lq8_round256(N * nd * LQ_G * 2);
-        int16_t *c_n = (int16_t *)(y + lq8_round256(N * nd * LQ_H));
+        int8_t *y = next + q8_round256(N * nd * LQ_G * 2);
+        int16_t *c_n = (int16_t *)(y + q8_round256(N * nd * LQ_H));
         rc = ww_lq8_proj_fwd(ctx, cur, i8(p), i32(p + 1), i32(p + 2), i32(p + 3), N, Kp, nd * LQ_G, u, stream);
         if (rc != WW_OK) return rc;
         rc = ww_lq8_lstm_layer_fwd(ctx, u, i8(p + 4), i32(p + 5), i32(p + 6), i32(p + 7), (const int16_t *)tab[np + 3],
@@ -337,7 +271,7 @@ extern "C" int ww_lq8_lstm_fwd(ww_ctx *ctx, const void *const *tab, const ww_lq8
         if (rc != WW_OK) return rc;
         cur = y;
         Kp = nd * LQ_H;
-        next = (int8_t *)c_n + lq8_round256((long)B * nd * LQ_H * 2);
+        next = (int8_t *)c_n + q8_round256((long)B * nd * LQ_H * 2);
     }
     return ww_lq8_head_fwd(ctx, cur, B, T, nd, i8(np), i32(np + 1), (const float *)tab[np + 2], io->num_classes, next, logits, stream);
 }

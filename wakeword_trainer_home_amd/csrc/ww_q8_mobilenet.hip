@@ -1,36 +1,31 @@
 // Integer-only inference of an exported int8 MobileNetV3Wakeword bundle (DESIGN.md "Export", the int8 law, subsection "MobileNetV3").
-//   k_mq8_pw   : 1x1 conv (expand, project, 96 -> 576, classifier.0 on the pooled rows) as a GEMM on v_mfma_i32_16x16x64_i8, with
-//                one of three epilogues: RELU   out = clamp(-128 + R(acc), -128, 127)
-//                                        HSWISH u = clamp(z_u + R(acc), -128, 127), out = T[u + 128]      (T: the layer's int8 table)
-//                                        SIGNED out = clamp(R(acc) [+ R(res, m_r, sh_r)], -128, 127)       (z_out = 0, res signed)
+//   the 1x1 conv : expand, project, 96 -> 576, classifier.0 on the pooled rows: the one-segment geometry of the int8 tap-GEMM core
+//                (ww_q8_tap_gemm.h: the lane map), one 16-row tile per wave and item, weights streamed, with one of three epilogues:
+//                    RELU   out = clamp(-128 + R(acc), -128, 127)
+//                    HSWISH u = clamp(z_u + R(acc), -128, 127), out = T[u + 128]      (T: the layer's int8 table)
+//                    SIGNED out = clamp(R(acc) [+ R(res, m_r, sh_r)], -128, 127)       (z_out = 0, res signed)
 //   k_mq8_dw   : depthwise k x k (k = 3, 5), stride 1 or 2, pad k / 2, and the 3x3 stride-2 one-channel stem: VALU int32, one lane per
 //                (output pixel, 16 channels), RELU or HSWISH epilogue
 //   k_mq8_se   : squeeze-excitation, one workgroup per image: channel sums through LDS, the pooled vector, fc1 + ReLU, fc2 + the
 //                Hardsigmoid gate G (uint8, scale 1 / 255)
 //   k_mq8_gate : y = clamp(z_a + R((q_a - z_a) G, m_g, sh_g), -128, 127), a pass over the tensor (the pass form; in the fused form the
-//                projection's k_mq8_pw applies the same expression to its pixel fragments and y is never stored)
+//                projection's geometry MqGated applies the same expression to its pixel fragments and y is never stored)
 //   k_mq8_pool, k_mq8_fc : the head's pool (one workgroup per image) and classifier.3 (one wave per class)
 // Quantisation is ww_q8_quantize.  Activations are int8 NHWC (B,H,W,Cp), Cp = the channel count rounded up to 64: a pixel's channels are
 // whole 64-deep K chunks of the instruction.  Pad channels hold the tensor's zero point and meet zero weights; pad OUTPUT channels have
 // zero weights, a zero bias and m = 2^30, sh = 31, so they come out as the zero point of the tensor written (T[z_u + 128] = z_out).
-//
-// The product, under the lane map of k_q8_pw / k_rq8_conv (DESIGN.md mfma_i8_map): D = A x B, A = weights (row = output channel),
-// B = pixels (column = row l & 15 of the tile).  Lane l supplies, for K chunk kc, the 16 bytes [64 kc + 16 g, + 16), g = l >> 4, of ITS
-// pixel and the same 16 k of weight row 16 (i >> 2) + 4 m + (i & 3), i = l & 15, for product m = 0..3: the lane ends with the sixteen
-// consecutive channels 64 ct + 16 g .. + 15 of its row and stores one 16-byte vector.  Rows are pixels of the whole batch, so a 16-row
-// tile may span images.  Persistent over (row tile, channel tile) items, one per wave and trip.
+// Rows of the 1x1 conv are pixels of the whole batch, so a 16-row tile may span images.
 //
 // bias arguments of the conv kernels are the EFFECTIVE bias q_b - z_in * sum(q_w) (host, once per bundle), so "a source pixel outside
 // the image" and "a pad channel" are both z_in bytes.  k_mq8_se and k_mq8_fc subtract the zero point themselves and take the law's own
 // q_b.  All adds that may wrap are unsigned.
-#include "ww_internal.h"
+#include "ww_q8_tap_gemm.h"
 
 #include <cstdlib>
 #include <cstring>
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int MQ_BLOCK = 256;
 constexpr int MQ_WAVES = MQ_BLOCK / 64;
 constexpr int MQ_MAX_CP = 1024;                // widest tensor the one-workgroup-per-image kernels sum (their LDS image)
@@ -38,113 +33,80 @@ constexpr int MQ_MAX_SQ = 256;                 // widest squeeze vector of k_mq8
 enum { MQ_RELU = 0, MQ_HSWISH = 1, MQ_SIGNED = 2 };
 constexpr bool MQ_GATE_FUSED_DEFAULT = false;  // decided by the A/B of tools/bench_q8_mobilenetv3.py (profiles/q8_mobilenetv3_measured.txt)
 
-// R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh, arithmetic shift; |a| < 2^31, 2^30 <= m < 2^31, 1 <= sh <= 62
-__device__ __forceinline__ long long mq8_round(int a, int m, int sh) {
-    return ((long long)a * (long long)m + (1ll << (sh - 1))) >> sh;
+// the RELU and HSWISH epilogues of one value r = R(acc, m, sh); tab: the layer's table in LDS
+template <int EP> __device__ __forceinline__ int mq8_act(long long r, int zu, const signed char *tab) {
+    if (EP == MQ_RELU) return q8_clamp(r);
+    return (int)tab[q8_clamp_signed(r + zu) + 128];
 }
 
-__device__ __forceinline__ int mq8_clamp8(long long r) { return (int)(r < -128 ? -128 : (r > 127 ? 127 : r)); }
-
-template <int J> __device__ __forceinline__ int mq8_byte(int d) { return (int)(signed char)((unsigned)d >> (8 * J)); }
-
-__device__ __forceinline__ int mq8_pack4(int a, int b, int c, int d) {
-    return (int)((unsigned)(a & 255) | ((unsigned)(b & 255) << 8) | ((unsigned)(c & 255) << 16) | ((unsigned)(d & 255) << 24));
-}
-
-__device__ __forceinline__ void mq8_unpack4(int d, int (&q)[4]) {
-    q[0] = mq8_byte<0>(d); q[1] = mq8_byte<1>(d); q[2] = mq8_byte<2>(d); q[3] = mq8_byte<3>(d);
-}
-
-// the RELU and HSWISH epilogues of one value; tab: the layer's table in LDS
-template <int EP> __device__ __forceinline__ int mq8_finish(int acc, int m, int sh, int zu, const signed char *tab) {
-    const long long r = mq8_round(acc, m, sh);
-    if (EP == MQ_RELU) return mq8_clamp8(r - 128);
-    return (int)tab[mq8_clamp8(r + zu) + 128];
-}
-
-struct mq8_pw_args {
-    const int8_t *in, *w;                      // in (N, Cin); w (Cout, Cin) [out][in]
-    const int *bias, *mult, *shift;            // (Cout) each
-    const int8_t *tab;                         // HSWISH: int8 (256)
-    const int8_t *res;                         // SIGNED: the residual tensor (N, Cout), zero point 0, or null
-    int8_t *out;                               // (N, Cout)
+// The fused gate form of the one-segment geometry: `in` is the depthwise output a, not y; the gate multiply
+// y = clamp(z_a + R((q_a - z_a) G, m_g, sh_g)) is applied to the pixel fragment as it is loaded, so it stays in registers and no y
+// tensor is written or read.  gate: (N / HW, Cin), the row of the image a pixel belongs to.
+struct MqGated {
+    const int8_t *in;
     long N;
-    int Cin, Cout, zfill, zu, res_m, res_sh;
-    const uint8_t *gate;                       // GATED: the squeeze-excitation gate (N / HW, Cin) of the image a row belongs to
+    int Cin, zfill;
+    const uint8_t *gate;
     int HW, zero, gate_m, gate_sh;
+    struct Row { long n; };
+    struct Src { const int8_t *p; const uint8_t *gp; bool live; };
+    __device__ int nseg() const { return 1; }
+    __device__ int K() const { return Cin; }
+    __device__ void row(long n, Row &r) const { r.n = n; }
+    __device__ void seg(const Row &r, int, int g, Src &s) const {
+        s.live = r.n < N;
+        s.p = in + r.n * Cin + 16 * g;                          // both dereferenced only where live
+        s.gp = gate + r.n / HW * Cin + 16 * g;
+    }
+    __device__ v4i load(const Src &s, int kc) const {
+        v4i bq = {zfill, zfill, zfill, zfill};
+        if (s.live) {
+            bq = *(const v4i *)(s.p + 64 * kc);
+            const v4i gv = *(const v4i *)(s.gp + 64 * kc);
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                int q[4];
+                q8_unpack4(bq[d], q);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    q[e] = q8_clamp_signed(zero + q8_round((q[e] - zero) * (int)(((unsigned)gv[d] >> (8 * e)) & 255u), gate_m, gate_sh));
+                bq[d] = q8_pack4(q[0], q[1], q[2], q[3]);
+            }
+        }
+        return bq;
+    }
 };
 
-// GATED (the fused gate form): `in` is the depthwise output a, not y; the gate multiply y = clamp(z_a + R((q_a - z_a) G, m_g, sh_g))
-// is applied to the pixel fragment as it is loaded, so it stays in registers and no y tensor is written or read.
-template <int EP, bool GATED> __global__ __launch_bounds__(MQ_BLOCK) void k_mq8_pw(mq8_pw_args a) {
-    __shared__ signed char s_tab[256];
-    if (EP == MQ_HSWISH) {
-        s_tab[threadIdx.x] = a.tab[threadIdx.x];
-        __syncthreads();
-    }
-    const int lane = threadIdx.x & 63, p = lane & 15, g = lane >> 4;
-    const int ctn = a.Cout / 64, kcn = a.Cin / 64;
-    const long items = (a.N + 15) / 16 * ctn;
-    const v4i zvec = {a.zfill, a.zfill, a.zfill, a.zfill};
-    for (long item = (long)blockIdx.x * MQ_WAVES + (threadIdx.x >> 6); item < items; item += (long)gridDim.x * MQ_WAVES) {
-        const int ct = (int)(item % ctn);
-        const long n = item / ctn * 16 + p;
-        const bool ok = n < a.N;
-        const int8_t *src = a.in + n * a.Cin + 16 * g;                  // dereferenced only where ok
-        const uint8_t *gsrc = GATED && ok ? a.gate + n / a.HW * a.Cin + 16 * g : nullptr;
-        const int8_t *wrow[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) wrow[m] = a.w + (long)(64 * ct + 16 * (p >> 2) + 4 * m + (p & 3)) * a.Cin + 16 * g;
-        v4i acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = v4i{0, 0, 0, 0};
-        for (int kc = 0; kc < kcn; ++kc) {
-            v4i bq = zvec;
-            if (ok) bq = *(const v4i *)(src + 64 * kc);
-            if (GATED && ok) {
-                const v4i gv = *(const v4i *)(gsrc + 64 * kc);
-#pragma unroll
-                for (int d = 0; d < 4; ++d) {
-                    int q[4];
-                    mq8_unpack4(bq[d], q);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        q[e] = mq8_clamp8(a.zero + mq8_round((q[e] - a.zero) * (int)(((unsigned)gv[d] >> (8 * e)) & 255u), a.gate_m, a.gate_sh));
-                    bq[d] = mq8_pack4(q[0], q[1], q[2], q[3]);
-                }
-            }
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                acc[m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(*(const v4i *)(wrow[m] + 64 * kc), bq, acc[m], 0, 0, 0);
+__shared__ signed char mq8_s_tab[256];         // the Hardswish table of the 1x1 conv a workgroup runs (MqAct<MQ_HSWISH>)
+
+template <int EP> struct MqAct : Q8Chan {      // RELU and HSWISH
+    const int8_t *tab;                         // HSWISH: int8 (256)
+    int8_t *out;                               // (N, Cout)
+    int zu;
+    __device__ void begin() const {
+        if (EP == MQ_HSWISH) {
+            mq8_s_tab[threadIdx.x] = tab[threadIdx.x];
+            __syncthreads();
         }
-        if (!ok) continue;
-        const int c0 = 64 * ct + 16 * g;
+    }
+    __device__ void store(const v4i (&acc)[4], long n, int c0) const {
+        q8_tap_store(*this, acc, v4i{0, 0, 0, 0}, out, n, c0, [&](long long v, int) { return mq8_act<EP>(v, zu, mq8_s_tab); });
+    }
+};
+
+struct MqSigned : Q8Chan {                     // out = clamp(R(acc) [+ R(res, m_r, sh_r)]); res: (N, Cout), zero point 0, or null
+    const int8_t *res;
+    int8_t *out;
+    int res_m, res_sh;
+    __device__ void store(const v4i (&acc)[4], long n, int c0) const {
         v4i hv = {0, 0, 0, 0};
-        if (EP == MQ_SIGNED && a.res) hv = *(const v4i *)(a.res + n * a.Cout + c0);
-        v4i ov;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const v4i b = *(const v4i *)(a.bias + c0 + 4 * m);
-            const v4i mu = *(const v4i *)(a.mult + c0 + 4 * m);
-            const v4i sh = *(const v4i *)(a.shift + c0 + 4 * m);
-            int h[4], q[4];
-            mq8_unpack4(hv[m], h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int v = (int)((unsigned)acc[m][e] + (unsigned)b[e]);
-                if (EP == MQ_SIGNED) {
-                    long long r = mq8_round(v, mu[e], sh[e]);
-                    if (a.res) r += mq8_round(h[e], a.res_m, a.res_sh);
-                    q[e] = mq8_clamp8(r);
-                } else {
-                    q[e] = mq8_finish<EP>(v, mu[e], sh[e], a.zu, s_tab);
-                }
-            }
-            ov[m] = mq8_pack4(q[0], q[1], q[2], q[3]);
-        }
-        *(v4i *)(a.out + n * a.Cout + c0) = ov;
+        if (res) hv = *(const v4i *)(res + n * Cout + c0);
+        q8_tap_store(*this, acc, hv, out, n, c0, [&](long long v, int h) {
+            if (res) v += q8_round(h, res_m, res_sh);
+            return q8_clamp_signed(v);
+        });
     }
-}
+};
 
 struct mq8_dw_args {
     const int8_t *in, *w;                      // in (B,H,W,Cp) -- STEM: (B,H,W) --; w (k k, Cp) [tap][channel]
@@ -191,8 +153,8 @@ template <int EP, bool STEM> __global__ __launch_bounds__(MQ_BLOCK) void k_mq8_d
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
                     int q[4], ww[4];
-                    mq8_unpack4(x[d], q);
-                    mq8_unpack4(wv[d], ww);
+                    q8_unpack4(x[d], q);
+                    q8_unpack4(wv[d], ww);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[4 * d + e] += ww[e] * q[e];
                 }
@@ -207,8 +169,8 @@ template <int EP, bool STEM> __global__ __launch_bounds__(MQ_BLOCK) void k_mq8_d
             int q[4];
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                q[e] = mq8_finish<EP>((int)((unsigned)acc[4 * d + e] + (unsigned)bb[e]), mu[e], sh[e], a.zu, s_tab);
-            ov[d] = mq8_pack4(q[0], q[1], q[2], q[3]);
+                q[e] = mq8_act<EP>(q8_round((int)((unsigned)acc[4 * d + e] + (unsigned)bb[e]), mu[e], sh[e]), a.zu, s_tab);
+            ov[d] = q8_pack4(q[0], q[1], q[2], q[3]);
         }
         *(v4i *)(a.out + pix * a.Cp + 16 * v) = ov;
     }
@@ -224,7 +186,7 @@ __device__ __forceinline__ void mq8_pool_image(const int8_t *__restrict__ img, i
         int sum[4] = {0, 0, 0, 0};
         for (int t = slot; t < HW; t += slots) {
             int q[4];
-            mq8_unpack4(*(const int *)(img + (long)t * Cp + 4 * col), q);
+            q8_unpack4(*(const int *)(img + (long)t * Cp + 4 * col), q);
 #pragma unroll
             for (int e = 0; e < 4; ++e) sum[e] += q[e] - zero;
         }
@@ -235,7 +197,7 @@ __device__ __forceinline__ void mq8_pool_image(const int8_t *__restrict__ img, i
     for (int c = tid; c < Cp; c += MQ_BLOCK) {
         int S = 0;
         for (int s = 0; s < slots; ++s) S += s_part[s * Cp + c];
-        const int pq = mq8_clamp8(zero + mq8_round(S, pm, psh));
+        const int pq = q8_clamp_signed(zero + q8_round(S, pm, psh));
         if (pool_out) pool_out[(long)blockIdx.x * Cp + c] = (int8_t)pq;
         s_pool[c] = pq - zero;
     }
@@ -269,7 +231,7 @@ __global__ __launch_bounds__(MQ_BLOCK) void k_mq8_se(mq8_se_args a) {
         unsigned acc = (unsigned)a.b1[j];
         const int8_t *w = a.w1 + (long)j * a.C;
         for (int c = 0; c < a.C; ++c) acc += (unsigned)((int)w[c] * s_pool[c]);
-        const int hq = mq8_clamp8(mq8_round((int)acc, a.m1[j], a.sh1[j]) - 128);
+        const int hq = q8_clamp_signed(q8_round((int)acc, a.m1[j], a.sh1[j]) - 128);
         a.h[b * a.Csq + j] = (int8_t)hq;
         s_h[j] = hq + 128;
     }
@@ -280,7 +242,7 @@ __global__ __launch_bounds__(MQ_BLOCK) void k_mq8_se(mq8_se_args a) {
             unsigned acc = (unsigned)a.b2[c];
             const int8_t *w = a.w2 + (long)c * a.Csq;
             for (int j = 0; j < a.Csq; ++j) acc += (unsigned)((int)w[j] * s_h[j]);
-            const long long r = mq8_round((int)acc, a.m2[c], a.sh2[c]);
+            const long long r = q8_round((int)acc, a.m2[c], a.sh2[c]);
             gq = (int)(r < 0 ? 0 : (r > 255 ? 255 : r));
         }
         a.gate[b * a.Cp + c] = (uint8_t)gq;
@@ -300,13 +262,13 @@ __global__ __launch_bounds__(MQ_BLOCK) void k_mq8_gate(const int8_t *__restrict_
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             int q[4], y[4];
-            mq8_unpack4(x[d], q);
+            q8_unpack4(x[d], q);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int G = (int)(((unsigned)gv[d] >> (8 * e)) & 255u);
-                y[e] = mq8_clamp8(zero + mq8_round((q[e] - zero) * G, gm, gsh));
+                y[e] = q8_clamp_signed(zero + q8_round((q[e] - zero) * G, gm, gsh));
             }
-            ov[d] = mq8_pack4(y[0], y[1], y[2], y[3]);
+            ov[d] = q8_pack4(y[0], y[1], y[2], y[3]);
         }
         *(v4i *)(out + pix * Cp + 16 * v) = ov;
     }
@@ -327,11 +289,7 @@ __global__ __launch_bounds__(MQ_BLOCK) void k_mq8_fc(const int8_t *__restrict__ 
     }
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-inline long mq8_round256(long n) { return (n + 255) / 256 * 256; }
-inline int mq8_pad64(int c) { return (c + 63) / 64 * 64; }
 inline int mq8_half(int n) { return (n - 1) / 2 + 1; }           // floor((n + 2 p - k) / 2) + 1 for (k, p) = (3, 1) and (5, 2)
-inline bool mq8_mult_ok(int m, int sh) { return m >= (1 << 30) && sh >= 1 && sh <= 62; }
 inline bool mq8_zero_ok(int z) { return z >= -128 && z <= 127; }
 
 template <int EP, bool STEM> int mq8_launch_dw(ww_ctx *ctx, const mq8_dw_args &a, hipStream_t st) {
@@ -357,13 +315,13 @@ struct mq8_plan {                              // byte offsets of every tensor t
 bool mq8_make_plan(int B, int F, int T, mq8_plan *p) {
     if (B < 1 || F < 1 || T < 1 || (long)B * F * T > (1l << 28)) return false;
     long off = 0;
-    auto take = [&](long bytes) { const long at = off; off += mq8_round256(bytes); return at; };
+    auto take = [&](long bytes) { const long at = off; off += q8_round256(bytes); return at; };
     int H = mq8_half(F), W = mq8_half(T);
     p->xq = take((long)B * F * T);
     p->stem = take((long)B * H * W * 64);
     for (int i = 0; i < WW_MQ8_BLOCKS; ++i) {
         const mq8_block &c = MQ_CONF[i];
-        const int ep = mq8_pad64(c.exp);
+        const int ep = q8_pad64(c.exp);
         p->Hin[i] = H; p->Win[i] = W;
         p->expand[i] = c.exp != c.cin ? take((long)B * H * W * ep) : -1;
         if (c.stride == 2) { H = mq8_half(H); W = mq8_half(W); }
@@ -373,7 +331,7 @@ bool mq8_make_plan(int B, int F, int T, mq8_plan *p) {
         p->h[i] = c.sq ? take((long)B * c.sq) : -1;
         p->gate[i] = c.sq ? take((long)B * ep) : -1;
         p->y[i] = c.sq ? take((long)B * H * W * ep) : -1;
-        p->out[i] = take((long)B * H * W * mq8_pad64(c.cout));
+        p->out[i] = take((long)B * H * W * q8_pad64(c.cout));
     }
     p->last = take((long)B * H * W * WW_MQ8_LAST);
     p->pool = take((long)B * WW_MQ8_LAST);
@@ -389,7 +347,7 @@ extern "C" int ww_mq8_conv1x1_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w
                                   const int8_t *residual, int res_mult, int res_shift, const uint8_t *gate, int HW, int gate_mult,
                                   int gate_shift, int8_t *out, ww_stream_t stream) {
     WW_REQUIRE(ctx && in && w && bias && mult && shift && out, WW_E_INVALID, "ww_mq8_conv1x1_fwd: null argument");
-    WW_REQUIRE(!gate || (epilogue == WW_MQ8_SIGNED && HW >= 1 && N % HW == 0 && mq8_mult_ok(gate_mult, gate_shift) && aligned16(gate)),
+    WW_REQUIRE(!gate || (epilogue == WW_MQ8_SIGNED && HW >= 1 && N % HW == 0 && q8_mult_ok(gate_mult, gate_shift) && aligned16(gate)),
                WW_E_INVALID, "ww_mq8_conv1x1_fwd: a gate goes with the signed epilogue, HW = %d dividing N, multiplier %d / shift %d", HW,
                gate_mult, gate_shift);
     WW_REQUIRE(N >= 1 && N <= (1l << 31), WW_E_INVALID, "ww_mq8_conv1x1_fwd: N=%ld", N);
@@ -401,31 +359,23 @@ extern "C" int ww_mq8_conv1x1_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w
     WW_REQUIRE((epilogue == WW_MQ8_HSWISH) == (tab != nullptr), WW_E_INVALID,
                "ww_mq8_conv1x1_fwd: the Hardswish epilogue, and only it, takes a table");
     WW_REQUIRE(!residual || epilogue == WW_MQ8_SIGNED, WW_E_INVALID, "ww_mq8_conv1x1_fwd: only the signed epilogue takes a residual");
-    WW_REQUIRE(!residual || mq8_mult_ok(res_mult, res_shift), WW_E_INVALID,
+    WW_REQUIRE(!residual || q8_mult_ok(res_mult, res_shift), WW_E_INVALID,
                "ww_mq8_conv1x1_fwd: residual multiplier %d / shift %d out of range", res_mult, res_shift);
     WW_REQUIRE(aligned16(in) && aligned16(w) && aligned16(bias) && aligned16(mult) && aligned16(shift) && aligned16(out) &&
                aligned16(residual), WW_E_INVALID, "ww_mq8_conv1x1_fwd: tensors must be 16-byte aligned");
     WW_REQUIRE(in != out && residual != out, WW_E_INVALID, "ww_mq8_conv1x1_fwd: in place");
-    mq8_pw_args a{in, w, bias, mult, shift, tab, residual, out, N, Cin, Cout, (zero & 255) * 0x01010101, zero_u, res_mult, res_shift,
-                  gate, HW, zero, gate_mult, gate_shift};
+    const Q8Rows geo{in, N, Cin, (zero & 255) * 0x01010101};
+    const Q8Chan chan{bias, mult, shift, Cout};
     hipStream_t st = (hipStream_t)stream;
-    const long items = (N + 15) / 16 * (Cout / 64), want = (items + MQ_WAVES - 1) / MQ_WAVES;
     ww_prof_scope prof(ctx, WW_K_PW_FWD, st);
-    if (epilogue == WW_MQ8_RELU) {
-        const int grid = ww_conv_grid(ctx, (const void *)k_mq8_pw<MQ_RELU, false>, MQ_BLOCK, 0, want, 1 << 20);
-        hipLaunchKernelGGL((k_mq8_pw<MQ_RELU, false>), dim3(grid), dim3(MQ_BLOCK), 0, st, a);
-    } else if (epilogue == WW_MQ8_HSWISH) {
-        const int grid = ww_conv_grid(ctx, (const void *)k_mq8_pw<MQ_HSWISH, false>, MQ_BLOCK, 0, want, 1 << 20);
-        hipLaunchKernelGGL((k_mq8_pw<MQ_HSWISH, false>), dim3(grid), dim3(MQ_BLOCK), 0, st, a);
-    } else if (gate) {
-        const int grid = ww_conv_grid(ctx, (const void *)k_mq8_pw<MQ_SIGNED, true>, MQ_BLOCK, 0, want, 1 << 20);
-        hipLaunchKernelGGL((k_mq8_pw<MQ_SIGNED, true>), dim3(grid), dim3(MQ_BLOCK), 0, st, a);
-    } else {
-        const int grid = ww_conv_grid(ctx, (const void *)k_mq8_pw<MQ_SIGNED, false>, MQ_BLOCK, 0, want, 1 << 20);
-        hipLaunchKernelGGL((k_mq8_pw<MQ_SIGNED, false>), dim3(grid), dim3(MQ_BLOCK), 0, st, a);
+    if (epilogue == WW_MQ8_RELU) return q8_tap_launch_stream<Q8Rows, MqAct<MQ_RELU>, 1>(ctx, geo, {chan, tab, out, zero_u}, w, st);
+    if (epilogue == WW_MQ8_HSWISH) return q8_tap_launch_stream<Q8Rows, MqAct<MQ_HSWISH>, 1>(ctx, geo, {chan, tab, out, zero_u}, w, st);
+    const MqSigned epi{chan, residual, out, res_mult, res_shift};
+    if (gate) {
+        const MqGated gated{in, N, Cin, geo.zfill, gate, HW, zero, gate_mult, gate_shift};
+        return q8_tap_launch_stream<MqGated, MqSigned, 1>(ctx, gated, epi, w, st);
     }
-    WW_LAUNCH_CHECK();
-    return WW_OK;
+    return q8_tap_launch_stream<Q8Rows, MqSigned, 1>(ctx, geo, epi, w, st);
 }
 
 extern "C" int ww_mq8_dwconv_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w, const int32_t *bias, const int32_t *mult,
@@ -470,9 +420,9 @@ extern "C" int ww_mq8_se_fwd(ww_ctx *ctx, const int8_t *in, int B, int HW, int C
     WW_REQUIRE(ctx && in && w1 && b1 && m1 && sh1 && w2 && b2 && m2 && sh2 && pool_out && h_out && gate_out, WW_E_INVALID,
                "ww_mq8_se_fwd: null argument");
     WW_REQUIRE(B >= 1 && HW >= 1 && HW <= (1 << 22), WW_E_INVALID, "ww_mq8_se_fwd: B=%d HW=%d", B, HW);
-    WW_REQUIRE(C >= 1 && Cp == mq8_pad64(C) && Cp <= MQ_MAX_CP && Csq >= 1 && Csq <= MQ_MAX_SQ, WW_E_INVALID,
+    WW_REQUIRE(C >= 1 && Cp == q8_pad64(C) && Cp <= MQ_MAX_CP && Csq >= 1 && Csq <= MQ_MAX_SQ, WW_E_INVALID,
                "ww_mq8_se_fwd: C=%d Cp=%d Csq=%d (Cp = C rounded up to 64, at most %d; Csq at most %d)", C, Cp, Csq, MQ_MAX_CP, MQ_MAX_SQ);
-    WW_REQUIRE(mq8_zero_ok(zero) && mq8_mult_ok(pool_mult, pool_shift), WW_E_INVALID,
+    WW_REQUIRE(mq8_zero_ok(zero) && q8_mult_ok(pool_mult, pool_shift), WW_E_INVALID,
                "ww_mq8_se_fwd: zero point %d / multiplier %d / shift %d out of range", zero, pool_mult, pool_shift);
     WW_REQUIRE(aligned16(in) && aligned16(gate_out), WW_E_INVALID, "ww_mq8_se_fwd: the activations and the gate must be 16-byte aligned");
     mq8_se_args a{in, w1, w2, b1, m1, sh1, b2, m2, sh2, pool_out, h_out, gate_out, HW, C, Cp, Csq, zero, pool_mult, pool_shift};
@@ -487,7 +437,7 @@ extern "C" int ww_mq8_gate_fwd(ww_ctx *ctx, const int8_t *in, const uint8_t *gat
     WW_REQUIRE(ctx && in && gate && out, WW_E_INVALID, "ww_mq8_gate_fwd: null argument");
     WW_REQUIRE(B >= 1 && HW >= 1 && (long)B * HW <= (1l << 31) && Cp >= 16 && Cp % 16 == 0, WW_E_INVALID,
                "ww_mq8_gate_fwd: B=%d HW=%d Cp=%d", B, HW, Cp);
-    WW_REQUIRE(mq8_zero_ok(zero) && mq8_mult_ok(gate_mult, gate_shift), WW_E_INVALID,
+    WW_REQUIRE(mq8_zero_ok(zero) && q8_mult_ok(gate_mult, gate_shift), WW_E_INVALID,
                "ww_mq8_gate_fwd: zero point %d / multiplier %d / shift %d out of range", zero, gate_mult, gate_shift);
     WW_REQUIRE(aligned16(in) && aligned16(gate) && aligned16(out), WW_E_INVALID, "ww_mq8_gate_fwd: tensors must be 16-byte aligned");
     const long nvec = (long)B * HW * (Cp / 16);
@@ -507,7 +457,7 @@ extern "C" int ww_mq8_head_fwd(ww_ctx *ctx, const int8_t *in, int B, int HW, int
                "ww_mq8_head_fwd: null argument");
     WW_REQUIRE(B >= 1 && HW >= 1 && HW <= (1 << 22), WW_E_INVALID, "ww_mq8_head_fwd: B=%d HW=%d", B, HW);
     WW_REQUIRE(num_classes >= 2 && num_classes <= 64, WW_E_INVALID, "ww_mq8_head_fwd: num_classes=%d outside [2, 64]", num_classes);
-    WW_REQUIRE(mq8_zero_ok(zero) && mq8_zero_ok(zero_h) && mq8_mult_ok(pool_mult, pool_shift), WW_E_INVALID,
+    WW_REQUIRE(mq8_zero_ok(zero) && mq8_zero_ok(zero_h) && q8_mult_ok(pool_mult, pool_shift), WW_E_INVALID,
                "ww_mq8_head_fwd: zero points %d / %d, multiplier %d / shift %d out of range", zero, zero_h, pool_mult, pool_shift);
     WW_REQUIRE(aligned16(in) && aligned16(pool_out), WW_E_INVALID, "ww_mq8_head_fwd: the activations must be 16-byte aligned");
     {
@@ -562,7 +512,7 @@ extern "C" int ww_mq8_mobilenetv3_fwd(ww_ctx *ctx, const void *const *tab, const
     int zcur = io->stem_zo;
     for (int i = 0; i < WW_MQ8_BLOCKS; ++i) {
         const mq8_block &c = MQ_CONF[i];
-        const int t = 5 + WW_MQ8_BLOCK_NPTR * i, cinp = mq8_pad64(c.cin), ep = mq8_pad64(c.exp), ntab = c.hs ? 5 : 4;
+        const int t = 5 + WW_MQ8_BLOCK_NPTR * i, cinp = q8_pad64(c.cin), ep = q8_pad64(c.exp), ntab = c.hs ? 5 : 4;
         const int act = c.hs ? WW_MQ8_HSWISH : WW_MQ8_RELU;
         const int8_t *block_in = cur;
         if (c.exp != c.cin) {
@@ -599,7 +549,7 @@ extern "C" int ww_mq8_mobilenetv3_fwd(ww_ctx *ctx, const void *const *tab, const
         }
         WW_REQUIRE(have(t + 18, 4), WW_E_INVALID, "ww_mq8_mobilenetv3_fwd: block %d: a projection table entry is null", i);
         const bool res = c.stride == 1 && c.cin == c.cout;
-        rc = ww_mq8_conv1x1_fwd(ctx, cur, i8(t + 18), i32(t + 19), i32(t + 20), i32(t + 21), (long)B * HW, ep, mq8_pad64(c.cout), zcur,
+        rc = ww_mq8_conv1x1_fwd(ctx, cur, i8(t + 18), i32(t + 19), i32(t + 20), i32(t + 21), (long)B * HW, ep, q8_pad64(c.cout), zcur,
                                 WW_MQ8_SIGNED, 0, nullptr, res ? block_in : nullptr, io->res_mult[i], io->res_shift[i], gate, HW,
                                 io->gate_mult[i], io->gate_shift[i], base + p.out[i], stream);
         if (rc != WW_OK) return rc;

@@ -1,180 +1,83 @@
 // Integer-only inference of an exported int8 ResNet18Wakeword bundle (DESIGN.md "Export", the int8 law, subsection "ResNet18").
 //   k_rq8_stem    : 7x7 s2 p3, 1 -> 64 channels, on the matrix pipe: the 49-tap window padded to 64 is one K chunk
 //   k_rq8_maxpool : 3x3 s2 p1 maximum over the window positions inside the image; nothing is rounded
-//   k_rq8_conv    : dense k x k (k = 1, 3), stride 1 or 2, pad k / 2 Conv2d as an implicit GEMM on v_mfma_i32_16x16x64_i8, with
-//                   one of three epilogues: RELU  out = clamp(-128 + R(acc), -128, 127)            (z_out = -128)
-//                                           SIGNED out = clamp(R(acc), -128, 127)                   (z_out = 0: the downsample)
-//                                           ADD   out = clamp(-128 + R(acc) + R(res - z_res, m_r, sh_r), -128, 127)   (conv2)
+//   the conv      : dense k x k (k = 1, 3), stride 1 or 2, pad k / 2 Conv2d as an implicit GEMM, the RqPixel geometry of the int8
+//                   tap-GEMM core (ww_q8_tap_gemm.h: the lane map, the row tiles, the LDS weight slab), with one of three epilogues:
+//                       RELU   out = clamp(-128 + R(acc), -128, 127)            (z_out = -128)
+//                       SIGNED out = clamp(R(acc), -128, 127)                   (z_out = 0: the downsample)
+//                       ADD    out = clamp(-128 + R(acc) + R(res - z_res, m_r, sh_r), -128, 127)   (conv2)
 // Quantisation is ww_q8_quantize, pooling and the classifier are ww_tq8_pool_fc_fwd (T = H W, C = Cp = 512).
 // Activations are int8 NHWC (B,H,W,C), C a multiple of 64: a pixel's channels are whole 64-deep K chunks of the instruction.
 //
-// The product, under the lane map of k_q8_pw / k_tq8_conv (DESIGN.md mfma_i8_map): D = A x B, A = weights (row = output channel),
-// B = output pixels (column = row l & 15 of the tile).  Lane l supplies, for tap (kh, kw) and K chunk kc, the 16 bytes [64 kc + 16 g,
-// + 16), g = l >> 4, of the source pixel (ho s - p + kh, wo s - p + kw) of ITS row -- or 16 bytes of the input's zero point where
-// that pixel lies outside the image -- and the same 16 k of weight row 16 (i >> 2) + 4 m + (i & 3), i = l & 15, for product
-// m = 0..3: the lane ends with the sixteen consecutive channels 64 ct + 16 g .. + 15 of its row and stores one 16-byte vector.
 // The pixel index is per row, so a 16-row tile may span images.  A wave holds RT tiles of 16 rows at once (RT = 4, or 1 for
 // launches with few rows, so that the (row group x channel tile) grid still fills the machine).  The weights of a channel tile
-// (64 k k Cin bytes, re-laid (Cout, k k, Cin) by the host) are held in LDS in fragment order (k_rq8_conv_lds) or streamed
-// through L2 (k_rq8_conv); WW_RQ8_WEIGHTS=stream | lds in the environment forces one form (lds: wherever the tile fits LDS).
+// (64 k k Cin bytes, re-laid (Cout, k k, Cin) by the host) are held in LDS or streamed through L2; WW_RQ8_WEIGHTS=stream | lds in
+// the environment forces one form (lds: wherever the tile fits LDS).
 //
 // bias arguments are the EFFECTIVE bias q_b - z_in * sum(q_w) (host, once per bundle), so "a source pixel outside the image" and
 // "a row past the end" are both a vector of z_in bytes.  All adds that may wrap are unsigned.
-#include "ww_internal.h"
+#include "ww_q8_tap_gemm.h"
 
 #include <cstdlib>
 #include <cstring>
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int RQ_BLOCK = 256;
 constexpr int RQ_WAVES = RQ_BLOCK / 64;
-constexpr size_t RQ_SLAB_FITS = 144 * 1024;    // largest weight image of a channel tile k_rq8_conv_lds can hold (Cin = 256 at k = 3)
-// ... and the largest held in LDS by default: measured per launch (profiles/q8_resnet18_measured.txt), the LDS form is the faster
-// one at every shape of the model whose tile fits, the one-workgroup-a-CU 144 KB tiles of stage 3 included
-constexpr size_t RQ_SLAB_DEFAULT = RQ_SLAB_FITS;
+// the largest weight image of a channel tile held in LDS by default is the largest that fits (Cin = 256 at k = 3): measured per
+// launch (profiles/q8_resnet18_measured.txt), the LDS form is the faster one at every shape of the model whose tile fits, the
+// one-workgroup-a-CU 144 KB tiles of stage 3 included
+constexpr size_t RQ_SLAB_DEFAULT = Q8T_SLAB_FITS;
 constexpr long RQ_RT4_ITEMS = 1024;            // 64-row items from which a wave takes 64 rows: one per SIMD of the machine (256 CUs x 4)
 enum { RQ_RELU = 0, RQ_SIGNED = 1, RQ_ADD = 2 };
 
-// R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh, arithmetic shift; |a| < 2^31, 2^30 <= m < 2^31, 1 <= sh <= 62
-__device__ __forceinline__ long long rq8_round(int a, int m, int sh) {
-    return ((long long)a * (long long)m + (1ll << (sh - 1))) >> sh;
-}
-
-__device__ __forceinline__ int rq8_clamp(long long r) {       // clamp(-128 + r, -128, 127)
-    r = r < 0 ? 0 : (r > 255 ? 255 : r);
-    return (int)r - 128;
-}
-
-__device__ __forceinline__ int rq8_clamp_signed(long long r) { return (int)(r < -128 ? -128 : (r > 127 ? 127 : r)); }
-
-template <int J> __device__ __forceinline__ int rq8_byte(int d) { return (int)(signed char)((unsigned)d >> (8 * J)); }
-
-__device__ __forceinline__ int rq8_pack4(int a, int b, int c, int d) {
-    return (int)((unsigned)(a & 255) | ((unsigned)(b & 255) << 8) | ((unsigned)(c & 255) << 16) | ((unsigned)(d & 255) << 24));
-}
-
-__device__ __forceinline__ void rq8_unpack4(int d, int (&q)[4]) {
-    q[0] = rq8_byte<0>(d); q[1] = rq8_byte<1>(d); q[2] = rq8_byte<2>(d); q[3] = rq8_byte<3>(d);
-}
-
-struct rq8_conv_args {
-    const int8_t *in, *w;                      // in (B,H,W,Cin); w (Cout, k k, Cin) [out][tap][in]
-    const int *bias, *mult, *shift;            // (Cout) each
-    const int8_t *res;                         // ADD: the residual tensor (N, Cout)
-    int8_t *out;                               // (N, Cout), N = B Ho Wo
+// row n = output pixel (b, ho, wo) of (B,Ho,Wo); tap j = (kh, kw) reads pixel (ho s - p + kh, wo s - p + kw) of image b of
+// (B,H,W,Cin), or the zero point where that pixel lies outside the image
+struct RqPixel {
+    const int8_t *in;
     long N;
-    int H, W, Ho, Wo, Cin, Cout, k, stride, zfill, res_zero, res_m, res_sh;
+    int H, W, Ho, Wo, Cin, k, stride, zfill;
+    struct Row { long n, img; int h0, w0; };   // the window's first source pixel; a row past the end has none inside the image
+    struct Src { const int8_t *p; bool live; };
+    __device__ int nseg() const { return k * k; }
+    __device__ int K() const { return Cin; }
+    __device__ void row(long n, Row &r) const {
+        const int pad = k / 2;
+        const long b = n / ((long)Ho * Wo);
+        const int rem = (int)(n - b * Ho * Wo);
+        const bool ok = n < N;
+        r.n = n;
+        r.img = b * H;
+        r.h0 = ok ? rem / Wo * stride - pad : -(1 << 20);
+        r.w0 = ok ? rem % Wo * stride - pad : -(1 << 20);
+    }
+    __device__ void seg(const Row &r, int j, int g, Src &s) const {
+        const int kh = j / k, kw = j - kh * k;
+        const int hi = r.h0 + kh, wi = r.w0 + kw;
+        s.live = hi >= 0 && hi < H && wi >= 0 && wi < W;
+        s.p = in + ((r.img + hi) * W + wi) * Cin + 16 * g;      // dereferenced only where live
+    }
+    __device__ v4i load(const Src &s, int kc) const {
+        v4i bq = {zfill, zfill, zfill, zfill};
+        if (s.live) bq = *(const v4i *)(s.p + 64 * kc);
+        return bq;
+    }
 };
 
-// One item: 16 RT rows from row0 on, output channels [64 ct, 64 ct + 64).  SLAB: the weight fragments come from the workgroup's
-// LDS image of channel tile ct (k_rq8_conv_lds lays it out), else from global memory.
-template <int EP, bool SLAB, int RT>
-__device__ __forceinline__ void rq8_conv_item(const rq8_conv_args &a, int ct, long row0, int lane, const v4i *slab) {
-    const int p = lane & 15, g = lane >> 4;
-    const int kcn = a.Cin / 64, pad = a.k / 2;
-    const v4i zvec = {a.zfill, a.zfill, a.zfill, a.zfill};
-    const long wstride = (long)a.k * a.k * a.Cin;
-    long n[RT], img[RT];
-    int h0[RT], w0[RT];                        // the window's first source pixel; a row past the end has none inside the image
-#pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        n[r] = row0 + 16 * r + p;
-        const long b = n[r] / ((long)a.Ho * a.Wo);
-        const int rem = (int)(n[r] - b * a.Ho * a.Wo);
-        const bool ok = n[r] < a.N;
-        img[r] = b * a.H;
-        h0[r] = ok ? rem / a.Wo * a.stride - pad : -(1 << 20);
-        w0[r] = ok ? rem % a.Wo * a.stride - pad : -(1 << 20);
-    }
-    const int8_t *wrow[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) wrow[m] = a.w + (long)(64 * ct + 16 * (p >> 2) + 4 * m + (p & 3)) * wstride + 16 * g;
-    v4i acc[RT][4];
-#pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[r][m] = v4i{0, 0, 0, 0};
-    for (int j = 0; j < a.k * a.k; ++j) {
-        const int kh = j / a.k, kw = j - kh * a.k;
-        const int8_t *src[RT];
-        bool live[RT];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) {
-            const int hi = h0[r] + kh, wi = w0[r] + kw;
-            live[r] = hi >= 0 && hi < a.H && wi >= 0 && wi < a.W;
-            src[r] = a.in + ((img[r] + hi) * a.W + wi) * a.Cin + 16 * g;        // dereferenced only where live
-        }
-        for (int kc = 0; kc < kcn; ++kc) {
-            v4i wa[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                wa[m] = SLAB ? slab[((j * kcn + kc) * 4 + m) * 64 + lane] : *(const v4i *)(wrow[m] + (long)j * a.Cin + 64 * kc);
-#pragma unroll
-            for (int r = 0; r < RT; ++r) {
-                v4i bq = zvec;
-                if (live[r]) bq = *(const v4i *)(src[r] + 64 * kc);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc[r][m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa[m], bq, acc[r][m], 0, 0, 0);
-            }
-        }
-    }
-    const int c0 = 64 * ct + 16 * g;
-#pragma unroll
-    for (int r = 0; r < RT; ++r) {
-        if (n[r] >= a.N) continue;
+template <int EP> struct RqEpi : Q8Chan {
+    const int8_t *res;                         // ADD: the residual tensor (N, Cout)
+    int8_t *out;                               // (N, Cout), N = B Ho Wo
+    int res_zero, res_m, res_sh;
+    __device__ void store(const v4i (&acc)[4], long n, int c0) const {
         v4i hv = {0, 0, 0, 0};
-        if (EP == RQ_ADD) hv = *(const v4i *)(a.res + n[r] * a.Cout + c0);
-        v4i ov;
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const v4i b = *(const v4i *)(a.bias + c0 + 4 * m);
-            const v4i mu = *(const v4i *)(a.mult + c0 + 4 * m);
-            const v4i sh = *(const v4i *)(a.shift + c0 + 4 * m);
-            int h[4], q[4];
-            rq8_unpack4(hv[m], h);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                long long v = rq8_round((int)((unsigned)acc[r][m][e] + (unsigned)b[e]), mu[e], sh[e]);
-                if (EP == RQ_ADD) v += rq8_round(h[e] - a.res_zero, a.res_m, a.res_sh);
-                q[e] = EP == RQ_SIGNED ? rq8_clamp_signed(v) : rq8_clamp(v);
-            }
-            ov[m] = rq8_pack4(q[0], q[1], q[2], q[3]);
-        }
-        *(v4i *)(a.out + n[r] * a.Cout + c0) = ov;
+        if (EP == RQ_ADD) hv = *(const v4i *)(res + n * Cout + c0);
+        q8_tap_store(*this, acc, hv, out, n, c0, [&](long long v, int h) {
+            if (EP == RQ_ADD) v += q8_round(h - res_zero, res_m, res_sh);
+            return EP == RQ_SIGNED ? q8_clamp_signed(v) : q8_clamp(v);
+        });
     }
-}
-
-// weights streamed through L2: persistent over (row group, channel tile) items, one per wave and trip
-template <int EP, int RT> __global__ __launch_bounds__(RQ_BLOCK) void k_rq8_conv(rq8_conv_args a) {
-    const int ctn = a.Cout / 64;
-    const long items = (a.N + 16 * RT - 1) / (16 * RT) * ctn;
-    for (long item = (long)blockIdx.x * RQ_WAVES + (threadIdx.x >> 6); item < items; item += (long)gridDim.x * RQ_WAVES)
-        rq8_conv_item<EP, false, RT>(a, (int)(item % ctn), item / ctn * (16 * RT), threadIdx.x & 63, nullptr);
-}
-
-// weights of one channel tile resident in LDS, in FRAGMENT order: vector ((j kcn + kc) 4 + m) 64 + l is what lane l feeds product m
-// of tap j, K chunk kc -- any 16 lanes of a ds_read_b128 group read 16 distinct 16-byte slots, so the reads are conflict-free.
-// The grid is ctstep x (row workgroups): ctstep == Cout / 64 gives a workgroup ONE channel tile for its life, ctstep == 1 (a grid
-// smaller than that) makes every workgroup walk all the tiles.  Persistent over row groups.
-template <int EP, int RT> __global__ __launch_bounds__(RQ_BLOCK) void k_rq8_conv_lds(rq8_conv_args a, int ctstep) {
-    extern __shared__ v4i rq8_slab[];
-    const int ctn = a.Cout / 64, nvec = a.k * a.k * (a.Cin / 64) * 256;
-    const long groups = (a.N + 16 * RT - 1) / (16 * RT), wstride = (long)a.k * a.k * a.Cin;
-    const int rwg = blockIdx.x / ctstep, nrwg = gridDim.x / ctstep;
-    for (int ct = blockIdx.x % ctstep; ct < ctn; ct += ctstep) {
-        __syncthreads();                                        // every wave is done with the previous tile's image
-        for (int idx = threadIdx.x; idx < nvec; idx += RQ_BLOCK) {
-            const int l = idx & 63, m = (idx >> 6) & 3, chunk = idx >> 8;           // chunk = j kcn + kc: 64 bytes of a weight row
-            const int row = 64 * ct + 16 * ((l & 15) >> 2) + 4 * m + (l & 3);
-            rq8_slab[idx] = *(const v4i *)(a.w + row * wstride + 64 * chunk + 16 * (l >> 4));
-        }
-        __syncthreads();
-        for (long grp = (long)rwg * RQ_WAVES + (threadIdx.x >> 6); grp < groups; grp += (long)nrwg * RQ_WAVES)
-            rq8_conv_item<EP, true, RT>(a, ct, grp * (16 * RT), threadIdx.x & 63, rq8_slab);
-    }
-}
+};
 
 // The stem on the matrix pipe: a pixel's 49-byte window, padded to 64, is exactly one K chunk.  Persistent over 16-pixel tiles, one
 // per wave and trip, under the conv kernel's lane map: lane l gathers the taps [16 g, 16 g + 16) of the window of pixel l & 15 --
@@ -207,7 +110,7 @@ __global__ __launch_bounds__(RQ_BLOCK) void k_rq8_stem(const int8_t *__restrict_
                 q[e] = tap < 49 ? zero : 0;
                 if (ok && tap < 49 && hi >= 0 && hi < F && wi >= 0 && wi < T) q[e] = img[(long)hi * T + wi];
             }
-            bq[d] = rq8_pack4(q[0], q[1], q[2], q[3]);
+            bq[d] = q8_pack4(q[0], q[1], q[2], q[3]);
         }
         v4i acc[4];
 #pragma unroll
@@ -221,8 +124,8 @@ __global__ __launch_bounds__(RQ_BLOCK) void k_rq8_stem(const int8_t *__restrict_
             const v4i sh = *(const v4i *)(shift + 16 * g + 4 * m);
             int q[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) q[e] = rq8_clamp(rq8_round((int)((unsigned)acc[m][e] + (unsigned)bb[e]), mu[e], sh[e]));
-            ov[m] = rq8_pack4(q[0], q[1], q[2], q[3]);
+            for (int e = 0; e < 4; ++e) q[e] = q8_clamp(q8_round((int)((unsigned)acc[m][e] + (unsigned)bb[e]), mu[e], sh[e]));
+            ov[m] = q8_pack4(q[0], q[1], q[2], q[3]);
         }
         *(v4i *)(out + n * 64 + 16 * g) = ov;
     }
@@ -251,7 +154,7 @@ __global__ __launch_bounds__(RQ_BLOCK) void k_rq8_maxpool(const int8_t *__restri
 #pragma unroll
                 for (int d = 0; d < 4; ++d) {
                     int q[4];
-                    rq8_unpack4(x[d], q);
+                    q8_unpack4(x[d], q);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) best[4 * d + e] = q[e] > best[4 * d + e] ? q[e] : best[4 * d + e];
                 }
@@ -259,47 +162,26 @@ __global__ __launch_bounds__(RQ_BLOCK) void k_rq8_maxpool(const int8_t *__restri
         }
         v4i o;
 #pragma unroll
-        for (int d = 0; d < 4; ++d) o[d] = rq8_pack4(best[4 * d], best[4 * d + 1], best[4 * d + 2], best[4 * d + 3]);
+        for (int d = 0; d < 4; ++d) o[d] = q8_pack4(best[4 * d], best[4 * d + 1], best[4 * d + 2], best[4 * d + 3]);
         *(v4i *)(out + pix * C + 16 * v) = o;
     }
 }
 
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-inline long rq8_round256(long n) { return (n + 255) / 256 * 256; }
 inline int rq8_half(int n) { return (n - 1) / 2 + 1; }          // floor((n + 2 p - k) / 2) + 1 for (k, p) = (7, 3), (3, 1), (1, 0)
-inline bool rq8_mult_ok(int m, int sh) { return m >= (1 << 30) && sh >= 1 && sh <= 62; }
 
-template <int EP, int RT> int rq8_launch(ww_ctx *ctx, const rq8_conv_args &a, bool lds, size_t slab, hipStream_t st) {
-    const int ctn = a.Cout / 64;
-    const long groups = (a.N + 16 * RT - 1) / (16 * RT);
-    if (lds) {
-        // the launch asks for the next multiple of 16 KB, so the occupancy query sees few distinct sizes
-        const size_t smem = (slab + 16383) / 16384 * 16384;
-        const void *fn = (const void *)k_rq8_conv_lds<EP, RT>;
-        if (smem > 64 * 1024) WW_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RQ_SLAB_FITS));
-        int grid = ww_conv_grid(ctx, fn, RQ_BLOCK, smem, (groups + RQ_WAVES - 1) / RQ_WAVES * ctn, 1 << 20);
-        const int ctstep = grid >= ctn ? ctn : 1;
-        grid -= grid % ctstep;
-        hipLaunchKernelGGL((k_rq8_conv_lds<EP, RT>), dim3(grid), dim3(RQ_BLOCK), smem, st, a, ctstep);
-    } else {
-        const int grid = ww_conv_grid(ctx, (const void *)k_rq8_conv<EP, RT>, RQ_BLOCK, 0, (groups * ctn + RQ_WAVES - 1) / RQ_WAVES, 1 << 20);
-        hipLaunchKernelGGL((k_rq8_conv<EP, RT>), dim3(grid), dim3(RQ_BLOCK), 0, st, a);
-    }
-    WW_LAUNCH_CHECK();
-    return WW_OK;
-}
-
-template <int EP> int rq8_launch_rt(ww_ctx *ctx, const rq8_conv_args &a, bool lds, size_t slab, hipStream_t st) {
+template <int EP>
+int rq8_launch_rt(ww_ctx *ctx, const RqPixel &geo, const RqEpi<EP> &epi, const int8_t *w, bool lds, size_t slab, hipStream_t st) {
     // 64-row groups x channel tiles are the waves' work items: below one per SIMD of the machine a wave takes 16 rows, so that four
     // times as many waves share the launch (measured per launch: 16 rows win at every shape below the threshold, 64 rows at or
     // above it except two stride-2 convs by 5 and 12 %).  WW_RQ8_ROWTILE=1 | 4 in the environment forces one: the tests' shapes are
     // all below the threshold.
-    const long items4 = (a.N + 63) / 64 * (a.Cout / 64);
+    const long items4 = (geo.N + 63) / 64 * (epi.Cout / 64);
     const char *rt = getenv("WW_RQ8_ROWTILE");
     bool small = items4 < RQ_RT4_ITEMS;
     if (rt && !strcmp(rt, "1")) small = true;
     if (rt && !strcmp(rt, "4")) small = false;
-    return small ? rq8_launch<EP, 1>(ctx, a, lds, slab, st) : rq8_launch<EP, 4>(ctx, a, lds, slab, st);
+    return small ? q8_tap_launch<RqPixel, RqEpi<EP>, 1>(ctx, geo, epi, w, lds, slab, st)
+                 : q8_tap_launch<RqPixel, RqEpi<EP>, 4>(ctx, geo, epi, w, lds, slab, st);
 }
 
 }  // namespace
@@ -321,12 +203,12 @@ extern "C" int ww_rq8_conv2d_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w,
     WW_REQUIRE(aligned16(in) && aligned16(w) && aligned16(bias) && aligned16(mult) && aligned16(shift) && aligned16(out) &&
                aligned16(residual), WW_E_INVALID, "ww_rq8_conv2d_fwd: tensors must be 16-byte aligned");
     WW_REQUIRE(in != out && residual != out, WW_E_INVALID, "ww_rq8_conv2d_fwd: in place");
-    WW_REQUIRE(!residual || (rq8_mult_ok(res_mult, res_shift) && res_zero >= -128 && res_zero <= 127), WW_E_INVALID,
+    WW_REQUIRE(!residual || (q8_mult_ok(res_mult, res_shift) && res_zero >= -128 && res_zero <= 127), WW_E_INVALID,
                "ww_rq8_conv2d_fwd: residual multiplier %d / shift %d / zero point %d out of range", res_mult, res_shift, res_zero);
     const int Ho = stride == 2 ? rq8_half(H) : H, Wo = stride == 2 ? rq8_half(W) : W;
     const long N = (long)B * Ho * Wo;
-    rq8_conv_args a{in, w, bias, mult, shift, residual, out, N, H, W, Ho, Wo, Cin, Cout, k, stride, (zero & 255) * 0x01010101,
-                    res_zero, res_mult, res_shift};
+    const RqPixel geo{in, N, H, W, Ho, Wo, Cin, k, stride, (zero & 255) * 0x01010101};
+    const Q8Chan chan{bias, mult, shift, Cout};
     ww_prof_scope prof(ctx, WW_K_PW_FWD, (hipStream_t)stream);
     // One channel tile's weights are 64 k k Cin bytes.  Up to RQ_SLAB_DEFAULT they are held in LDS, beyond it streamed; the
     // environment's WW_RQ8_WEIGHTS (the A/B switch of tools/bench_q8_resnet18.py and the tests) forces a form.
@@ -334,11 +216,11 @@ extern "C" int ww_rq8_conv2d_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w,
     const char *mode = getenv("WW_RQ8_WEIGHTS");
     bool lds = slab <= RQ_SLAB_DEFAULT;
     if (mode && !strcmp(mode, "stream")) lds = false;
-    if (mode && !strcmp(mode, "lds")) lds = slab <= RQ_SLAB_FITS;
+    if (mode && !strcmp(mode, "lds")) lds = slab <= Q8T_SLAB_FITS;
     hipStream_t st = (hipStream_t)stream;
-    if (epilogue == WW_RQ8_RELU) return rq8_launch_rt<RQ_RELU>(ctx, a, lds, slab, st);
-    if (epilogue == WW_RQ8_SIGNED) return rq8_launch_rt<RQ_SIGNED>(ctx, a, lds, slab, st);
-    return rq8_launch_rt<RQ_ADD>(ctx, a, lds, slab, st);
+    if (epilogue == WW_RQ8_RELU) return rq8_launch_rt<RQ_RELU>(ctx, geo, {chan, residual, out, res_zero, res_mult, res_shift}, w, lds, slab, st);
+    if (epilogue == WW_RQ8_SIGNED) return rq8_launch_rt<RQ_SIGNED>(ctx, geo, {chan, residual, out, res_zero, res_mult, res_shift}, w, lds, slab, st);
+    return rq8_launch_rt<RQ_ADD>(ctx, geo, {chan, residual, out, res_zero, res_mult, res_shift}, w, lds, slab, st);
 }
 
 extern "C" int ww_rq8_stem_fwd(ww_ctx *ctx, const int8_t *xq, const int8_t *w, const int32_t *bias, const int32_t *mult,
@@ -380,7 +262,7 @@ const int RQ_PLANES[4] = {64, 128, 256, 512};
 bool rq8_make_plan(int B, int F, int T, rq8_plan *p) {
     if (B < 1 || F < 1 || T < 1 || (long)B * F * T > (1l << 31)) return false;
     long off = 0;
-    auto take = [&](long bytes) { const long at = off; off += rq8_round256(bytes); return at; };
+    auto take = [&](long bytes) { const long at = off; off += q8_round256(bytes); return at; };
     p->H[0] = rq8_half(F); p->W[0] = rq8_half(T);
     p->H[1] = rq8_half(p->H[0]); p->W[1] = rq8_half(p->W[0]);
     for (int s = 1; s < 4; ++s) { p->H[s + 1] = rq8_half(p->H[s]); p->W[s + 1] = rq8_half(p->W[s]); }

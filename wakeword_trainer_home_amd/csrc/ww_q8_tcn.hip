@@ -1,171 +1,71 @@
 // Integer-only inference of an exported int8 TCNWakeword bundle (DESIGN.md "Export", the int8 law, subsection "TCN").
 //   k_tq8_quantize_bt : fp32 features (B,F,T) -> int8 rows (B*T, Fp), q = clamp(rne(x / s_x) + z_x), transposed in the same pass
-//   k_tq8_conv        : causal dilated Conv1d as a shifted-row GEMM on v_mfma_i32_16x16x64_i8; epilogue (a) requantise + clamp,
-//                       (b) R(acc) + R(h2 + 128) + clamp: the downsample conv carrying the block's add and last ReLU
+//   the conv          : causal dilated Conv1d as a shifted-row GEMM, the TqTime geometry of the int8 tap-GEMM core (ww_q8_tap_gemm.h:
+//                       the lane map, the row tiles, the LDS weight slab); epilogue (a) requantise + clamp, (b) R(acc) + R(h2 + 128)
+//                       + clamp: the downsample conv carrying the block's add and last ReLU
 //   k_tq8_skip_add    : the identity-skip form of the add
 //   k_tq8_pool_fc     : sum over T, requantise, Linear(C, num_classes), one fp32 multiply per logit
 // Activations are int8 rows (B*T, Cp), Cp = the channel count rounded up to 64: every (row, tap) is a whole number of the
 // instruction's 64-deep K chunks.  Pad channels hold the tensor's zero point and meet zero weights; pad OUTPUT channels have zero
 // weights, a zero bias and m = 2^30, sh = 31, so they come out as -128, the zero point of every tensor a conv writes.
 //
-// The product, under the lane map of k_q8_pw (ww_q8.hip; DESIGN.md mfma_i8_map): D = A x B, A = weights (row = output channel),
-// B = time rows (column = row l & 15 of the tile).  Lane l supplies, for tap j and K chunk kc, the 16 bytes [64 kc + 16 g,
-// + 16), g = l >> 4, of the displaced row t - (k-1-j) d -- or 16 bytes of the zero point where that time is negative -- and
-// the same 16 k of weight row 16 (i >> 2) + 4 m + (i & 3), i = l & 15, for product m = 0..3: the lane ends with the sixteen
-// consecutive channels 64 ct + 16 g .. + 15 of its row and stores one 16-byte vector.  A wave holds TQ_RT tiles of 16 rows at
-// once, so a weight fragment it loaded meets TQ_RT row fragments.  The weights of a channel tile (64 k Cpi bytes) are held in LDS
-// in fragment order (k_tq8_conv_lds, the default up to 64 KB: measured 1.11 x faster over the default model's forward, DESIGN.md
-// 5.6) or streamed through L2 (k_tq8_conv: larger tiles, and WW_TQ8_WEIGHTS=stream in the environment, the A/B switch).
+// A wave holds TQ_RT tiles of 16 rows at once.  The weights of a channel tile (64 k Cpi bytes) are held in LDS (the default up to
+// 64 KB: measured 1.11 x faster over the default model's forward) or streamed through L2 (larger tiles, and
+// WW_TQ8_WEIGHTS=stream in the environment, the A/B switch).
 //
 // bias arguments are the EFFECTIVE bias q_b - z_in * sum(q_w) (host, once per bundle), so "a source time below 0", "a pad
 // channel" and "a row past the end" are all a vector of z_in bytes.  All adds that may wrap are unsigned.
-#include "ww_internal.h"
+#include "ww_q8_tap_gemm.h"
 
 #include <cstdlib>
 #include <cstring>
 
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 constexpr int TQ_BLOCK = 256;
-constexpr int TQ_WAVES = TQ_BLOCK / 64;
 constexpr int TQ_RT = 4;                       // 16-row tiles a wave holds at once
-constexpr int TQ_ROWS = 16 * TQ_RT;
 constexpr int TQ_MAX_CP = 1024;                // widest tensor k_tq8_pool_fc sums (its LDS image)
-constexpr size_t TQ_SLAB_MAX = 64 * 1024;      // largest weight image of one channel tile k_tq8_conv_lds keeps in LDS
+constexpr size_t TQ_SLAB_MAX = 64 * 1024;      // largest weight image of one channel tile the conv keeps in LDS
 
-// R(a, m, sh) = (int64(a) m + 2^(sh-1)) >> sh, arithmetic shift; |a| < 2^31, 2^30 <= m < 2^31, 1 <= sh <= 62
-__device__ __forceinline__ long long tq8_round(int a, int m, int sh) {
-    return ((long long)a * (long long)m + (1ll << (sh - 1))) >> sh;
-}
-
-__device__ __forceinline__ int tq8_clamp(long long r) {       // clamp(-128 + r, -128, 127)
-    r = r < 0 ? 0 : (r > 255 ? 255 : r);
-    return (int)r - 128;
-}
-
-template <int J> __device__ __forceinline__ int tq8_byte(int d) { return (int)(signed char)((unsigned)d >> (8 * J)); }
-
-__device__ __forceinline__ int tq8_pack4(int a, int b, int c, int d) {
-    return (int)((unsigned)(a & 255) | ((unsigned)(b & 255) << 8) | ((unsigned)(c & 255) << 16) | ((unsigned)(d & 255) << 24));
-}
-
-__device__ __forceinline__ void tq8_unpack4(int d, int (&q)[4]) {
-    q[0] = tq8_byte<0>(d); q[1] = tq8_byte<1>(d); q[2] = tq8_byte<2>(d); q[3] = tq8_byte<3>(d);
-}
-
-struct tq8_conv_args {
-    const int8_t *in, *w;                      // in (N, Cpi); w (Cpo, k, Cpi) [out][tap][in]
-    const int *bias, *mult, *shift;            // (Cpo) each
-    const int8_t *res;                         // ADD: the residual tensor h2 (N, Cpo)
-    int8_t *out;                               // (N, Cpo)
+// row n = (b, t) of (B*T, Cpi); tap j reads time t - (k-1-j) d of the same sample, or the zero point where that time is negative
+struct TqTime {
+    const int8_t *in;
     long N;
-    int T, Cpi, Cpo, k, dil, zfill, res_m, res_sh;
+    int T, Cpi, k, dil, zfill;
+    struct Row { long n; int t; };
+    struct Src { const int8_t *p; bool live; };
+    __device__ int nseg() const { return k; }
+    __device__ int K() const { return Cpi; }
+    __device__ void row(long n, Row &r) const {
+        r.n = n;
+        r.t = n < N ? (int)(n % T) : -1;       // a row past the end has no valid source time
+    }
+    __device__ void seg(const Row &r, int j, int g, Src &s) const {
+        const long off = (long)(k - 1 - j) * dil;
+        s.live = (long)r.t - off >= 0;
+        s.p = in + (r.n - off) * Cpi + 16 * g;  // dereferenced only where live
+    }
+    __device__ v4i load(const Src &s, int kc) const {
+        v4i bq = {zfill, zfill, zfill, zfill};
+        if (s.live) bq = *(const v4i *)(s.p + 64 * kc);
+        return bq;
+    }
 };
 
-// One item: TQ_ROWS rows from row0 on, output channels [64 ct, 64 ct + 64).  SLAB: the weight fragments come from the workgroup's
-// LDS image of channel tile ct (k_tq8_conv_lds lays it out), else from global memory.
-template <bool ADD, bool SLAB>
-__device__ __forceinline__ void tq8_conv_item(const tq8_conv_args &a, int ct, long row0, int lane, const v4i *slab) {
-    const int p = lane & 15, g = lane >> 4;
-    const int kcn = a.Cpi / 64;
-    const v4i zvec = {a.zfill, a.zfill, a.zfill, a.zfill};
-    const long wstride = (long)a.k * a.Cpi;
-    {
-        long n[TQ_RT];
-        int t[TQ_RT];
-#pragma unroll
-        for (int r = 0; r < TQ_RT; ++r) {
-            n[r] = row0 + 16 * r + p;
-            t[r] = n[r] < a.N ? (int)(n[r] % a.T) : -1;        // a row past the end has no valid source time
-        }
-        const int8_t *wrow[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) wrow[m] = a.w + (long)(64 * ct + 16 * (p >> 2) + 4 * m + (p & 3)) * wstride + 16 * g;
-        v4i acc[TQ_RT][4];
-#pragma unroll
-        for (int r = 0; r < TQ_RT; ++r)
-#pragma unroll
-            for (int m = 0; m < 4; ++m) acc[r][m] = v4i{0, 0, 0, 0};
-        for (int j = 0; j < a.k; ++j) {
-            const long off = (long)(a.k - 1 - j) * a.dil;
-            const int8_t *src[TQ_RT];
-            bool live[TQ_RT];
-#pragma unroll
-            for (int r = 0; r < TQ_RT; ++r) {
-                live[r] = (long)t[r] - off >= 0;
-                src[r] = a.in + (n[r] - off) * a.Cpi + 16 * g;  // dereferenced only where live
-            }
-            for (int kc = 0; kc < kcn; ++kc) {
-                v4i wa[4];
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-                    wa[m] = SLAB ? slab[((j * kcn + kc) * 4 + m) * 64 + lane] : *(const v4i *)(wrow[m] + (long)j * a.Cpi + 64 * kc);
-#pragma unroll
-                for (int r = 0; r < TQ_RT; ++r) {
-                    v4i bq = zvec;
-                    if (live[r]) bq = *(const v4i *)(src[r] + 64 * kc);
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) acc[r][m] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wa[m], bq, acc[r][m], 0, 0, 0);
-                }
-            }
-        }
-        const int c0 = 64 * ct + 16 * g;
-#pragma unroll
-        for (int r = 0; r < TQ_RT; ++r) {
-            if (n[r] >= a.N) continue;
-            v4i hv = {0, 0, 0, 0};
-            if (ADD) hv = *(const v4i *)(a.res + n[r] * a.Cpo + c0);
-            v4i ov;
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const v4i b = *(const v4i *)(a.bias + c0 + 4 * m);
-                const v4i mu = *(const v4i *)(a.mult + c0 + 4 * m);
-                const v4i sh = *(const v4i *)(a.shift + c0 + 4 * m);
-                int h[4], q[4];
-                tq8_unpack4(hv[m], h);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    long long v = tq8_round((int)((unsigned)acc[r][m][e] + (unsigned)b[e]), mu[e], sh[e]);
-                    if (ADD) v += tq8_round(h[e] + 128, a.res_m, a.res_sh);
-                    q[e] = tq8_clamp(v);
-                }
-                ov[m] = tq8_pack4(q[0], q[1], q[2], q[3]);
-            }
-            *(v4i *)(a.out + n[r] * a.Cpo + c0) = ov;
-        }
+// out = clamp(-128 + R(acc) [+ R(h2 + 128, m_a, sh_a)]); ADD: res is the residual tensor h2 (N, Cpo)
+template <bool ADD> struct TqEpi : Q8Chan {
+    const int8_t *res;
+    int8_t *out;
+    int res_m, res_sh;
+    __device__ void store(const v4i (&acc)[4], long n, int c0) const {
+        v4i hv = {0, 0, 0, 0};
+        if (ADD) hv = *(const v4i *)(res + n * Cout + c0);
+        q8_tap_store(*this, acc, hv, out, n, c0, [&](long long v, int h) {
+            if (ADD) v += q8_round(h + 128, res_m, res_sh);
+            return q8_clamp(v);
+        });
     }
-}
-
-// weights streamed through L2: persistent over (row group, channel tile) items, one per wave and trip
-template <bool ADD> __global__ __launch_bounds__(TQ_BLOCK) void k_tq8_conv(tq8_conv_args a) {
-    const int ctn = a.Cpo / 64;
-    const long items = (a.N + TQ_ROWS - 1) / TQ_ROWS * ctn;
-    for (long item = (long)blockIdx.x * TQ_WAVES + (threadIdx.x >> 6); item < items; item += (long)gridDim.x * TQ_WAVES)
-        tq8_conv_item<ADD, false>(a, (int)(item % ctn), item / ctn * TQ_ROWS, threadIdx.x & 63, nullptr);
-}
-
-// weights of one channel tile resident in LDS, in FRAGMENT order: vector ((j kcn + kc) 4 + m) 64 + l is what lane l feeds product m
-// of tap j, K chunk kc -- any 16 lanes of a ds_read_b128 group read 16 distinct 16-byte slots, so the reads are conflict-free.
-// The grid is ctstep x (row workgroups): ctstep == Cpo / 64 gives a workgroup ONE channel tile for its life, ctstep == 1 (a grid
-// smaller than that, or not a multiple of it) makes every workgroup walk all the tiles.  Persistent over row groups.
-template <bool ADD> __global__ __launch_bounds__(TQ_BLOCK) void k_tq8_conv_lds(tq8_conv_args a, int ctstep) {
-    extern __shared__ v4i tq8_slab[];
-    const int ctn = a.Cpo / 64, nvec = a.k * (a.Cpi / 64) * 256;
-    const long groups = (a.N + TQ_ROWS - 1) / TQ_ROWS, wstride = (long)a.k * a.Cpi;
-    const int rwg = blockIdx.x / ctstep, nrwg = gridDim.x / ctstep;
-    for (int ct = blockIdx.x % ctstep; ct < ctn; ct += ctstep) {
-        __syncthreads();                                        // every wave is done with the previous tile's image
-        for (int idx = threadIdx.x; idx < nvec; idx += TQ_BLOCK) {
-            const int l = idx & 63, m = (idx >> 6) & 3, chunk = idx >> 8;           // chunk = j kcn + kc: 64 bytes of a weight row
-            const int row = 64 * ct + 16 * ((l & 15) >> 2) + 4 * m + (l & 3);
-            tq8_slab[idx] = *(const v4i *)(a.w + row * wstride + 64 * chunk + 16 * (l >> 4));
-        }
-        __syncthreads();
-        for (long grp = (long)rwg * TQ_WAVES + (threadIdx.x >> 6); grp < groups; grp += (long)nrwg * TQ_WAVES)
-            tq8_conv_item<ADD, true>(a, ct, grp * TQ_ROWS, threadIdx.x & 63, tq8_slab);
-    }
-}
+};
 
 // out = clamp(-128 + R(q_in - z_in, m_i, sh_i) + R(q_h2 + 128, m_a, sh_a)) over nvec 16-byte vectors
 __global__ __launch_bounds__(TQ_BLOCK) void k_tq8_skip_add(const int8_t *__restrict__ in, const int8_t *__restrict__ h2, long nvec,
@@ -176,11 +76,11 @@ __global__ __launch_bounds__(TQ_BLOCK) void k_tq8_skip_add(const int8_t *__restr
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             int xs[4], hs[4], q[4];
-            tq8_unpack4(x[d], xs);
-            tq8_unpack4(h[d], hs);
+            q8_unpack4(x[d], xs);
+            q8_unpack4(h[d], hs);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) q[e] = tq8_clamp(tq8_round(xs[e] - z_in, m_i, sh_i) + tq8_round(hs[e] + 128, m_a, sh_a));
-            o[d] = tq8_pack4(q[0], q[1], q[2], q[3]);
+            for (int e = 0; e < 4; ++e) q[e] = q8_clamp(q8_round(xs[e] - z_in, m_i, sh_i) + q8_round(hs[e] + 128, m_a, sh_a));
+            o[d] = q8_pack4(q[0], q[1], q[2], q[3]);
         }
         *(v4i *)(out + 16 * i) = o;
     }
@@ -207,7 +107,7 @@ __global__ __launch_bounds__(TQ_BLOCK) void k_tq8_quantize_bt(const float *__res
                 q[e] = v < -128 ? -128 : (v > 127 ? 127 : v);
             }
         }
-        *(int *)(out + (b * T + t) * Fp + 4 * fq) = tq8_pack4(q[0], q[1], q[2], q[3]);
+        *(int *)(out + (b * T + t) * Fp + 4 * fq) = q8_pack4(q[0], q[1], q[2], q[3]);
     }
 }
 
@@ -225,7 +125,7 @@ __global__ __launch_bounds__(TQ_BLOCK) void k_tq8_pool_fc(const int8_t *__restri
         int sum[4] = {0, 0, 0, 0};
         for (int t = slot; t < T; t += slots) {
             int q[4];
-            tq8_unpack4(*(const int *)(img + (long)t * Cp + 4 * col), q);
+            q8_unpack4(*(const int *)(img + (long)t * Cp + 4 * col), q);
 #pragma unroll
             for (int e = 0; e < 4; ++e) sum[e] += q[e] + 128;
         }
@@ -236,7 +136,7 @@ __global__ __launch_bounds__(TQ_BLOCK) void k_tq8_pool_fc(const int8_t *__restri
     for (int c = tid; c < C; c += TQ_BLOCK) {
         int S = 0;
         for (int s = 0; s < slots; ++s) S += s_part[s * Cp + c];
-        const int pq = tq8_clamp(tq8_round(S, pool_m, pool_sh));
+        const int pq = q8_clamp(q8_round(S, pool_m, pool_sh));
         pool_out[(long)blockIdx.x * C + c] = (int8_t)pq;
         s_pool[c] = pq + 128;
     }
@@ -247,11 +147,6 @@ __global__ __launch_bounds__(TQ_BLOCK) void k_tq8_pool_fc(const int8_t *__restri
         logits[(long)blockIdx.x * nc + tid] = (float)(int)acc * fc_scale[tid];
     }
 }
-
-inline bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-inline long tq8_round256(long n) { return (n + 255) / 256 * 256; }
-inline int tq8_pad64(int c) { return (c + 63) / 64 * 64; }
-inline bool tq8_mult_ok(int m, int sh) { return m >= (1 << 30) && sh >= 1 && sh <= 62; }
 
 }  // namespace
 
@@ -283,43 +178,20 @@ extern "C" int ww_tq8_conv1d_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *w,
     WW_REQUIRE(aligned16(in) && aligned16(w) && aligned16(bias) && aligned16(mult) && aligned16(shift) && aligned16(out) &&
                aligned16(residual), WW_E_INVALID, "ww_tq8_conv1d_fwd: tensors must be 16-byte aligned");
     WW_REQUIRE(in != out && residual != out, WW_E_INVALID, "ww_tq8_conv1d_fwd: in place");
-    WW_REQUIRE(!residual || tq8_mult_ok(res_mult, res_shift), WW_E_INVALID,
+    WW_REQUIRE(!residual || q8_mult_ok(res_mult, res_shift), WW_E_INVALID,
                "ww_tq8_conv1d_fwd: residual multiplier %d / shift %d out of range", res_mult, res_shift);
     const long N = (long)B * T;
-    tq8_conv_args a{in, w, bias, mult, shift, residual, out, N, T, Cpi, Cpo, k, dilation, (zero & 255) * 0x01010101, res_mult, res_shift};
-    const long items = (N + TQ_ROWS - 1) / TQ_ROWS * (Cpo / 64);
-    const long want = (items + TQ_WAVES - 1) / TQ_WAVES;
-    ww_prof_scope prof(ctx, WW_K_PW_FWD, (hipStream_t)stream);
-    // One channel tile's weights are 64 k Cpi bytes.  Up to TQ_SLAB_MAX they are held in LDS (the launch asks for the next
-    // multiple of 16 KB, so the occupancy query sees few distinct sizes); beyond it, or with WW_TQ8_WEIGHTS=stream in the
-    // environment (the A/B switch of tools/bench_q8_tcn.py and the tests), they are streamed.
+    const TqTime geo{in, N, T, Cpi, k, dilation, (zero & 255) * 0x01010101};
+    const Q8Chan chan{bias, mult, shift, Cpo};
+    hipStream_t st = (hipStream_t)stream;
+    ww_prof_scope prof(ctx, WW_K_PW_FWD, st);
+    // One channel tile's weights are 64 k Cpi bytes.  Up to TQ_SLAB_MAX they are held in LDS; beyond it, or with
+    // WW_TQ8_WEIGHTS=stream in the environment (the A/B switch of tools/bench_q8_tcn.py and the tests), they are streamed.
     const size_t slab = (size_t)64 * k * Cpi;
     const char *mode = getenv("WW_TQ8_WEIGHTS");
-    if (slab <= TQ_SLAB_MAX && !(mode && !strcmp(mode, "stream"))) {
-        const size_t smem = (slab + 16383) / 16384 * 16384;
-        const int ctn = Cpo / 64;
-        const long groups = (N + TQ_ROWS - 1) / TQ_ROWS;
-        const long want_lds = (groups + TQ_WAVES - 1) / TQ_WAVES * ctn;
-        const void *fn = residual ? (const void *)k_tq8_conv_lds<true> : (const void *)k_tq8_conv_lds<false>;
-        int grid = ww_conv_grid(ctx, fn, TQ_BLOCK, smem, want_lds, 1 << 20);
-        const int ctstep = grid >= ctn ? ctn : 1;
-        grid -= grid % ctstep;
-        if (residual)
-            hipLaunchKernelGGL(k_tq8_conv_lds<true>, dim3(grid), dim3(TQ_BLOCK), smem, (hipStream_t)stream, a, ctstep);
-        else
-            hipLaunchKernelGGL(k_tq8_conv_lds<false>, dim3(grid), dim3(TQ_BLOCK), smem, (hipStream_t)stream, a, ctstep);
-        WW_LAUNCH_CHECK();
-        return WW_OK;
-    }
-    if (residual) {
-        const int grid = ww_conv_grid(ctx, (const void *)k_tq8_conv<true>, TQ_BLOCK, 0, want, 1 << 20);
-        hipLaunchKernelGGL(k_tq8_conv<true>, dim3(grid), dim3(TQ_BLOCK), 0, (hipStream_t)stream, a);
-    } else {
-        const int grid = ww_conv_grid(ctx, (const void *)k_tq8_conv<false>, TQ_BLOCK, 0, want, 1 << 20);
-        hipLaunchKernelGGL(k_tq8_conv<false>, dim3(grid), dim3(TQ_BLOCK), 0, (hipStream_t)stream, a);
-    }
-    WW_LAUNCH_CHECK();
-    return WW_OK;
+    const bool lds = slab <= TQ_SLAB_MAX && !(mode && !strcmp(mode, "stream"));
+    if (residual) return q8_tap_launch<TqTime, TqEpi<true>, TQ_RT>(ctx, geo, {chan, residual, out, res_mult, res_shift}, w, lds, slab, st);
+    return q8_tap_launch<TqTime, TqEpi<false>, TQ_RT>(ctx, geo, {chan, nullptr, out, 0, 0}, w, lds, slab, st);
 }
 
 extern "C" int ww_tq8_skip_add_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *h2, long N, int Cp, int zero, int skip_mult,
@@ -327,7 +199,7 @@ extern "C" int ww_tq8_skip_add_fwd(ww_ctx *ctx, const int8_t *in, const int8_t *
     WW_REQUIRE(ctx && in && h2 && out, WW_E_INVALID, "ww_tq8_skip_add_fwd: null argument");
     WW_REQUIRE(N >= 1 && N <= (1l << 40) && Cp >= 64 && Cp % 64 == 0, WW_E_INVALID, "ww_tq8_skip_add_fwd: N=%ld Cp=%d", N, Cp);
     WW_REQUIRE(zero >= -128 && zero <= 127, WW_E_INVALID, "ww_tq8_skip_add_fwd: zero point %d outside int8", zero);
-    WW_REQUIRE(tq8_mult_ok(skip_mult, skip_shift) && tq8_mult_ok(add_mult, add_shift), WW_E_INVALID,
+    WW_REQUIRE(q8_mult_ok(skip_mult, skip_shift) && q8_mult_ok(add_mult, add_shift), WW_E_INVALID,
                "ww_tq8_skip_add_fwd: a multiplier or shift out of range");
     WW_REQUIRE(aligned16(in) && aligned16(h2) && aligned16(out), WW_E_INVALID, "ww_tq8_skip_add_fwd: tensors must be 16-byte aligned");
     const long nvec = N * (Cp / 16);
@@ -343,10 +215,10 @@ extern "C" int ww_tq8_pool_fc_fwd(ww_ctx *ctx, const int8_t *in, int B, int T, i
                                   int8_t *pool_out, float *logits, ww_stream_t stream) {
     WW_REQUIRE(ctx && in && fc_w && fc_bias && fc_scale && pool_out && logits, WW_E_INVALID, "ww_tq8_pool_fc_fwd: null argument");
     WW_REQUIRE(B >= 1 && T >= 1 && T <= (1 << 23), WW_E_INVALID, "ww_tq8_pool_fc_fwd: B=%d T=%d", B, T);
-    WW_REQUIRE(C >= 1 && Cp == tq8_pad64(C) && Cp <= TQ_MAX_CP, WW_E_INVALID, "ww_tq8_pool_fc_fwd: C=%d Cp=%d (Cp = C rounded up to 64, at most %d)",
+    WW_REQUIRE(C >= 1 && Cp == q8_pad64(C) && Cp <= TQ_MAX_CP, WW_E_INVALID, "ww_tq8_pool_fc_fwd: C=%d Cp=%d (Cp = C rounded up to 64, at most %d)",
                C, Cp, TQ_MAX_CP);
     WW_REQUIRE(num_classes >= 2 && num_classes <= 64, WW_E_INVALID, "ww_tq8_pool_fc_fwd: num_classes=%d outside [2, 64]", num_classes);
-    WW_REQUIRE(tq8_mult_ok(pool_mult, pool_shift), WW_E_INVALID, "ww_tq8_pool_fc_fwd: multiplier %d / shift %d out of range", pool_mult,
+    WW_REQUIRE(q8_mult_ok(pool_mult, pool_shift), WW_E_INVALID, "ww_tq8_pool_fc_fwd: multiplier %d / shift %d out of range", pool_mult,
                pool_shift);
     WW_REQUIRE(aligned16(in), WW_E_INVALID, "ww_tq8_pool_fc_fwd: the activations must be 16-byte aligned");
     ww_prof_scope prof(ctx, WW_K_GAP_FWD, (hipStream_t)stream);
@@ -358,12 +230,12 @@ extern "C" int ww_tq8_pool_fc_fwd(ww_ctx *ctx, const int8_t *in, int B, int T, i
 
 extern "C" size_t ww_tq8_tcn_workspace_bytes(int B, int F, int T, int n_blocks, const int32_t *channels) {
     if (B < 1 || F < 1 || T < 1 || n_blocks < 1 || n_blocks > WW_TQ8_MAX_BLOCKS || !channels) return 0;
-    long bytes = tq8_round256((long)B * T * tq8_pad64(F));
+    long bytes = q8_round256((long)B * T * q8_pad64(F));
     for (int i = 0; i < n_blocks; ++i) {
         if (channels[i] < 1) return 0;
-        bytes += 3 * tq8_round256((long)B * T * tq8_pad64(channels[i]));
+        bytes += 3 * q8_round256((long)B * T * q8_pad64(channels[i]));
     }
-    return (size_t)(bytes + tq8_round256((long)B * channels[n_blocks - 1]));
+    return (size_t)(bytes + q8_round256((long)B * channels[n_blocks - 1]));
 }
 
 extern "C" int ww_tq8_tcn_fwd(ww_ctx *ctx, const void *const *tab, const ww_tq8_io *io, const float *x, int B, int T, void *ws,
@@ -379,13 +251,13 @@ extern "C" int ww_tq8_tcn_fwd(ww_ctx *ctx, const void *const *tab, const ww_tq8_
     auto i32 = [&](int i) { return (const int32_t *)tab[i]; };
     const long N = (long)B * T;
     int8_t *cur = (int8_t *)ws;
-    int Cpi = tq8_pad64(F), zin = io->in_zero;
+    int Cpi = q8_pad64(F), zin = io->in_zero;
     int rc = ww_tq8_quantize_bt(ctx, x, B, F, T, Cpi, io->in_scale, zin, cur, stream);
     if (rc != WW_OK) return rc;
-    int8_t *next = cur + tq8_round256(N * Cpi);
+    int8_t *next = cur + q8_round256(N * Cpi);
     for (int i = 0; i < nb; ++i) {
-        const int Cpo = tq8_pad64(io->channels[i]), d = 1 << i, p = WW_TQ8_BLOCK_NPTR * i;
-        const long act = tq8_round256(N * Cpo);
+        const int Cpo = q8_pad64(io->channels[i]), d = 1 << i, p = WW_TQ8_BLOCK_NPTR * i;
+        const long act = q8_round256(N * Cpo);
         int8_t *h1 = next, *h2 = next + act, *out = next + 2 * act;
         for (int j = 0; j < 8; ++j) WW_REQUIRE(tab[p + j], WW_E_INVALID, "ww_tq8_tcn_fwd: table entry %d is null", p + j);
         rc = ww_tq8_conv1d_fwd(ctx, cur, i8(p), i32(p + 1), i32(p + 2), i32(p + 3), B, T, Cpi, Cpo, k, d, zin, nullptr, 0, 0, h1, stream);

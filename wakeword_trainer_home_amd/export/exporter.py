@@ -9,7 +9,7 @@ aliases.  Parity with onnxruntime's ``quantize_dynamic`` is not claimed."""
 import logging
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Any, Dict, Iterable, Optional, Tuple
+from typing import Any, Callable, Dict, Iterable, Optional, Tuple
 
 import numpy as np
 import torch
@@ -54,6 +54,28 @@ def _state_numpy(model: nn.Module) -> Dict[str, np.ndarray]:
     return {k: v.detach().cpu().numpy() for k, v in model.state_dict().items()}
 
 
+def _calibration_batch(x, dev, feature_extractor, F, T=None, sequences=False):
+    """One calibration batch as float32 (B,1,F,T) features on the device: waveforms (B,N) go through ``feature_extractor``, (B,F,T)
+    gets its channel dimension, and another shape is refused.  ``T``: ``None`` for any length.  ``sequences``: a 3-dim batch that
+    was given as such is (B,T,F) sequences and stays as it is (the LSTM)."""
+    x = torch.as_tensor(x).to(dev)
+    waveforms = x.dim() == 2
+    if waveforms:
+        if feature_extractor is None:
+            raise QuantizationError("calibration waveforms need a feature_extractor")
+        x = feature_extractor(x)
+    if x.dim() == 3 and (waveforms or not sequences):
+        x = x[:, None]
+    if sequences:
+        ok = (x.dim() == 4 and x.shape[1] == 1 and x.shape[2] == F) or (x.dim() == 3 and x.shape[2] == F)
+        if not ok or x.numel() == 0:
+            raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},T) or (B,T,{F})")
+        return x.float()
+    if x.dim() != 4 or tuple(x.shape[1:3]) != (1, F) or (x.shape[3] != T if T is not None else x.shape[3] < 1):
+        raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{'T' if T is None else T})")
+    return x.float().contiguous()
+
+
 def _calibrate_conv_stack(model, batches, feature_shape, dev, feature_extractor, whole=None):
     """The loop ``calibrate_cnn_small`` and ``calibrate_crnn`` share, over a ``CNNSmallWakeword`` conv stack in eval mode: the
     input's minimum and maximum and the maximum of every conv's post-ReLU output, through the model's own per-layer entry points
@@ -72,16 +94,7 @@ def _calibrate_conv_stack(model, batches, feature_shape, dev, feature_extractor,
     seen = 0
     with torch.no_grad():
         for x in batches:
-            x = torch.as_tensor(x).to(dev)
-            if x.dim() == 2:
-                if feature_extractor is None:
-                    raise QuantizationError("calibration waveforms need a feature_extractor")
-                x = feature_extractor(x)
-            if x.dim() == 3:
-                x = x[:, None]
-            if x.dim() != 4 or tuple(x.shape[1:3]) != (1, F) or (x.shape[3] != T if T is not None else x.shape[3] < 1):
-                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{'T' if T is None else T})")
-            x = x.float().contiguous()
+            x = _calibration_batch(x, dev, feature_extractor, F, T)
             lo, hi = torch.minimum(lo, x.min()), torch.maximum(hi, x.max())
             if whole is not None:
                 t_max = torch.maximum(t_max, whole(x).max())
@@ -160,16 +173,7 @@ def calibrate_tcn(model, batches: Iterable[torch.Tensor], feature_shape, device,
     seen = 0
     with torch.no_grad():
         for x in batches:
-            x = torch.as_tensor(x).to(dev)
-            if x.dim() == 2:
-                if feature_extractor is None:
-                    raise QuantizationError("calibration waveforms need a feature_extractor")
-                x = feature_extractor(x)
-            if x.dim() == 3:
-                x = x[:, None]
-            if x.dim() != 4 or tuple(x.shape[1:]) != (1, F, T):
-                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{T})")
-            x = x.float().contiguous()
+            x = _calibration_batch(x, dev, feature_extractor, F, T)
             lo, hi = torch.minimum(lo, x.min()), torch.maximum(hi, x.max())
             h = x[:, 0].transpose(1, 2).contiguous()
             for i, blk in enumerate(blocks):
@@ -210,16 +214,7 @@ def calibrate_resnet18(model, batches: Iterable[torch.Tensor], feature_shape, de
     seen = 0
     with torch.no_grad():
         for x in batches:
-            x = torch.as_tensor(x).to(dev)
-            if x.dim() == 2:
-                if feature_extractor is None:
-                    raise QuantizationError("calibration waveforms need a feature_extractor")
-                x = feature_extractor(x)
-            if x.dim() == 3:
-                x = x[:, None]
-            if x.dim() != 4 or tuple(x.shape[1:]) != (1, F, T):
-                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{T})")
-            x = x.float().contiguous()
+            x = _calibration_batch(x, dev, feature_extractor, F, T)
             lo, hi = torch.minimum(lo, x.min()), torch.maximum(hi, x.max())
             a = bn(net.bn1, nat.conv2d_stem_fwd(x[:, 0].contiguous(), net.conv1.weight, net.conv1.stride), nat.LIN_RELU)
             m["stem"][0] = torch.maximum(m["stem"][0], a.max())
@@ -290,16 +285,7 @@ def calibrate_mobilenetv3(model, batches: Iterable[torch.Tensor], feature_shape,
     seen = 0
     with torch.no_grad():
         for x in batches:
-            x = torch.as_tensor(x).to(dev)
-            if x.dim() == 2:
-                if feature_extractor is None:
-                    raise QuantizationError("calibration waveforms need a feature_extractor")
-                x = feature_extractor(x)
-            if x.dim() == 3:
-                x = x[:, None]
-            if x.dim() != 4 or tuple(x.shape[1:]) != (1, F, T):
-                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},{T})")
-            x = see("", x.float().contiguous())
+            x = see("", _calibration_batch(x, dev, feature_extractor, F, T))
             h = cba(net.features[0], x, "stem")
             for i, blk in enumerate(list(net.features)[1:-1]):
                 p, h_in = f"b{i}.", h
@@ -345,17 +331,7 @@ def calibrate_lstm(model, batches: Iterable[torch.Tensor], input_size, device, f
     seen = 0
     with torch.no_grad():
         for x in batches:
-            x = torch.as_tensor(x).to(dev)
-            if x.dim() == 2:
-                if feature_extractor is None:
-                    raise QuantizationError("calibration waveforms need a feature_extractor")
-                x = feature_extractor(x)
-                if x.dim() == 3:
-                    x = x[:, None]
-            ok = (x.dim() == 4 and x.shape[1] == 1 and x.shape[2] == F) or (x.dim() == 3 and x.shape[2] == F)
-            if not ok or x.numel() == 0:
-                raise QuantizationError(f"calibration batch of shape {tuple(x.shape)}: expected (B,1,{F},T) or (B,T,{F})")
-            x = x.float()
+            x = _calibration_batch(x, dev, feature_extractor, F, sequences=True)
             lo, hi = torch.minimum(lo, x.min()), torch.maximum(hi, x.max())
             seen += x.shape[0]
     if seen == 0:
@@ -443,7 +419,8 @@ class ModelExporter:
         return write_bundle(path, dict(header, kind="fp16"), float_arrays(state, fp16=True))
 
     def _write_int8(self, output_path: Path, header: dict, state: dict, config: ExportConfig) -> Path:
-        if header["architecture"] not in ("cnn_small", "crnn", "mobilenetv3", "TCNWakeword", "ResNet18Wakeword", "LSTMWakeword"):
+        entry = _INT8.get(header["architecture"])
+        if entry is None:
             raise QuantizationError("int8 export covers cnn_small only among the factory's architectures -- with crnn, whose conv "
                                     "stack is cnn_small's, and mobilenetv3 -- and TCNWakeword, ResNet18Wakeword and LSTMWakeword; not "
                                     f"{header['architecture']!r}")
@@ -455,66 +432,72 @@ class ModelExporter:
         if fe is None:
             from ..data.feature_extraction import FeatureExtractor
             fe = FeatureExtractor(n_mels=F, device=self.device)
-        if header["architecture"] == "TCNWakeword":
-            check_tcn_args(header["tcn"], header["num_classes"])
-            cal = calibrate_tcn(self.model, self.calibration, (F, T), self.device, fe)
-            if config.verbose:
-                logger.info("calibrated ranges: %s", cal)
-            arrays, scales = quantize_tcn(state, header["tcn"], (F, T), cal["x_min"], cal["x_max"], cal["a_max"], cal["p_max"])
-            layers = [k[:-2] for k in arrays if k.endswith(".w") and k.startswith("b")] + ["pool", "fc"]
-            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
-            check_bundle(h, arrays)
-            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
-        if header["architecture"] == "LSTMWakeword":
-            check_lstm_args(header["lstm"], header["num_classes"])
-            cal = calibrate_lstm(self.model, self.calibration, F, self.device, fe)
-            if config.verbose:
-                logger.info("calibrated ranges: %s", cal)
-            arrays, scales = quantize_lstm(state, header["lstm"], cal["x_min"], cal["x_max"])
-            layers = [k[:-2] for k in arrays if k.endswith(".w")]
-            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
-            check_bundle(h, arrays)
-            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
-        if header["architecture"] == "crnn":
-            if "crnn" not in header:
-                raise QuantizationError("the header of a crnn bundle holds no crnn entry (hidden_size, num_layers, bidirectional)")
-            check_crnn_args(header["crnn"], header["num_classes"])
-            cal = calibrate_crnn(self.model, self.calibration, F, self.device, fe)
-            if config.verbose:
-                logger.info("calibrated ranges: %s", cal)
-            arrays, scales = quantize_crnn(state, header["crnn"], F, cal, eps=self.model.front.stem.bn.eps)
-            layers = [k[:-2] for k in arrays if k.endswith(".w") and k != "fc.w"] + ["fmean", "fc"]
-            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
-            check_bundle(h, arrays)
-            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
-        if header["architecture"] == "mobilenetv3":
-            cal = calibrate_mobilenetv3(self.model, self.calibration, (F, T), self.device, fe)
-            if config.verbose:
-                logger.info("calibrated ranges: %s", cal)
-            arrays, scales = quantize_mobilenetv3(state, (F, T), cal, eps=self.model.mobilenet.features[0][1].eps)
-            layers = [k[:-2] for k in arrays if k.endswith(".w") and k != "fc.w"] + ["pool", "fc"]
-            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
-            check_bundle(h, arrays)
-            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
-        if header["architecture"] == "ResNet18Wakeword":
-            cal = calibrate_resnet18(self.model, self.calibration, (F, T), self.device, fe)
-            if config.verbose:
-                logger.info("calibrated ranges: %s", cal)
-            arrays, scales = quantize_resnet18(state, (F, T), cal, eps=self.model.resnet.bn1.eps)
-            layers = [k[:-2] for k in arrays if k.endswith(".w") and k != "fc.w"] + ["pool", "fc"]
-            h = dict(header, kind="int8", layers=layers, feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
-            check_bundle(h, arrays)
-            return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
-        cal = calibrate_cnn_small(self.model, self.calibration, (F, T), self.device, fe)
+        entry.check(header)
+        cal = entry.calibrate(self.model, self.calibration, F, T, self.device, fe)
         if config.verbose:
             logger.info("calibrated ranges: %s", cal)
-        arrays, scales = quantize_cnn_small(state, (F, T), cal["x_min"], cal["x_max"], cal["a_max"], cal["p_max"],
-                                            eps=self.model.stem.bn.eps)
-        h = dict(header, kind="int8", layers=CONVS + ["pool", "fc"], feature_shape=[int(F), int(T)], scales=scales,
-                 calibration=cal)
+        arrays, scales = entry.quantize(self.model, state, header, F, T, cal)
+        h = dict(header, kind="int8", layers=entry.layers(arrays), feature_shape=[int(F), int(T)], scales=scales, calibration=cal)
         check_bundle(h, arrays)
-        path = output_path.parent / f"{output_path.stem}_int8.npz"
-        return write_bundle(path, h, arrays)
+        return write_bundle(output_path.parent / f"{output_path.stem}_int8.npz", h, arrays)
+
+
+@dataclass(frozen=True)
+class _Int8:
+    """What the int8 export of one architecture is made of.  ``check(header)`` refuses arguments the law does not cover;
+    ``calibrate(model, batches, F, T, device, feature_extractor)`` -> the ranges; ``quantize(model, state, header, F, T, cal)`` ->
+    (arrays, scales); ``layers(arrays)`` -> the header's layer names; ``runtime``: the class that runs the bundle."""
+    runtime: type
+    check: Callable
+    calibrate: Callable
+    quantize: Callable
+    layers: Callable
+
+
+def _check_crnn_header(header):
+    if "crnn" not in header:
+        raise QuantizationError("the header of a crnn bundle holds no crnn entry (hidden_size, num_layers, bidirectional)")
+    check_crnn_args(header["crnn"], header["num_classes"])
+
+
+def _conv_layers(tail):
+    return lambda arrays: [k[:-2] for k in arrays if k.endswith(".w") and k != "fc.w"] + tail
+
+
+_INT8 = {
+    "cnn_small": _Int8(
+        QuantizedCNNSmall, lambda header: None,
+        lambda model, batches, F, T, dev, fe: calibrate_cnn_small(model, batches, (F, T), dev, fe),
+        lambda model, state, header, F, T, cal: quantize_cnn_small(state, (F, T), cal["x_min"], cal["x_max"], cal["a_max"], cal["p_max"],
+                                                                   eps=model.stem.bn.eps),
+        lambda arrays: CONVS + ["pool", "fc"]),
+    "TCNWakeword": _Int8(
+        QuantizedTCN, lambda header: check_tcn_args(header["tcn"], header["num_classes"]),
+        lambda model, batches, F, T, dev, fe: calibrate_tcn(model, batches, (F, T), dev, fe),
+        lambda model, state, header, F, T, cal: quantize_tcn(state, header["tcn"], (F, T), cal["x_min"], cal["x_max"], cal["a_max"],
+                                                             cal["p_max"]),
+        lambda arrays: [k[:-2] for k in arrays if k.endswith(".w") and k.startswith("b")] + ["pool", "fc"]),
+    "ResNet18Wakeword": _Int8(
+        QuantizedResNet18, lambda header: None,
+        lambda model, batches, F, T, dev, fe: calibrate_resnet18(model, batches, (F, T), dev, fe),
+        lambda model, state, header, F, T, cal: quantize_resnet18(state, (F, T), cal, eps=model.resnet.bn1.eps),
+        _conv_layers(["pool", "fc"])),
+    "LSTMWakeword": _Int8(
+        QuantizedLSTM, lambda header: check_lstm_args(header["lstm"], header["num_classes"]),
+        lambda model, batches, F, T, dev, fe: calibrate_lstm(model, batches, F, dev, fe),
+        lambda model, state, header, F, T, cal: quantize_lstm(state, header["lstm"], cal["x_min"], cal["x_max"]),
+        lambda arrays: [k[:-2] for k in arrays if k.endswith(".w")]),
+    "crnn": _Int8(
+        QuantizedCRNN, _check_crnn_header,
+        lambda model, batches, F, T, dev, fe: calibrate_crnn(model, batches, F, dev, fe),
+        lambda model, state, header, F, T, cal: quantize_crnn(state, header["crnn"], F, cal, eps=model.front.stem.bn.eps),
+        _conv_layers(["fmean", "fc"])),
+    "mobilenetv3": _Int8(
+        QuantizedMobileNetV3, lambda header: None,
+        lambda model, batches, F, T, dev, fe: calibrate_mobilenetv3(model, batches, (F, T), dev, fe),
+        lambda model, state, header, F, T, cal: quantize_mobilenetv3(state, (F, T), cal, eps=model.mobilenet.features[0][1].eps),
+        _conv_layers(["pool", "fc"])),
+}
 
 
 def export_model(checkpoint_path: Path, output_path: Path, opset_version: int = 14, dynamic_batch: bool = True,
@@ -547,9 +530,7 @@ def load_exported_model(path: Path, device: str = "cuda") -> nn.Module:
     header, arrays = load_bundle(path)
     check_bundle(header, arrays)
     if header["kind"] == "int8":
-        cls = {"TCNWakeword": QuantizedTCN, "ResNet18Wakeword": QuantizedResNet18, "LSTMWakeword": QuantizedLSTM,
-               "crnn": QuantizedCRNN, "mobilenetv3": QuantizedMobileNetV3}.get(header["architecture"], QuantizedCNNSmall)
-        return cls(header, arrays).to(device)
+        return _INT8.get(header["architecture"], _INT8["cnn_small"]).runtime(header, arrays).to(device)
     if header["architecture"] == "ResNet18Wakeword":
         from ..models import ResNet18Wakeword
         model = ResNet18Wakeword(num_classes=header["num_classes"])
