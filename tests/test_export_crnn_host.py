@@ -193,6 +193,21 @@ def test_export_refuses_what_the_law_cannot_hold():
         QZ.quantize_crnn(state, args, 13, dict(ranges, f_max=float("nan")))
     with pytest.raises(QZ.QuantizationError, match="calibrated maxima"):
         QZ.quantize_crnn(state, args, 13, dict(ranges, a_max=ranges["a_max"][:8]))
+    # the argument and entry checks are shared with the LSTM: every message still names this model, and no input_size is asked for
+    for changes, nc, text in (({"hidden_size": 64}, 2, "the int8 CRNN implements hidden_size == 128, got hidden_size 64"),
+                              ({"num_layers": 9}, 2, "the int8 CRNN takes 1..8 layers, got num_layers 9"),
+                              ({}, 65, "the int8 CRNN takes 2..64 classes, got num_classes 65")):
+        with pytest.raises(QZ.QuantizationError) as e:
+            QZ.check_crnn_args(dict(args, **changes), num_classes=nc)
+        assert str(e.value) == text
+    assert QZ.check_crnn_args(dict(args, input_size=0), num_classes=64) == (2, 2)
+    for changes, text in (({"hidden_size": 64}, ": hidden_size 128, 1..8 layers"), ({"num_layers": 9}, ": hidden_size 128, 1..8 layers"),
+                          ({"num_layers": 2.0}, ": integer hidden_size and num_layers, a boolean bidirectional")):
+        with pytest.raises(BU.BundleError) as e:
+            BU.check_crnn_entry({"crnn": dict(args, **changes)})
+        assert str(e.value).startswith("the crnn entry {") and str(e.value).endswith(text)
+    with pytest.raises(BU.BundleError, match=r"the crnn entry None is not \{hidden_size, num_layers, bidirectional\}"):
+        BU.check_crnn_entry({})
 
 
 # ------------------------------------------------------------------ the bundle file

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import q8_crnn_cases as CQ
 from tests import q8_lstm_cases as LQ
 
 pytestmark = pytest.mark.gpu
@@ -140,6 +141,53 @@ def test_global_tables_form_gives_the_same_bits(cases, grid_cap, global_tables):
     _whole(cases["saturating"])
     grid_cap(1)
     _whole(cases["trips"])
+
+
+def _gru_layer0(args, arrays):
+    """(w_hh, bias, mult, shift, tab_sigmoid, tab_tanh) of layer 0 of a GRU stack case on the device, as ``cq8_gru_layer_fwd`` reads
+    them."""
+    from wakeword_trainer_home_amd.export.runtime import device_gru_layer
+    layer = device_gru_layer(arrays, 0, len(CQ.dirs(args)), int(arrays["input_zero"][0]))
+    return tuple(_dev(t) for t in layer[4:] + (arrays["tab.sigmoid"], arrays["tab.tanh"]))
+
+
+@pytest.mark.parametrize("cell", ["lstm", "gru"])
+def test_recurrence_frame_two_trips_one_live_row_one_direction(cases, grid_cap, cell):
+    """The edges of the frame both cells share that no other case meets: ``uni`` (one direction, one layer, I = 24, T = 4) at 17
+    batch rows under a grid cap of 1 is a launch at gridDim.y = 1 whose one workgroup makes two trips, the second with a single
+    live row.  (T = 1 on this shape would need a case builder that takes T; ``tiny`` is T = 1.)"""
+    from wakeword_trainer_home_amd import _native as nat
+    if cell == "lstm":
+        ref, model = LQ.case("uni", batch=17)[3], cases["uni"][4]         # the bundle does not depend on the batch size
+        fwd, state = nat.lq8_lstm_layer_fwd, "c"
+        params = model.layer(0)[4:] + (model.tab_sigmoid, model.tab_tanh)
+    else:
+        args, arrays, _, ref = CQ.stack_case("uni", batch=17)[:4]
+        fwd, state, params = nat.cq8_gru_layer_fwd, "h", _gru_layer0(args, arrays)
+    assert ref["l0.fwd.u"].shape[:2] == (17, 4) and "l0.rev.u" not in ref
+    grid_cap(1)
+    y, s_n = fwd(_dev(ref["l0.fwd.u"]), *params)
+    _same(y, ref["l0.fwd.y"], f"{cell} recurrence, y")
+    _same(s_n, ref[f"l0.fwd.{state}"], f"{cell} recurrence, final state")
+
+
+def test_the_gru_ignores_the_lstm_table_switch(cases, global_tables):
+    """WW_LQ8_TABLES=global is the LSTM's switch alone: under it the GRU recurrence gives the restated law's bits, and the LSTM
+    recurrence launched right after it gives its own in both table forms."""
+    from wakeword_trainer_home_amd import _native as nat
+    args, arrays, _, ref = CQ.stack_case("odd")[:4]
+    y, h_n = nat.cq8_gru_layer_fwd(_dev(_stacked(ref, args, 0, "u")), *_gru_layer0(args, arrays))
+    _same(y, _stacked(ref, args, 0, "y"), "GRU recurrence, y")
+    _same(h_n, _stacked(ref, args, 0, "h"), "GRU recurrence, h_n")
+    header, _, _, ref, model = cases["odd"]
+    got = {}
+    for tables in ("global", "lds"):
+        os.environ["WW_LQ8_TABLES"] = tables                     # (the fixture puts the old value back)
+        got[tables] = nat.lq8_lstm_layer_fwd(_dev(_stacked(ref, header["lstm"], 0, "u")), *model.layer(0)[4:], model.tab_sigmoid,
+                                             model.tab_tanh)
+        _same(got[tables][0], _stacked(ref, header["lstm"], 0, "y"), f"LSTM recurrence, tables {tables}, y")
+        _same(got[tables][1], _stacked(ref, header["lstm"], 0, "c"), f"LSTM recurrence, tables {tables}, c")
+    assert all(torch.equal(a, b) for a, b in zip(got["global"], got["lds"]))
 
 
 def test_nan_and_infinite_inputs_on_the_device(cases):

@@ -156,6 +156,23 @@ def test_export_refuses_what_the_law_cannot_hold():
         QZ.check_lstm_args(args, num_classes=65)
     with pytest.raises(QZ.QuantizationError, match="not finite"):
         QZ.quantize_lstm(state, args, -10.0, float("inf"))
+    # the argument and entry checks are shared with the CRNN: every message still names this model
+    for changes, nc, text in (({"hidden_size": 64}, 2, "the int8 LSTM implements hidden_size == 128, got hidden_size 64"),
+                              ({"num_layers": 9}, 2, "the int8 LSTM takes 1..8 layers, got num_layers 9"),
+                              ({"input_size": 0}, 2, "the int8 LSTM takes a positive input_size, got 0"),
+                              ({}, 65, "the int8 LSTM takes 2..64 classes, got num_classes 65")):
+        with pytest.raises(QZ.QuantizationError) as e:
+            QZ.check_lstm_args(dict(args, **changes), num_classes=nc)
+        assert str(e.value) == text
+    assert QZ.check_lstm_args(args, num_classes=64) == (40, 2, 2)
+    for changes, text in (({"hidden_size": 64}, ": hidden_size 128, 1..8 layers, a positive input_size"),
+                          ({"num_layers": 9}, ": hidden_size 128, 1..8 layers, a positive input_size"),
+                          ({"num_layers": 2.0}, ": integer input_size, hidden_size and num_layers, a boolean bidirectional")):
+        with pytest.raises(BU.BundleError) as e:
+            BU.check_lstm_entry({"lstm": dict(args, **changes)})
+        assert str(e.value).startswith("the lstm entry {") and str(e.value).endswith(text)
+    with pytest.raises(BU.BundleError, match=r"the lstm entry None is not \{input_size, hidden_size, num_layers, bidirectional\}"):
+        BU.check_lstm_entry({})
 
 
 # ------------------------------------------------------------------ the bundle file

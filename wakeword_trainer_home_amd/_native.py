@@ -2649,22 +2649,32 @@ def lq8_proj_fwd(a, w, bias, mult, shift):
     return u
 
 
+# what tells the two int8 recurrences apart in the binding: (entry point, gate rows of a direction)
+_Q8_LSTM, _Q8_GRU = ("lq8_lstm_layer_fwd", 512), ("cq8_gru_layer_fwd", 384)
+
+
+def _q8_rnn_layer_fwd(cell, u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh):
+    entry, rows = cell
+    dev = _dev(u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh)
+    G = w_hh.shape[0]
+    if u.dtype != torch.int16 or u.dim() != 3 or u.shape[2] != G or G not in (rows, 2 * rows) or \
+            w_hh.dtype != torch.int8 or tuple(w_hh.shape) != (G, 128) or \
+            any(t.dtype != torch.int32 or t.numel() != G for t in (bias, mult, shift)) or \
+            any(t.dtype != torch.int16 or t.numel() != 4096 for t in (tab_sigmoid, tab_tanh)) or not u.is_contiguous():
+        raise ValueError(f"{entry}: u int16 (B,T,G), w_hh int8 (G,128), bias / mult / shift int32 (G), tables int16 (4096)")
+    B, T, nd = u.shape[0], u.shape[1], G // rows
+    y = torch.empty((B, T, nd * 128), dtype=torch.int8, device=dev)
+    s_n = torch.empty((B, nd * 128), dtype=torch.int16, device=dev)
+    with _guard(dev):
+        _check(getattr(load(), "ww_" + entry)(ctx(dev), _p(u), _p(w_hh), _p(bias), _p(mult), _p(shift), _p(tab_sigmoid), _p(tab_tanh),
+                                              B, T, nd, _p(y), _p(s_n), _stream(dev)), "ww_" + entry)
+    return y, s_n
+
+
 def lq8_lstm_layer_fwd(u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh):
     """u int16 (B,T,nd*512), w_hh int8 (nd*512,128), bias / mult / shift int32 (nd*512), the two int16 (4096) tables ->
     (y int8 (B,T,nd*128), c_n int16 (B,nd*128))."""
-    dev = _dev(u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh)
-    G = w_hh.shape[0]
-    if u.dtype != torch.int16 or u.dim() != 3 or u.shape[2] != G or G not in (512, 1024) or w_hh.dtype != torch.int8 or \
-            tuple(w_hh.shape) != (G, 128) or any(t.dtype != torch.int32 or t.numel() != G for t in (bias, mult, shift)) or \
-            any(t.dtype != torch.int16 or t.numel() != 4096 for t in (tab_sigmoid, tab_tanh)):
-        raise ValueError("lq8_lstm_layer_fwd: u int16 (B,T,G), w_hh int8 (G,128), bias / mult / shift int32 (G), tables int16 (4096)")
-    B, T, nd = u.shape[0], u.shape[1], G // 512
-    y = torch.empty((B, T, nd * 128), dtype=torch.int8, device=dev)
-    c_n = torch.empty((B, nd * 128), dtype=torch.int16, device=dev)
-    with _guard(dev):
-        _check(load().ww_lq8_lstm_layer_fwd(ctx(dev), _p(u), _p(w_hh), _p(bias), _p(mult), _p(shift), _p(tab_sigmoid), _p(tab_tanh),
-                                            B, T, nd, _p(y), _p(c_n), _stream(dev)), "ww_lq8_lstm_layer_fwd")
-    return y, c_n
+    return _q8_rnn_layer_fwd(_Q8_LSTM, u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh)
 
 
 def lq8_head_fwd(y, fc_w, fc_bias, fc_scale):
@@ -2697,22 +2707,30 @@ def lq8_lstm_fwd(tab, io: Lq8Io, x, ws, logits):
                                       ws.numel() * ws.element_size(), _p(logits), _stream(dev)), "ww_lq8_lstm_fwd")
 
 
+def _r256(n):
+    return (n + 255) // 256 * 256
+
+
+def _q8_rnn_views(out, i8, off, B, T, num_layers, nd, rows, state):
+    """Carves the per-layer u | y | state regions of a recurrent stack from ``i8`` at byte ``off`` into ``out``; returns the offset
+    past the last layer."""
+    for k in range(num_layers):
+        for name, dtype, shape in ((f"l{k}.u", torch.int16, (B, T, nd * rows)), (f"l{k}.y", torch.int8, (B, T, nd * 128)),
+                                   (f"l{k}.{state}", torch.int16, (B, nd * 128))):
+            n = math.prod(shape) * dtype.itemsize
+            out[name] = i8[off:off + n].view(dtype).view(shape)
+            off += _r256(n)
+    return off
+
+
 def lq8_workspace_views(ws, B, T, input_size, num_layers, num_directions):
     """The tensors ww_lq8_lstm_fwd left in ``ws`` (uint8), by stage name: xq (B,T,Fp) PADDED, per layer l{k}.u int16 (B,T,nd*512),
     l{k}.y int8 (B,T,nd*128) and l{k}.c int16 (B,nd*128), directions stacked, then hcat (B,nd*128) -- the layout include/wwhip.h
     states."""
-    r256 = lambda n: (n + 255) // 256 * 256       # noqa: E731
     i8, nd = ws.view(torch.int8), num_directions
     Fp = tq8_pad(input_size)
-    out, off = {"xq": i8[:B * T * Fp].view(B, T, Fp)}, r256(B * T * Fp)
-    for k in range(num_layers):
-        n = B * T * nd * 512 * 2
-        out[f"l{k}.u"] = i8[off:off + n].view(torch.int16).view(B, T, nd * 512)
-        off += r256(n)
-        out[f"l{k}.y"] = i8[off:off + B * T * nd * 128].view(B, T, nd * 128)
-        off += r256(B * T * nd * 128)
-        out[f"l{k}.c"] = i8[off:off + B * nd * 256].view(torch.int16).view(B, nd * 128)
-        off += r256(B * nd * 256)
+    out, off = {"xq": i8[:B * T * Fp].view(B, T, Fp)}, _r256(B * T * Fp)
+    off = _q8_rnn_views(out, i8, off, B, T, num_layers, nd, 512, "c")
     out["hcat"] = i8[off:off + B * nd * 128].view(B, nd * 128)
     return out
 
@@ -2735,19 +2753,7 @@ def cq8_fmean_fwd(a, mult, shift):
 def cq8_gru_layer_fwd(u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh):
     """u int16 (B,T,nd*384), w_hh int8 (nd*384,128), bias / mult / shift int32 (nd*384), the two int16 (4096) tables ->
     (y int8 (B,T,nd*128), h_n int16 (B,nd*128))."""
-    dev = _dev(u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh)
-    G = w_hh.shape[0]
-    if u.dtype != torch.int16 or u.dim() != 3 or u.shape[2] != G or G not in (384, 768) or w_hh.dtype != torch.int8 or \
-            tuple(w_hh.shape) != (G, 128) or any(t.dtype != torch.int32 or t.numel() != G for t in (bias, mult, shift)) or \
-            any(t.dtype != torch.int16 or t.numel() != 4096 for t in (tab_sigmoid, tab_tanh)) or not u.is_contiguous():
-        raise ValueError("cq8_gru_layer_fwd: u int16 (B,T,G), w_hh int8 (G,128), bias / mult / shift int32 (G), tables int16 (4096)")
-    B, T, nd = u.shape[0], u.shape[1], G // 384
-    y = torch.empty((B, T, nd * 128), dtype=torch.int8, device=dev)
-    h_n = torch.empty((B, nd * 128), dtype=torch.int16, device=dev)
-    with _guard(dev):
-        _check(load().ww_cq8_gru_layer_fwd(ctx(dev), _p(u), _p(w_hh), _p(bias), _p(mult), _p(shift), _p(tab_sigmoid), _p(tab_tanh),
-                                           B, T, nd, _p(y), _p(h_n), _stream(dev)), "ww_cq8_gru_layer_fwd")
-    return y, h_n
+    return _q8_rnn_layer_fwd(_Q8_GRU, u, w_hh, bias, mult, shift, tab_sigmoid, tab_tanh)
 
 
 def cq8_crnn_workspace_bytes(B, F, T, num_layers, num_directions):
@@ -2767,23 +2773,14 @@ def cq8_workspace_views(ws, B, F, T, num_layers, num_directions):
     """The tensors ww_cq8_crnn_fwd left in ``ws`` (uint8), by stage name: xq (B,F,T), front.stem and front.pw0 .. front.pw3
     (B,H',W',64), seq (B,W',64), per layer l{k}.u int16 (B,W',nd*384), l{k}.y int8 (B,W',nd*128) and l{k}.h int16 (B,nd*128),
     directions stacked, then hcat (B,nd*128) -- the layout include/wwhip.h states."""
-    r256 = lambda n: (n + 255) // 256 * 256       # noqa: E731
     i8, nd = ws.view(torch.int8), num_directions
     H, W = (F + 1) // 2, (T + 1) // 2
-    out, off, act = {"xq": i8[:B * F * T].view(B, F, T)}, r256(B * F * T), B * H * W * 64
+    out, off, act = {"xq": i8[:B * F * T].view(B, F, T)}, _r256(B * F * T), B * H * W * 64
     for name in ["stem"] + [f"pw{j}" for j in range(4)]:
         out["front." + name] = i8[off:off + act].view(B, H, W, 64)
-        off += r256(act)
+        off += _r256(act)
     out["seq"] = i8[off:off + B * W * 64].view(B, W, 64)
-    off += r256(B * W * 64)
-    for k in range(num_layers):
-        n = B * W * nd * 384 * 2
-        out[f"l{k}.u"] = i8[off:off + n].view(torch.int16).view(B, W, nd * 384)
-        off += r256(n)
-        out[f"l{k}.y"] = i8[off:off + B * W * nd * 128].view(B, W, nd * 128)
-        off += r256(B * W * nd * 128)
-        out[f"l{k}.h"] = i8[off:off + B * nd * 256].view(torch.int16).view(B, nd * 128)
-        off += r256(B * nd * 256)
+    off = _q8_rnn_views(out, i8, off + _r256(B * W * 64), B, W, num_layers, nd, 384, "h")
     out["hcat"] = i8[off:off + B * nd * 128].view(B, nd * 128)
     return out
 

@@ -67,6 +67,15 @@ def _check_mult(arrays, prefix, n):
         raise BundleError(f"{prefix}.sh: a shift outside [1, 62]")
 
 
+def _check_fc(arrays, nc, K):
+    w = _need(arrays, "fc.w", np.int8, (nc, K))
+    if (w == -128).any():
+        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
+    _need(arrays, "fc.b", np.int32, (nc,))
+    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
+        raise BundleError("fc.scale is not finite")
+
+
 def check_tcn_entry(header: dict):
     """The header's ``tcn`` entry as (input_size, [channels], kernel_size), within the limits of the int8 TCN path."""
     tcn = header.get("tcn")
@@ -103,12 +112,7 @@ def _check_tcn(header, arrays, fs):
         _check_mult(arrays, f"b{i}.add", 1)
         cin = c
     _check_mult(arrays, "pool", 1)
-    w = _need(arrays, "fc.w", np.int8, (nc, cin))
-    if (w == -128).any():
-        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
-    _need(arrays, "fc.b", np.int32, (nc,))
-    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
-        raise BundleError("fc.scale is not finite")
+    _check_fc(arrays, nc, cin)
 
 
 def _check_resnet18(header, arrays):
@@ -126,68 +130,57 @@ def _check_resnet18(header, arrays):
         _need(arrays, p + ".b", np.int32, (cout,))
         _check_mult(arrays, p, cout)
     _check_mult(arrays, "pool", 1)
-    w = _need(arrays, "fc.w", np.int8, (nc, 512))
-    if (w == -128).any():
-        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
-    _need(arrays, "fc.b", np.int32, (nc,))
-    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
-        raise BundleError("fc.scale is not finite")
+    _check_fc(arrays, nc, 512)
+
+
+def _check_rnn_entry(header, key, with_input):
+    e = header.get(key)
+    keys = (("input_size",) if with_input else ()) + ("hidden_size", "num_layers", "bidirectional")
+    if not (isinstance(e, dict) and all(k in e for k in keys)):
+        raise BundleError(f"the {key} entry {e!r} is not {{{', '.join(keys)}}}")
+    *ints, bi = (e[k] for k in keys)
+    if not (all(isinstance(v, int) and not isinstance(v, bool) for v in ints) and isinstance(bi, bool)):
+        raise BundleError(f"the {key} entry {e!r}: integer {', '.join(keys[:-2])} and num_layers, a boolean bidirectional")
+    *I, H, L = ints
+    if H != LSTM_HIDDEN or not 1 <= L <= 8 or any(v < 1 for v in I):
+        raise BundleError(f"the {key} entry {e!r}: hidden_size {LSTM_HIDDEN}, 1..8 layers" + (", a positive input_size" if I else ""))
+    return (*I, L, 2 if bi else 1)
 
 
 def check_lstm_entry(header: dict):
     """The header's ``lstm`` entry as (input_size, num_layers, num_directions), within the limits of ``LSTMWakeword``."""
-    e = header.get("lstm")
-    keys = ("input_size", "hidden_size", "num_layers", "bidirectional")
-    if not (isinstance(e, dict) and all(k in e for k in keys)):
-        raise BundleError(f"the lstm entry {e!r} is not {{input_size, hidden_size, num_layers, bidirectional}}")
-    I, H, L, bi = (e[k] for k in keys)
-    if not (all(isinstance(v, int) and not isinstance(v, bool) for v in (I, H, L)) and isinstance(bi, bool)):
-        raise BundleError(f"the lstm entry {e!r}: integer input_size, hidden_size and num_layers, a boolean bidirectional")
-    if H != LSTM_HIDDEN or not 1 <= L <= 8 or I < 1:
-        raise BundleError(f"the lstm entry {e!r}: hidden_size {LSTM_HIDDEN}, 1..8 layers, a positive input_size")
-    return I, L, 2 if bi else 1
-
-
-def _check_lstm(header, arrays, fs):
-    I, L, nd = check_lstm_entry(header)
-    nc, H = header["num_classes"], LSTM_HIDDEN
-    if not (isinstance(nc, int) and 2 <= nc <= 64):
-        raise BundleError(f"num_classes {nc!r} is outside [2, 64]")
-    if fs[0] != I:
-        raise BundleError(f"feature_shape {fs!r} does not have the LSTM's {I} features per frame")
-    for layer in range(L):
-        for d in LSTM_DIRS[:nd]:
-            for part, K in (("ih", I if layer == 0 else nd * H), ("hh", H)):
-                p = f"l{layer}.{d}.{part}"
-                w = _need(arrays, p + ".w", np.int8, (4 * H, K))
-                if (w == -128).any():
-                    raise BundleError(f"{p}.w holds -128: weights are symmetric, in [-127, 127]")
-                _need(arrays, p + ".b", np.int32, (4 * H,))
-                _check_mult(arrays, p, 4 * H)
-    for name, lo in (("tab.sigmoid", 0), ("tab.tanh", -32767)):
-        t = _need(arrays, name, np.int16, (LSTM_TABLE,)).astype(np.int64)
-        if (np.diff(t) < 0).any() or t.min() < lo or t.max() > 32767:
-            raise BundleError(f"{name} is not a non-decreasing table within [{lo}, 32767]")
-    w = _need(arrays, "fc.w", np.int8, (nc, nd * H))
-    if (w == -128).any():
-        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
-    _need(arrays, "fc.b", np.int32, (nc,))
-    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
-        raise BundleError("fc.scale is not finite")
+    return _check_rnn_entry(header, "lstm", True)
 
 
 def check_crnn_entry(header: dict):
     """The header's ``crnn`` entry as (num_layers, num_directions), within the limits of the int8 GRU stack."""
-    e = header.get("crnn")
-    keys = ("hidden_size", "num_layers", "bidirectional")
-    if not (isinstance(e, dict) and all(k in e for k in keys)):
-        raise BundleError(f"the crnn entry {e!r} is not {{hidden_size, num_layers, bidirectional}}")
-    H, L, bi = (e[k] for k in keys)
-    if not (all(isinstance(v, int) and not isinstance(v, bool) for v in (H, L)) and isinstance(bi, bool)):
-        raise BundleError(f"the crnn entry {e!r}: integer hidden_size and num_layers, a boolean bidirectional")
-    if H != LSTM_HIDDEN or not 1 <= L <= 8:
-        raise BundleError(f"the crnn entry {e!r}: hidden_size {LSTM_HIDDEN}, 1..8 layers")
-    return L, 2 if bi else 1
+    return _check_rnn_entry(header, "crnn", False)
+
+
+def _check_rnn_stack(arrays, gates, K0, L, nd):
+    """L layers of nd directions of ``gates`` gate blocks (LSTM 4, GRU 3) over K0 input columns, then the two gate tables."""
+    G, H = gates * LSTM_HIDDEN, LSTM_HIDDEN
+    for layer in range(L):
+        for d in LSTM_DIRS[:nd]:
+            for part, K in (("ih", K0 if layer == 0 else nd * H), ("hh", H)):
+                p = f"l{layer}.{d}.{part}"
+                w = _need(arrays, p + ".w", np.int8, (G, K))
+                if (w == -128).any():
+                    raise BundleError(f"{p}.w holds -128: weights are symmetric, in [-127, 127]")
+                _need(arrays, p + ".b", np.int32, (G,))
+                _check_mult(arrays, p, G)
+    _check_tables(arrays)
+
+
+def _check_lstm(header, arrays, fs):
+    I, L, nd = check_lstm_entry(header)
+    nc = header["num_classes"]
+    if not (isinstance(nc, int) and 2 <= nc <= 64):
+        raise BundleError(f"num_classes {nc!r} is outside [2, 64]")
+    if fs[0] != I:
+        raise BundleError(f"feature_shape {fs!r} does not have the LSTM's {I} features per frame")
+    _check_rnn_stack(arrays, 4, I, L, nd)
+    _check_fc(arrays, nc, nd * LSTM_HIDDEN)
 
 
 def _check_tables(arrays):
@@ -199,7 +192,7 @@ def _check_tables(arrays):
 
 def _check_crnn(header, arrays):
     L, nd = check_crnn_entry(header)
-    nc, H = header["num_classes"], LSTM_HIDDEN
+    nc = header["num_classes"]
     if not (isinstance(nc, int) and 2 <= nc <= 64):
         raise BundleError(f"num_classes {nc!r} is outside [2, 64]")
     for name in CONVS:
@@ -210,22 +203,8 @@ def _check_crnn(header, arrays):
         _need(arrays, p + ".b", np.int32, (64,))
         _check_mult(arrays, p, 64)
     _check_mult(arrays, "fmean", 1)
-    for layer in range(L):
-        for d in LSTM_DIRS[:nd]:
-            for part, K in (("ih", 64 if layer == 0 else nd * H), ("hh", H)):
-                p = f"l{layer}.{d}.{part}"
-                w = _need(arrays, p + ".w", np.int8, (3 * H, K))
-                if (w == -128).any():
-                    raise BundleError(f"{p}.w holds -128: weights are symmetric, in [-127, 127]")
-                _need(arrays, p + ".b", np.int32, (3 * H,))
-                _check_mult(arrays, p, 3 * H)
-    _check_tables(arrays)
-    w = _need(arrays, "fc.w", np.int8, (nc, nd * H))
-    if (w == -128).any():
-        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
-    _need(arrays, "fc.b", np.int32, (nc,))
-    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
-        raise BundleError("fc.scale is not finite")
+    _check_rnn_stack(arrays, 3, 64, L, nd)
+    _check_fc(arrays, nc, nd * LSTM_HIDDEN)
 
 
 def _check_mbv3_layer(arrays, p, cout, k_in, hs=False):
@@ -270,12 +249,7 @@ def _check_mobilenetv3(header, arrays, fs):
     _check_mbv3_layer(arrays, "last", MBV3_LAST, blocks[-1]["cout"], hs=True)
     _check_mbv3_pool(arrays, "pool", blocks[-1]["hw"][0] * blocks[-1]["hw"][1])
     _check_mbv3_layer(arrays, "cls0", MBV3_HIDDEN, MBV3_LAST, hs=True)
-    w = _need(arrays, "fc.w", np.int8, (nc, MBV3_HIDDEN))
-    if (w == -128).any():
-        raise BundleError("fc.w holds -128: weights are symmetric, in [-127, 127]")
-    _need(arrays, "fc.b", np.int32, (nc,))
-    if not np.isfinite(_need(arrays, "fc.scale", np.float32, (nc,))).all():
-        raise BundleError("fc.scale is not finite")
+    _check_fc(arrays, nc, MBV3_HIDDEN)
 
 
 def check_bundle(header: dict, arrays: dict) -> None:

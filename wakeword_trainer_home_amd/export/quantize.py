@@ -297,19 +297,26 @@ LSTM_MAX_LAYERS, LSTM_MAX_CLASSES = 8, 64
 S_H = 2.0 ** -7                        # the fixed scale of the hidden operand q_h (zero point 0)
 
 
+def _check_rnn_args(what, args, num_classes, input_size=None):
+    """What ``check_lstm_args`` and ``check_crnn_args`` share; ``what`` is the model word of the messages, ``input_size`` is checked
+    where the model has one.  -> (num_layers, num_directions)."""
+    H, L = int(args["hidden_size"]), int(args["num_layers"])
+    if H != LSTM_HIDDEN:
+        raise QuantizationError(f"the int8 {what} implements hidden_size == {LSTM_HIDDEN}, got hidden_size {H}")
+    if not 1 <= L <= LSTM_MAX_LAYERS:
+        raise QuantizationError(f"the int8 {what} takes 1..{LSTM_MAX_LAYERS} layers, got num_layers {L}")
+    if input_size is not None and input_size < 1:
+        raise QuantizationError(f"the int8 {what} takes a positive input_size, got {input_size}")
+    if not 2 <= int(num_classes) <= LSTM_MAX_CLASSES:
+        raise QuantizationError(f"the int8 {what} takes 2..{LSTM_MAX_CLASSES} classes, got num_classes {num_classes}")
+    return L, 2 if args["bidirectional"] else 1
+
+
 def check_lstm_args(lstm_args, num_classes=2):
     """The limits of the LSTM int8 path: hidden size 128 (the implemented size of ``LSTMWakeword``), 1..8 layers, a positive
     input size, 2 <= num_classes <= 64.  -> (input_size, num_layers, num_directions) as ints."""
-    I, H, L = int(lstm_args["input_size"]), int(lstm_args["hidden_size"]), int(lstm_args["num_layers"])
-    if H != LSTM_HIDDEN:
-        raise QuantizationError(f"the int8 LSTM implements hidden_size == {LSTM_HIDDEN}, got hidden_size {H}")
-    if not 1 <= L <= LSTM_MAX_LAYERS:
-        raise QuantizationError(f"the int8 LSTM takes 1..{LSTM_MAX_LAYERS} layers, got num_layers {L}")
-    if I < 1:
-        raise QuantizationError(f"the int8 LSTM takes a positive input_size, got {I}")
-    if not 2 <= int(num_classes) <= LSTM_MAX_CLASSES:
-        raise QuantizationError(f"the int8 LSTM takes 2..{LSTM_MAX_CLASSES} classes, got num_classes {num_classes}")
-    return I, L, 2 if lstm_args["bidirectional"] else 1
+    I = int(lstm_args["input_size"])
+    return (I,) + _check_rnn_args("LSTM", lstm_args, num_classes, I)
 
 
 def lstm_tables():
@@ -334,6 +341,34 @@ def _quantize_gates(arrays, name, wf, bf, s_in, acc_max):
     arrays[name + ".sh"] = np.array([s for _, s in ms], np.int32)
 
 
+def _quantize_rnn_stack(arrays, st, gates, rnn, fc, input_size, num_layers, num_directions, s_in0):
+    """A recurrent stack of ``gates`` gate blocks per direction (the law's subsections "LSTM": 4, "GRU": 3) into ``arrays``: per
+    layer and direction ``l{l}.{fwd|rev}.{ih,hh}.{w,b,m,sh}``, then ``fc.*`` and ``tab.*``.  ``st``: float64 state; ``rnn`` / ``fc``:
+    the key prefixes of the stack and of its classifier in it; ``s_in0``: the scale of the layer-0 input.  Raises
+    ``QuantizationError`` where the law refuses."""
+    H, nd = LSTM_HIDDEN, num_directions
+    for layer in range(num_layers):
+        K, s_in = (input_size, float(s_in0)) if layer == 0 else (nd * H, S_H)
+        for d in range(nd):
+            sfx, name = f"_l{layer}" + ("_reverse" if d else ""), f"l{layer}.{LSTM_DIRS[d]}"
+            for key, shape in ((f"{rnn}weight_ih{sfx}", (gates * H, K)), (f"{rnn}weight_hh{sfx}", (gates * H, H)),
+                               (f"{rnn}bias_ih{sfx}", (gates * H,)), (f"{rnn}bias_hh{sfx}", (gates * H,))):
+                if key not in st or st[key].shape != shape:
+                    raise QuantizationError(f"{key}: expected a tensor of shape {shape}")
+            _quantize_gates(arrays, name + ".ih", st[f"{rnn}weight_ih{sfx}"], st[f"{rnn}bias_ih{sfx}"], s_in, K * 127 * 255)
+            _quantize_gates(arrays, name + ".hh", st[f"{rnn}weight_hh{sfx}"], st[f"{rnn}bias_hh{sfx}"], S_H, H * 127 * 128)
+    fw, fb = st.get(fc + "weight"), st.get(fc + "bias")
+    if fw is None or fb is None or fw.ndim != 2 or fw.shape[1] != nd * H or fb.shape != (fw.shape[0],):
+        raise QuantizationError(f"{fc}weight: expected weights of shape (num_classes, {nd * H}) and their bias")
+    if not np.isfinite(fw).all():
+        raise QuantizationError("classifier: a weight is not finite")
+    q_w, s_w = quantize_weights(fw)
+    arrays["fc.w"] = q_w
+    arrays["fc.b"] = quantize_bias(fb, S_H, s_w, nd * H * 127 * 128, "classifier", unit="row")
+    arrays["fc.scale"] = (S_H * s_w).astype(np.float32)
+    arrays["tab.sigmoid"], arrays["tab.tanh"] = lstm_tables()
+
+
 def quantize_lstm(state: Dict[str, np.ndarray], lstm_args: dict, x_min: float, x_max: float):
     """The arrays of an int8 LSTMWakeword bundle and its scales (the law's subsection "LSTM").  ``lstm_args``: ``input_size``,
     ``hidden_size``, ``num_layers``, ``bidirectional``.  Only the input range is calibrated: hidden state, gates and cell have
@@ -343,73 +378,25 @@ def quantize_lstm(state: Dict[str, np.ndarray], lstm_args: dict, x_min: float, x
         raise QuantizationError("the state holds no LSTMWakeword (lstm.weight_ih_l0, fc.1.weight)")
     num_classes = st["fc.1.weight"].shape[0]
     I, L, nd = check_lstm_args(lstm_args, num_classes)
-    H = LSTM_HIDDEN
+    if st["fc.1.weight"].shape != (num_classes, nd * LSTM_HIDDEN):
+        raise QuantizationError(f"fc.1.weight: expected weights of shape {(num_classes, nd * LSTM_HIDDEN)}")
     s_x, z_x = input_qparams(x_min, x_max)
     arrays = {"input_scale": np.array([s_x], np.float32), "input_zero": np.array([z_x], np.int32)}
-    scales = {"input": float(s_x), "hidden": S_H}
-    for layer in range(L):
-        K, s_in = (I, float(s_x)) if layer == 0 else (nd * H, S_H)
-        for d in range(nd):
-            sfx, name = f"_l{layer}" + ("_reverse" if d else ""), f"l{layer}.{LSTM_DIRS[d]}"
-            for key, shape in ((f"lstm.weight_ih{sfx}", (4 * H, K)), (f"lstm.weight_hh{sfx}", (4 * H, H)),
-                               (f"lstm.bias_ih{sfx}", (4 * H,)), (f"lstm.bias_hh{sfx}", (4 * H,))):
-                if key not in st or st[key].shape != shape:
-                    raise QuantizationError(f"{key}: expected a tensor of shape {shape}")
-            _quantize_gates(arrays, name + ".ih", st[f"lstm.weight_ih{sfx}"], st[f"lstm.bias_ih{sfx}"], s_in, K * 127 * 255)
-            _quantize_gates(arrays, name + ".hh", st[f"lstm.weight_hh{sfx}"], st[f"lstm.bias_hh{sfx}"], S_H, H * 127 * 128)
-    if st["fc.1.weight"].shape != (num_classes, nd * H):
-        raise QuantizationError(f"fc.1.weight: expected weights of shape {(num_classes, nd * H)}")
-    if not np.isfinite(st["fc.1.weight"]).all():
-        raise QuantizationError("classifier: a weight is not finite")
-    q_w, s_w = quantize_weights(st["fc.1.weight"])
-    arrays["fc.w"] = q_w
-    arrays["fc.b"] = quantize_bias(st["fc.1.bias"], S_H, s_w, nd * H * 127 * 128, "classifier", unit="row")
-    arrays["fc.scale"] = (S_H * s_w).astype(np.float32)
-    arrays["tab.sigmoid"], arrays["tab.tanh"] = lstm_tables()
-    return arrays, scales
-
-
-GRU_MAX_LAYERS, GRU_MAX_CLASSES = 8, 64
+    _quantize_rnn_stack(arrays, st, 4, "lstm.", "fc.1.", I, L, nd, s_x)
+    return arrays, {"input": float(s_x), "hidden": S_H}
 
 
 def check_crnn_args(crnn_args, num_classes=2):
     """The limits of the CRNN int8 path: hidden size 128 (the implemented size of the GRU stack), 1..8 layers,
     2 <= num_classes <= 64.  -> (num_layers, num_directions) as ints."""
-    H, L = int(crnn_args["hidden_size"]), int(crnn_args["num_layers"])
-    if H != LSTM_HIDDEN:
-        raise QuantizationError(f"the int8 CRNN implements hidden_size == {LSTM_HIDDEN}, got hidden_size {H}")
-    if not 1 <= L <= GRU_MAX_LAYERS:
-        raise QuantizationError(f"the int8 CRNN takes 1..{GRU_MAX_LAYERS} layers, got num_layers {L}")
-    if not 2 <= int(num_classes) <= GRU_MAX_CLASSES:
-        raise QuantizationError(f"the int8 CRNN takes 2..{GRU_MAX_CLASSES} classes, got num_classes {num_classes}")
-    return L, 2 if crnn_args["bidirectional"] else 1
+    return _check_rnn_args("CRNN", crnn_args, num_classes)
 
 
 def quantize_gru_stack(arrays, st, prefix, input_size, num_layers, num_directions, s_in0):
     """The GRU stack of the law's subsection "GRU" into ``arrays``: per layer and direction ``l{l}.{fwd|rev}.{ih,hh}.{w,b,m,sh}``
     (gate rows r, z, n), then ``fc.*`` and ``tab.*``.  ``st``: float64 state; ``prefix``: where the stack lives in it (``gru.*`` and
     ``fc.1.*`` below it); ``s_in0``: the scale of the layer-0 input.  Raises ``QuantizationError`` where the law refuses."""
-    H, nd = LSTM_HIDDEN, num_directions
-    for layer in range(num_layers):
-        K, s_in = (input_size, float(s_in0)) if layer == 0 else (nd * H, S_H)
-        for d in range(nd):
-            sfx, name = f"_l{layer}" + ("_reverse" if d else ""), f"l{layer}.{LSTM_DIRS[d]}"
-            for key, shape in ((f"{prefix}gru.weight_ih{sfx}", (3 * H, K)), (f"{prefix}gru.weight_hh{sfx}", (3 * H, H)),
-                               (f"{prefix}gru.bias_ih{sfx}", (3 * H,)), (f"{prefix}gru.bias_hh{sfx}", (3 * H,))):
-                if key not in st or st[key].shape != shape:
-                    raise QuantizationError(f"{key}: expected a tensor of shape {shape}")
-            _quantize_gates(arrays, name + ".ih", st[f"{prefix}gru.weight_ih{sfx}"], st[f"{prefix}gru.bias_ih{sfx}"], s_in, K * 127 * 255)
-            _quantize_gates(arrays, name + ".hh", st[f"{prefix}gru.weight_hh{sfx}"], st[f"{prefix}gru.bias_hh{sfx}"], S_H, H * 127 * 128)
-    fw, fb = st.get(prefix + "fc.1.weight"), st.get(prefix + "fc.1.bias")
-    if fw is None or fb is None or fw.ndim != 2 or fw.shape[1] != nd * H or fb.shape != (fw.shape[0],):
-        raise QuantizationError(f"{prefix}fc.1.weight: expected weights of shape (num_classes, {nd * H}) and their bias")
-    if not np.isfinite(fw).all():
-        raise QuantizationError("classifier: a weight is not finite")
-    q_w, s_w = quantize_weights(fw)
-    arrays["fc.w"] = q_w
-    arrays["fc.b"] = quantize_bias(fb, S_H, s_w, nd * H * 127 * 128, "classifier", unit="row")
-    arrays["fc.scale"] = (S_H * s_w).astype(np.float32)
-    arrays["tab.sigmoid"], arrays["tab.tanh"] = lstm_tables()
+    _quantize_rnn_stack(arrays, st, 3, prefix + "gru.", prefix + "fc.1.", input_size, num_layers, num_directions, s_in0)
 
 
 def quantize_crnn(state: Dict[str, np.ndarray], crnn_args: dict, F: int, ranges: dict, eps: float = 1e-5):

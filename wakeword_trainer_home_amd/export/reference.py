@@ -248,10 +248,15 @@ def run_int8_resnet18(header, arrays, x, want_acc=False):
 LSTM_HIDDEN, LSTM_TABLE, LSTM_DIRS = 128, 4096, ("fwd", "rev")
 
 
+def _rnn_stack_stages(args, state):
+    """Per layer and direction ``l{l}.{fwd|rev}.u``, ``.y`` and the final state ``.c`` / ``.h``."""
+    dirs = LSTM_DIRS if args["bidirectional"] else LSTM_DIRS[:1]
+    return [f"l{k}.{d}.{s}" for k in range(int(args["num_layers"])) for d in dirs for s in ("u", "y", state)]
+
+
 def lstm_stages(lstm):
     """``xq``, per layer and direction ``l{l}.{fwd|rev}.u``, ``.y`` and ``.c``, then ``hcat`` and ``logits``."""
-    dirs = LSTM_DIRS if lstm["bidirectional"] else LSTM_DIRS[:1]
-    return ["xq"] + [f"l{k}.{d}.{s}" for k in range(int(lstm["num_layers"])) for d in dirs for s in ("u", "y", "c")] + ["hcat", "logits"]
+    return ["xq"] + _rnn_stack_stages(lstm, "c") + ["hcat", "logits"]
 
 
 def look(tab, a):
@@ -264,74 +269,34 @@ def _exact_matmul(q, w):
     return (q.astype(np.float64) @ w.astype(np.float64).T).astype(np.int64)
 
 
-def run_int8_lstm(header, arrays, x, want_acc=False):
-    """Every stage of an int8 LSTMWakeword bundle on (B,1,F,T) features or (B,T,F) sequences, any T >= 1: ``xq`` (B,T,F) int8; per
-    layer and direction ``l{l}.{fwd|rev}.u`` (B,T,512) int16 (the input projection in Q8, gate order i, f, g, o), ``.y`` (B,T,128)
-    int8 (q_h at every step, in time order) and ``.c`` (B,128) int16 (the cell after the direction's last step); ``hcat``
-    (B, nd 128) int8; ``logits`` float32.  ``want_acc`` adds nothing: the law has no hidden accumulators beyond ``u``."""
-    x = np.asarray(x, np.float32)
-    lstm = header["lstm"]
-    F, L, H = int(lstm["input_size"]), int(lstm["num_layers"]), LSTM_HIDDEN
-    if x.ndim == 4 and x.shape[1] == 1:
-        x = x[:, 0].transpose(0, 2, 1)
-    if x.ndim != 3 or x.shape[2] != F or x.shape[1] < 1:
-        raise ValueError(f"this bundle is for features of shape (B,1,{F},T) or sequences (B,T,{F}), got {tuple(x.shape)}")
-    a, out = arrays, {}
-    dirs = LSTM_DIRS if lstm["bidirectional"] else LSTM_DIRS[:1]
-    sig, tanh = a["tab.sigmoid"], a["tab.tanh"]
-    z_in = int(a["input_zero"][0])
-    q_in = np.ascontiguousarray(quantize_input(x, a["input_scale"][0], z_in))
-    out["xq"] = q_in
-    B, T, _ = q_in.shape
-    hcat = []
-    for k in range(L):
-        ys = []
-        for d in dirs:
-            p = f"l{k}.{d}"
-            acc = _wrap32(_exact_matmul(q_in.astype(np.int64) - z_in, a[p + ".ih.w"]) + a[p + ".ih.b"].astype(np.int64))
-            u = np.clip(round_shift(acc, a[p + ".ih.m"], a[p + ".ih.sh"]), -32768, 32767)
-            y = np.zeros((B, T, H), np.int8)
-            q_h, c = np.zeros((B, H), np.int64), np.zeros((B, H), np.int64)
-            for t in (range(T) if d == "fwd" else range(T - 1, -1, -1)):
-                acc = _wrap32(_exact_matmul(q_h, a[p + ".hh.w"]) + a[p + ".hh.b"].astype(np.int64))
-                g_in = u[:, t] + round_shift(acc, a[p + ".hh.m"], a[p + ".hh.sh"])
-                i, f = look(sig, g_in[:, :H]), look(sig, g_in[:, H:2 * H])
-                g, o = look(tanh, g_in[:, 2 * H:3 * H]), look(sig, g_in[:, 3 * H:])
-                c = np.clip((f * c + ((i * g + 8) >> 4) + 2 ** 14) >> 15, -32768, 32767)
-                h16 = (o * look(tanh, (c + 4) >> 3) + 2 ** 14) >> 15
-                q_h = np.clip((h16 + 128) >> 8, -128, 127)
-                y[:, t] = q_h
-            out[p + ".u"], out[p + ".y"], out[p + ".c"] = u.astype(np.int16), y, c.astype(np.int16)
-            ys.append(y)
-            if k == L - 1:
-                hcat.append(y[:, T - 1] if d == "fwd" else y[:, 0])
-        q_in, z_in = np.concatenate(ys, axis=2), 0
-    hcat = np.concatenate(hcat, axis=1)
-    out["hcat"] = hcat
-    acc = _wrap32(_exact_matmul(hcat, a["fc.w"]) + a["fc.b"].astype(np.int64))
-    out["logits"] = acc.astype(np.float32) * a["fc.scale"].astype(np.float32)
-    return out
+def _lstm_step(sig, tanh, u, v, c):
+    """One LSTM step on Q8 pre-activations u + v (B,512), gate order i, f, g, o; the state is the cell c.  -> (c, h16)."""
+    H, g_in = LSTM_HIDDEN, u + v
+    i, f = look(sig, g_in[:, :H]), look(sig, g_in[:, H:2 * H])
+    g, o = look(tanh, g_in[:, 2 * H:3 * H]), look(sig, g_in[:, 3 * H:])
+    c = np.clip((f * c + ((i * g + 8) >> 4) + 2 ** 14) >> 15, -32768, 32767)
+    return c, (o * look(tanh, (c + 4) >> 3) + 2 ** 14) >> 15
 
 
-GRU_GATES = 3                          # gate rows of a GRU direction: r, z, n, 3 H in all
+def _gru_step(sig, tanh, u, v, h16):
+    """One GRU step on the Q8 input part u and hidden part v (B,384), gate order r, z, n; the state is h16.  -> (h16, h16)."""
+    H = LSTM_HIDDEN
+    r, z = look(sig, u[:, :H] + v[:, :H]), look(sig, u[:, H:2 * H] + v[:, H:2 * H])
+    n = look(tanh, u[:, 2 * H:] + ((r * v[:, 2 * H:] + 2 ** 14) >> 15))
+    h16 = ((32768 - z) * n + z * h16 + 2 ** 14) >> 15
+    return h16, h16
 
 
-def gru_stack_stages(args):
-    """Per layer and direction ``l{l}.{fwd|rev}.u``, ``.y`` and ``.h``."""
-    dirs = LSTM_DIRS if args["bidirectional"] else LSTM_DIRS[:1]
-    return [f"l{k}.{d}.{s}" for k in range(int(args["num_layers"])) for d in dirs for s in ("u", "y", "h")]
+LSTM_CELL, GRU_CELL = ("c", _lstm_step), ("h", _gru_step)      # the name of the final state among the stages, the step
 
 
-def crnn_stages(crnn):
-    return ["xq"] + ["front." + c for c in CONVS] + ["seq"] + gru_stack_stages(crnn) + ["hcat", "logits"]
-
-
-def run_int8_gru_stack(arrays, q_in, z_in, args):
-    """The GRU stack of the law's subsection "GRU" on int8 rows ``q_in`` (B,T,K) with zero point ``z_in``; ``args``:
-    ``num_layers``, ``bidirectional``.  -> ({``l{l}.{fwd|rev}.u`` (B,T,384) int16 (the input projection in Q8, gate order r, z, n),
-    ``.y`` (B,T,128) int8 (q_h at every step, in time order), ``.h`` (B,128) int16 (h16 after the direction's last step)},
-    hcat (B, nd 128) int8)."""
+def run_int8_gru_stack(arrays, q_in, z_in, args, cell=GRU_CELL):
+    """The recurrent stack of the law's subsections "GRU" (the default ``cell``) and "LSTM" on int8 rows ``q_in`` (B,T,K) with
+    zero point ``z_in``; ``args``: ``num_layers``, ``bidirectional``.  -> ({``l{l}.{fwd|rev}.u`` (B,T,384 | 512) int16 (the input
+    projection in Q8, gate order r, z, n | i, f, g, o), ``.y`` (B,T,128) int8 (q_h at every step, in time order), ``.h`` | ``.c``
+    (B,128) int16 (h16 | the cell after the direction's last step)}, hcat (B, nd 128) int8)."""
     a, out, H = arrays, {}, LSTM_HIDDEN
+    state, step = cell
     dirs = LSTM_DIRS if args["bidirectional"] else LSTM_DIRS[:1]
     sig, tanh = a["tab.sigmoid"], a["tab.tanh"]
     L = int(args["num_layers"])
@@ -345,21 +310,49 @@ def run_int8_gru_stack(arrays, q_in, z_in, args):
             acc = _wrap32(_exact_matmul(q_in.astype(np.int64) - z_in, a[p + ".ih.w"]) + a[p + ".ih.b"].astype(np.int64))
             u = np.clip(round_shift(acc, a[p + ".ih.m"], a[p + ".ih.sh"]), -32768, 32767)
             y = np.zeros((B, T, H), np.int8)
-            q_h, h16 = np.zeros((B, H), np.int64), np.zeros((B, H), np.int64)
+            q_h, s = np.zeros((B, H), np.int64), np.zeros((B, H), np.int64)
             for t in (range(T) if d == "fwd" else range(T - 1, -1, -1)):
                 acc = _wrap32(_exact_matmul(q_h, a[p + ".hh.w"]) + a[p + ".hh.b"].astype(np.int64))
-                v = round_shift(acc, a[p + ".hh.m"], a[p + ".hh.sh"])
-                r, z = look(sig, u[:, t, :H] + v[:, :H]), look(sig, u[:, t, H:2 * H] + v[:, H:2 * H])
-                n = look(tanh, u[:, t, 2 * H:] + ((r * v[:, 2 * H:] + 2 ** 14) >> 15))
-                h16 = ((32768 - z) * n + z * h16 + 2 ** 14) >> 15
+                s, h16 = step(sig, tanh, u[:, t], round_shift(acc, a[p + ".hh.m"], a[p + ".hh.sh"]), s)
                 q_h = np.clip((h16 + 128) >> 8, -128, 127)
                 y[:, t] = q_h
-            out[p + ".u"], out[p + ".y"], out[p + ".h"] = u.astype(np.int16), y, h16.astype(np.int16)
+            out[p + ".u"], out[p + ".y"], out[f"{p}.{state}"] = u.astype(np.int16), y, s.astype(np.int16)
             ys.append(y)
             if k == L - 1:
                 hcat.append(y[:, T - 1] if d == "fwd" else y[:, 0])
         q_in, z_in = np.concatenate(ys, axis=2), 0
     return out, np.concatenate(hcat, axis=1)
+
+
+def run_int8_lstm(header, arrays, x, want_acc=False):
+    """Every stage of an int8 LSTMWakeword bundle on (B,1,F,T) features or (B,T,F) sequences, any T >= 1: ``xq`` (B,T,F) int8; per
+    layer and direction ``l{l}.{fwd|rev}.u`` (B,T,512) int16 (the input projection in Q8, gate order i, f, g, o), ``.y`` (B,T,128)
+    int8 (q_h at every step, in time order) and ``.c`` (B,128) int16 (the cell after the direction's last step); ``hcat``
+    (B, nd 128) int8; ``logits`` float32.  ``want_acc`` adds nothing: the law has no hidden accumulators beyond ``u``."""
+    x = np.asarray(x, np.float32)
+    F = int(header["lstm"]["input_size"])
+    if x.ndim == 4 and x.shape[1] == 1:
+        x = x[:, 0].transpose(0, 2, 1)
+    if x.ndim != 3 or x.shape[2] != F or x.shape[1] < 1:
+        raise ValueError(f"this bundle is for features of shape (B,1,{F},T) or sequences (B,T,{F}), got {tuple(x.shape)}")
+    a = arrays
+    z_in = int(a["input_zero"][0])
+    out = {"xq": np.ascontiguousarray(quantize_input(x, a["input_scale"][0], z_in))}
+    stack, hcat = run_int8_gru_stack(a, out["xq"], z_in, header["lstm"], LSTM_CELL)
+    out.update(stack)
+    out["hcat"] = hcat
+    acc = _wrap32(_exact_matmul(hcat, a["fc.w"]) + a["fc.b"].astype(np.int64))
+    out["logits"] = acc.astype(np.float32) * a["fc.scale"].astype(np.float32)
+    return out
+
+
+def gru_stack_stages(args):
+    """Per layer and direction ``l{l}.{fwd|rev}.u``, ``.y`` and ``.h``."""
+    return _rnn_stack_stages(args, "h")
+
+
+def crnn_stages(crnn):
+    return ["xq"] + ["front." + c for c in CONVS] + ["seq"] + gru_stack_stages(crnn) + ["hcat", "logits"]
 
 
 def run_int8_crnn(header, arrays, x, want_acc=False):

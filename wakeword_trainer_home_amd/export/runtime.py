@@ -232,10 +232,10 @@ class QuantizedResNet18(_QuantizedNet):
         self._finish(nat.RQ8_NPTR)                                 # conv(): ``stem`` or ``l{s}.{b}.conv1|conv2|down``
 
 
-def device_lstm_layer(arrays: dict, layer: int, num_directions: int, z_in: int):
-    """The eight tensors of one LSTM layer as ``ww_lq8_proj_fwd`` and ``ww_lq8_lstm_layer_fwd`` read them, the directions stacked
-    (forward first): w_ih (nd*512, Kp) with zero pad columns, its EFFECTIVE bias, mult, shift; w_hh (nd*512, 128), the law's q_bh,
-    mult, shift."""
+def device_rnn_layer(arrays: dict, layer: int, num_directions: int, z_in: int):
+    """The eight tensors of one LSTM or GRU layer as ``ww_lq8_proj_fwd`` and ``ww_lq8_lstm_layer_fwd`` / ``ww_cq8_gru_layer_fwd``
+    read them, the directions stacked (forward first): w_ih (nd*G, Kp), G = 512 or 384 gate rows, with zero pad columns, its
+    EFFECTIVE bias, mult, shift; w_hh (nd*G, 128), the law's q_bh, mult, shift.  The layout does not depend on the gate count."""
     names = [f"l{layer}.{d}" for d in LSTM_DIRS[:num_directions]]
     w_ih = np.concatenate([arrays[n + ".ih.w"] for n in names])
     wd = np.zeros((w_ih.shape[0], nat.tq8_pad(w_ih.shape[1])), np.int8)
@@ -243,6 +243,9 @@ def device_lstm_layer(arrays: dict, layer: int, num_directions: int, z_in: int):
     cat = lambda key: np.concatenate([arrays[n + key] for n in names])       # noqa: E731
     return (wd, effective_bias(cat(".ih.b"), w_ih, z_in), cat(".ih.m"), cat(".ih.sh"),
             np.ascontiguousarray(cat(".hh.w")), cat(".hh.b"), cat(".hh.m"), cat(".hh.sh"))
+
+
+device_lstm_layer = device_gru_layer = device_rnn_layer
 
 
 class QuantizedLSTM(_QuantizedNet):
@@ -263,7 +266,7 @@ class QuantizedLSTM(_QuantizedNet):
         self.io = nat.Lq8Io(float(arrays["input_scale"][0]), z_x, self.input_size, self.num_layers, self.num_directions,
                             self.num_classes)
         for k in range(self.num_layers):
-            self._add_group(f"l{k}", device_lstm_layer(arrays, k, self.num_directions, z_x if k == 0 else 0), LAYER8)
+            self._add_group(f"l{k}", device_rnn_layer(arrays, k, self.num_directions, z_x if k == 0 else 0), LAYER8)
         self._add_tail(arrays, RNN_TAIL)
         self._finish(nat.LQ8_LAYER_NPTR * self.num_layers + nat.LQ8_TAIL_NPTR)
 
@@ -277,13 +280,6 @@ class QuantizedLSTM(_QuantizedNet):
 
     def _workspace_bytes(self, B, F, T):
         return nat.lq8_lstm_workspace_bytes(B, T, F, self.num_layers, self.num_directions)
-
-
-def device_gru_layer(arrays: dict, layer: int, num_directions: int, z_in: int):
-    """The eight tensors of one GRU layer as ``ww_lq8_proj_fwd`` and ``ww_cq8_gru_layer_fwd`` read them, the directions stacked
-    (forward first): w_ih (nd*384, Kp) with zero pad columns, its EFFECTIVE bias, mult, shift; w_hh (nd*384, 128), the law's q_bh,
-    mult, shift."""
-    return device_lstm_layer(arrays, layer, num_directions, z_in)       # the layout does not depend on the gate count
 
 
 class QuantizedCRNN(_QuantizedNet):
@@ -307,7 +303,7 @@ class QuantizedCRNN(_QuantizedNet):
         for name in CONVS:
             self._add_group(name, device_conv(front, name, z_x if name == "stem" else -128))
         for k in range(self.num_layers):
-            self._add_group(f"l{k}", device_gru_layer(arrays, k, self.num_directions, -128 if k == 0 else 0), LAYER8)
+            self._add_group(f"l{k}", device_rnn_layer(arrays, k, self.num_directions, -128 if k == 0 else 0), LAYER8)
         self._add_tail(arrays, RNN_TAIL)
         self._finish(nat.CQ8_CONV_NPTR + nat.CQ8_LAYER_NPTR * self.num_layers + nat.CQ8_TAIL_NPTR)
 
